@@ -11,10 +11,15 @@ Frames shard embarrassingly over ranks (one process per GPU, weak scaling: each 
 the only collective is the end-of-run reduction of the pair count / RMSD sum (RCCL all_reduce).
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload search_fit|rdf|membrane]
+                       [--full] [--dump-outputs DIR]
         N>1 from a bare shell: the script re-launches itself as N ranks through torch.distributed.run
         (127.0.0.1 rendezvous); under torch.distributed.run it uses the RANK/LOCAL_RANK/WORLD_SIZE it finds.
         --workload rdf is BASELINE.json configs[3] in the same frame-sharded shape: 250k-atom frames, fused
         1200-bin radial histogram with the bins resident in HBM, ONE all_reduce of 1200 x int64 at the end.
+        A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds everything
+        else the line used to carry: the self-check of the timed frames, the per-kernel event passes and the
+        roofline, the pairs-only mode, the CPU baseline and the secondary C4 / C5 legs.
+        --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (rank 0).
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -53,6 +58,38 @@ def make_frames(nframes, rank, box, device):
     ref = base.float().contiguous()
     torch.cuda.synchronize()      # made on torch's stream; the engine reads them on its own
     return frames, ref
+
+
+DUMP_PAIR_SAMPLE = 1 << 20            # (i, j, d) records in the seeded sample of the pair list --dump-outputs writes
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+class DevArray:
+    """A device buffer of the engine (address, element count, numpy typestr) as something torch.as_tensor takes."""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy, float32 kept, everything else as float64 (the integers written are
+    below 2**53: exact); refuses more than DUMP_LIMIT_BYTES in all."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        out[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def split_u64(v):
+    """A 64-bit checksum (Python int, possibly negative) as its low and high 32-bit halves: exact in float64."""
+    v %= 1 << 64
+    return [v & 0xFFFFFFFF, v >> 32]
 
 
 def cpu_baseline(frame0, ref, box, mass, idx, warmup=5, reps=10):
@@ -298,6 +335,8 @@ def run_rdf_xtc(args, rank, local_rank, world, device, cdev):
         t_con += consume(bufs[w % 2], k)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:        # the bins the timed frames filled, as the caller holds them (this rank's)
+        dump_outputs(args.dump_outputs, {"rdf_bins": bins.cpu().numpy()})
     total_bins = reduce_counts(bins.cpu().numpy(), device=cdev)       # the only collective
     t = max_over_ranks(elapsed, device=cdev)
     sides = gather_float64(np.array([K / max(t_dec, 1e-9), K / max(t_con, 1e-9), K / elapsed]), device=cdev)
@@ -403,15 +442,19 @@ def run_rdf(args, rank, local_rank, world, device, cdev):
     barrier()
     elapsed = time.perf_counter() - t0
     timed_bins = bins.cpu().numpy().copy()
-    # per-kernel event times from a second, untimed pass over the same frames: an event record is a barrier packet on the stream
-    # (~5-10 us each, five per frame), so the timed region carries none
-    eng.profile_enable(True)
-    eng.profile_read()
-    KP = min(K, max(args.profile_steps, 1))
-    run(W, KP)
-    barrier()
-    prof = eng.profile_read()
-    eng.profile_enable(False)
+    if args.dump_outputs and rank == 0:        # the bins the timed frames filled, as the caller holds them (this rank's)
+        dump_outputs(args.dump_outputs, {"rdf_bins": timed_bins})
+    # --full: per-kernel event times from a second, untimed pass over the same frames: an event record is a barrier packet on
+    # the stream (~5-10 us each, five per frame), so the timed region carries none
+    prof = None
+    if args.full:
+        eng.profile_enable(True)
+        eng.profile_read()
+        KP = min(K, max(args.profile_steps, 1))
+        run(W, KP)
+        barrier()
+        prof = eng.profile_read()
+        eng.profile_enable(False)
     total_bins = reduce_counts(timed_bins, device=cdev)       # the only collective
     t = max_over_ranks(elapsed, device=cdev)
     from molar_amd.distributed import collective_view, gather_float64 as _gf
@@ -432,24 +475,6 @@ def run_rdf(args, rank, local_rank, world, device, cdev):
                     e2.synchronize()
             check = bool(np.array_equal(chk.cpu().numpy(), total_bins))
         pairs = float(total_bins.sum())
-        hist_ms, hist_n = prof["pair_fill"]
-        hist_launches = hist_n
-        hist_n = KP          # per FRAME: a launch of the frames form carries up to 8 frames
-        # algorithmic work of one frame: the plan's candidate evaluations, 13.5 * N * mean cell
-        # population (13 neighbour cells in full, the own cell as a triangle), 9 flop each; the kernels skip part of
-        # them by bounding boxes, the reference evaluates all
-        ext = np.asarray(box, np.float32).sum(axis=1)              # get_lab_extents: row sums (periodic_box.rs:369-375)
-        gd = np.maximum(np.floor(ext / np.float32(CUTOFF)), 1).astype(np.int64)     # Grid::from_cutoff_and_extents (:103-110)
-        ncell = max(int(gd[0]) * int(gd[1]) * int(gd[2]), 1)
-        cand = 13.5 * n * (n / ncell)
-        valu_peak = 157.3
-        # what the kernels really evaluate: the lean kernel skips the (row, 64-atom chunk) steps its bounding boxes rule out.
-        # Counted by a debug build in a separate run (tools/hist_wave_times.py -> profiles/hist_steps.json), like roofline.traffic.
-        executed = None
-        try:
-            executed = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "hist_steps.json")))["executed_candidate_evaluations"]
-        except Exception:
-            pass
         line = ({
             "metric": "frames/sec, 250k-atom frames -> fused 1200-bin radial distance histogram, bins reduced over ranks",
             "value": K * world / t, "unit": "frames/s", "pairs_binned_per_sec": pairs / t,
@@ -461,21 +486,42 @@ def run_rdf(args, rank, local_rank, world, device, cdev):
                        "call_form": "one call per frame" if args.rdf_single_calls else "molar_hip_search_histogram_frames over blocks of the resident frames (groups of <= 8 frames per launch)",
                        "pairs_per_frame": pairs / (K * world)},
             "per_rank_fps": per_rank, "collective": comm,
-            "kernel_ms_per_frame": {k: v[0] / KP for k, v in prof.items()},
-            "kernel_ms_source": f"HIP events on the engine's stream in a separate untimed pass over {KP} of the same frames",
-            "roofline": {"kernel": "hist_plan_kernel + hist_kernel<SINGLE> + pair_kernel<SINGLE,HIST>", "bound": "valu",
-                         "note": "12*N + 8*nbins bytes per frame: not an HBM-bound path (SURVEY.md 8d); priced as the plan's "
-                                 "candidate evaluations x 9 flop against the fp32 vector peak",
-                         "achieved": cand * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12, "peak": valu_peak, "unit": "TFLOP/s",
-                         "frac": cand * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12 / valu_peak, "traffic": None,
-                         "frac_on_executed_evaluations": (executed * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12 / valu_peak) if executed else None,
-                         "executed_candidate_evals_per_frame": executed,
-                         "executed_source": "profiles/hist_steps.json: steps counted by a -DMOLAR_HIP_DEBUG_KNOBS build on this workload's frame (separate run)",
-                         "avg_launch_ms": hist_ms / max(hist_n, 1), "avg_launch_ms_is": "histogram kernels' time per FRAME",
-                         "launches_in_profile_pass": hist_launches, "frames_in_profile_pass": KP, "grid_dims": [int(x) for x in gd],
-                         "candidate_evals_per_frame": cand, "candidate_evals_per_sec": cand * K * world / t},
             "reduced_bins_equal_single_rank": check,
         })
+        if prof is not None:        # --full: the event pass and the roofline
+            hist_ms, hist_n = prof["pair_fill"]
+            hist_launches = hist_n
+            hist_n = KP          # per FRAME: a launch of the frames form carries up to 8 frames
+            # algorithmic work of one frame: the plan's candidate evaluations, 13.5 * N * mean cell
+            # population (13 neighbour cells in full, the own cell as a triangle), 9 flop each; the kernels skip part of
+            # them by bounding boxes, the reference evaluates all
+            ext = np.asarray(box, np.float32).sum(axis=1)              # get_lab_extents: row sums (periodic_box.rs:369-375)
+            gd = np.maximum(np.floor(ext / np.float32(CUTOFF)), 1).astype(np.int64)     # Grid::from_cutoff_and_extents (:103-110)
+            ncell = max(int(gd[0]) * int(gd[1]) * int(gd[2]), 1)
+            cand = 13.5 * n * (n / ncell)
+            valu_peak = 157.3
+            # what the kernels really evaluate: the lean kernel skips the (row, 64-atom chunk) steps its bounding boxes rule out.
+            # Counted by a debug build in a separate run (tools/hist_wave_times.py -> profiles/hist_steps.json), like roofline.traffic.
+            executed = None
+            try:
+                executed = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "hist_steps.json")))["executed_candidate_evaluations"]
+            except Exception:
+                pass
+            line.update({
+                "kernel_ms_per_frame": {k: v[0] / KP for k, v in prof.items()},
+                "kernel_ms_source": f"HIP events on the engine's stream in a separate untimed pass over {KP} of the same frames",
+                "roofline": {"kernel": "hist_plan_kernel + hist_kernel<SINGLE> + pair_kernel<SINGLE,HIST>", "bound": "valu",
+                             "note": "12*N + 8*nbins bytes per frame: not an HBM-bound path (SURVEY.md 8d); priced as the plan's "
+                                     "candidate evaluations x 9 flop against the fp32 vector peak",
+                             "achieved": cand * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12, "peak": valu_peak, "unit": "TFLOP/s",
+                             "frac": cand * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12 / valu_peak, "traffic": None,
+                             "frac_on_executed_evaluations": (executed * 9 / (hist_ms / max(hist_n, 1) * 1e-3) / 1e12 / valu_peak) if executed else None,
+                             "executed_candidate_evals_per_frame": executed,
+                             "executed_source": "profiles/hist_steps.json: steps counted by a -DMOLAR_HIP_DEBUG_KNOBS build on this workload's frame (separate run)",
+                             "avg_launch_ms": hist_ms / max(hist_n, 1), "avg_launch_ms_is": "histogram kernels' time per FRAME",
+                             "launches_in_profile_pass": hist_launches, "frames_in_profile_pass": KP, "grid_dims": [int(x) for x in gd],
+                             "candidate_evals_per_frame": cand, "candidate_evals_per_sec": cand * K * world / t},
+            })
         line["_failed"] = check is False
         return line
     return None
@@ -589,6 +635,7 @@ def run_membrane(args, rank, local_rank, world, device, cdev):
         acc = np.zeros(per_frame[0].shape if count else 4, np.float64)
         for row in per_frame:
             acc += row
+        last_row[:] = per_frame[-1:]
         return acc, dt
 
     def barrier():
@@ -598,6 +645,7 @@ def run_membrane(args, rank, local_rank, world, device, cdev):
             e.synchronize()
         torch.cuda.synchronize()
 
+    last_row = []            # the per-frame sums of the last frame run_frames went through
     t_pre = time.perf_counter()
     while args.preheat > 0 and time.perf_counter() - t_pre < args.preheat:
         run_frames(16)
@@ -605,6 +653,8 @@ def run_membrane(args, rank, local_rank, world, device, cdev):
     barrier()
     acc, elapsed = run_frames(K, first_frame=W)
     barrier()
+    if args.dump_outputs and rank == 0 and K > 0:       # (valid lipids, vertices, area, |mean curvature|, Scd per carbon)
+        dump_outputs(args.dump_outputs, {"membrane_sums": acc, "membrane_last_frame_sums": last_row[0]})
     # sums over ranks: the integer entries exactly, the float sums in rank order on rank 0
     from molar_amd.distributed import gather_float64
     parts = gather_float64(acc, device=cdev)
@@ -673,6 +723,7 @@ def secondary_legs(args, rank, local_rank, world, device, cdev):
                                                          xtc_window=16, decoder="host", decode_threads=0, xtc_path="")),
                            ("membrane", run_membrane, dict(workload="membrane", steps=args.secondary_membrane_steps, warmup=8, verify=True,
                                                            preheat=min(args.preheat, 1.0), streams=4))):
+        over["dump_outputs"] = ""          # --dump-outputs holds the headline's outputs only
         a2 = copy.copy(args)
         for k, v in over.items():
             setattr(a2, k, v)
@@ -741,6 +792,13 @@ def main():
     ap.add_argument("--share-gpu", action="store_true",
                     help="functional check of the N>1 code path on a box with fewer GPUs: ranks share the visible GPUs "
                          "(rank r uses GPU r mod count) and reduce over gloo; the line it prints is NOT a scaling result")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else: the self-check of the last timed frames, the per-kernel "
+                         "event passes and the roofline, the pairs-only mode, the CPU baseline and the secondary legs "
+                         "(--no-cpu-baseline, --no-secondary, --secondary and --no-pairs-only refine it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, a fixed seeded sample of the pair list; at most 64 MB in all)")
     args = ap.parse_args()
     if args.streams <= 0:         # default: one context for the search workloads; the membrane workload (a frame = ~35 latency-bound
         args.streams = 4 if args.workload == "membrane" else 1      # launches on 4000 lipids) runs four contexts on alternate frames
@@ -861,19 +919,19 @@ def main():
             descs[k][0][0].xyz1 = fr.data_ptr()
             cnt, pp_, dp_ = e.search_resident_desc(descs[k][0][0])       # count + scan + fill, one round trip
             return cnt, None, pp_, dp_
-        cnt, _, _ = e.search_resident(api.SEARCH_SINGLE, CUTOFF, fr, box=box, pbc=7)
+        cnt, pp_, dp_ = e.search_resident(api.SEARCH_SINGLE, CUTOFF, fr, box=box, pbc=7)
         out = e.fit_rmsd_batch(fr.unsqueeze(0), mass, ref, idx=idx, apply=True)
-        return cnt, float(out["rmsd"][0])
+        return cnt, out, pp_, dp_
 
     def collect_fits(k, count):
-        """The `count` fit results (RMSD after the fit) of context k, in frame order; all of them are part of the timed work."""
-        vals = []
+        """The `count` fit results of context k, in frame order; all of them are part of the timed work."""
+        outs = []
         for _ in range(count):
             out = done[k].get()
             if isinstance(out, Exception):
                 raise out
-            vals.append(float(out["rmsd"][0]))
-        return vals
+            outs.append(out)
+        return outs
 
     def barrier():
         if world > 1:
@@ -884,22 +942,19 @@ def main():
 
     fits = []
     last_results = []      # (frame number, pair count, pairs device address, distances device address) of the newest results
+    last_fit = []          # (frame number, fit result) of the last step
 
     def checksum_planes(cnt, pp, dp):
         """Order-sensitive 64-bit checksums of a result's pair plane and distance plane where they lie in HBM: sum of
         value_i * (2 i + 1) in wrapping int64 arithmetic over the (i, j) records as u64 words / the distances' bit patterns."""
         if cnt == 0:
             return 0, 0
-
-        class _Dev:
-            def __init__(self, ptr, n, typestr):
-                self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False), "version": 2}
         w = torch.arange(cnt, device=device, dtype=torch.int64) * 2 + 1
-        pv = torch.as_tensor(_Dev(pp, cnt, "<i8"), device=device)
+        pv = torch.as_tensor(DevArray(pp, cnt, "<i8"), device=device)
         a = int((pv * w).sum().item())
         b = 0
         if dp:                 # (the pairs-only mode has no distance plane)
-            dv = torch.as_tensor(_Dev(dp, cnt, "<i4"), device=device).to(torch.int64)
+            dv = torch.as_tensor(DevArray(dp, cnt, "<i4"), device=device).to(torch.int64)
             b = int((dv * w).sum().item())
             del dv
         del w, pv
@@ -912,6 +967,7 @@ def main():
         (ctypes releases the GIL inside the library).  Every frame is begun AND ended in here."""
         res = [None] * count
         rms = [0.0] * count
+        fit_outs = [None] * count             # each step's whole fit result (R, t, rmsd, com, gyration)
         newest = [[] for _ in range(S)]       # per context: (frame number, pair count, device addresses) of its newest results
 
         def context_loop(k):
@@ -934,6 +990,7 @@ def main():
                     if not overlap:      # the fit of the frame runs behind its search on the same stream
                         out = e.fit_rmsd_batch(fr.unsqueeze(0), mass, ref, idx=idx, apply=True)
                         rms[s_] = float(out["rmsd"][0])
+                        fit_outs[s_] = out
                 if prev is not None:
                     r_ = e.search_resident_end(prev[1])
                     res[prev[0]] = (r_[0], None)
@@ -943,12 +1000,13 @@ def main():
                 for s_ in mine:
                     res[s_] = step(e, first + s_)
                     if not overlap:
-                        rms[s_] = res[s_][1]
-                    elif len(res[s_]) == 4:
-                        newest[k] = [(first + s_, res[s_][0], res[s_][2], res[s_][3])]     # the context's one result set
+                        rms[s_] = float(res[s_][1]["rmsd"][0])
+                        fit_outs[s_] = res[s_][1]
+                    newest[k] = [(first + s_, res[s_][0], res[s_][2], res[s_][3])]     # the context's one result set
             if overlap:
-                for s_, v in zip(mine, collect_fits(k, len(mine))):
-                    rms[s_] = v
+                for s_, out in zip(mine, collect_fits(k, len(mine))):
+                    rms[s_] = float(out["rmsd"][0])
+                    fit_outs[s_] = out
 
         if S == 1:
             context_loop(0)
@@ -969,6 +1027,8 @@ def main():
             if errors:
                 raise errors[0]
         last_results[:] = sorted(x for k in range(S) for x in newest[k])[-2:]
+        if count:
+            last_fit[:] = [first + count - 1, fit_outs[-1]]
         return [int(r[0]) for r in res], [float(v) for v in rms]
 
     # Untimed pre-heat: the same steps for --preheat seconds, so that the W warm-up steps and the K timed steps run at
@@ -989,13 +1049,38 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     pairs, rsum = sum(counts), sum(rms)
-    # ---- self-check of the timed code path (untimed, every run): the pair lists of the LAST TWO timed frames are still in
+    # ---- --dump-outputs: what a caller of the timed path holds after its last step, read before anything else runs on the
+    # engines - the pair list of the last frame (its count, a fixed seeded sample of the (i, j, d) records and order-sensitive
+    # checksums of both whole planes) and that frame's fit (R, t, RMSD, COM, gyration, the moved selection)
+    if args.dump_outputs and rank == 0 and K > 0:
+        fno, fit = last_fit
+        arrays = {}
+        mine = [x for x in last_results if x[0] == fno]
+        if mine:
+            _, cnt, pp, dp = mine[0]
+            m = min(cnt, DUMP_PAIR_SAMPLE)
+            pos = (np.sort((np.random.default_rng(20240607).random(m) * cnt).astype(np.int64)) if cnt > m
+                   else np.arange(cnt, dtype=np.int64))
+            pos_d = torch.from_numpy(pos).to(device)
+            arrays["pair_count"] = np.array([cnt])
+            arrays["pair_sample_index"] = pos
+            arrays["pair_sample_ij"] = torch.as_tensor(DevArray(pp, 2 * cnt, "<i4"), device=device).view(cnt, 2)[pos_d].cpu().numpy()
+            if dp:
+                arrays["pair_sample_dist"] = torch.as_tensor(DevArray(dp, cnt, "<f4"), device=device)[pos_d].cpu().numpy()
+            # (pairs low, pairs high, distances low, distances high) 32-bit halves
+            arrays["pair_plane_checksums"] = np.array([v for c in checksum_planes(cnt, pp, dp) for v in split_u64(c)])
+        for key in ("rmsd", "R", "t", "com", "gyration"):
+            arrays["fit_" + key] = fit[key][0]
+        moved = work[(K - 1) % S] if overlap else frames[fno % nres]
+        arrays["fit_moved_selection"] = moved[idx].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
+    # ---- self-check of the timed code path (untimed, --full): the pair lists of the LAST TWO timed frames are still in
     # the context's two result sets.  A fresh context recomputes those frames alone (one search at a time, fit on the same
     # stream): pair counts, order-sensitive 64-bit checksums of both result planes and the RMSD must agree.  --verify
     # additionally recomputes ALL frames' counts and RMSDs.
     t_chk = time.perf_counter()
     self_check = None
-    if overlap and K >= 2 * S and len(last_results) == 2 and (pipelined or S >= 2):
+    if args.full and overlap and K >= 2 * S and len(last_results) == 2 and (pipelined or S >= 2):
         self_check = True
         e3 = api.Engine(local_rank)
         for (fno, cnt, pp, dp) in last_results:
@@ -1013,47 +1098,49 @@ def main():
                       f"rmsd {r_timed!r} vs {r_alone!r}", file=sys.stderr)
         del e3
     self_check_s = time.perf_counter() - t_chk
-    # ---- a second, untimed pass of the same steps with HIP events around every kernel group (per-kernel times and
-    # the roofline of the fill kernel).  The events sit on each engine's own stream; with more than one context per GPU
-    # the other contexts' kernels overlap the bracketed ones, so this pass runs the contexts one frame at a time.
-    prof_engines = list(engines) + ([m for m in m_engines if m not in engines])
-    for e in prof_engines:
-        e.profile_enable(True)
-        e.profile_read()
-    KP = min(K, args.profile_steps)
-    S_timed, S = S, 1
-    run_steps(W, KP)
-    barrier()
     prof = None
-    for e in prof_engines:
-        p1 = e.profile_read()
-        e.profile_enable(False)
-        prof = p1 if prof is None else {k: (prof[k][0] + p1[k][0], prof[k][1] + p1[k][1]) for k in prof}
-    # ---- a third untimed pass: ONE event pair per frame around count + offsets + fill (molar_hip_profile_enable(ctx, 2)).  The
-    # pass above brackets every kernel group with its own pair, and an event record is a barrier packet of 5-10 us on the
-    # stream: its three entries read longer than the kernels run and used to add up to MORE than ms_per_step.
-    for e in engines:
-        e.profile_enable(2)
-        e.profile_read()
-    barrier()
-    t_span = time.perf_counter()
-    run_steps(W, KP)
-    barrier()
-    frame_span_pass_ms = (time.perf_counter() - t_span) * 1e3 / max(KP, 1)      # this pass's own period per step (its events included)
-    frame_span_ms, frame_span_n = 0.0, 0
-    for e in engines:
-        p2 = e.profile_read()["search_frame"]
-        e.profile_enable(False)
-        frame_span_ms += p2[0]
-        frame_span_n += p2[1]
-    S = S_timed
+    if args.full:
+        # ---- a second, untimed pass of the same steps with HIP events around every kernel group (per-kernel times and
+        # the roofline of the fill kernel).  The events sit on each engine's own stream; with more than one context per GPU
+        # the other contexts' kernels overlap the bracketed ones, so this pass runs the contexts one frame at a time.
+        prof_engines = list(engines) + ([m for m in m_engines if m not in engines])
+        for e in prof_engines:
+            e.profile_enable(True)
+            e.profile_read()
+        KP = min(K, args.profile_steps)
+        S_timed, S = S, 1
+        run_steps(W, KP)
+        barrier()
+        prof = None
+        for e in prof_engines:
+            p1 = e.profile_read()
+            e.profile_enable(False)
+            prof = p1 if prof is None else {k: (prof[k][0] + p1[k][0], prof[k][1] + p1[k][1]) for k in prof}
+        # ---- a third untimed pass: ONE event pair per frame around count + offsets + fill (molar_hip_profile_enable(ctx, 2)).  The
+        # pass above brackets every kernel group with its own pair, and an event record is a barrier packet of 5-10 us on the
+        # stream: its three entries read longer than the kernels run and used to add up to MORE than ms_per_step.
+        for e in engines:
+            e.profile_enable(2)
+            e.profile_read()
+        barrier()
+        t_span = time.perf_counter()
+        run_steps(W, KP)
+        barrier()
+        frame_span_pass_ms = (time.perf_counter() - t_span) * 1e3 / max(KP, 1)      # this pass's own period per step (its events included)
+        frame_span_ms, frame_span_n = 0.0, 0
+        for e in engines:
+            p2 = e.profile_read()["search_frame"]
+            e.profile_enable(False)
+            frame_span_ms += p2[0]
+            frame_span_n += p2[1]
+        S = S_timed
 
     # ---- a measured MODE, never `value`: the same steps with the resident searches filling the (i, j) plane only - the output
     # form of the reference's (usize, usize) consumers (distance_search.rs:14-20; SearchConnectivity, the membrane's patches):
     # 8 instead of 12 bytes per result and no square roots.  Checked: every frame's pair count against the timed run's, the
     # pair plane of the last frame by checksum against the full mode's.
     pairs_only = None
-    if overlap and pipelined and K >= 2 * S and not args.no_pairs_only:
+    if args.full and overlap and pipelined and K >= 2 * S and not args.no_pairs_only:
         for e in engines:
             e.search_resident_planes(False)
         K2 = min(K, 100)
@@ -1124,20 +1211,7 @@ def main():
 
     if rank == 0:
         frames_total = K * world
-        fill_ms, fill_n = prof["pair_fill"]
         p_per_frame = total_pairs / frames_total
-        alg_bytes = 12.0 * NATOMS + 12.0 * p_per_frame            # 12*N + 12*P per frame
-        fill_avg_ms = fill_ms / max(fill_n, 1)
-        achieved = alg_bytes / (fill_avg_ms * 1e-3) / 1e9 if fill_avg_ms > 0 else 0.0
-        traffic = None
-        tp = os.path.join(ROOT, "profiles", "traffic.json")        # HBM bytes per fill launch from rocprofv3 PMC passes
-        if os.path.exists(tp):
-            try:
-                traffic = json.load(open(tp)).get("pair_fill_hbm_bytes_per_launch")
-            except Exception:
-                traffic = None
-        copy_peak = eng.copy_bandwidth(1 << 30, 10)                # best float4 copy kernel, same run
-        write_peak = eng.write_bandwidth(1 << 30, 10)              # write-only float4 stream, same run
         line = {
             "metric": "frames/sec + Matom-pairs/sec, 1M-atom PBC neighbor search + RMSD fit",
             "value": frames_total / t,
@@ -1167,43 +1241,59 @@ def main():
             "per_rank_fps": [K / v for v in per_rank_s],
             # N > 1: the collective library's own view of the job (RCCL version, world size, every rank's device)
             "collective": comm,
-            "pairs_only": pairs_only_line,
             "verified_against_single_context": self_check_all if verified is None else (verified and self_check_all is not False),
             "verification": ("last two timed frames of every rank recomputed on a fresh single context after the timed region: "
                              "pair counts, order-sensitive 64-bit checksums of the pair and distance planes in HBM, RMSD (1e-6 rel)"
                              + ("; --verify: every frame's pair count and RMSD as well" if verified is not None else "")
                              if self_check_all is not None else
                              ("--verify: every frame's pair count and RMSD" if verified is not None else None)),
-            "self_check_s": self_check_s,
-            "kernel_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k != "search_frame"},
-            "kernel_ms_note": f"HIP-event times from a separate untimed pass of {KP} of the same steps on one context (events are "
-                              "not recorded inside the timed region); grid_build (side stream) and measure (second context) "
-                              "OVERLAP the search kernels, so the entries do not add up to ms_per_step",
-            # the same numbers sorted by what they mean for the frame period: only the first group adds up (to ms_per_step less
-            # ~0.05 ms of plan kernels and launch gaps); the second runs beside it and is stretched by the contention
-            "critical_stream_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k in ("pair_count", "offset_scan", "pair_fill")},
-            "overlapped_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k in ("grid_build", "measure")},
-            # count + offsets + fill of a frame between ONE pair of events (third pass): what the critical stream spends per frame
-            # besides the plan kernels (~0.02 ms) and the gaps between frames.  The pass is a separate one and carries its own event
-            # pair per frame (a few us): compare it with ITS period (critical_path_pass_ms_per_step, <= 1 by construction), not to the
-            # last digit with ms_per_step of the timed region
-            "critical_path_ms_per_frame": frame_span_ms / max(frame_span_n, 1),
-            "critical_path_pass_ms_per_step": frame_span_pass_ms,
-            "critical_path_frac_of_its_pass": (frame_span_ms / max(frame_span_n, 1)) / frame_span_pass_ms if frame_span_pass_ms else None,
-            "critical_path_source": f"one HIP-event pair per frame around count + offsets + fill, separate untimed pass of {KP} steps "
-                                    "(the per-class entries above carry one event pair EACH and read 5-10 us longer per class than the kernels run)",
-            "critical_path_sum_of_bracketed_classes_ms": sum(v[0] for k, v in prof.items() if k in ("pair_count", "offset_scan", "pair_fill")) / KP,
-            "roofline": {
-                "kernel": "pair_kernel<SINGLE,FILL>", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_source": "profiles/traffic.json (rocprofv3 PMC FETCH_SIZE/WRITE_SIZE passes, separate run of this command)",
-                "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": fill_avg_ms,
-                "end_to_end_frac": alg_bytes * frames_total / t / 1e9 / HBM_PEAK_GBS / world,
-                "copy_peak_measured": copy_peak, "frac_of_copy_peak": achieved / copy_peak if copy_peak > 0 else None,
-                "write_peak_measured": write_peak, "frac_of_write_peak": achieved / write_peak if write_peak > 0 else None,
-            },
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:       # what the headline does not need: event passes, roofline, pairs-only mode, CPU baseline
+            fill_ms, fill_n = prof["pair_fill"]
+            alg_bytes = 12.0 * NATOMS + 12.0 * p_per_frame            # 12*N + 12*P per frame
+            fill_avg_ms = fill_ms / max(fill_n, 1)
+            achieved = alg_bytes / (fill_avg_ms * 1e-3) / 1e9 if fill_avg_ms > 0 else 0.0
+            traffic = None
+            tp = os.path.join(ROOT, "profiles", "traffic.json")        # HBM bytes per fill launch from rocprofv3 PMC passes
+            if os.path.exists(tp):
+                try:
+                    traffic = json.load(open(tp)).get("pair_fill_hbm_bytes_per_launch")
+                except Exception:
+                    traffic = None
+            copy_peak = eng.copy_bandwidth(1 << 30, 10)                # best float4 copy kernel, same run
+            write_peak = eng.write_bandwidth(1 << 30, 10)              # write-only float4 stream, same run
+            line.update({
+                "pairs_only": pairs_only_line,
+                "self_check_s": self_check_s,
+                "kernel_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k != "search_frame"},
+                "kernel_ms_note": f"HIP-event times from a separate untimed pass of {KP} of the same steps on one context (events are "
+                                  "not recorded inside the timed region); grid_build (side stream) and measure (second context) "
+                                  "OVERLAP the search kernels, so the entries do not add up to ms_per_step",
+                # the same numbers sorted by what they mean for the frame period: only the first group adds up (to ms_per_step less
+                # ~0.05 ms of plan kernels and launch gaps); the second runs beside it and is stretched by the contention
+                "critical_stream_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k in ("pair_count", "offset_scan", "pair_fill")},
+                "overlapped_ms_per_frame": {k: v[0] / KP for k, v in prof.items() if k in ("grid_build", "measure")},
+                # count + offsets + fill of a frame between ONE pair of events (third pass): what the critical stream spends per frame
+                # besides the plan kernels (~0.02 ms) and the gaps between frames.  The pass is a separate one and carries its own event
+                # pair per frame (a few us): compare it with ITS period (critical_path_pass_ms_per_step, <= 1 by construction), not to the
+                # last digit with ms_per_step of the timed region
+                "critical_path_ms_per_frame": frame_span_ms / max(frame_span_n, 1),
+                "critical_path_pass_ms_per_step": frame_span_pass_ms,
+                "critical_path_frac_of_its_pass": (frame_span_ms / max(frame_span_n, 1)) / frame_span_pass_ms if frame_span_pass_ms else None,
+                "critical_path_source": f"one HIP-event pair per frame around count + offsets + fill, separate untimed pass of {KP} steps "
+                                        "(the per-class entries above carry one event pair EACH and read 5-10 us longer per class than the kernels run)",
+                "critical_path_sum_of_bracketed_classes_ms": sum(v[0] for k, v in prof.items() if k in ("pair_count", "offset_scan", "pair_fill")) / KP,
+                "roofline": {
+                    "kernel": "pair_kernel<SINGLE,FILL>", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": "profiles/traffic.json (rocprofv3 PMC FETCH_SIZE/WRITE_SIZE passes, separate run of this command)",
+                    "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": fill_avg_ms,
+                    "end_to_end_frac": alg_bytes * frames_total / t / 1e9 / HBM_PEAK_GBS / world,
+                    "copy_peak_measured": copy_peak, "frac_of_copy_peak": achieved / copy_peak if copy_peak > 0 else None,
+                    "write_peak_measured": write_peak, "frac_of_write_peak": achieved / write_peak if write_peak > 0 else None,
+                },
+            })
+        if args.full and not args.no_cpu_baseline and world == 1:
             f0 = frames[0].cpu().numpy()        # frame 0 was fitted in place during warm-up; any frame serves
             line["cpu_baseline"] = cpu_baseline(f0, ref.cpu().numpy(), box, mass.cpu().numpy(),
                                                 idx_np.astype(np.uint64))
@@ -1211,7 +1301,7 @@ def main():
     # ---- the two other BASELINE configs on the same clock (never `value`): short legs of --workload rdf (C4) and --workload
     # membrane (C5) with their own self-checks, attached to the line as `secondary`.  N = 1 only unless --secondary is given
     # (a failure inside a leg's collectives must not cost a multi-GPU run its headline line).
-    if (world == 1 and not args.no_secondary) or args.secondary:
+    if args.full and ((world == 1 and not args.no_secondary) or args.secondary):
         sec = secondary_legs(args, rank, local_rank, world, device, cdev)
         if rank == 0:
             line["secondary"] = sec

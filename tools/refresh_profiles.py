@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Turns the raw outputs of tools/profile_bench.sh (gpurun_out/$ROUND) into the committed files of profiles/."""
+"""Turns the raw outputs of tools/profile_bench.sh ($OUT, default profile_out/$ROUND) into the committed files of profiles/."""
 import collections, csv, glob, json, os, shutil
 TAG = os.environ.get("ROUND", "r02")
-R = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", TAG)
+R = os.environ.get("OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profile_out", TAG)
 P = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
 def newest(pat):
     return max(glob.glob(pat, recursive=True), key=os.path.getmtime)
