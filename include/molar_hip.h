@@ -494,6 +494,9 @@ int molar_hip_membrane_smooth_curvature(size_t nlipids, const uint8_t *valid, co
  * among the valid lipids' head markers and the patch lists in push order (compute_patches, lib.rs:539-558) ->
  * compute_initial_normals (:456-505, including the second pass that updates normals in place in lipid order) ->
  * max_smooth_iter iterations of smooth (:661-812) -> lipid_tail_order of every tail with its lipid's normal (:435-443).
+ * With the neighbour-shell options (molar_hip_membrane_plan_set_shells, lib.rs:562-621) the chain also covers
+ * patches_from_nth_shell - a first smoothing pass on the search patches, the patches rebuilt as the n-th Voronoi shell on
+ * the device, then max_smooth_iter passes on them - and smooth_curvature after the passes.
  * The stages are the ones behind molar_hip_unwrap_simple_batch, _center_batch, _search_*, _membrane_patches_from_pairs,
  * _membrane_initial_normals, _membrane_smooth and _lipid_tail_order, and give the same bits; what differs is that the
  * pair list, the patches and every per-lipid array stay in device memory between them.
@@ -504,10 +507,9 @@ int molar_hip_membrane_smooth_curvature(size_t nlipids, const uint8_t *valid, co
  *     begin(frame k+1); end(frame k); fetch / use the device view of k; ...
  * so the host work of a frame hides behind the kernels of the one before it.  Frames are chained on the context's
  * stream in begin order, `valid` included.  The result of a frame stays readable until the second _begin after its own.
- * Sizes that vary with the frame (pairs, patch entries) are provisioned from earlier frames; a frame that outgrows
- * them is repeated inside _end, transparently.  Options outside this entry (patches from the n-th neighbour shell,
- * curvature smoothing over shells: lib.rs:562-621) stay with the staged calls.  All pointers of the description are
- * host memory and are copied at creation. */
+ * Sizes that vary with the frame (pairs, patch entries, shell-patch entries) are provisioned from earlier frames; a
+ * frame that outgrows them is repeated inside _end, transparently.  All pointers of the description are host memory and
+ * are copied at creation. */
 typedef struct molar_hip_membrane_plan molar_hip_membrane_plan;
 typedef struct {
     size_t natoms, nlipids;
@@ -565,6 +567,14 @@ void molar_hip_membrane_plan_destroy(molar_hip_membrane_plan *plan);
  * a ticket pending the call changes nothing and returns MOLAR_HIP_ERR_INVALID_ARGUMENT - end the frames first (the flags
  * feed the kernels of a frame from its first launch on). */
 int molar_hip_membrane_plan_set_valid(molar_hip_membrane_plan *plan, const uint8_t *valid);
+/* n_shells_patch / n_shells_smoothing of MembraneOptions (molar_membrane/src/lib.rs:53-85); 0 / 0 (the default) = the chain
+ * as before.  With n_shells_patch > 0 a frame smooths once on the search patches, rebuilds every valid lipid's patch as its
+ * n-th neighbour shell (the definition of molar_hip_membrane_nth_shell_patches, ids ascending; invalid lipids keep their
+ * patch), re-slots the state from zero and smooths max_smooth_iter more times; with n_shells_smoothing > 0 the curvatures are
+ * averaged over the n-th shell of the final patches (molar_hip_membrane_smooth_curvature).  Same bits as those staged calls.
+ * The view and the fetch then report the FINAL patch lists (patch_entries = entries of the shell patches).  No frame may be in
+ * flight (as for _plan_set_valid): with a ticket pending the call changes nothing and returns ERR_INVALID_ARGUMENT. */
+int molar_hip_membrane_plan_set_shells(molar_hip_membrane_plan *plan, size_t n_shells_patch, size_t n_shells_smoothing);
 /* xyz: float[natoms][3], device memory (unwrapped in place, and read until the frame ends) or host memory (uploaded;
  * the unwrapped frame is written back before _begin returns).  box9: column-major box matrix.  Returns with a ticket
  * (0 or 1) without waiting for the frame. */

@@ -728,6 +728,11 @@ class MembraneFrames {
     ~MembraneFrames() { molar_hip_membrane_plan_destroy(plan_); }      // waits for the frames in flight
     // reset_valid_lipids (lib.rs:269-273) with nullptr, or the caller's flags; no frame may be in flight
     void set_valid(const uint8_t *valid) { check(molar_hip_membrane_plan_set_valid(plan_, valid)); }
+    // n_shells_patch / n_shells_smoothing of MembraneOptions (lib.rs:53-85) for the frames pushed from now on; (0, 0) = none.
+    // No frame may be in flight (finish() first)
+    void set_shells(size_t n_shells_patch, size_t n_shells_smoothing) {
+        check(molar_hip_membrane_plan_set_shells(plan_, n_shells_patch, n_shells_smoothing));
+    }
     // xyz: float[natoms][3] in device memory (unwrapped in place, read until the frame has been handed back) or host memory
     std::optional<molar_hip_membrane_view> push(float *xyz, const PeriodicBox &pbox) {
         int32_t t = -1;

@@ -172,6 +172,7 @@ SYMBOLS = {
     "molar_hip_membrane_plan_create": (_I, [_P, _P, _P]),
     "molar_hip_membrane_plan_destroy": (None, [_P]),
     "molar_hip_membrane_plan_set_valid": (_I, [_P, _P]),
+    "molar_hip_membrane_plan_set_shells": (_I, [_P, _SZ, _SZ]),
     "molar_hip_membrane_frame_begin": (_I, [_P, _P, _P, _P]),
     "molar_hip_membrane_frame_end": (_I, [_P, _I, _P]),
     "molar_hip_membrane_frame_fetch": (_I, [_P, _I, _P]),

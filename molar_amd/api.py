@@ -1203,6 +1203,11 @@ class MembranePlan:
         v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
         check(self.lib.molar_hip_membrane_plan_set_valid(self.handle, None if v is None else v.ctypes.data))
 
+    def set_shells(self, n_shells_patch=0, n_shells_smoothing=0):
+        """n_shells_patch / n_shells_smoothing of MembraneOptions (lib.rs:53-85) for the frames to come; (0, 0) = no shells.
+        No frame may be in flight."""
+        check(self.lib.molar_hip_membrane_plan_set_shells(self.handle, int(n_shells_patch), int(n_shells_smoothing)))
+
     def begin(self, xyz, box):
         """Enqueue one frame; xyz: float32 [N,3] torch CUDA tensor (unwrapped in place) or numpy array (unwrapped in place
         as well, through a copy).  Returns the ticket."""

@@ -201,6 +201,7 @@ struct molar_hip_ctx {
     } tickets[2];
     int next_ticket = 0;
     bool resident_no_dist = false;          // molar_hip_search_resident_planes: the resident searches fill the (i, j) plane only
+    bool grid_drop_nonfinite = false;       // the grid being built leaves atoms with a non-finite coordinate out (search_resident_enqueue)
     unsigned long long search_serial = 0;   // counts resident searches enqueued on this context
     // Resident searches launch their count and fill passes over the slots the plan of the SEARCH BEFORE came to (+ 3 % + 512)
     // instead of the host's bound (14 N / 64 + entries: 13 % above the real count on the headline frame - 3.7e4 workgroups per

@@ -920,13 +920,17 @@ extern "C" int molar_hip_membrane_smooth_curvature(size_t K, const uint8_t *vali
 
 namespace {
 
-struct FrameInfo {                 // device block of a frame, read back with its results
+// (16-byte multiple: the memset that clears it at the start of a frame stays ONE fill launch; the host copy at H_INFO holds 64 bytes)
+struct alignas(16) FrameInfo {     // device block of a frame, read back with its results
     unsigned long long npairs;     // pairs of the marker search taken into the patches
     unsigned long long E;          // patch entries (2 * npairs)
     int overflow;                  // more pairs than the search buffers, or more entries than the patch arrays, hold
     int st_center, st_order;       // MOLAR_HIP_ERR_* raised by the marker / order kernels
     int changed;                   // the smoothing of this frame dropped a lipid (the valid flags it leaves differ from those it found)
+    int shell_overflow;            // the shell patches outgrew their arrays (Es_need entries): _end repeats the frame with more room
+    unsigned long long Es, Es_need;  // entries of the shell patches (n_shells_patch > 0)
 };
+static_assert(sizeof(FrameInfo) % 16 == 0 && sizeof(FrameInfo) <= 64, "FrameInfo: one aligned fill, 64 bytes of host room");
 
 // first kernel of a frame's B part: the valid flags as this frame finds them are remembered (or, on a repeat of B after
 // its buffers were grown, put back), markers split into their arrays, the search input made
@@ -1228,6 +1232,373 @@ float half_pi_cos_threshold() {
     return hi;
 }
 
+// ---- neighbour shells on the device (patches_from_nth_shell / smooth_curvature, lib.rs:562-621): the definitions of
+// nth_shell_of above - a valid lipid's set starts as its Voronoi neighbours and is widened (n - 2) times by the neighbours of
+// every member; a member's neighbour count is clamped to its slots; members ascend.  Widening by the members added last is
+// the same as widening by all of them (the neighbours of the older ones are in the set already).
+//   k_shell_patches / k_curv_shells  sixteen lanes per lipid, the set in LDS (insertion order, deduplicated there), then
+//                                     sorted by rank; a set of more than SH_CAP members flags the lipid (redo) for
+//   k_shell_wide                      one workgroup per flagged lipid, the sets as K-bit maps in HBM, ascending = bit order.
+constexpr uint32_t SH_G = 16;            // lanes per lipid
+constexpr uint32_t SH_CAP = 128;         // members of a shell the LDS path holds (a flat bilayer: 6 / 19 / 37 for n <= 2 / 3 / 4)
+constexpr uint32_t SH_WIDE_WG = 128;     // workgroups of the fallback, three K-bit maps each
+
+struct ShellGraph {
+    uint32_t K, n;                       // lipids, n_shells (>= 1)
+    const uint64_t *slot_off;            // [K+1] the patch lists neib is slotted by
+    const uint32_t *nvert;
+    const uint64_t *neib;
+    const uint8_t *valid;
+};
+
+// lipid l's neighbour count, clamped to its slots (an invalid member keeps what an earlier pass left there); s0: first slot
+__device__ __forceinline__ uint32_t shell_nb(const ShellGraph &G, uint32_t l, uint64_t &s0) {
+    const uint64_t a = G.slot_off[l], b = G.slot_off[l + 1];
+    s0 = a + 4ull * l;
+    const uint64_t cap = b - a + 4ull;
+    const uint32_t nv = G.nvert[l];
+    return nv < cap ? nv : (uint32_t)cap;
+}
+
+__device__ __forceinline__ uint32_t wave_max16(uint32_t v) {     // the largest of the four groups' values, in every lane
+    v = max(v, (uint32_t)__shfl_xor((int)v, 16));
+    v = max(v, (uint32_t)__shfl_xor((int)v, 32));
+    return v;
+}
+
+// The members of lipid i's shell into mem[0 .. cnt) by the sixteen lanes of group `gl` (first lane); `live`: the group has a
+// lipid.  Returns cnt, or SH_CAP + 1 when the set does not fit.  Loops run over the largest count of the wave, so every
+// shuffle, ballot and barrier is reached by all 64 lanes.
+__device__ uint32_t shell_build(const ShellGraph &G, uint32_t i, bool live, uint32_t sub, uint32_t gl, uint32_t *mem) {
+    uint32_t cnt = 0;
+    bool over = false;
+    // one batch: every lane offers one id; it joins if it is neither in the set nor offered by a lower lane of the batch
+    auto offer = [&](uint64_t id) {
+        bool has = id < G.K && !over;
+        const uint32_t cand = (uint32_t)id;
+        for (uint32_t q = 0; has && q < cnt; ++q) has = mem[q] != cand;
+        const int h0 = has ? 1 : 0;
+#pragma unroll
+        for (uint32_t j = 0; j < SH_G; ++j) {
+            const uint32_t oc = (uint32_t)__shfl((int)cand, (int)j, (int)SH_G);
+            const int oh = __shfl(h0, (int)j, (int)SH_G);
+            has = has && !(j < sub && oh && oc == cand);
+        }
+        const uint32_t m = (uint32_t)(__ballot(has) >> gl) & 0xffffu;
+        const uint32_t pos = cnt + (uint32_t)__builtin_popcount(m & ((1u << sub) - 1u));
+        if (has && pos < SH_CAP) mem[pos] = cand;
+        cnt += (uint32_t)__builtin_popcount(m);
+        over = over || cnt > SH_CAP;
+        __syncthreads();
+    };
+    uint64_t s0 = 0;
+    const uint32_t nv = live ? shell_nb(G, i, s0) : 0u;
+    const uint32_t r0 = wave_max16((nv + SH_G - 1u) / SH_G);
+    for (uint32_t r = 0; r < r0; ++r) {
+        const uint32_t k = r * SH_G + sub;
+        offer(k < nv ? G.neib[s0 + k] : ~0ull);
+    }
+    uint32_t a = 0, b = cnt;                 // the members the last round added
+    for (uint32_t sh = 2; sh < G.n; ++sh) {
+        const bool more = live && !over && b > a;
+        if (!__ballot(more)) break;          // every set of the wave is complete (or too large)
+        const uint32_t len = more ? b - a : 0u;
+        const uint32_t wl = wave_max16(len);
+        for (uint32_t q = 0; q < wl; ++q) {
+            const bool on = q < len && !over;
+            uint64_t s1 = 0;
+            const uint32_t nl = on ? shell_nb(G, mem[a + q], s1) : 0u;
+            const uint32_t wr = wave_max16((nl + SH_G - 1u) / SH_G);
+            for (uint32_t r = 0; r < wr; ++r) {
+                const uint32_t k = r * SH_G + sub;
+                offer(k < nl ? G.neib[s1 + k] : ~0ull);
+            }
+        }
+        a = b;
+        b = cnt;
+    }
+    return over ? SH_CAP + 1u : cnt;
+}
+
+// mem[0 .. cnt) (distinct ids) ascending into srt, by rank
+__device__ __forceinline__ void shell_sort(const uint32_t *mem, uint32_t cnt, uint32_t sub, uint32_t *srt) {
+    for (uint32_t q = sub; q < cnt; q += SH_G) {
+        const uint32_t v = mem[q];
+        uint32_t r = 0;
+        for (uint32_t p = 0; p < cnt; ++p) r += mem[p] < v ? 1u : 0u;
+        srt[r] = v;
+    }
+}
+
+// patches_from_nth_shell, first step: per lipid the length of its new list (valid: its shell, sorted into `scratch`, SH_CAP
+// ids per lipid; not valid: the patch it has) or the redo flag.  Also zeroes `zero` (degrees and cursors of the transpose).
+__global__ __launch_bounds__(64) void k_shell_patches(ShellGraph G, const uint64_t *__restrict__ poff, uint32_t *__restrict__ scratch,
+                                                      uint32_t *__restrict__ cnt_out, uint8_t *__restrict__ redo, uint32_t *__restrict__ zero,
+                                                      uint32_t nzero) {
+    __shared__ uint32_t mem_s[64 / SH_G][SH_CAP], srt_s[64 / SH_G][SH_CAP];
+    const uint32_t lane = threadIdx.x, g = lane / SH_G, sub = lane % SH_G;
+    const uint32_t i = blockIdx.x * (64u / SH_G) + g;
+    if (blockIdx.x * 64u + lane < nzero) zero[blockIdx.x * 64u + lane] = 0u;
+    const bool in = i < G.K, live = in && G.valid[i];
+    const uint32_t c = shell_build(G, i, live, sub, g * SH_G, mem_s[g]);
+    const bool fits = live && c <= SH_CAP;
+    if (fits) shell_sort(mem_s[g], c, sub, srt_s[g]);
+    __syncthreads();
+    if (!in) return;
+    if (!live) {                                     // not touched by the reference loop: the lipid keeps its patch
+        if (sub == 0u) { cnt_out[i] = (uint32_t)(poff[i + 1] - poff[i]); redo[i] = 0; }
+        return;
+    }
+    if (!fits) {
+        if (sub == 0u) { cnt_out[i] = 0u; redo[i] = 1; }
+        return;
+    }
+    for (uint32_t q = sub; q < c; q += SH_G) scratch[(size_t)i * SH_CAP + q] = srt_s[g][q];
+    if (sub == 0u) { cnt_out[i] = c; redo[i] = 0; }
+}
+
+// exclusive scan of cnt[0 .. K) into spoff[0 .. K] (one workgroup).  A total above `cap` leaves every list empty (the frame's
+// kernels behind it then stay inside their buffers) and asks _end for a repeat with more room (FrameInfo::shell_overflow).
+__global__ __launch_bounds__(1024) void k_shell_scan(uint32_t K, const uint32_t *__restrict__ cnt, uint64_t *__restrict__ spoff,
+                                                     unsigned long long cap, FrameInfo *__restrict__ info) {
+    __shared__ unsigned long long wsum[16];
+    __shared__ unsigned long long carry_s;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry_s = 0ull;
+    __syncthreads();
+    for (uint32_t base = 0; base < K + 1u; base += 1024u) {
+        const uint32_t i = base + threadIdx.x;
+        const unsigned long long v = i < K ? cnt[i] : 0ull;
+        unsigned long long x = v;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long y = __shfl_up(x, o, 64);
+            if ((int)lane >= o) x += y;
+        }
+        if (lane == 63u) wsum[wave] = x;
+        __syncthreads();
+        unsigned long long before = carry_s;
+        for (uint32_t w = 0; w < wave; ++w) before += wsum[w];
+        if (i < K + 1u) spoff[i] = before + x - v;
+        __syncthreads();
+        if (threadIdx.x == 1023u) carry_s = before + x;
+        __syncthreads();
+    }
+    const unsigned long long total = carry_s;
+    if (total > cap) {
+        for (uint32_t i = threadIdx.x; i < K + 1u; i += 1024u) spoff[i] = 0ull;
+        if (threadIdx.x == 0) { info->Es = 0ull; info->Es_need = total; info->shell_overflow = 1; }
+    } else if (threadIdx.x == 0) {
+        info->Es = total;
+    }
+}
+
+// second step: the lists of the lipids the LDS path did (and of the invalid ones) into the CSR, the owner of every entry, and
+// the entries per target lipid (rdeg, for the transpose)
+__global__ __launch_bounds__(256) void k_shell_fill(uint32_t K, const uint8_t *__restrict__ valid, const uint8_t *__restrict__ redo,
+                                                    const uint64_t *__restrict__ poff, const uint64_t *__restrict__ pids,
+                                                    const uint32_t *__restrict__ scratch, const uint64_t *__restrict__ spoff,
+                                                    uint64_t *__restrict__ spids, uint32_t *__restrict__ sowner, uint32_t *__restrict__ rdeg) {
+    const uint32_t i = blockIdx.x * 16u + (threadIdx.x >> 4), sub = threadIdx.x & 15u;
+    if (i >= K || redo[i]) return;
+    const uint64_t s0 = spoff[i];
+    const uint32_t n = (uint32_t)(spoff[i + 1] - s0);
+    const bool v = valid[i] != 0;
+    for (uint32_t q = sub; q < n; q += 16u) {
+        const uint64_t id = v ? (uint64_t)scratch[(size_t)i * SH_CAP + q] : pids[poff[i] + q];
+        spids[s0 + q] = id;
+        sowner[s0 + q] = i;
+        atomicAdd(&rdeg[id], 1u);
+    }
+}
+
+// The fallback: one workgroup per flagged lipid (grid-stride), its set S, the last round's additions F and the round's new
+// ids N as K-bit maps in the workgroup's share of `maps` (accessed with device-scope atomics: other waves of the workgroup
+// read what one wrote).  mode 0: count into cnt_out; 1: the ids, ascending, into the CSR (+ owner, rdeg); 2: the curvature
+// average of smooth_curvature, summed by one lane in ascending id.
+struct WideArgs {
+    ShellGraph G;
+    const uint8_t *redo;
+    uint32_t *maps;                      // [gridDim.x][3][W]
+    uint32_t W;
+    int mode;
+    uint32_t *cnt_out;                                       // mode 0
+    const uint64_t *spoff;                                   // mode 1
+    uint64_t *spids;
+    uint32_t *sowner, *rdeg;
+    const float *mean0, *gauss0;                             // mode 2
+    float *mean, *gauss;
+};
+__device__ __forceinline__ uint32_t map_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void map_st(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(256) void k_shell_wide(WideArgs A) {
+    __shared__ uint32_t pre_s[256];
+    __shared__ uint32_t total_s;
+    const ShellGraph &G = A.G;
+    const uint32_t t = threadIdx.x, W = A.W;
+    uint32_t *S = A.maps + (size_t)blockIdx.x * 3u * W, *F = S + W, *N = F + W;
+    for (uint32_t i = blockIdx.x; i < G.K; i += gridDim.x) {
+        if (!A.redo[i]) continue;
+        for (uint32_t w = t; w < W; w += 256u) { map_st(S + w, 0u); map_st(F + w, 0u); }
+        __syncthreads();
+        {
+            uint64_t s0;
+            const uint32_t nv = shell_nb(G, i, s0);
+            for (uint32_t k = t; k < nv; k += 256u) {
+                const uint64_t id = G.neib[s0 + k];
+                if (id < G.K) {
+                    atomicOr(S + (id >> 5), 1u << (id & 31u));
+                    atomicOr(F + (id >> 5), 1u << (id & 31u));
+                }
+            }
+        }
+        __syncthreads();
+        for (uint32_t sh = 2; sh < G.n; ++sh) {
+            for (uint32_t w = t; w < W; w += 256u) map_st(N + w, 0u);
+            __syncthreads();
+            for (uint32_t w = t; w < W; w += 256u) {
+                uint32_t f = map_ld(F + w);
+                while (f) {
+                    const uint32_t l = w * 32u + (uint32_t)__builtin_ctz(f);
+                    f &= f - 1u;
+                    uint64_t s1;
+                    const uint32_t nl = shell_nb(G, l, s1);
+                    for (uint32_t k = 0; k < nl; ++k) {
+                        const uint64_t id = G.neib[s1 + k];
+                        if (id < G.K && !((map_ld(S + (id >> 5)) >> (id & 31u)) & 1u)) atomicOr(N + (id >> 5), 1u << (id & 31u));
+                    }
+                }
+            }
+            __syncthreads();
+            int any = 0;
+            for (uint32_t w = t; w < W; w += 256u) {
+                const uint32_t s = map_ld(S + w), nw = map_ld(N + w) & ~s;
+                map_st(F + w, nw);
+                map_st(S + w, s | nw);
+                any |= nw != 0u;
+            }
+            if (!__syncthreads_or(any)) break;
+        }
+        if (A.mode == 2) {                   // smooth_curvature (lib.rs:584-621): host order of additions
+            if (t == 0) {
+                float m = 0.0f, g = 0.0f;
+                uint32_t n_valid = 0;
+                for (uint32_t w = 0; w < W; ++w) {
+                    uint32_t s = map_ld(S + w);
+                    while (s) {
+                        const uint32_t id = w * 32u + (uint32_t)__builtin_ctz(s);
+                        s &= s - 1u;
+                        if (!G.valid[id]) continue;
+                        m += A.mean0[id];
+                        g += A.gauss0[id];
+                        ++n_valid;
+                    }
+                }
+                A.mean[i] = (A.mean0[i] + m) / (float)(n_valid + 1u);
+                A.gauss[i] = (A.gauss0[i] + g) / (float)(n_valid + 1u);
+            }
+            __syncthreads();
+            continue;
+        }
+        // count (mode 0) or ascending fill (mode 1), 256 words a round
+        if (t == 0) total_s = 0u;
+        __syncthreads();
+        const uint64_t base = A.mode == 1 ? A.spoff[i] : 0ull;
+        const uint64_t room = A.mode == 1 ? A.spoff[i + 1] - base : 0ull;
+        for (uint32_t w0 = 0; w0 < W; w0 += 256u) {
+            const uint32_t w = w0 + t;
+            uint32_t s = w < W ? map_ld(S + w) : 0u;
+            pre_s[t] = (uint32_t)__builtin_popcount(s);
+            __syncthreads();
+            if (t == 0) {                    // serial scan of 256 counts (the fallback's rare lipids only)
+                uint32_t run = total_s;
+                for (uint32_t k = 0; k < 256u; ++k) { const uint32_t c = pre_s[k]; pre_s[k] = run; run += c; }
+                total_s = run;
+            }
+            __syncthreads();
+            if (A.mode == 1) {
+                uint64_t at = pre_s[t];
+                while (s) {
+                    const uint32_t id = w * 32u + (uint32_t)__builtin_ctz(s);
+                    s &= s - 1u;
+                    if (at < room) {
+                        A.spids[base + at] = id;
+                        A.sowner[base + at] = i;
+                        atomicAdd(&A.rdeg[id], 1u);
+                    }
+                    ++at;
+                }
+            }
+            __syncthreads();
+        }
+        if (A.mode == 0 && t == 0) A.cnt_out[i] = total_s;
+        __syncthreads();
+    }
+}
+
+// the transpose of the shell lists for k_membrane_average (which needs, for lipid t, the entries q that hold t in the order of
+// q = (owner lipid, position in its list)): entries bucketed per target in any order, then ranked by q inside the bucket
+__global__ __launch_bounds__(256) void k_rev_bucket(const FrameInfo *__restrict__ info, const uint64_t *__restrict__ spids,
+                                                    const uint32_t *__restrict__ roff, uint32_t *__restrict__ cursor,
+                                                    uint32_t *__restrict__ bucket) {
+    const unsigned long long q = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (q >= info->Es) return;
+    const uint64_t t = spids[q];
+    bucket[roff[t] + atomicAdd(&cursor[t], 1u)] = (uint32_t)q;
+}
+
+__global__ __launch_bounds__(256) void k_rev_sort(uint32_t K, const uint32_t *__restrict__ roff, const uint32_t *__restrict__ bucket,
+                                                  const uint32_t *__restrict__ sowner, uint32_t *__restrict__ rev_entry,
+                                                  uint32_t *__restrict__ rev_owner) {
+    const uint32_t t = blockIdx.x * 16u + (threadIdx.x >> 4), sub = threadIdx.x & 15u;
+    if (t >= K) return;
+    const uint32_t a = roff[t], b = roff[t + 1];
+    for (uint32_t e = a + sub; e < b; e += 16u) {
+        const uint32_t q = bucket[e];
+        uint32_t r = 0;
+        for (uint32_t f = a; f < b; ++f) r += bucket[f] < q ? 1u : 0u;
+        rev_entry[a + r] = q;
+        rev_owner[a + r] = sowner[q];
+    }
+}
+
+// smooth_curvature (lib.rs:584-621) for the lipids whose shell fits SH_CAP: members gathered by the group, then added by one
+// lane in ascending id, in f32, from the values before the call (mean0 / gauss0), as the host loop does
+__global__ __launch_bounds__(64) void k_curv_shells(ShellGraph G, const float *__restrict__ mean0, const float *__restrict__ gauss0,
+                                                    float *__restrict__ mean, float *__restrict__ gauss, uint8_t *__restrict__ redo) {
+    __shared__ uint32_t mem_s[64 / SH_G][SH_CAP], srt_s[64 / SH_G][SH_CAP];
+    __shared__ float m_s[64 / SH_G][SH_CAP], g_s[64 / SH_G][SH_CAP];
+    const uint32_t lane = threadIdx.x, g = lane / SH_G, sub = lane % SH_G;
+    const uint32_t i = blockIdx.x * (64u / SH_G) + g;
+    const bool in = i < G.K, live = in && G.valid[i];
+    const uint32_t c = shell_build(G, i, live, sub, g * SH_G, mem_s[g]);
+    const bool fits = live && c <= SH_CAP;
+    if (fits) shell_sort(mem_s[g], c, sub, srt_s[g]);
+    __syncthreads();
+    if (fits)
+        for (uint32_t q = sub; q < c; q += SH_G) {
+            const uint32_t id = srt_s[g][q];
+            const bool ok = G.valid[id] != 0;
+            mem_s[g][q] = ok ? 1u : 0u;
+            m_s[g][q] = ok ? mean0[id] : 0.0f;
+            g_s[g][q] = ok ? gauss0[id] : 0.0f;
+        }
+    __syncthreads();
+    if (!in) return;
+    if (sub == 0u) redo[i] = live && !fits ? 1 : 0;
+    if (!fits || sub != 0u) return;
+    float m = 0.0f, gg = 0.0f;
+    uint32_t n_valid = 0;
+    for (uint32_t q = 0; q < c; ++q) {
+        if (!mem_s[g][q]) continue;
+        m += m_s[g][q];
+        gg += g_s[g][q];
+        ++n_valid;
+    }
+    mean[i] = (mean0[i] + m) / (float)(n_valid + 1u);
+    gauss[i] = (gauss0[i] + gg) / (float)(n_valid + 1u);
+}
+
 struct Blob2 {
     size_t size = 0;
     size_t take(size_t bytes) {
@@ -1241,12 +1612,18 @@ struct FrameLayout {       // byte offsets inside a frame slot's device blob, fo
     size_t info, roff, normals0, valid_prev, pids32;       // (one block, see frame_layout)
     size_t mk, head, mid, tail, head_search, valid_out, thv, poff, pids, owner, rev_entry, rev_owner;
     size_t zero_begin, s_head, s_normals, coefs, pcurv, pdirs, area, nvert, neib, voro, fitted, zero_end, mean, gauss;
-    size_t saved, vwork, pwork, tnorm, order, bytes;
+    size_t saved, vwork, pwork, tnorm, order;
+    // neighbour shells (Scap > 0): the shell patches (Scap entries), their transpose, the build's work, the curvature snapshot
+    size_t spoff, spids, sowner, srev_off, srev_entry, srev_owner, sbucket, stmp, scnt, sdeg, sredo, sscratch, mean0, maps;
+    size_t bytes;
 };
 
-FrameLayout frame_layout(size_t K, size_t Ecap, size_t ntails, size_t norder) {
+uint32_t shell_map_words(size_t K) { return (uint32_t)((K + 31) / 32); }
+
+FrameLayout frame_layout(size_t K, size_t Ecap, size_t ntails, size_t norder, size_t Scap = 0) {
     FrameLayout L{};
     Blob2 B;
+    Ecap = std::max(Ecap, Scap);          // the slotted state follows whichever patch lists are longer
     const size_t slots = Ecap + 4 * K;
     // [info | roff | normals0 | valid_prev | pids32]: what the host pass of the normals reads, brought over in one copy
     L.info = B.take(sizeof(FrameInfo));
@@ -1265,6 +1642,14 @@ FrameLayout frame_layout(size_t K, size_t Ecap, size_t ntails, size_t norder) {
     L.mean = B.take(K * 4); L.gauss = B.take(K * 4);
     L.saved = B.take(K * 12); L.vwork = B.take(slots * 16); L.pwork = B.take(Ecap * 16 + 16);
     L.tnorm = B.take(ntails * 12); L.order = B.take(norder * 4 + 16);
+    if (Scap) {
+        L.spoff = B.take((K + 1) * 8); L.spids = B.take(Scap * 8); L.sowner = B.take(Scap * 4);
+        L.srev_off = B.take((K + 1) * 4); L.srev_entry = B.take(Scap * 4); L.srev_owner = B.take(Scap * 4); L.sbucket = B.take(Scap * 4);
+        L.stmp = B.take((K + 1) * 8); L.scnt = B.take(K * 4); L.sdeg = B.take((2 * K + 1) * 4); L.sredo = B.take(K);
+        L.sscratch = B.take(K * SH_CAP * 4);
+        L.mean0 = B.take(L.gauss - L.mean + K * 4);
+        L.maps = B.take((size_t)std::min<size_t>(K, SH_WIDE_WG) * 3 * shell_map_words(K) * 4);
+    }
     L.bytes = B.size;
     return L;
 }
@@ -1297,6 +1682,8 @@ struct molar_hip_membrane_plan {
     DevBuf valid;                 // [K]
     DevBuf work;                  // deg[K+1] | cursor[K] | t_ord / t_oth / t_grp [Ecap]
     size_t Ecap = 0;              // patch entries the slot blobs and `work` are laid out for
+    uint32_t shells_patch = 0, shells_smooth = 0;   // n_shells_patch / n_shells_smoothing (molar_hip_membrane_plan_set_shells)
+    size_t Scap = 0;              // shell-patch entries the slot blobs are laid out for (0 while no shell option was ever set)
     hipStream_t copy_stream = nullptr;
     void *h_fetch = nullptr;      // pinned staging of molar_hip_membrane_frame_fetch
     size_t h_fetch_cap = 0;
@@ -1306,6 +1693,8 @@ struct molar_hip_membrane_plan {
         DevBuf xyz_stage;         // a frame handed over in host memory is staged here
         FrameLayout lay{};
         size_t Ecap = 0;
+        size_t Scap = 0;          // (0: the layout has no shell arrays)
+        uint32_t shp = 0, shs = 0;   // the shell options of the frame in this slot
         void *h = nullptr;        // pinned: 16 bytes of search sizes | FrameInfo at the end of the frame
         void *h_mid = nullptr;    // pinned: what the host pass reads (roff | n1 | valid_prev | pids32) and writes (n2)
         size_t h_mid_cap = 0;
@@ -1334,11 +1723,15 @@ constexpr size_t H_SIZES = 0, H_INFO = 64, H_BYTES = 128;
 size_t mid_bytes(const FrameLayout &L, size_t Ecap) { return L.pids32 + Ecap * 4; }
 size_t mid_n2(const FrameLayout &L, size_t Ecap) { return (mid_bytes(L, Ecap) + 255) & ~size_t(255); }
 
+// shell arrays only for frames that use them: without shell options the layout is the one the chain always had
+size_t slot_scap(const molar_hip_membrane_plan *P, const molar_hip_membrane_plan::Slot &S) { return S.shp || S.shs ? P->Scap : 0; }
+
 int ensure_capacity(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S) {
-    if (S.Ecap == P->Ecap && S.blob.p) return 0;
-    S.lay = frame_layout(P->K, P->Ecap, P->ntails, P->norder);
+    if (S.Ecap == P->Ecap && S.Scap == slot_scap(P, S) && S.blob.p) return 0;
+    S.lay = frame_layout(P->K, P->Ecap, P->ntails, P->norder, slot_scap(P, S));
     MH_TRY(S.blob.reserve(S.lay.bytes));
     S.Ecap = P->Ecap;
+    S.Scap = slot_scap(P, S);
     const size_t need = mid_n2(S.lay, P->Ecap) + P->K * 12;
     if (need > S.h_mid_cap) {
         if (S.h_mid) (void)hipHostFree(S.h_mid);
@@ -1385,7 +1778,7 @@ int enqueue_b(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
     molar_hip_ctx *c = P->c;
     const size_t K = P->K;
     const uint32_t K32 = (uint32_t)K;
-    if (S.Ecap != P->Ecap) {
+    if (S.Ecap != P->Ecap || S.Scap != slot_scap(P, S)) {
         // the layout changes with the capacity: carry the results of A (markers, status) and the remembered flags over
         const FrameLayout old = S.lay;
         DevBuf keep;
@@ -1426,7 +1819,8 @@ int enqueue_b(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
     q.pbc = MOLAR_HIP_PBC_FULL;
     const unsigned long long *total_dev = nullptr;
     const uint32_t *pairs_dev = nullptr;
-    MH_TRY(search_resident_enqueue(c, &q, (char *)S.h + H_SIZES, &S.L, &total_dev, &pairs_dev));
+    // (the invalid lipids' NaN markers stay out of the grid: with most lipids dropped they would crowd one cell)
+    MH_TRY(search_resident_enqueue(c, &q, (char *)S.h + H_SIZES, &S.L, &total_dev, &pairs_dev, /*drop_nonfinite=*/true));
     S.cap_pairs = S.L.cap0;
     const size_t Ecap = S.Ecap;
     uint32_t *deg = P->work.as<uint32_t>(), *cursor = deg + (K + 1), *t_ord = cursor + K, *t_oth = t_ord + Ecap, *t_grp = t_oth + Ecap;
@@ -1490,6 +1884,68 @@ int host_pass(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
     return 0;
 }
 
+// patches_from_nth_shell (lib.rs:562-583) between the first smoothing pass and the next: the shell patches of the frame, their
+// transpose, and the slotted state re-slotted by them and started from zero (what Engine.membrane_smooth does when the patch
+// structure changes).  A's patch lists and transpose become the shell ones.
+int enqueue_shell_patches(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, SmoothDev &A) {
+    const size_t K = P->K;
+    const uint32_t K32 = (uint32_t)K;
+    char *d = S.blob.as<char>();
+    const FrameLayout &L = S.lay;
+    hipStream_t st = P->c->stream;
+    FrameInfo *info = reinterpret_cast<FrameInfo *>(d + L.info);
+    const ShellGraph G{K32, S.shp, A.poff, A.nvert, A.neib, A.valid};
+    uint64_t *spoff = (uint64_t *)(d + L.spoff), *spids = (uint64_t *)(d + L.spids);
+    uint32_t *sowner = (uint32_t *)(d + L.sowner), *scnt = (uint32_t *)(d + L.scnt), *sdeg = (uint32_t *)(d + L.sdeg),
+             *scur = sdeg + (K + 1), *sroff = (uint32_t *)(d + L.srev_off), *scratch = (uint32_t *)(d + L.sscratch);
+    uint8_t *redo = (uint8_t *)(d + L.sredo);
+    const uint32_t nb4 = (K32 + 3u) / 4u, nb16 = (K32 + 15u) / 16u;
+    hipLaunchKernelGGL(k_shell_patches, dim3(nb4), dim3(64), 0, st, G, A.poff, scratch, scnt, redo, sdeg, (uint32_t)(2 * K + 1));
+    WideArgs W{};
+    W.G = G; W.redo = redo; W.maps = (uint32_t *)(d + L.maps); W.W = shell_map_words(K);
+    W.cnt_out = scnt; W.spoff = spoff; W.spids = spids; W.sowner = sowner; W.rdeg = sdeg;
+    const uint32_t nwide = (uint32_t)std::min<size_t>(K, SH_WIDE_WG);
+    W.mode = 0;
+    hipLaunchKernelGGL(k_shell_wide, dim3(nwide), dim3(256), 0, st, W);
+    hipLaunchKernelGGL(k_shell_scan, dim3(1), dim3(1024), 0, st, K32, (const uint32_t *)scnt, spoff, (unsigned long long)S.Scap, info);
+    hipLaunchKernelGGL(k_shell_fill, dim3(nb16), dim3(256), 0, st, K32, (const uint8_t *)A.valid, (const uint8_t *)redo, A.poff, A.pids,
+                       (const uint32_t *)scratch, (const uint64_t *)spoff, spids, sowner, sdeg);
+    W.mode = 1;
+    hipLaunchKernelGGL(k_shell_wide, dim3(nwide), dim3(256), 0, st, W);
+    hipLaunchKernelGGL(k_patch_scan, dim3(1), dim3(1024), 0, st, K32, (const uint32_t *)sdeg, (uint64_t *)(d + L.stmp), sroff);
+    const uint32_t nbS = (uint32_t)((S.Scap + 255) / 256);
+    hipLaunchKernelGGL(k_rev_bucket, dim3(nbS), dim3(256), 0, st, (const FrameInfo *)info, (const uint64_t *)spids, (const uint32_t *)sroff,
+                       scur, (uint32_t *)(d + L.sbucket));
+    hipLaunchKernelGGL(k_rev_sort, dim3(nb16), dim3(256), 0, st, K32, (const uint32_t *)sroff, (const uint32_t *)(d + L.sbucket),
+                       (const uint32_t *)sowner, (uint32_t *)(d + L.srev_entry), (uint32_t *)(d + L.srev_owner));
+    MH_HIP(hipGetLastError());
+    // re-slot: nvert, neib_ids, voro_vertexes and fitted_patch_points start from zero (one block of the layout)
+    MH_HIP(hipMemsetAsync(d + L.nvert, 0, L.zero_end - L.nvert, st));
+    A.poff = spoff; A.pids = spids;
+    A.rev_off = sroff; A.rev_entry = (const uint32_t *)(d + L.srev_entry); A.rev_owner = (const uint32_t *)(d + L.srev_owner);
+    return 0;
+}
+
+// smooth_curvature (lib.rs:584-621) over the final patch lists, from a snapshot of the curvatures
+int enqueue_shell_curvature(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, const SmoothDev &A) {
+    const size_t K = P->K;
+    const uint32_t K32 = (uint32_t)K;
+    char *d = S.blob.as<char>();
+    const FrameLayout &L = S.lay;
+    hipStream_t st = P->c->stream;
+    MH_HIP(hipMemcpyAsync(d + L.mean0, d + L.mean, L.gauss - L.mean + K * 4, hipMemcpyDeviceToDevice, st));
+    const float *mean0 = (const float *)(d + L.mean0), *gauss0 = (const float *)(d + L.mean0 + (L.gauss - L.mean));
+    const ShellGraph G{K32, S.shs, A.poff, A.nvert, A.neib, A.valid};
+    uint8_t *redo = (uint8_t *)(d + L.sredo);
+    hipLaunchKernelGGL(k_curv_shells, dim3((K32 + 3u) / 4u), dim3(64), 0, st, G, mean0, gauss0, A.mean, A.gauss, redo);
+    WideArgs W{};
+    W.G = G; W.redo = redo; W.maps = (uint32_t *)(d + L.maps); W.W = shell_map_words(K);
+    W.mode = 2; W.mean0 = mean0; W.gauss0 = gauss0; W.mean = A.mean; W.gauss = A.gauss;
+    hipLaunchKernelGGL(k_shell_wide, dim3((uint32_t)std::min<size_t>(K, SH_WIDE_WG)), dim3(256), 0, st, W);
+    MH_HIP(hipGetLastError());
+    return 0;
+}
+
 // C: smoothing on a fresh per-lipid state, order
 int enqueue_c(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool info_to_host = true) {
     molar_hip_ctx *c = P->c;
@@ -1517,7 +1973,10 @@ int enqueue_c(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
     A.fitted = (float *)(d + L.fitted); A.vwork = (float4 *)(d + L.vwork); A.pwork = (float4 *)(d + L.pwork);
     A.rev_off = (const uint32_t *)(d + L.roff); A.rev_entry = (const uint32_t *)(d + L.rev_entry);
     A.rev_owner = (const uint32_t *)(d + L.rev_owner);
-    for (int it = 0; it < P->max_iter; ++it) {
+    // with n_shells_patch: a first pass on the search patches, then max_smooth_iter passes on the shell patches (lib.rs:417-432)
+    const int passes = P->max_iter + (S.shp ? 1 : 0);
+    for (int it = 0; it < passes; ++it) {
+        if (it == 1 && S.shp) MH_TRY(enqueue_shell_patches(P, S, A));
         // the markers before the iteration: the frame's own for the first one (the working copy starts as their image)
         if (it == 0) A.saved = (const float *)(d + L.head);
         else {
@@ -1528,6 +1987,7 @@ int enqueue_c(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
         // (a lane of the averaging kernel reads the fitted marker of its own lipid only, before it overwrites it)
         hipLaunchKernelGGL(k_membrane_average, dim3((uint32_t)((K + 3) / 4)), dim3(64), 0, st, A, (const float *)A.head);
     }
+    if (S.shs) MH_TRY(enqueue_shell_curvature(P, S, A));
     {
         const uint32_t nt = (uint32_t)P->ntails, nmax = std::max(K32, nt);
         hipLaunchKernelGGL(k_flags_tail_normals, dim3((nmax + 255u) / 256u), dim3(256), 0, st, K32, (const uint8_t *)(d + L.valid_prev), valid,
@@ -1688,6 +2148,19 @@ extern "C" int molar_hip_membrane_plan_set_valid(molar_hip_membrane_plan *P, con
     return MOLAR_HIP_OK;
 }
 
+extern "C" int molar_hip_membrane_plan_set_shells(molar_hip_membrane_plan *P, size_t n_shells_patch, size_t n_shells_smoothing) {
+    if (!P) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_plan_set_shells: null plan");
+    for (int t = 0; t < 2; ++t)
+        if (P->slot[t].pending) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_plan_set_shells: frame %d is in flight: end it first", t);
+    // a shell stops growing within K rounds (the graph has K vertices), so larger counts give the same sets
+    const size_t most = P->K + 2;
+    P->shells_patch = (uint32_t)std::min(n_shells_patch, most);
+    P->shells_smooth = (uint32_t)std::min(n_shells_smoothing, most);
+    if ((P->shells_patch || P->shells_smooth) && P->Scap == 0)
+        P->Scap = 8 * P->K + 1024;       // a flat bilayer's direct neighbours (about six a lipid); frames that need more grow it
+    return MOLAR_HIP_OK;
+}
+
 extern "C" int molar_hip_membrane_frame_begin(molar_hip_membrane_plan *P, float *xyz, const float *box9, int32_t *ticket) {
     if (!P || !xyz || !box9 || !ticket) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_frame_begin: null argument");
     molar_hip_ctx *c = P->c;
@@ -1708,6 +2181,8 @@ extern "C" int molar_hip_membrane_frame_begin(molar_hip_membrane_plan *P, float 
     S.ended = false;
     S.b_enqueued = false;
     S.serial = ++P->serial;
+    S.shp = P->shells_patch;
+    S.shs = P->shells_smooth;
     MH_TRY(enqueue_a(P, S));
     // B needs the valid flags the older frame's C will leave, and that C is not enqueued yet (it follows the host pass in
     // the older frame's _end).  Smoothing rarely drops a lipid, so B runs now on the flags as they are - the GPU works on
@@ -1730,6 +2205,10 @@ static void fill_view(molar_hip_membrane_plan *P, const molar_hip_membrane_plan:
     V->nlipids = P->K; V->patch_entries = (size_t)S.info.E; V->npairs = (size_t)S.info.npairs;
     V->head = (const float *)(d + L.head); V->mid = (const float *)(d + L.mid); V->tail = (const float *)(d + L.tail);
     V->patch_offsets = (const uint64_t *)(d + L.poff); V->patch_ids = (const uint64_t *)(d + L.pids);
+    if (S.shp) {          // the final patch lists: the shells (the slotted arrays follow them)
+        V->patch_entries = (size_t)S.info.Es;
+        V->patch_offsets = (const uint64_t *)(d + L.spoff); V->patch_ids = (const uint64_t *)(d + L.spids);
+    }
     V->initial_normals = (const float *)(d + L.normals0);
     V->valid = (const uint8_t *)(d + L.valid_out);
     V->smoothed_head = (const float *)(d + L.s_head); V->normals = (const float *)(d + L.s_normals);
@@ -1839,20 +2318,40 @@ int frame_end(molar_hip_membrane_plan *P, int32_t ticket, molar_hip_membrane_vie
     if (!S.b_enqueued) MH_TRY(enqueue_b(P, S, /*restore=*/false));     // (only after an error left the chain short)
     if (!S.passed) MH_TRY(host_pass(P, S, /*may_repeat=*/true));
     FetchJob J;
-    if (out) MH_TRY(fetch_prepare(P, S, out, J));
-    const bool packed = !J.items.empty();
-    MH_TRY(enqueue_c(P, S, /*info_to_host=*/!packed));
-    if (packed) {  // the caller's arrays leave on the frame's own stream, right behind C - no second round trip for them -, and
-                   // the frame's status words ride in the same launch
-        char *d = S.blob.as<char>();
-        MH_TRY(fetch_enqueue(P, J, P->c->stream, d + S.lay.info, (char *)S.h + H_INFO, sizeof(FrameInfo)));
-        MH_HIP(hipEventRecord(S.done, P->c->stream));
-    }
+    auto run_c = [&]() -> int {
+        J = FetchJob{};
+        if (out) MH_TRY(fetch_prepare(P, S, out, J));
+        const bool packed = !J.items.empty();
+        MH_TRY(enqueue_c(P, S, /*info_to_host=*/!packed));
+        if (packed) {  // the caller's arrays leave on the frame's own stream, right behind C - no second round trip for them -,
+                       // and the frame's status words ride in the same launch
+            char *d = S.blob.as<char>();
+            MH_TRY(fetch_enqueue(P, J, P->c->stream, d + S.lay.info, (char *)S.h + H_INFO, sizeof(FrameInfo)));
+            MH_HIP(hipEventRecord(S.done, P->c->stream));
+        }
+        return 0;
+    };
+    MH_TRY(run_c());
     // while the GPU smooths this frame: the host pass of the younger one, whose B is already through (it sits ahead of
     // this C on the stream)
     if (O.pending && O.b_enqueued && !O.passed) MH_TRY(host_pass(P, O, /*may_repeat=*/false));
     MH_HIP(hipEventSynchronize(S.done));
     std::memcpy(&S.info, (char *)S.h + H_INFO, sizeof(FrameInfo));
+    // shell patches longer than the frame's arrays: the frame again from B - flags as B found them, a layout with room for
+    // what the shells needed, C's status words cleared - behind everything on the stream
+    for (int attempt = 0; S.info.shell_overflow; ++attempt) {
+        if (attempt >= 3) return fail(MOLAR_HIP_ERR_HIP, "membrane frame: shell buffers did not settle");
+        const size_t need = (size_t)S.info.Es_need;
+        if (need >= (1ull << 32)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "membrane frame: %zu shell patch entries (32-bit entry indices)", need);
+        P->Scap = std::max(P->Scap, need + need / 4 + 1024);
+        MH_TRY(enqueue_b(P, S, /*restore=*/true));
+        char *d = S.blob.as<char>();
+        MH_HIP(hipMemsetAsync(d + S.lay.info + offsetof(FrameInfo, st_order), 0, sizeof(FrameInfo) - offsetof(FrameInfo, st_order), P->c->stream));
+        MH_TRY(host_pass(P, S, /*may_repeat=*/true));
+        MH_TRY(run_c());
+        MH_HIP(hipEventSynchronize(S.done));
+        std::memcpy(&S.info, (char *)S.h + H_INFO, sizeof(FrameInfo));
+    }
     if (O.pending && (!O.b_enqueued || (O.speculative && S.info.changed))) MH_TRY(enqueue_b(P, O, /*restore=*/false));
     O.speculative = false;
     S.pending = false;

@@ -48,6 +48,7 @@ struct BinParams {
     uint32_t dx, dy, dz;
     uint32_t pbc;
     uint32_t use_box;
+    uint32_t drop_nonfinite;    // atoms with a NaN / infinite coordinate go into no cell (they pair with nothing anyway)
     float lower[3], upper[3];
     molar_hip_box box;
 };
@@ -61,6 +62,12 @@ struct CellOfAtom {
 __device__ __forceinline__ CellOfAtom classify(const BinParams &P, V3 p) {
     CellOfAtom r;
     r.pos = p;
+    // (the reference bins a NaN atom into cell 0, where it pairs with nothing; a chained stage that marks the atoms it leaves out
+    // as NaN asks for them to be dropped instead, so that thousands of them do not crowd one cell)
+    if (P.drop_nonfinite && !(__builtin_isfinite(p.x) && __builtin_isfinite(p.y) && __builtin_isfinite(p.z))) {
+        r.key = DROPPED;
+        return r;
+    }
     if (P.use_box) {
         V3 rel = mat_vec(P.box.inv, p);
         float rl[3] = {rel.x, rel.y, rel.z};
@@ -1247,6 +1254,7 @@ static BinParams grid_bin_params(const molar_hip_ctx *c, const GridSet &S) {
     P.dz = c->dims[2];
     P.pbc = c->pbc;
     P.use_box = c->use_box ? 1u : 0u;
+    P.drop_nonfinite = c->grid_drop_nonfinite ? 1u : 0u;
     for (int d = 0; d < 3; ++d) {
         P.lower[d] = c->lower[d];
         P.upper[d] = c->upper[d];
@@ -2522,7 +2530,7 @@ static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::De
 
 // stages.hpp: the resident search for callers that chain device work behind it
 int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, void *sizes_pinned, ResidentLaunch *L,
-                                const unsigned long long **total_dev, const uint32_t **pairs_dev) {
+                                const unsigned long long **total_dev, const uint32_t **pairs_dev, bool drop_nonfinite) {
     std::memset(sizes_pinned, 0, 24);
     {   // the chained stages (the membrane's patches) read the (i, j) plane only; their passes launch the bound (searches of 1e4
         // markers: nothing to trim, and nobody reads the plan's size back in between)
@@ -2530,7 +2538,9 @@ int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q
         const unsigned long long keep_trim = c->trim_real;
         c->resident_no_dist = true;
         c->trim_real = 0;
+        c->grid_drop_nonfinite = drop_nonfinite;
         const int rc = resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, L);
+        c->grid_drop_nonfinite = false;
         c->resident_no_dist = keep;
         c->trim_real = keep_trim;
         MH_TRY(rc);

@@ -32,8 +32,10 @@ struct ResidentLaunch {
     // behind the search must look (the host only finds out at its next wait) and treat the list as not there.
     const unsigned long long *mask_units_dev = nullptr;
 };
+// drop_nonfinite: atoms with a non-finite coordinate are binned into no cell (the reference puts a NaN atom into cell 0; it pairs
+// with nothing either way, so the pair list is the same)
 int search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, void *sizes_pinned, ResidentLaunch *L,
-                            const unsigned long long **total_dev, const uint32_t **pairs_dev);
+                            const unsigned long long **total_dev, const uint32_t **pairs_dev, bool drop_nonfinite = false);
 // true if the sizes delivered for launch L fitted; otherwise the buffers have been grown and the search must be
 // enqueued again
 int search_resident_fits(molar_hip_ctx *c, const void *sizes_pinned, const ResidentLaunch &L, bool *fits);

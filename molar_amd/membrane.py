@@ -44,7 +44,7 @@ class MembraneOptions:          # molar_membrane/src/lib.rs:53-85 (subset)
     n_shells_smoothing: int = 0 # >0: average curvatures over the n-th neighbour shell
     global_normal: object = None
     unwrap: bool = True
-    fused: bool = True          # one chained call per frame (molar_hip_membrane_frame_*) where the options allow it
+    fused: bool = True          # one chained call per frame (molar_hip_membrane_frame_*); False: the stage-by-stage calls
 
 
 def pope_like_template() -> LipidTemplate:
@@ -181,8 +181,9 @@ class Membrane:
 
     # ---- the chained form: one begin/end pair per frame, two frames in flight
     def fusable(self):
-        """The options the chained call covers (everything but the n-th shell variants, lib.rs:562-621)."""
-        return self.opt.fused and self.opt.n_shells_patch == 0 and self.opt.n_shells_smoothing == 0
+        """Whether compute() takes the chained call (it covers every option, the n-th shell variants of lib.rs:562-621
+        included)."""
+        return self.opt.fused
 
     def _plan(self):
         if getattr(self, "_plan_obj", None) is None:
@@ -193,12 +194,19 @@ class Membrane:
                                               self.opt.unwrap, self.opt.global_normal)
             self._valid_dev = None              # the flags the plan is known to hold (None: push self.valid first)
             self._inflight = 0
+            self._shells = (0, 0)               # the shell options the plan holds
+        if self._inflight == 0 and self._shells != (self.opt.n_shells_patch, self.opt.n_shells_smoothing):
+            self._shells = (self.opt.n_shells_patch, self.opt.n_shells_smoothing)
+            self._plan_obj.set_shells(*self._shells)
         return self._plan_obj
 
     def compute_begin(self, xyz, box):
         """Enqueue one frame without waiting for it; returns a ticket for compute_end.  Frames are chained in begin
-        order, the valid flags included, so begin(k+1) may come before end(k)."""
+        order, the valid flags included, so begin(k+1) may come before end(k).  The shell options reach the plan between
+        frames: changing them while a frame is in flight raises ValueError (end the frames first)."""
         plan = self._plan()
+        if self._shells != (self.opt.n_shells_patch, self.opt.n_shells_smoothing):
+            raise ValueError("n_shells_patch / n_shells_smoothing changed while a frame is in flight: end it first")
         if self._inflight == 0 and (self._valid_dev is None or not np.array_equal(self._valid_dev, self.valid)):
             plan.set_valid(self.valid)              # first frame, reset_valid_lipids, or flags edited by the caller
         t = plan.begin(xyz, box)

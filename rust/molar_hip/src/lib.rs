@@ -679,6 +679,14 @@ impl<'e> MembraneFrames<'e> {
         Ok(last)
     }
 
+    /// `n_shells_patch` / `n_shells_smoothing` of `MembraneOptions` (lib.rs:53-85) for the frames pushed from now on
+    /// (0, 0: none); ends the frame in flight first.
+    pub fn set_shells(&mut self, n_shells_patch: usize, n_shells_smoothing: usize) -> Result<Option<MembraneFrame>, EngineError> {
+        let last = self.finish()?;
+        self.engine.plugin.check(unsafe { (self.engine.plugin.fns.membrane_plan_set_shells)(self.plan, n_shells_patch, n_shells_smoothing) })?;
+        Ok(last)
+    }
+
     /// Enqueue one frame (coordinates are unwrapped in place) and collect the frame pushed before it.
     pub fn push(&mut self, coords: &mut [[f32; 3]], box9: &[f32; 9]) -> Result<Option<MembraneFrame>, EngineError> {
         if coords.len() != self.natoms {
