@@ -425,6 +425,13 @@ int molar_hip_center_batch(molar_hip_ctx *ctx, const float *xyz, size_t natoms, 
 /* Modify::unwrap_simple_dim (modify.rs:40-54) applied to every selection of the CSR list, in place. */
 int molar_hip_unwrap_simple_batch(molar_hip_ctx *ctx, float *xyz, size_t natoms, const uint64_t *idx,
                                   const uint64_t *offsets, size_t nsel, const float *box9, uint8_t pbc);
+/* The two batch entries above in f64 (MolAR's `f64` feature), same arguments with double: centres in the reference's serial
+ * order of additions (COM with masses, COG without), and unwrap_simple_dim per selection in place (ERR_NO_PBC if box9 ==
+ * NULL).  Pointers may be host or device memory, as for the other _f64 entries. */
+int molar_hip_center_batch_f64(molar_hip_ctx *ctx, const double *xyz, size_t natoms, const uint64_t *idx,
+                               const uint64_t *offsets, size_t nsel, const double *mass, double *out);
+int molar_hip_unwrap_simple_batch_f64(molar_hip_ctx *ctx, double *xyz, size_t natoms, const uint64_t *idx,
+                                      const uint64_t *offsets, size_t nsel, const double *box9, uint8_t pbc);
 /* Membrane::compute_initial_normals (molar_membrane/src/lib.rs:456-505), host arithmetic: tail->head unit
  * vectors, then two neighbour-averaging passes over the patches (CSR patch_offsets/patch_ids; the second
  * pass updates normals in place, in lipid order, exactly like the reference loop).  valid may be NULL. */
@@ -488,6 +495,37 @@ int molar_hip_membrane_nth_shell_patches(size_t nlipids, const uint8_t *valid, c
 int molar_hip_membrane_smooth_curvature(size_t nlipids, const uint8_t *valid, const uint64_t *patch_offsets,
                                         const uint32_t *nvert, const uint64_t *neib_ids, size_t n_shells,
                                         float *mean_curv, float *gauss_curv);
+
+/* The staged Membrane::compute in f64 (MolAR's `f64` feature, molar_membrane's `f64 = ["molar/f64"]`).  The state is
+ * molar_hip_membrane_state with double in place of float; the integer parts of the chain (search_count_f64 / _fill_f64,
+ * membrane_patches_from_pairs, membrane_nth_shell_patches) and lipid_tail_order_f64 are shared with the other entries. */
+typedef struct {
+    double *head_markers;            /* [K][3]  required */
+    double *normals;                 /* [K][3]  required: in = normal defining the local frame, out = fitted normal */
+    uint8_t *valid;                  /* [K]     required */
+    double *quad_coefs;              /* [K][6]  a,b,c,d,e,f of z = a x^2 + b y^2 + c xy + d x + e y + f */
+    double *mean_curv, *gauss_curv;  /* [K] */
+    double *princ_curvs;             /* [K][2] */
+    double *princ_dirs;              /* [K][2][3] */
+    double *area;                    /* [K] */
+    uint32_t *nvert;                 /* [K] */
+    uint64_t *neib_ids;              /* [E + 4K] slotted like molar_hip_membrane_state */
+    double *voro_vertexes;           /* [E + 4K][3] slotted */
+    double *fitted_patch_points;     /* [E][3] aligned with patch_ids */
+} molar_hip_membrane_state_f64;
+/* One iteration of Membrane::smooth (lib.rs:661-812) in f64: the contract of molar_hip_membrane_smooth (host pointers,
+ * IN/OUT state, invalid lipids keep their values, slot layout, princ_curvs descending with the same sign convention on
+ * princ_dirs, error codes), every operation in double in the reference's order. */
+int molar_hip_membrane_smooth_f64(molar_hip_ctx *ctx, const molar_hip_membrane_patches *patches, const double *box9,
+                                  molar_hip_membrane_state_f64 *state);
+/* compute_initial_normals (lib.rs:456-505) and smooth_curvature (:584-621) in f64: host arithmetic, the arguments of
+ * molar_hip_membrane_initial_normals / _smooth_curvature with double. */
+int molar_hip_membrane_initial_normals_f64(size_t nlipids, const double *head_markers, const double *tail_markers,
+                                           const uint64_t *patch_offsets, const uint64_t *patch_ids,
+                                           const uint8_t *valid, double *normals_out);
+int molar_hip_membrane_smooth_curvature_f64(size_t nlipids, const uint8_t *valid, const uint64_t *patch_offsets,
+                                            const uint32_t *nvert, const uint64_t *neib_ids, size_t n_shells,
+                                            double *mean_curv, double *gauss_curv);
 
 /* One whole frame of Membrane::compute (molar_membrane/src/lib.rs:410-454) as a chain of kernels with no host round
  * trip inside: unwrap of every lipid (lipid_molecule.rs:75-76) -> head / mid / tail-end markers (:65-99) -> PBC search

@@ -169,6 +169,11 @@ SYMBOLS = {
     "molar_hip_membrane_patches_from_pairs": (_I, [_P, _SZ, _SZ, _P, _P]),
     "molar_hip_membrane_nth_shell_patches": (_I, [_SZ, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _P]),
     "molar_hip_membrane_smooth_curvature": (_I, [_SZ, _P, _P, _P, _P, _SZ, _P, _P]),
+    "molar_hip_center_batch_f64": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
+    "molar_hip_unwrap_simple_batch_f64": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
+    "molar_hip_membrane_smooth_f64": (_I, [_P, _P, _P, _P]),
+    "molar_hip_membrane_initial_normals_f64": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_membrane_smooth_curvature_f64": (_I, [_SZ, _P, _P, _P, _P, _SZ, _P, _P]),
     "molar_hip_membrane_plan_create": (_I, [_P, _P, _P]),
     "molar_hip_membrane_plan_destroy": (None, [_P]),
     "molar_hip_membrane_plan_set_valid": (_I, [_P, _P]),

@@ -736,20 +736,11 @@ class Engine:
         per-lipid arrays updated IN PLACE (see new_membrane_state); a lipid that turns invalid keeps its old
         values, like the fields of the reference's LipidMolecule."""
         pb = box if isinstance(box, PeriodicBox) else PeriodicBox.from_matrix(box)
-        po = _u64(patch_offsets); pi = _u64(patch_ids)
-        K = len(po) - 1
-        E = int(po[-1]); slots = E + 4 * K
-        st = state
-        if st["neib_ids"].shape[0] != max(slots, 1):                       # patch structure changed: re-slot
-            st["neib_ids"] = np.zeros(max(slots, 1), np.uint64)
-            st["voro_vertexes"] = np.zeros((max(slots, 1), 3), np.float32)
-            st["fitted_patch_points"] = np.zeros((max(E, 1), 3), np.float32)
-            st["nvert"][:] = 0
-        P = _MembranePatches(K, po.ctypes.data, pi.ctypes.data if E else None)
-        S = _MembraneState(*[st[k].ctypes.data for k in _MEMBRANE_FIELDS])
+        if state["head_markers"].dtype != np.float32:
+            raise TypeError("Engine.membrane_smooth takes a float32 state; MeasureF64.membrane_smooth the float64 one")
         m9 = pb.colmajor9()
-        check(self.lib.molar_hip_membrane_smooth(self.ctx, C.byref(P), m9.ctypes.data, C.byref(S)))
-        return st
+        return _membrane_smooth_call(self.lib.molar_hip_membrane_smooth, self.ctx, m9.ctypes.data, state, patch_offsets,
+                                     patch_ids, np.float32)
 
     def lipid_tail_order(self, xyz, tails, order_type, normals, bond_orders):
         """Batched Measure::lipid_tail_order (measure.rs:270-422).  tails: list of index arrays (the
@@ -1088,6 +1079,24 @@ class MeasureF64:
             res.append(out[pos:pos + int(n) - 2].copy()); pos += int(n) - 2
         return res
 
+    def lipid_tail_order_csr(self, xyz, idx, tail_offsets, order_type, normals, normal_offsets, bond_orders):
+        """lipid_tail_order in f64 with the CSR arrays prepared by the caller (as Engine.lipid_tail_order_csr)."""
+        xyz = _f64(xyz)
+        xa, kx = _addr(xyz)
+        idx = _u64(idx); tail_offsets = np.ascontiguousarray(tail_offsets, np.uint64)
+        normal_offsets = np.ascontiguousarray(normal_offsets, np.uint64)
+        normals = np.ascontiguousarray(normals, np.float64)
+        if not _is_torch(bond_orders):
+            bond_orders = np.ascontiguousarray(bond_orders, np.uint8)
+        ia, ki = _addr(idx); ba, kb = _addr(bond_orders)
+        K = len(tail_offsets) - 1
+        nout = int(tail_offsets[-1]) - 2 * K
+        out = np.zeros(max(nout, 1), np.float64)
+        natoms = xyz.shape[0] if xyz.ndim == 2 else xyz.shape[0] // 3
+        check(self.lib.molar_hip_lipid_tail_order_f64(self.ctx, xa, natoms, ia, tail_offsets.ctypes.data, K, int(order_type),
+                                                      normals.ctypes.data, normal_offsets.ctypes.data, ba, out.ctypes.data))
+        return out[:nout]
+
     def rotate(self, xyz, unit_axis, angle, idx=None):
         if not _is_torch(xyz):
             assert xyz.dtype == np.float64 and xyz.flags.c_contiguous, "rotate works in place"
@@ -1113,6 +1122,42 @@ class MeasureF64:
         t3 = np.ascontiguousarray(t, np.float64)
         check(self.lib.molar_hip_apply_transform_f64(self.ctx, *a[:4], R9.ctypes.data, t3.ctypes.data))
 
+    def center_batch(self, xyz, idx, offsets, mass=None):
+        """Centres of K CSR selections (idx, offsets[K+1]) in f64: center_of_mass if `mass` is given, else
+        center_of_geometry, the reference's serial sums.  Returns float64 [K,3]."""
+        xyz = _f64(xyz); idx = _u64(idx); offsets = _u64(offsets); mass = _f64(mass)
+        xa, k1 = _addr(xyz); ia, k2 = _addr(idx); oa, k3 = _addr(offsets); ma, k4 = _addr(mass)
+        K = offsets.shape[0] - 1
+        out = np.zeros((K, 3), np.float64)
+        natoms = xyz.shape[0] if xyz.ndim == 2 else xyz.shape[0] // 3
+        check(self.lib.molar_hip_center_batch_f64(self.ctx, xa, natoms, ia, oa, K, ma, out.ctypes.data))
+        return out
+
+    def unwrap_simple_batch(self, xyz, idx, offsets, box, dims=PBC_FULL):
+        """unwrap_simple on each of K CSR selections in f64, in place (numpy float64 C-contiguous or torch CUDA float64)."""
+        if not _is_torch(xyz):
+            assert xyz.dtype == np.float64 and xyz.flags.c_contiguous, "unwrap_simple_batch works in place"
+        else:
+            import torch
+            assert xyz.dtype == torch.float64 and xyz.is_contiguous(), "unwrap_simple_batch works in place"
+        idx = _u64(idx); offsets = _u64(offsets)
+        xa, k1 = _addr(xyz); ia, k2 = _addr(idx); oa, k3 = _addr(offsets)
+        ba, kb = self._box9(box)
+        natoms = xyz.shape[0] if xyz.ndim == 2 else xyz.shape[0] // 3
+        check(self.lib.molar_hip_unwrap_simple_batch_f64(self.ctx, xa, natoms, ia, oa, offsets.shape[0] - 1, ba,
+                                                         pbc_mask(dims)))
+        return xyz
+
+    def membrane_smooth(self, box, state, patch_offsets, patch_ids):
+        """One iteration of Membrane::smooth (molar_membrane/src/lib.rs:661-812) in f64.  `state`: a float64 dict of
+        new_membrane_state(..., dtype=np.float64), updated IN PLACE as by Engine.membrane_smooth."""
+        if state["head_markers"].dtype != np.float64:
+            raise TypeError("MeasureF64.membrane_smooth takes a float64 state (new_membrane_state(..., dtype=np.float64))")
+        pb = box.get_matrix() if isinstance(box, PeriodicBox) else box
+        ba, kb = self._box9(pb)
+        return _membrane_smooth_call(self.lib.molar_hip_membrane_smooth_f64, self.ctx, ba, state, patch_offsets, patch_ids,
+                                     np.float64)
+
 
 _MEMBRANE_FIELDS = ("head_markers", "normals", "valid", "quad_coefs", "mean_curv", "gauss_curv", "princ_curvs",
                     "princ_dirs", "area", "nvert", "neib_ids", "voro_vertexes", "fitted_patch_points")
@@ -1126,19 +1171,44 @@ class _MembraneState(C.Structure):       # molar_hip_membrane_state
     _fields_ = [(k, C.c_void_p) for k in _MEMBRANE_FIELDS]
 
 
-def new_membrane_state(head_markers, normals, valid=None, npatch_entries=0):
-    """Per-lipid state with the defaults of Membrane::new (molar_membrane/src/lib.rs:152-177)."""
-    head = np.array(head_markers, np.float32, order="C").reshape(-1, 3)
+def new_membrane_state(head_markers, normals, valid=None, npatch_entries=0, dtype=np.float32):
+    """Per-lipid state with the defaults of Membrane::new (molar_membrane/src/lib.rs:152-177); dtype np.float32 (the
+    engine's f32 pass) or np.float64 (MeasureF64.membrane_smooth)."""
+    f = np.dtype(dtype)
+    if f not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"membrane state dtype must be float32 or float64, not {f}")
+    head = np.array(head_markers, f, order="C").reshape(-1, 3)
     K = len(head)
     slots = max(npatch_entries + 4 * K, 1)
     return dict(
-        head_markers=head, normals=np.array(normals, np.float32, order="C").reshape(K, 3),
+        head_markers=head, normals=np.array(normals, f, order="C").reshape(K, 3),
         valid=np.ones(K, np.uint8) if valid is None else np.array(valid, np.uint8, order="C"),
-        quad_coefs=np.zeros((K, 6), np.float32), mean_curv=np.full(K, -100.0, np.float32),
-        gauss_curv=np.full(K, -100.0, np.float32), princ_curvs=np.zeros((K, 2), np.float32),
-        princ_dirs=np.zeros((K, 2, 3), np.float32), area=np.zeros(K, np.float32), nvert=np.zeros(K, np.uint32),
-        neib_ids=np.zeros(slots, np.uint64), voro_vertexes=np.zeros((slots, 3), np.float32),
-        fitted_patch_points=np.zeros((max(npatch_entries, 1), 3), np.float32))
+        quad_coefs=np.zeros((K, 6), f), mean_curv=np.full(K, -100.0, f),
+        gauss_curv=np.full(K, -100.0, f), princ_curvs=np.zeros((K, 2), f),
+        princ_dirs=np.zeros((K, 2, 3), f), area=np.zeros(K, f), nvert=np.zeros(K, np.uint32),
+        neib_ids=np.zeros(slots, np.uint64), voro_vertexes=np.zeros((slots, 3), f),
+        fitted_patch_points=np.zeros((max(npatch_entries, 1), 3), f))
+
+
+def _membrane_smooth_call(fn, ctx, box9_addr, state, patch_offsets, patch_ids, real):
+    """The call behind Engine.membrane_smooth (f32) and MeasureF64.membrane_smooth (f64): re-slots the state when the patch
+    structure changed, then one smoothing pass in place."""
+    po = _u64(patch_offsets); pi = _u64(patch_ids)
+    K = len(po) - 1
+    E = int(po[-1]); slots = E + 4 * K
+    st = state
+    if st["neib_ids"].shape[0] != max(slots, 1):                       # patch structure changed: re-slot
+        st["neib_ids"] = np.zeros(max(slots, 1), np.uint64)
+        st["voro_vertexes"] = np.zeros((max(slots, 1), 3), real)
+        st["fitted_patch_points"] = np.zeros((max(E, 1), 3), real)
+        st["nvert"][:] = 0
+    for k in _MEMBRANE_FIELDS:
+        if k not in ("valid", "nvert", "neib_ids") and st[k].dtype != real:
+            raise TypeError(f"membrane state: {k} is {st[k].dtype}, the pass works in {np.dtype(real)}")
+    P = _MembranePatches(K, po.ctypes.data, pi.ctypes.data if E else None)
+    S = _MembraneState(*[st[k].ctypes.data for k in _MEMBRANE_FIELDS])
+    check(fn(ctx, C.byref(P), box9_addr, C.byref(S)))
+    return st
 
 
 class MembranePlan:
@@ -1296,23 +1366,27 @@ def membrane_smooth_curvature(valid, patch_offsets, nvert, neib_ids, n_shells, m
     lib = _lib.load()
     v = np.ascontiguousarray(valid, np.uint8); po = np.ascontiguousarray(patch_offsets, np.uint64)
     nv = np.ascontiguousarray(nvert, np.uint32); nb = np.ascontiguousarray(neib_ids, np.uint64)
-    m = np.array(mean_curv, np.float32, order="C"); g = np.array(gauss_curv, np.float32, order="C")
-    check(lib.molar_hip_membrane_smooth_curvature(len(v), v.ctypes.data, po.ctypes.data, nv.ctypes.data, nb.ctypes.data, int(n_shells),
-                                                  m.ctypes.data, g.ctypes.data))
+    f64 = np.asarray(mean_curv).dtype == np.float64          # float64 curvatures: the f64 entry
+    real = np.float64 if f64 else np.float32
+    fn = lib.molar_hip_membrane_smooth_curvature_f64 if f64 else lib.molar_hip_membrane_smooth_curvature
+    m = np.array(mean_curv, real, order="C"); g = np.array(gauss_curv, real, order="C")
+    check(fn(len(v), v.ctypes.data, po.ctypes.data, nv.ctypes.data, nb.ctypes.data, int(n_shells), m.ctypes.data, g.ctypes.data))
     return m, g
 
 
 def membrane_initial_normals(head_markers, tail_markers, patch_offsets, patch_ids, valid=None, normals=None):
     """Membrane::compute_initial_normals (molar_membrane/src/lib.rs:456-505); host arithmetic of the engine."""
     lib = _lib.load()
-    head = np.ascontiguousarray(head_markers, np.float32); tail = np.ascontiguousarray(tail_markers, np.float32)
+    f64 = np.asarray(head_markers).dtype == np.float64       # float64 markers: the f64 entry
+    real = np.float64 if f64 else np.float32
+    fn = lib.molar_hip_membrane_initial_normals_f64 if f64 else lib.molar_hip_membrane_initial_normals
+    head = np.ascontiguousarray(head_markers, real); tail = np.ascontiguousarray(tail_markers, real)
     po = np.ascontiguousarray(patch_offsets, np.uint64); pi = np.ascontiguousarray(patch_ids, np.uint64)
     K = len(head)
-    out = np.zeros((K, 3), np.float32) if normals is None else np.ascontiguousarray(normals, np.float32)
+    out = np.zeros((K, 3), real) if normals is None else np.ascontiguousarray(normals, real)
     v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
-    check(lib.molar_hip_membrane_initial_normals(K, head.ctypes.data, tail.ctypes.data, po.ctypes.data,
-                                                 pi.ctypes.data if len(pi) else None, None if v is None else v.ctypes.data,
-                                                 out.ctypes.data))
+    check(fn(K, head.ctypes.data, tail.ctypes.data, po.ctypes.data, pi.ctypes.data if len(pi) else None,
+             None if v is None else v.ctypes.data, out.ctypes.data))
     return out
 
 

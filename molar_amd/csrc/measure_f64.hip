@@ -1058,3 +1058,138 @@ int molar_hip_principal_transform_f64(molar_hip_ctx *c, const double *xyz, size_
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- batched (CSR) selections in f64: one wave each
+// selection k = idx[offsets[k] .. offsets[k+1]): the marker centres and the per-lipid unwrap of the staged f64 membrane pass
+// (molar_membrane/src/lib.rs:135-137, lipid_molecule.rs:65-99)
+
+namespace {
+
+// A wave gathers 64 atoms of the selection at a time and adds their terms in selection order (shuffles), so the sums are
+// the reference's serial ones (center_of_mass / center_of_geometry, measure.rs:60-82) whatever the selection's length.
+__global__ void __launch_bounds__(256) k64_center_batch(const double *__restrict__ xyz, const uint64_t *__restrict__ idx,
+                                                        const uint64_t *__restrict__ off, uint32_t nsel,
+                                                        const double *__restrict__ mass, double *__restrict__ out,
+                                                        int *__restrict__ status) {
+    const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (k >= nsel) return;                          // uniform over the wave
+    const uint64_t s = off[k], e = off[k + 1];
+    double sm = 0.0, sx = 0.0, sy = 0.0, sz = 0.0;
+    for (uint64_t q0 = s; q0 < e; q0 += 64) {
+        const uint64_t q = q0 + lane;
+        double m = 0.0, x = 0.0, y = 0.0, z = 0.0;
+        if (q < e) {
+            const uint64_t a = idx[q];
+            const double *p = xyz + 3 * a;
+            if (mass) {
+                m = mass[a];
+                x = p[0] * m; y = p[1] * m; z = p[2] * m;
+            } else {
+                x = p[0]; y = p[1]; z = p[2];
+            }
+        }
+        const int cnt = (int)(e - q0 < 64 ? e - q0 : 64);
+        for (int j = 0; j < cnt; ++j) {
+            sx += __shfl(x, j, 64);
+            sy += __shfl(y, j, 64);
+            sz += __shfl(z, j, 64);
+            sm += __shfl(m, j, 64);
+        }
+    }
+    if (lane == 0) {
+        const double den = mass ? sm : (double)(e - s);
+        if (mass && den == 0.0) {
+            atomicMax(status, MOLAR_HIP_ERR_ZERO_MASS);
+            out[3 * k] = out[3 * k + 1] = out[3 * k + 2] = 0.0;
+        } else {
+            out[3 * k] = sx / den;
+            out[3 * k + 1] = sy / den;
+            out[3 * k + 2] = sz / den;
+        }
+    }
+}
+
+// unwrap_simple_dim (modify.rs:40-54) per selection: every atom after the first to its closest image of the first
+__global__ void __launch_bounds__(256) k64_unwrap_batch(double *__restrict__ xyz, const uint64_t *__restrict__ idx,
+                                                        const uint64_t *__restrict__ off, uint32_t nsel, const BoxD *box,
+                                                        uint32_t pbc) {
+    const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (k >= nsel) return;
+    const uint64_t s = off[k], e = off[k + 1];
+    if (e - s < 2) return;
+    const BoxD &B = *box;
+    const double *q0 = xyz + 3 * idx[s];
+    const D3 p0 = D3{q0[0], q0[1], q0[2]};
+    for (uint64_t q = s + 1 + lane; q < e; q += 64) {
+        double *p = xyz + 3 * idx[q];
+        const D3 im = closest_image(B, D3{p[0], p[1], p[2]}, p0, pbc);
+        p[0] = im.x; p[1] = im.y; p[2] = im.z;
+    }
+}
+
+// offsets[nsel] (host or device): the length of idx
+int csr_total(const uint64_t *offsets, size_t nsel, uint64_t *last) {
+    if (is_device_ptr(offsets)) MH_HIP(hipMemcpy(last, offsets + nsel, 8, hipMemcpyDeviceToHost));
+    else *last = offsets[nsel];
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int molar_hip_center_batch_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx,
+                               const uint64_t *offsets, size_t nsel, const double *mass, double *out) {
+    MH64_CTX(c);
+    if (!xyz || !idx || !offsets || !out) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "center_batch_f64: null argument");
+    if (nsel == 0) return MOLAR_HIP_OK;
+    if (nsel >= 0xFFFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "center_batch_f64: %zu selections", nsel);
+    uint64_t last = 0;
+    MH_TRY(csr_total(offsets, nsel, &last));
+    const double *d_xyz, *d_mass = nullptr;
+    const uint64_t *d_idx, *d_off;
+    MH_TRY(to_device(c, xyz, natoms * 3, c->m_xyz1, &d_xyz));
+    MH_TRY(to_device(c, idx, (size_t)last, c->m_idx1, &d_idx));
+    MH_TRY(to_device(c, offsets, nsel + 1, c->m_idx2, &d_off));
+    if (mass) MH_TRY(to_device(c, mass, natoms, c->m_mass1, &d_mass));
+    const bool out_dev = is_device_ptr(out);
+    MH_TRY(c->m_out.reserve(nsel * 24 + 16));
+    double *d_out = out_dev ? out : c->m_out.as<double>();
+    MH_TRY(c->m_results.reserve(64));
+    int *status = c->m_results.as<int>();
+    MH_HIP(hipMemsetAsync(status, 0, 4, c->stream));
+    hipLaunchKernelGGL(k64_center_batch, dim3((uint32_t)((nsel + 3) / 4)), dim3(256), 0, c->stream, d_xyz, d_idx, d_off,
+                       (uint32_t)nsel, d_mass, d_out, status);
+    MH_HIP(hipGetLastError());
+    int st = 0;
+    MH_HIP(hipMemcpyAsync(&st, status, 4, hipMemcpyDeviceToHost, c->stream));
+    if (!out_dev) MH_HIP(hipMemcpyAsync(out, d_out, nsel * 24, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (st) return fail(st, "zero mass");
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_unwrap_simple_batch_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx,
+                                      const uint64_t *offsets, size_t nsel, const double *box9, uint8_t pbc) {
+    MH64_CTX(c);
+    if (!xyz || !idx || !offsets) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_simple_batch_f64: null argument");
+    const BoxD *d_box;
+    MH_TRY(box64_to_device(c, box9, &d_box));
+    if (nsel == 0) return MOLAR_HIP_OK;
+    if (nsel >= 0xFFFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "unwrap_simple_batch_f64: %zu selections", nsel);
+    uint64_t last = 0;
+    MH_TRY(csr_total(offsets, nsel, &last));
+    const double *d_xyz;
+    const uint64_t *d_idx, *d_off;
+    MH_TRY(to_device(c, (const double *)xyz, natoms * 3, c->m_xyz1, &d_xyz));
+    MH_TRY(to_device(c, idx, (size_t)last, c->m_idx1, &d_idx));
+    MH_TRY(to_device(c, offsets, nsel + 1, c->m_idx2, &d_off));
+    hipLaunchKernelGGL(k64_unwrap_batch, dim3((uint32_t)((nsel + 3) / 4)), dim3(256), 0, c->stream, const_cast<double *>(d_xyz),
+                       d_idx, d_off, (uint32_t)nsel, d_box, (uint32_t)(pbc & 7u));
+    MH_HIP(hipGetLastError());
+    if (!is_device_ptr(xyz)) MH_HIP(hipMemcpyAsync(xyz, d_xyz, natoms * 24, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    return MOLAR_HIP_OK;
+}
+
+}  // extern "C"

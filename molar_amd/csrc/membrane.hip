@@ -814,8 +814,9 @@ extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membr
 // neighbours of every member (so from n = 3 on a lipid is a member of its own set - the reference's HashSet picks it up on
 // the way back, and so does this).  The reference iterates a HashSet, whose order is unspecified; here members are in
 // ascending lipid id.  Graph bookkeeping over a few thousand short lists per frame: host loops, like the reference's.
+// (namespace mh: membrane_f64.hip walks the same shells for its smooth_curvature)
 
-namespace {
+namespace mh {
 
 // members of lipid i's n-th shell, ascending; `stamp` (K entries, values < 2 * (i + 1) on entry) marks membership
 void nth_shell_of(size_t i, size_t n_shells, const uint64_t *slot_off, const uint32_t *nvert, const uint64_t *neib, size_t K,
@@ -857,7 +858,7 @@ int check_shell_args(size_t K, const uint8_t *valid, const uint64_t *patch_offse
     return 0;
 }
 
-}  // namespace
+}  // namespace mh
 
 extern "C" int molar_hip_membrane_nth_shell_patches(size_t K, const uint8_t *valid, const uint64_t *patch_offsets, const uint64_t *patch_ids,
                                                     const uint32_t *nvert, const uint64_t *neib_ids, size_t n_shells,

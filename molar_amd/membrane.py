@@ -107,14 +107,23 @@ def build_bilayer(nlipids_per_leaflet: int, natoms_total: int, seed: int = 20240
 
 
 class Membrane:
+    precision = "f32"           # class defaults: set per instance by __init__
+    real = np.float32
+
     def __init__(self, engine: api.Engine, natoms: int, lipid_first_atom, template: LipidTemplate, masses,
-                 options: MembraneOptions | None = None):
+                 options: MembraneOptions | None = None, precision: str = "f32"):
+        """precision "f32" (default) or "f64": the staged Membrane::compute of MolAR's `f64` feature - float64 masses and
+        frames, every per-lipid stage through the engine's _f64 entries, float64 results (the chained call is f32 only)."""
+        if precision not in ("f32", "f64"):
+            raise ValueError(f'precision must be "f32" or "f64", not {precision!r}')
         self.eng = engine
         self.opt = options or MembraneOptions()
+        self.precision = precision
+        self.real = np.float64 if precision == "f64" else np.float32
         self.tpl = template
         self.first = np.asarray(lipid_first_atom, np.uint64)
         self.K = len(self.first)
-        self.masses = np.ascontiguousarray(masses, np.float32)
+        self.masses = np.ascontiguousarray(masses, self.real)
         f = self.first[:, None]
         # CSR of the three marker selections, lipid-major: [head_0, mid_0, tail_0, head_1, ...]
         parts, lens = [], []
@@ -143,7 +152,7 @@ class Membrane:
         if len(ids) and (ids.min() < 0 or ids.max() >= self.K):
             raise ValueError(f"lipid id out of bounds 0:{self.K}")                # lib.rs:303-309
         if name not in self.groups:
-            self.groups[name] = LipidGroup(self.species_names, {sp: self.tail_lens for sp in self.species_names})
+            self.groups[name] = LipidGroup(self.species_names, {sp: self.tail_lens for sp in self.species_names}, self.real)
         self.groups[name].lipid_ids = np.concatenate([self.groups[name].lipid_ids, ids])
 
     def reset_groups(self):                                                     # lib.rs:261-267
@@ -182,8 +191,8 @@ class Membrane:
     # ---- the chained form: one begin/end pair per frame, two frames in flight
     def fusable(self):
         """Whether compute() takes the chained call (it covers every option, the n-th shell variants of lib.rs:562-621
-        included)."""
-        return self.opt.fused
+        included; f32 only)."""
+        return self.opt.fused and self.precision == "f32"
 
     def _plan(self):
         if getattr(self, "_plan_obj", None) is None:
@@ -203,7 +212,11 @@ class Membrane:
     def compute_begin(self, xyz, box):
         """Enqueue one frame without waiting for it; returns a ticket for compute_end.  Frames are chained in begin
         order, the valid flags included, so begin(k+1) may come before end(k).  The shell options reach the plan between
-        frames: changing them while a frame is in flight raises ValueError (end the frames first)."""
+        frames: changing them while a frame is in flight raises ValueError (end the frames first).  f32 only: an f64 membrane
+        raises ValueError."""
+        if self.precision != "f32":
+            raise ValueError("the chained frame call (compute_begin / compute_end) is f32 only: use compute() for precision f64")
+        self._check_frame(xyz)
         plan = self._plan()
         if self._shells != (self.opt.n_shells_patch, self.opt.n_shells_smoothing):
             raise ValueError("n_shells_patch / n_shells_smoothing changed while a frame is in flight: end it first")
@@ -247,6 +260,9 @@ class Membrane:
         """One frame (Membrane::compute, lib.rs:410-454).  xyz: float32 [N,3] (numpy; unwrapped in place when
         options.unwrap).  Returns a dict: markers, patch CSR, per-lipid state (valid, normals, curvatures, area,
         Voronoi neighbours/vertices) and order: list over tails of [K, n_t-2]."""
+        self._check_frame(xyz)
+        if self.precision == "f64":
+            return self._compute_f64(xyz, box)
         if self.fusable():
             return self.compute_end(self.compute_begin(xyz, box))
         e, K, opt = self.eng, self.K, self.opt
@@ -296,6 +312,67 @@ class Membrane:
         if self.groups:                                                         # lib.rs:448-451
             d = (head - tail).astype(np.float32)
             thv = d / np.sqrt((d * d).sum(1, dtype=np.float32))[:, None]        # tail_head_vec (lib.rs:459-461)
+            for g in self.groups.values():
+                g.frame_update(res, self.species_of_lipid, thv)
+        return res
+
+    def _check_frame(self, xyz):
+        """A frame in the membrane's precision (float32 / float64, numpy or torch): never cast silently."""
+        dt = str(xyz.dtype).replace("torch.", "")
+        want = "float64" if self.precision == "f64" else "float32"
+        if dt != want:
+            raise TypeError(f"a Membrane of precision {self.precision} takes {want} coordinates, not {dt}")
+
+    def _compute_f64(self, xyz, box):
+        """compute() in f64: the staged loop above through the engine's _f64 entries (unwrap, markers, marker search, patches,
+        initial normals, smoothing passes with the n-th shell options, tail order, curvature shells); float64 results."""
+        e, K, opt = self.eng, self.K, self.opt
+        if getattr(self, "_m64", None) is None:
+            self._m64 = api.MeasureF64(e)
+        m64 = self._m64
+        box = np.asarray(box.get_matrix() if isinstance(box, api.PeriodicBox) else box, np.float64)
+        cst = self._constants(xyz)
+        if opt.unwrap:                                                          # lipid_molecule.rs:75-76
+            m64.unwrap_simple_batch(xyz, cst["lipid_idx"], self.lipid_off, box)
+        mk = m64.center_batch(xyz, cst["marker_idx"], self.marker_off, cst["masses"]).reshape(K, 3, 3)
+        head, mid, tail = mk[:, 0].copy(), mk[:, 1].copy(), mk[:, 2].copy()
+        # compute_patches (lib.rs:539-558): the f64 search among the valid lipids' head markers, ids = lipid ids
+        vidx = np.flatnonzero(self.valid).astype(np.uint64)
+        i, j, _ = e.search_f64(api.SEARCH_SINGLE, opt.cutoff, head, idx1=vidx, box=box, pbc=api.PBC_FULL, ids_local=False)
+        patch_off, patch_ids = api.membrane_patches_from_pairs(np.stack([i, j], 1).astype(np.uint32), K)
+        normals = api.membrane_initial_normals(head, tail, patch_off, patch_ids, valid=self.valid)
+        st = api.new_membrane_state(head, normals, self.valid, len(patch_ids), dtype=np.float64)
+        it = 0
+        while True:                                                             # lib.rs:417-432 (at least one pass)
+            if opt.n_shells_patch > 0 and it == 0:
+                m64.membrane_smooth(box, st, patch_off, patch_ids)
+                patch_off, patch_ids = api.membrane_nth_shell_patches(st["valid"], patch_off, patch_ids, st["nvert"], st["neib_ids"],
+                                                                      opt.n_shells_patch)
+            m64.membrane_smooth(box, st, patch_off, patch_ids)
+            it += 1
+            if it >= opt.max_smooth_iter:
+                break
+        self.valid[:] = st["valid"]
+        # compute_order (lib.rs:435-443): one normal per lipid (or the global one), shared by its tails
+        nl = st["normals"] if opt.global_normal is None else np.tile(np.asarray(opt.global_normal, np.float64), (K, 1))
+        nrm = np.repeat(nl, self.ntails, axis=0)
+        noff = np.arange(K * self.ntails + 1, dtype=np.uint64)
+        flat = m64.lipid_tail_order_csr(xyz, cst["tail_idx"], self.tail_off, opt.order_type, nrm, noff, cst["tail_bonds"])
+        flat = flat.reshape(K, sum(l - 2 for l in self.tail_lens))
+        out, pos = [], 0
+        for l in self.tail_lens:
+            out.append(flat[:, pos:pos + l - 2].copy()); pos += l - 2
+        if opt.n_shells_smoothing > 0:              # smooth_curvature (lib.rs:584-621)
+            st["mean_curv"], st["gauss_curv"] = api.membrane_smooth_curvature(st["valid"], patch_off, st["nvert"], st["neib_ids"],
+                                                                              opt.n_shells_smoothing, st["mean_curv"], st["gauss_curv"])
+        res = dict(head=head, mid=mid, tail=tail, patch_off=patch_off, patch_ids=patch_ids, normals=st["normals"],
+                   initial_normals=normals, order=out, valid=st["valid"].copy(), smoothed_head=st["head_markers"])
+        for k in ("quad_coefs", "mean_curv", "gauss_curv", "princ_curvs", "princ_dirs", "area", "nvert", "neib_ids",
+                  "voro_vertexes", "fitted_patch_points"):
+            res[k] = st[k]
+        if self.groups:                                                         # lib.rs:448-451
+            d = head - tail
+            thv = d / np.sqrt((d * d).sum(1))[:, None]                          # tail_head_vec (lib.rs:459-461)
             for g in self.groups.values():
                 g.frame_update(res, self.species_of_lipid, thv)
         return res

@@ -8,7 +8,8 @@ passes produce):
     LipidGroup        lipid_group.rs:9-37  frame_update over the group's valid lipids
     save_*            stats.rs:63-118, 238-293  the reference's text formats
 
-Arithmetic is float32 like the reference's `Float`; sums over the lipids of a frame are vectorised (the reference adds
+Arithmetic is in the reference's `Float`: float32 by default, float64 for a membrane of precision "f64" (MolAR's `f64`
+feature; the accumulators take `real`); sums over the lipids of a frame are vectorised (the reference adds
 them one by one, so the last bits of the f32 accumulators can differ)."""
 from __future__ import annotations
 
@@ -20,11 +21,13 @@ F = np.float32
 
 
 class Histogram1D:
-    def __init__(self, vmin, vmax, n_bins):
+    def __init__(self, vmin, vmax, n_bins, real=F):
+        self.F = F = real
         self.min, self.max = F(vmin), F(vmax)
         self.bins = np.zeros(n_bins, F)
 
     def add_many(self, vals):
+        F = self.F
         v = np.asarray(vals, F).reshape(-1)
         n = len(self.bins)
         with np.errstate(invalid="ignore", over="ignore"):
@@ -37,10 +40,12 @@ class Histogram1D:
         self.add_many([val])
 
     def normalize_density(self):
+        F = self.F
         d = (self.max - self.min) / F(len(self.bins))
         self.bins = (self.bins / (self.bins.sum(dtype=F) * d)).astype(F)
 
     def save_to_file(self, fname):
+        F = self.F
         d = (self.max - self.min) / F(len(self.bins))
         with open(fname, "w") as f:
             for i, val in enumerate(self.bins):
@@ -48,35 +53,41 @@ class Histogram1D:
 
 
 class MeanStd:
-    def __init__(self):
+    def __init__(self, real=F):
+        self.F = F = real
         self.x = F(0); self.x2 = F(0); self.n = F(0)
 
     def add(self, val):
+        F = self.F
         val = F(val)
         self.x = F(self.x + val); self.x2 = F(self.x2 + val * val); self.n = F(self.n + F(1))
 
     def add_many(self, vals):
+        F = self.F
         v = np.asarray(vals, F).reshape(-1)
         self.x = F(self.x + v.sum(dtype=F)); self.x2 = F(self.x2 + (v * v).sum(dtype=F)); self.n = F(self.n + F(len(v)))
 
     def compute(self):
         if self.n == 0:
             raise ValueError("no values accumulated in MeanStd")
+        F = self.F
         mean = F(self.x / self.n); x2n = F(self.x2 / self.n); m2 = F(mean * mean)
         return mean, (F(np.sqrt(F(x2n - m2))) if x2n > m2 else F(0))
 
 
 class MeanStdVec:
-    def __init__(self, size):
+    def __init__(self, size, real=F):
+        self.F = F = real
         self.x = np.zeros(size, F); self.x2 = np.zeros(size, F); self.n = F(0)
 
     def add_many(self, rows):
+        F = self.F
         r = np.asarray(rows, F).reshape(-1, len(self.x))
         self.x = (self.x + r.sum(0, dtype=F)).astype(F); self.x2 = (self.x2 + (r * r).sum(0, dtype=F)).astype(F)
         self.n = F(self.n + F(len(r)))
 
     def add(self, val):
-        val = np.asarray(val, F)
+        val = np.asarray(val, self.F)
         if len(val) != len(self.x):
             raise ValueError(f"incompatible vector size in MeanStdVec::add: {len(val)} provided, {len(self.x)} expected")
         self.add_many(val[None, :])
@@ -84,6 +95,7 @@ class MeanStdVec:
     def compute(self):
         if self.n == 0:
             raise ValueError("no values accumulated in MeanStd")
+        F = self.F
         mean = (self.x / self.n).astype(F)
         with np.errstate(invalid="ignore"):
             std = np.sqrt((self.x2 / self.n).astype(F) - mean * mean).astype(F)
@@ -91,23 +103,26 @@ class MeanStdVec:
 
 
 class SpeciesStats:
-    def __init__(self, tail_lens, all_species):
-        self.num_lip = MeanStd(); self.area = MeanStd(); self.tilt = MeanStd(); self.num_neib = MeanStd()
-        self.mean_curv = MeanStd(); self.gauss_curv = MeanStd()
-        self.order = [MeanStdVec(l - 2) for l in tail_lens]          # bond_orders.len() - 1 = n_carbons - 2
-        self.neib_species = {sp: MeanStd() for sp in all_species}
+    def __init__(self, tail_lens, all_species, real=F):
+        M = lambda: MeanStd(real)
+        self.num_lip = M(); self.area = M(); self.tilt = M(); self.num_neib = M()
+        self.mean_curv = M(); self.gauss_curv = M()
+        self.order = [MeanStdVec(l - 2, real) for l in tail_lens]    # bond_orders.len() - 1 = n_carbons - 2
+        self.neib_species = {sp: M() for sp in all_species}
 
 
 class LipidGroup:
     """lipid_group.rs + GroupProperties: ids of the group, one SpeciesStats per species present in the membrane."""
 
-    def __init__(self, species_names, species_tail_lens):
+    def __init__(self, species_names, species_tail_lens, real=F):
+        self.F = real
         self.lipid_ids = np.zeros(0, np.int64)
         self.names = list(species_names)
-        self.per_species = {sp: SpeciesStats(species_tail_lens[sp], self.names) for sp in self.names}
+        self.per_species = {sp: SpeciesStats(species_tail_lens[sp], self.names, real) for sp in self.names}
 
     def frame_update(self, res, species_of_lipid, tail_head_vec):
         """res: the dict Membrane.compute returns; species_of_lipid: int array (index into names) per lipid."""
+        F = self.F
         valid = res["valid"].astype(bool)
         ids = self.lipid_ids[valid[self.lipid_ids]]
         K = len(valid)
@@ -143,6 +158,7 @@ class LipidGroup:
 
     def save(self, out_dir, gr_name):
         """gr_<name>_stats.dat, gr_<name>_neib_stats.dat, gr_<name>_order_<species>.dat (stats.rs:63-118, 238-293)."""
+        F = self.F
         os.makedirs(out_dir, exist_ok=True)
         s = "#species\tnum\tnum_std\tarea\tarea_std\ttilt\ttilt_std\tmean_curv\tmean_curv_std\tgauss_curv\tgauss_curv_std\n"
         for sp, st in self.per_species.items():

@@ -116,6 +116,24 @@ pub struct MolarHipMembraneState {
     pub fitted_patch_points: *mut f32,
 }
 
+/// `molar_hip_membrane_state_f64`: the same arrays in f64, for molar_membrane built with its `f64` feature.
+#[repr(C)]
+pub struct MolarHipMembraneStateF64 {
+    pub head_markers: *mut f64,
+    pub normals: *mut f64,
+    pub valid: *mut u8,
+    pub quad_coefs: *mut f64,
+    pub mean_curv: *mut f64,
+    pub gauss_curv: *mut f64,
+    pub princ_curvs: *mut f64,
+    pub princ_dirs: *mut f64,
+    pub area: *mut f64,
+    pub nvert: *mut u32,
+    pub neib_ids: *mut u64,
+    pub voro_vertexes: *mut f64,
+    pub fitted_patch_points: *mut f64,
+}
+
 /// `molar_hip_membrane_plan`: opaque handle of the chained bilayer frame call (molar_hip_membrane_frame_*).
 #[repr(C)]
 pub struct MolarHipMembranePlan {
