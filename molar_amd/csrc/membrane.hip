@@ -5,19 +5,25 @@
 //   k_membrane_fit      one lane per lipid: local frame, patch markers into the frame (PBC shortest vector),
 //                       6x6 normal equations + Cholesky, Voronoi cell by half-plane clipping, curvatures,
 //                       fitted normal, cell area, fitted patch points, marker moved onto the surface;
-//   k_membrane_average  one lane per lipid: gathers the fitted images of its marker from every valid patch
+//   k_membrane_average  sixteen lanes per lipid: gathers the fitted images of its marker from every valid patch
 //                       that contains it, in the order the reference's scatter loop adds them (owner lipid
-//                       ascending, patch order inside), so the f32 sum is the same sum.
-// molar_hip_membrane_frame_* (second half of this file) chains a whole frame of Membrane::compute on the stream.
+//                       ascending, patch order inside), so the sum is the same sum.
+// Both are templates over the precision: float for MolAR's default build, double for its `f64` feature (Float = f64,
+// molar/src/aliases.rs:10-13; molar_membrane's own `f64 = ["molar/f64"]`), where the quadric fit is why it exists - the
+// normal equations are poorly conditioned, and in f32 the Gaussian curvature of a flat-ish bilayer (~1e-3) is about as
+// large as its own error.  f32 adds k_membrane_fit_lanes (sixteen lanes per lipid) ahead of the one-lane fit.
+// molar_hip_membrane_frame_* (second half of this file) chains a whole frame of Membrane::compute on the stream, in f32.
 // Per-lipid state of unbounded length (local points, Voronoi vertices) lives in HBM slices owned by the lane;
 // the work per lipid is ~30 neighbours, so the kernel is latency bound and tiny next to the neighbour search.
-// f32 throughout, in the reference's operation order (nalgebra gemv/cross/normalize, Cholesky::new + solve).
+// Every operation in the reference's order (nalgebra gemv/cross/normalize, Cholesky::new + solve), no contraction.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include <cmath>
 
 #include "boxmath.hpp"
+#include "boxmath64.hpp"
 #include "common.hpp"
 #include "stages.hpp"
 
@@ -25,41 +31,92 @@ namespace {
 
 using namespace mh;
 
-struct SmoothDev {
+// Voronoi vertex {x, y, ccw neighbour, id of the point that made the ccw edge} and patch member in the lipid's local
+// frame {x, y, z, id}, as the kernels see them
+template <class R>
+struct Vert {
+    R x, y;
+    uint32_t next;
+    int32_t id;
+};
+template <class R>
+struct Pt {
+    R x, y, z;
+    uint32_t id;
+};
+static_assert(sizeof(Vert<double>) == 24 && sizeof(Pt<double>) == 32, "f64 LDS element sizes");
+
+// What differs between the precisions.  LDS elements: f32 packs a vertex and a point into one float4 each (bit casts), f64
+// stores the structs (24 and 32 bytes).  The one-lane fit keeps the same per-lane capacities in both (VORO_LDS vertices,
+// PTS_LDS points), so a lane needs 1984 bytes in f32 and 3456 in f64, and a workgroup holds at most 64 or 32 lanes
+// (124 / 108 KB).  The fit issues GATHER marker loads at a time.
+template <class R>
+struct Prec;
+template <>
+struct Prec<float> {
+    using V = V3;
+    using Box = molar_hip_box;
+    using State = molar_hip_membrane_state;
+    using VertL = float4;
+    using PtL = float4;
+    static constexpr uint32_t GATHER = 4, MAX_LANES = 64;
+    static int box_from_matrix(const float *m9, Box *b) { return molar_hip_box_from_matrix(m9, b); }
+};
+template <>
+struct Prec<double> {
+    using V = D3;
+    using Box = BoxD;
+    using State = molar_hip_membrane_state_f64;
+    using VertL = Vert<double>;
+    using PtL = Pt<double>;
+    static constexpr uint32_t GATHER = 2, MAX_LANES = 32;
+    static int box_from_matrix(const double *m9, Box *b) { return box64_from_matrix(m9, b); }
+};
+
+template <class R>
+struct SmoothDevT {
+    using P = Prec<R>;
     uint32_t K;
-    molar_hip_box box;         // by value: read through the scalar cache, never reloaded behind a store
-    const float *saved;        // [K][3] markers before the iteration
-    float *head;               // [K][3] in/out
-    float *normals;            // [K][3] in/out
+    typename P::Box box;       // by value: read through the scalar cache, never reloaded behind a store
+    const R *saved;            // [K][3] markers before the iteration
+    R *head;                   // [K][3] in/out
+    R *normals;                // [K][3] in/out
     uint8_t *valid;            // [K] in/out
     const uint64_t *poff;      // [K+1]
     const uint64_t *pids;      // [E]
-    float *coefs, *mean, *gauss, *pcurv, *pdirs, *area;
+    R *coefs, *mean, *gauss, *pcurv, *pdirs, *area;
     uint32_t *nvert;
     uint64_t *neib;            // [E+4K]
-    float *voro;               // [E+4K][3]
-    float *fitted;             // [E][3]
-    float4 *vwork;             // [E+4K]  Voronoi vertices {x, y, next, id} of the patches too long for LDS
-    float4 *pwork;             // [E]     local points {x, y, z, id} of those patches
+    R *voro;                   // [E+4K][3]
+    R *fitted;                 // [E][3]
+    typename P::VertL *vwork;  // [E+4K]  Voronoi vertices of the patches too long for LDS
+    typename P::PtL *pwork;    // [E]     local points of those patches
     const uint32_t *rev_off;   // [K+1]   transpose of the patch CSR
     const uint32_t *rev_entry; // [E]     flat patch entry
     const uint32_t *rev_owner; // [E]     lipid owning that entry
     uint8_t *redo = nullptr;   // [K] or NULL: k_membrane_fit_lanes leaves 1 for the lipids it hands to k_membrane_fit (which then
                                //             takes only those), 0 for the ones it has done
 };
+using SmoothDev = SmoothDevT<float>;     // the chained frame call and the sixteen-lane kernels are f32 only
 
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-    return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+// a vector of the precision (V3 / D3)
+template <class R>
+__device__ __forceinline__ typename Prec<R>::V vec(R x, R y, R z) { return typename Prec<R>::V{x, y, z}; }
+
+template <class V>
+__device__ __forceinline__ V cross(V a, V b) {
+    return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
 
 // nalgebra try_inverse for 3x3 (closed form, column-major)
-__device__ bool inverse3(const float *m, float *o) {
-    const float m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
-    const float mi1 = m22 * m33 - m32 * m23;
-    const float mi2 = m21 * m33 - m31 * m23;
-    const float mi3 = m21 * m32 - m31 * m22;
-    const float det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
-    if (det == 0.0f) return false;
+template <class R>
+__device__ bool inverse3(const R *m, R *o) {
+    const R m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
+    const R mi1 = m22 * m33 - m32 * m23;
+    const R mi2 = m21 * m33 - m31 * m23;
+    const R mi3 = m21 * m32 - m31 * m22;
+    const R det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
+    if (det == R(0)) return false;
     o[0] = mi1 / det;
     o[3] = (m13 * m32 - m33 * m12) / det;
     o[6] = (m12 * m23 - m22 * m13) / det;
@@ -73,82 +130,105 @@ __device__ bool inverse3(const float *m, float *o) {
 }
 
 // get_quad_coefs' solver (lib.rs:862): nalgebra Cholesky::new, then L y = b, L^T x = y.  a is column-major 6x6.
-__device__ bool cholesky6_solve(float *a, float *b) {
+template <class R>
+__device__ bool cholesky6_solve(R *a, R *b) {
     for (int j = 0; j < 6; ++j) {
         for (int k = 0; k < j; ++k) {
-            const float factor = -a[k * 6 + j];
+            const R factor = -a[k * 6 + j];
             for (int r = j; r < 6; ++r) a[j * 6 + r] = factor * a[k * 6 + r] + a[j * 6 + r];
         }
-        const float diag = a[j * 6 + j];
-        if (!(diag > 0.0f)) return false;
-        const float denom = __builtin_sqrtf(diag);
+        const R diag = a[j * 6 + j];
+        if (!(diag > R(0))) return false;
+        const R denom = sqrt(diag);
         a[j * 6 + j] = denom;
         for (int r = j + 1; r < 6; ++r) a[j * 6 + r] /= denom;
     }
     for (int i = 0; i < 6; ++i) {
-        const float coeff = b[i] / a[i * 6 + i];
+        const R coeff = b[i] / a[i * 6 + i];
         b[i] = coeff;
         for (int r = i + 1; r < 6; ++r) b[r] = (-coeff) * a[i * 6 + r] + b[r];
     }
     for (int i = 5; i >= 0; --i) {
-        float dot = 0.0f;
+        R dot = R(0);
         for (int r = i + 1; r < 6; ++r) dot += a[i * 6 + r] * b[r];
         b[i] = (b[i] - dot) / a[i * 6 + i];
     }
     return true;
 }
 
-__device__ __forceinline__ float z_surf(float x, float y, const float *c) {   // lib.rs:870-879
+template <class R>
+__device__ __forceinline__ R z_surf(R x, R y, const R *c) {   // lib.rs:870-879
     return ((((c[0] * x * x + c[1] * y * y) + c[2] * x * y) + c[3] * x) + c[4] * y) + c[5];
 }
 
-// Voronoi vertex {x, y, ccw neighbour, id of the point that made the ccw edge}.  A lane's vertices sit either in the
-// workgroup's LDS, vertex-major (element v of lane l at [v * lanes + l]: the cell is a linked list walked with dependent
-// loads, ~30 ns a step there against ~500 ns in HBM), or, for patches of more than VORO_LDS - 4 members, in the lane's
-// slice of `vwork` in HBM.  `Verts` hides which: base pointer (generic address space) + element stride.
-constexpr uint32_t VORO_LDS = 64;        // vertices per lane held in LDS (1 KB per lane)
-struct Vert {
-    float x, y;
-    uint32_t next;
-    int32_t id;
-};
-struct Verts {
-    float4 *p;
+// A lane's vertices sit either in the workgroup's LDS, vertex-major (element v of lane l at [v * lanes + l]: the cell is a
+// linked list walked with dependent loads, ~30 ns a step there against ~500 ns in HBM), or, for patches of more than
+// VORO_LDS - 4 members, in the lane's slice of `vwork` in HBM; its local points likewise (patches of up to PTS_LDS members in
+// LDS, else `pwork`).  `Lane` hides which: base pointer (generic address space) + element stride.
+constexpr uint32_t VORO_LDS = 64;        // vertices per lane held in LDS
+constexpr uint32_t PTS_LDS = 60;         // local points per lane held in LDS
+template <class T>
+struct Lane {
+    T *p;
     uint32_t stride;
-    __device__ __forceinline__ float4 &at(uint32_t i) const { return p[(size_t)i * stride]; }
+    __device__ __forceinline__ T &at(uint32_t i) const { return p[(size_t)i * stride]; }
 };
-__device__ __forceinline__ Vert vload(const Verts &w, uint32_t i) {
+// f32 elements: the structs bit-cast into float4
+__device__ __forceinline__ Vert<float> vload(const Lane<float4> &w, uint32_t i) {
     const float4 q = w.at(i);
-    return Vert{q.x, q.y, __float_as_uint(q.z), (int32_t)__float_as_uint(q.w)};
+    return Vert<float>{q.x, q.y, __float_as_uint(q.z), (int32_t)__float_as_uint(q.w)};
 }
-__device__ __forceinline__ void vstore(const Verts &w, uint32_t i, Vert v) {
+__device__ __forceinline__ void vstore(const Lane<float4> &w, uint32_t i, Vert<float> v) {
     w.at(i) = make_float4(v.x, v.y, __uint_as_float(v.next), __uint_as_float((uint32_t)v.id));
 }
-__device__ __forceinline__ float vdist(const Verts &w, uint32_t i, float lx, float ly, float r2) {
-    const float4 q = w.at(i);
+__device__ __forceinline__ uint32_t vnext(const Lane<float4> &w, uint32_t i) { return __float_as_uint(w.at(i).z); }
+__device__ __forceinline__ void set_next(const Lane<float4> &w, uint32_t i, uint32_t next) {
+    Vert<float> f = vload(w, i);
+    f.next = next;
+    vstore(w, i, f);
+}
+__device__ __forceinline__ Pt<float> pload(const Lane<float4> &p, uint32_t i) {
+    const float4 q = p.at(i);
+    return Pt<float>{q.x, q.y, q.z, __float_as_uint(q.w)};
+}
+__device__ __forceinline__ void pstore(const Lane<float4> &p, uint32_t i, Pt<float> v) {
+    p.at(i) = make_float4(v.x, v.y, v.z, __uint_as_float(v.id));
+}
+// f64 elements: the structs themselves
+__device__ __forceinline__ Vert<double> vload(const Lane<Vert<double>> &w, uint32_t i) { return w.at(i); }
+__device__ __forceinline__ void vstore(const Lane<Vert<double>> &w, uint32_t i, Vert<double> v) { w.at(i) = v; }
+__device__ __forceinline__ uint32_t vnext(const Lane<Vert<double>> &w, uint32_t i) { return w.at(i).next; }
+__device__ __forceinline__ void set_next(const Lane<Vert<double>> &w, uint32_t i, uint32_t next) { w.at(i).next = next; }
+__device__ __forceinline__ Pt<double> pload(const Lane<Pt<double>> &p, uint32_t i) { return p.at(i); }
+__device__ __forceinline__ void pstore(const Lane<Pt<double>> &p, uint32_t i, Pt<double> v) { p.at(i) = v; }
+
+template <class L, class R>
+__device__ __forceinline__ R vdist(const Lane<L> &w, uint32_t i, R lx, R ly, R r2) {
+    const L q = w.at(i);
     return (lx * q.x + ly * q.y) - r2;     // line.pos.dot(pos) - r2  (voronoi_cell.rs:83-85)
 }
 
 // VoronoiCell::add_point (voronoi_cell.rs:107-205).  Returns false only where the reference would never
 // return (no vertex on the inner side, e.g. NaN input) - the caller then drops the lipid.
-__device__ bool voro_add_point(const Verts &w, uint32_t &nv, uint32_t &init, float px, float py, int32_t id) {
-    const float TOL = 1e-10f;
-    const float lx = 0.5f * px, ly = 0.5f * py;
-    const float r2 = lx * lx + ly * ly;
+template <class L, class R>
+__device__ bool voro_add_point(const Lane<L> &w, uint32_t &nv, uint32_t &init, R px, R py, int32_t id) {
+    const R TOL = R(1e-10);
+    const R lx = R(0.5) * px, ly = R(0.5) * py;
+    const R r2 = lx * lx + ly * ly;
     uint32_t cur = init, guard = 0;
-    float cur_d = vdist(w, cur, lx, ly, r2);
+    R cur_d = vdist(w, cur, lx, ly, r2);
     while (cur_d >= TOL) {
-        cur = __float_as_uint(w.at(cur).z);
+        cur = vnext(w, cur);
         cur_d = vdist(w, cur, lx, ly, r2);
         if (++guard > nv) return false;
     }
     init = cur;
     uint32_t c1_in, c1_out, c2_in, c2_out;
-    float c1_ind, c1_outd, c2_ind, c2_outd;
+    R c1_ind, c1_outd, c2_ind, c2_outd;
     for (;;) {
-        const uint32_t nx = __float_as_uint(w.at(cur).z);
+        const uint32_t nx = vnext(w, cur);
         if (nx == init) return true;               // every vertex is inside: nothing to cut
-        const float nd = vdist(w, nx, lx, ly, r2);
+        const R nd = vdist(w, nx, lx, ly, r2);
         if (nd >= TOL) {
             c1_in = cur; c1_ind = cur_d; c1_out = nx; c1_outd = nd;
             cur = nx; cur_d = nd;
@@ -158,8 +238,8 @@ __device__ bool voro_add_point(const Verts &w, uint32_t &nv, uint32_t &init, flo
     }
     guard = 0;
     for (;;) {
-        const uint32_t nx = __float_as_uint(w.at(cur).z);
-        const float nd = vdist(w, nx, lx, ly, r2);
+        const uint32_t nx = vnext(w, cur);
+        const R nd = vdist(w, nx, lx, ly, r2);
         if (nd < TOL) {
             c2_out = cur; c2_outd = cur_d; c2_in = nx; c2_ind = nd;
             break;
@@ -168,27 +248,23 @@ __device__ bool voro_add_point(const Verts &w, uint32_t &nv, uint32_t &init, flo
         if (++guard > nv) return false;
     }
     {   // cut #2 (:173-195)
-        const Vert o = vload(w, c2_out), in = vload(w, c2_in);
-        const float frac = c2_outd / (fabsf(c2_ind) + c2_outd);
-        const float x = (1.0f - frac) * o.x + frac * in.x;
-        const float y = (1.0f - frac) * o.y + frac * in.y;
+        const Vert<R> o = vload(w, c2_out), in = vload(w, c2_in);
+        const R frac = c2_outd / (fabs(c2_ind) + c2_outd);
+        const R x = (R(1) - frac) * o.x + frac * in.x;
+        const R y = (R(1) - frac) * o.y + frac * in.y;
         if (c1_out != c2_out) {
-            vstore(w, c2_out, Vert{x, y, o.next, o.id});
-            Vert f = vload(w, c1_out);
-            f.next = c2_out;
-            vstore(w, c1_out, f);
+            vstore(w, c2_out, Vert<R>{x, y, o.next, o.id});
+            set_next(w, c1_out, c2_out);
         } else {
-            vstore(w, nv, Vert{x, y, c2_in, o.id});
-            Vert f = vload(w, c1_out);
-            f.next = nv;
-            vstore(w, c1_out, f);
+            vstore(w, nv, Vert<R>{x, y, c2_in, o.id});
+            set_next(w, c1_out, nv);
             nv += 1;
         }
     }
     {   // cut #1 (:197-202)
-        const Vert o = vload(w, c1_out), in = vload(w, c1_in);
-        const float frac = c1_outd / (fabsf(c1_ind) + c1_outd);
-        vstore(w, c1_out, Vert{(1.0f - frac) * o.x + frac * in.x, (1.0f - frac) * o.y + frac * in.y, o.next, id});
+        const Vert<R> o = vload(w, c1_out), in = vload(w, c1_in);
+        const R frac = c1_outd / (fabs(c1_ind) + c1_outd);
+        vstore(w, c1_out, Vert<R>{(R(1) - frac) * o.x + frac * in.x, (R(1) - frac) * o.y + frac * in.y, o.next, id});
     }
     return true;
 }
@@ -196,40 +272,57 @@ __device__ bool voro_add_point(const Verts &w, uint32_t &nv, uint32_t &init, flo
 // Eigenpairs of the symmetric 2x2 [[a, b], [b, c]].  nalgebra's symmetric_eigen leaves order and sign
 // unspecified; this engine returns descending eigenvalues and eigenvectors whose first non-zero component
 // is positive.
-__device__ void eig2_sym(float a, float b, float c, float *w, float *v) {
-    const float t = 0.5f * (a - c), m = 0.5f * (a + c);
-    const float h = __builtin_sqrtf(t * t + b * b);
+template <class R>
+__device__ void eig2_sym(R a, R b, R c, R *w, R *v) {
+    const R t = R(0.5) * (a - c), m = R(0.5) * (a + c);
+    const R h = sqrt(t * t + b * b);
     w[0] = m + h;
     w[1] = m - h;
-    float x, y;
-    if (b == 0.0f) {
-        x = a >= c ? 1.0f : 0.0f;
-        y = a >= c ? 0.0f : 1.0f;
+    R x, y;
+    if constexpr (std::is_same<R, float>::value) {
+        if (b == 0.0f) {
+            x = a >= c ? 1.0f : 0.0f;
+            y = a >= c ? 0.0f : 1.0f;
+        } else {
+            if (t >= 0.0f) { x = t + h; y = b; } else { x = b; y = h - t; }
+            const float n = sqrt(x * x + y * y);
+            x /= n; y /= n;
+            if (x < 0.0f || (x == 0.0f && y < 0.0f)) { x = -x; y = -y; }
+        }
     } else {
-        if (t >= 0.0f) { x = t + h; y = b; } else { x = b; y = h - t; }
-        const float n = __builtin_sqrtf(x * x + y * y);
+        // both cases evaluated, then selected: a divergent if / else here makes the compiler put a VGPR copy ahead of an
+        // EXEC restore in the double kernel (the pattern build.py's ISA audit refuses); the b == 0 case discards the
+        // other's values (0 / 0 included)
+        x = t >= R(0) ? t + h : b;
+        y = t >= R(0) ? b : h - t;
+        const R n = sqrt(x * x + y * y);
         x /= n; y /= n;
-        if (x < 0.0f || (x == 0.0f && y < 0.0f)) { x = -x; y = -y; }
+        const bool flip = x < R(0) || (x == R(0) && y < R(0));
+        x = flip ? -x : x; y = flip ? -y : y;
+        x = b == R(0) ? (a >= c ? R(1) : R(0)) : x;
+        y = b == R(0) ? (a >= c ? R(0) : R(1)) : y;
     }
     v[0] = x; v[1] = y;
-    float x2 = -y, y2 = x;
-    if (x2 < 0.0f || (x2 == 0.0f && y2 < 0.0f)) { x2 = -x2; y2 = -y2; }
+    R x2 = -y, y2 = x;
+    if (x2 < R(0) || (x2 == R(0) && y2 < R(0))) { x2 = -x2; y2 = -y2; }
     v[2] = x2; v[3] = y2;
 }
 
-// A patch member in the lipid's local frame {x, y, z, id}: in LDS beside the Voronoi vertices (patches of up to PTS_LDS
-// members), else in the lane's slice of `pwork`.
-constexpr uint32_t PTS_LDS = 60;
-constexpr size_t FIT_LDS_BYTES = (size_t)(VORO_LDS + PTS_LDS) * 64 * sizeof(float4);      // 124 KB for a 64-lane workgroup
-struct Pts {
-    float4 *p;
-    uint32_t stride;
-    __device__ __forceinline__ float4 &at(uint32_t i) const { return p[(size_t)i * stride]; }
-};
+template <class R>
+constexpr size_t fit_lane_bytes() {
+    return VORO_LDS * sizeof(typename Prec<R>::VertL) + PTS_LDS * sizeof(typename Prec<R>::PtL);
+}
+static_assert(fit_lane_bytes<float>() * Prec<float>::MAX_LANES <= 160 * 1024 &&
+              fit_lane_bytes<double>() * Prec<double>::MAX_LANES <= 160 * 1024, "gfx950 LDS");
 
 // One lane per lipid; every loop over the patch is a chain of dependent steps, so what a lane touches more than once
-// (local points, cell vertices) sits in LDS and the gathers of the neighbours' markers are issued four at a time.
-__global__ __launch_bounds__(64) void k_membrane_fit(SmoothDev A) {
+// (local points, cell vertices) sits in LDS and the gathers of the neighbours' markers are issued GATHER at a time.
+template <class R>
+__global__ __launch_bounds__(Prec<R>::MAX_LANES) void k_membrane_fit(SmoothDevT<R> A) {
+    using V = typename Prec<R>::V;
+    using VertL = typename Prec<R>::VertL;
+    using PtL = typename Prec<R>::PtL;
+    constexpr uint32_t GW = Prec<R>::GATHER;
     extern __shared__ float4 fit_lds[];
     const uint32_t lanes = blockDim.x;               // lipids per workgroup (16, 32 or 64: launch_fit)
     const uint32_t i = blockIdx.x * lanes + threadIdx.x;
@@ -238,37 +331,38 @@ __global__ __launch_bounds__(64) void k_membrane_fit(SmoothDev A) {
     const uint64_t p0 = A.poff[i];
     const uint32_t np = (uint32_t)(A.poff[i + 1] - p0);
     const uint64_t slot = p0 + 4ull * i;
-    const V3 nrm = v3(A.normals[3 * i], A.normals[3 * i + 1], A.normals[3 * i + 2]);
-    float to_lab[9], to_local[9];
+    const V nrm = vec(A.normals[3 * i], A.normals[3 * i + 1], A.normals[3 * i + 2]);
+    R to_lab[9], to_local[9];
     {   // get_to_lab_transform (lipid_molecule.rs:190-196)
-        const V3 c0 = cross(nrm, v3(1.0f, 0.0f, 0.0f));
-        const V3 c1 = cross(nrm, c0);
+        const V c0 = cross(nrm, vec(R(1), R(0), R(0)));
+        const V c1 = cross(nrm, c0);
         to_lab[0] = c0.x; to_lab[1] = c0.y; to_lab[2] = c0.z;
         to_lab[3] = c1.x; to_lab[4] = c1.y; to_lab[5] = c1.z;
         to_lab[6] = -nrm.x; to_lab[7] = -nrm.y; to_lab[8] = -nrm.z;
     }
     if (!inverse3(to_lab, to_local)) { A.valid[i] = 0; return; }
-    const V3 c = v3(A.saved[3 * i], A.saved[3 * i + 1], A.saved[3 * i + 2]);
-    const molar_hip_box &box = A.box;
+    const V c = vec(A.saved[3 * i], A.saved[3 * i + 1], A.saved[3 * i + 2]);
+    const typename Prec<R>::Box &box = A.box;
     const bool in_lds = np + 4u <= VORO_LDS && np <= PTS_LDS;
-    const Verts w = in_lds ? Verts{fit_lds + threadIdx.x, lanes} : Verts{A.vwork + slot, 1u};
-    const Pts pt = in_lds ? Pts{fit_lds + VORO_LDS * lanes + threadIdx.x, lanes} : Pts{A.pwork + p0, 1u};
-    float m[36], cf[6];
-    for (int k = 0; k < 36; ++k) m[k] = 0.0f;
-    for (int k = 0; k < 6; ++k) cf[k] = 0.0f;
-    for (uint32_t q0 = 0; q0 < np; q0 += 4u) {   // local points + normal equations (lib.rs:685-689, 851-860)
-        uint32_t jj[4];
-        V3 ss[4];
+    VertL *const lds_v = reinterpret_cast<VertL *>(fit_lds);     // VORO_LDS vertices of every lane, then PTS_LDS points
+    const Lane<VertL> w = in_lds ? Lane<VertL>{lds_v + threadIdx.x, lanes} : Lane<VertL>{A.vwork + slot, 1u};
+    const Lane<PtL> pt = in_lds ? Lane<PtL>{reinterpret_cast<PtL *>(lds_v + VORO_LDS * lanes) + threadIdx.x, lanes} : Lane<PtL>{A.pwork + p0, 1u};
+    R m[36], cf[6];
+    for (int k = 0; k < 36; ++k) m[k] = R(0);
+    for (int k = 0; k < 6; ++k) cf[k] = R(0);
+    for (uint32_t q0 = 0; q0 < np; q0 += GW) {     // local points + normal equations (lib.rs:685-689, 851-860)
+        uint32_t jj[GW];
+        V ss[GW];
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) jj[u] = (uint32_t)A.pids[p0 + (q0 + u < np ? q0 + u : np - 1u)];
+        for (uint32_t u = 0; u < GW; ++u) jj[u] = (uint32_t)A.pids[p0 + (q0 + u < np ? q0 + u : np - 1u)];
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) ss[u] = v3(A.saved[3 * jj[u]], A.saved[3 * jj[u] + 1], A.saved[3 * jj[u] + 2]);
+        for (uint32_t u = 0; u < GW; ++u) ss[u] = vec(A.saved[3 * jj[u]], A.saved[3 * jj[u] + 1], A.saved[3 * jj[u] + 2]);
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
+        for (uint32_t u = 0; u < GW; ++u) {
             if (q0 + u >= np) break;
-            const V3 l = mat_vec(to_local, shortest_vector(box, ss[u] - c, MOLAR_HIP_PBC_FULL));
-            pt.at(q0 + u) = make_float4(l.x, l.y, l.z, __uint_as_float(jj[u]));
-            const float pw[6] = {l.x * l.x, l.y * l.y, l.x * l.y, l.x, l.y, 1.0f};
+            const V l = mat_vec(to_local, shortest_vector(box, ss[u] - c, MOLAR_HIP_PBC_FULL));
+            pstore(pt, q0 + u, Pt<R>{l.x, l.y, l.z, jj[u]});
+            const R pw[6] = {l.x * l.x, l.y * l.y, l.x * l.y, l.x, l.y, R(1)};
 #pragma unroll
             for (int cc = 0; cc < 6; ++cc)
 #pragma unroll
@@ -279,20 +373,20 @@ __global__ __launch_bounds__(64) void k_membrane_fit(SmoothDev A) {
     }
     if (!cholesky6_solve(m, cf)) { A.valid[i] = 0; return; }
 
-    vstore(w, 0, Vert{-10.0f, -10.0f, 1u, -1});     // VoronoiCell::new(-10, 10, -10, 10)  (voronoi_cell.rs:62-80)
-    vstore(w, 1, Vert{10.0f, -10.0f, 2u, -2});
-    vstore(w, 2, Vert{10.0f, 10.0f, 3u, -3});
-    vstore(w, 3, Vert{-10.0f, 10.0f, 0u, -4});
+    vstore(w, 0, Vert<R>{R(-10), R(-10), 1u, -1});     // VoronoiCell::new(-10, 10, -10, 10)  (voronoi_cell.rs:62-80)
+    vstore(w, 1, Vert<R>{R(10), R(-10), 2u, -2});
+    vstore(w, 2, Vert<R>{R(10), R(10), 3u, -3});
+    vstore(w, 3, Vert<R>{R(-10), R(10), 0u, -4});
     uint32_t nv = 4, init = 0;
     for (uint32_t q = 0; q < np; ++q) {
-        const float4 r = pt.at(q);
-        if (!voro_add_point(w, nv, init, r.x, r.y, (int32_t)__float_as_uint(r.w))) { A.valid[i] = 0; return; }
+        const Pt<R> r = pload(pt, q);
+        if (!voro_add_point(w, nv, init, r.x, r.y, (int32_t)r.id)) { A.valid[i] = 0; return; }
     }
     uint32_t n_vert = 0, n_neib = 0;                 // direct neighbours (lib.rs:706-726)
     {
         uint32_t cur = init;
         do {
-            const Vert v = vload(w, cur);
+            const Vert<R> v = vload(w, cur);
             if (v.id >= 0) A.neib[slot + n_neib++] = (uint64_t)v.id;
             ++n_vert;
             cur = v.next;
@@ -303,62 +397,62 @@ __global__ __launch_bounds__(64) void k_membrane_fit(SmoothDev A) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) A.coefs[6 * i + k] = cf[k];
     {   // compute_curvature_and_normal (lipid_molecule.rs:134-187)
-        const float a = cf[0], b = cf[1], cq = cf[2], d = cf[3], e = cf[4];
-        const float E = 1.0f + d * d, F = d * e, G = 1.0f + e * e;
-        const float L = 2.0f * a, M = cq, N = 2.0f * b;
-        const float Z = E * G - F * F;
+        const R a = cf[0], b = cf[1], cq = cf[2], d = cf[3], e = cf[4];
+        const R E = R(1) + d * d, F = d * e, G = R(1) + e * e;
+        const R L = R(2) * a, M = cq, N = R(2) * b;
+        const R Z = E * G - F * F;
         A.gauss[i] = (L * N - M * M) / Z;
-        A.mean[i] = 0.5f * ((E * N - 2.0f * F * M) + G * L) / Z;
-        const float gl = __builtin_sqrtf((d * d + e * e) + 1.0f);
-        const V3 fn = mat_vec(to_lab, v3(d / gl, e / gl, -1.0f / gl));
+        A.mean[i] = R(0.5) * ((E * N - R(2) * F * M) + G * L) / Z;
+        const R gl = sqrt((d * d + e * e) + R(1));
+        const V fn = mat_vec(to_lab, vec(d / gl, e / gl, R(-1) / gl));
         A.normals[3 * i] = fn.x; A.normals[3 * i + 1] = fn.y; A.normals[3 * i + 2] = fn.z;
-        float ev[2], evec[4];
+        R ev[2], evec[4];
         eig2_sym((E * L - F * M) / Z, (G * M - F * L) / Z, (G * N - F * M) / Z, ev, evec);
         A.pcurv[2 * i] = ev[0]; A.pcurv[2 * i + 1] = ev[1];
         for (int k = 0; k < 2; ++k) {
-            const V3 pd = mat_vec(to_lab, v3(evec[2 * k], evec[2 * k + 1], 0.0f));
+            const V pd = mat_vec(to_lab, vec(evec[2 * k], evec[2 * k + 1], R(0)));
             A.pdirs[6 * i + 3 * k] = pd.x; A.pdirs[6 * i + 3 * k + 1] = pd.y; A.pdirs[6 * i + 3 * k + 2] = pd.z;
         }
     }
     {   // cell vertices on the fitted surface, lab frame, still relative to the marker; fan area (lib.rs:731-752)
         uint32_t cur = init;
-        V3 first = v3(0, 0, 0), prev = v3(0, 0, 0);
-        float ar = 0.0f;
+        V first = vec(R(0), R(0), R(0)), prev = vec(R(0), R(0), R(0));
+        R ar = R(0);
         for (uint32_t k = 0; k < n_vert; ++k) {
-            const Vert v = vload(w, cur);
-            const V3 p = mat_vec(to_lab, v3(v.x, v.y, z_surf(v.x, v.y, cf)));
-            float *dst = A.voro + 3 * (slot + k);
+            const Vert<R> v = vload(w, cur);
+            const V p = mat_vec(to_lab, vec(v.x, v.y, z_surf(v.x, v.y, cf)));
+            R *dst = A.voro + 3 * (slot + k);
             dst[0] = p.x; dst[1] = p.y; dst[2] = p.z;
             if (k == 0) first = p;
-            else ar += 0.5f * __builtin_sqrtf(norm2(cross(prev, p)));
+            else ar += R(0.5) * sqrt(norm2(cross(prev, p)));
             prev = p;
             cur = v.next;
         }
-        ar += 0.5f * __builtin_sqrtf(norm2(cross(prev, first)));
+        ar += R(0.5) * sqrt(norm2(cross(prev, first)));
         A.area[i] = ar;
     }
-    float *fp = A.fitted + 3 * p0;
-    for (uint32_t q0 = 0; q0 < np; q0 += 4u) {   // fitted patch points (lib.rs:760-768)
-        float4 r[4];
-        V3 ss[4];
+    R *fp = A.fitted + 3 * p0;
+    for (uint32_t q0 = 0; q0 < np; q0 += GW) {     // fitted patch points (lib.rs:760-768)
+        Pt<R> r[GW];
+        V ss[GW];
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) r[u] = pt.at(q0 + u < np ? q0 + u : np - 1u);
+        for (uint32_t u = 0; u < GW; ++u) r[u] = pload(pt, q0 + u < np ? q0 + u : np - 1u);
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
-            const uint32_t j = __float_as_uint(r[u].w);
-            ss[u] = v3(A.saved[3 * j], A.saved[3 * j + 1], A.saved[3 * j + 2]);
+        for (uint32_t u = 0; u < GW; ++u) {
+            const uint32_t j = r[u].id;
+            ss[u] = vec(A.saved[3 * j], A.saved[3 * j + 1], A.saved[3 * j + 2]);
         }
 #pragma unroll
-        for (uint32_t u = 0; u < 4u; ++u) {
+        for (uint32_t u = 0; u < GW; ++u) {
             if (q0 + u >= np) break;
-            const V3 t = mat_vec(to_lab, v3(0.0f, 0.0f, z_surf(r[u].x, r[u].y, cf) - r[u].z));
+            const V t = mat_vec(to_lab, vec(R(0), R(0), z_surf(r[u].x, r[u].y, cf) - r[u].z));
             fp[3 * (q0 + u)] = ss[u].x + t.x;
             fp[3 * (q0 + u) + 1] = ss[u].y + t.y;
             fp[3 * (q0 + u) + 2] = ss[u].z + t.z;
         }
     }
-    if (fabsf(cf[5]) > 0.5f) { A.valid[i] = 0; return; }   // fitted surface too far from the marker (lib.rs:774-777)
-    const V3 t = mat_vec(to_lab, v3(0.0f, 0.0f, cf[5]));
+    if (fabs(cf[5]) > R(0.5)) { A.valid[i] = 0; return; }   // fitted surface too far from the marker (lib.rs:774-777)
+    const V t = mat_vec(to_lab, vec(R(0), R(0), cf[5]));
     A.head[3 * i] += t.x; A.head[3 * i + 1] += t.y; A.head[3 * i + 2] += t.z;
 }
 
@@ -629,28 +723,33 @@ __global__ __launch_bounds__(64) void k_membrane_fit_lanes(SmoothDev A) {
 }
 
 // the fit kernel needs more LDS than a kernel gets by default
-int launch_fit(molar_hip_ctx *c, const SmoothDev &A0) {
-    SmoothDev A = A0;
-    // sixteen lanes per lipid first; what it hands back (cells of more than 16 vertices, patches of more than 96 members) goes
-    // through the one-lane kernel below
+template <class R>
+int launch_fit(molar_hip_ctx *c, const SmoothDevT<R> &A0) {
+    SmoothDevT<R> A = A0;
     A.redo = nullptr;
+    if constexpr (std::is_same<R, float>::value) {
+        // sixteen lanes per lipid first; what it hands back (cells of more than 16 vertices, patches of more than 96 members)
+        // goes through the one-lane kernel below
 #ifndef MH_FIT_ONE_LANE          // (-DMH_FIT_ONE_LANE: the one-lane kernel alone, for A/B runs and bit-for-bit comparisons)
-    MH_TRY(c->fit_redo.reserve(A.K));
-    A.redo = c->fit_redo.as<uint8_t>();
-    hipLaunchKernelGGL(k_membrane_fit_lanes, dim3((A.K + 64u / FIT_G - 1u) / (64u / FIT_G)), dim3(64), 0, c->stream, A);
+        MH_TRY(c->fit_redo.reserve(A.K));
+        A.redo = c->fit_redo.as<uint8_t>();
+        hipLaunchKernelGGL(k_membrane_fit_lanes, dim3((A.K + 64u / FIT_G - 1u) / (64u / FIT_G)), dim3(64), 0, c->stream, A);
 #endif
+    }
+    constexpr uint32_t max_lanes = Prec<R>::MAX_LANES;
     static bool ready[64] = {};          // per device: the attribute belongs to the device's copy of the kernel
     const int dev = c->device & 63;
     if (!ready[dev]) {
-        MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_membrane_fit), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FIT_LDS_BYTES));
+        MH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_membrane_fit<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)(fit_lane_bytes<R>() * max_lanes)));
         ready[dev] = true;
     }
     // A wave costs the same whether 16 or 64 of its lanes hold a lipid, and its time is that of its slowest lane: small
     // bilayers go 16 lipids to a workgroup (4000 lipids: 250 workgroups on 256 compute units instead of 63), large ones fill
-    // the waves
+    // the waves (up to 64 lanes in f32, 32 in f64: the LDS of one workgroup)
     const uint32_t cus = (uint32_t)std::max(c->num_cus, 1);
-    const uint32_t lanes = A.K <= 16u * 2u * cus ? 16u : (A.K <= 32u * 2u * cus ? 32u : 64u);
-    hipLaunchKernelGGL(k_membrane_fit, dim3((A.K + lanes - 1u) / lanes), dim3(lanes), FIT_LDS_BYTES / 64u * lanes, c->stream, A);
+    const uint32_t lanes = A.K <= 16u * 2u * cus ? 16u : (A.K <= 32u * 2u * cus ? 32u : max_lanes);
+    hipLaunchKernelGGL(k_membrane_fit<R>, dim3((A.K + lanes - 1u) / lanes), dim3(lanes), fit_lane_bytes<R>() * lanes, c->stream, A);
     return 0;
 }
 
@@ -659,40 +758,42 @@ int launch_fit(molar_hip_ctx *c, const SmoothDev &A0) {
 // loads that one lane would walk one after the other), then the group adds them in the order of the reference's scatter
 // loop from shuffles, every lane holding the same sum.  Rounds are counted per wave, so the shuffles run with all lanes on.
 constexpr uint32_t AVG_G = 16;
-__global__ __launch_bounds__(64) void k_membrane_average(SmoothDev A, const float *fitted_head) {
+template <class R>
+__global__ __launch_bounds__(64) void k_membrane_average(SmoothDevT<R> A, const R *fitted_head) {
+    using V = typename Prec<R>::V;
     const uint32_t i = blockIdx.x * (64u / AVG_G) + threadIdx.x / AVG_G, sub = threadIdx.x % AVG_G;
     const bool live = i < A.K && A.valid[i];
     const uint32_t r0 = live ? A.rev_off[i] : 0u, r1 = live ? A.rev_off[i + 1] : 0u;
     uint32_t rounds = (r1 - r0 + AVG_G - 1u) / AVG_G;
     rounds = max(rounds, (uint32_t)__shfl_xor((int)rounds, 16));
     rounds = max(rounds, (uint32_t)__shfl_xor((int)rounds, 32));
-    float n = 1.0f;
-    V3 s = live ? v3(fitted_head[3 * i], fitted_head[3 * i + 1], fitted_head[3 * i + 2]) : v3(0.0f, 0.0f, 0.0f);
+    R n = R(1);
+    V s = live ? vec(fitted_head[3 * i], fitted_head[3 * i + 1], fitted_head[3 * i + 2]) : vec(R(0), R(0), R(0));
     for (uint32_t q = 0; q < rounds; ++q) {
         const uint32_t r = r0 + q * AVG_G + sub;
         bool ok = false;
-        float px = 0.0f, py = 0.0f, pz = 0.0f;
+        R px = R(0), py = R(0), pz = R(0);
         if (r < r1 && A.valid[A.rev_owner[r]]) {
-            const float *p = A.fitted + 3ull * A.rev_entry[r];
+            const R *p = A.fitted + 3ull * A.rev_entry[r];
             ok = true; px = p[0]; py = p[1]; pz = p[2];
         }
         const uint32_t okmask = (uint32_t)(__ballot(ok) >> (threadIdx.x / AVG_G * AVG_G)) & 0xffffu;
 #pragma unroll
         for (uint32_t j = 0; j < AVG_G; ++j) {
-            const float x = __shfl(px, (int)j, (int)AVG_G), y = __shfl(py, (int)j, (int)AVG_G), z = __shfl(pz, (int)j, (int)AVG_G);
+            const R x = __shfl(px, (int)j, (int)AVG_G), y = __shfl(py, (int)j, (int)AVG_G), z = __shfl(pz, (int)j, (int)AVG_G);
             const bool take = (okmask >> j) & 1u;
-            const V3 t = s + v3(x, y, z);
-            n = take ? n + 1.0f : n;
+            const V t = s + vec(x, y, z);
+            n = take ? n + R(1) : n;
             s.x = take ? t.x : s.x; s.y = take ? t.y : s.y; s.z = take ? t.z : s.z;
         }
     }
     if (!live) return;
-    const V3 h = v3(s.x / n, s.y / n, s.z / n);
+    const V h = vec(s.x / n, s.y / n, s.z / n);
     if (sub == 0) { A.head[3 * i] = h.x; A.head[3 * i + 1] = h.y; A.head[3 * i + 2] = h.z; }
     const uint64_t slot = A.poff[i] + 4ull * i;
     const uint32_t nv = A.nvert[i];
     for (uint32_t k = sub; k < nv; k += AVG_G) {
-        float *v = A.voro + 3 * (slot + k);
+        R *v = A.voro + 3 * (slot + k);
         v[0] += h.x; v[1] += h.y; v[2] += h.z;
     }
 }
@@ -706,33 +807,35 @@ struct Blob {
     }
 };
 
-}  // namespace
-
-extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membrane_patches *P, const float *box9,
-                                         molar_hip_membrane_state *S) {
+// molar_hip_membrane_smooth / _f64; `what` names the entry in error messages
+template <class R>
+int membrane_smooth(molar_hip_ctx *c, const molar_hip_membrane_patches *P, const R *box9, typename Prec<R>::State *S,
+                    const char *what) {
+    using VertL = typename Prec<R>::VertL;
+    using PtL = typename Prec<R>::PtL;
     if (!c) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context");
     MH_HIP(hipSetDevice(c->device));
-    if (!P || !S || !box9) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: null argument");
+    if (!P || !S || !box9) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", what);
     const size_t K = P->nlipids;
     if (K == 0) return MOLAR_HIP_OK;
     if (!P->patch_offsets || !S->head_markers || !S->normals || !S->valid)
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: null array");
-    if (K >= (1ull << 31)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "membrane_smooth: lipid ids must fit i32 (voronoi_cell.rs:17)");
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null array", what);
+    if (K >= (1ull << 31)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: lipid ids must fit i32 (voronoi_cell.rs:17)", what);
     const size_t E = (size_t)P->patch_offsets[K];
-    if (E && !P->patch_ids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: patch_ids missing");
-    if (E >= (1ull << 32)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "membrane_smooth: %zu patch entries", E);
-    if (P->patch_offsets[0] != 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: patch_offsets[0] != 0");
-    molar_hip_box box;
-    MH_TRY(molar_hip_box_from_matrix(box9, &box));
+    if (E && !P->patch_ids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: patch_ids missing", what);
+    if (E >= (1ull << 32)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: %zu patch entries", what, E);
+    if (P->patch_offsets[0] != 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: patch_offsets[0] != 0", what);
+    typename Prec<R>::Box box;
+    MH_TRY(Prec<R>::box_from_matrix(box9, &box));
     const size_t slots = E + 4 * K;
 
     // transpose of the patch CSR: for each lipid, the patch entries that point at it, ordered by
     // (owner lipid, position in the owner's patch) = the order of the reference's scatter loop
     std::vector<uint32_t> rev_off(K + 1, 0), rev_entry(E), rev_owner(E);
     for (size_t i = 0; i < K; ++i) {
-        if (P->patch_offsets[i + 1] < P->patch_offsets[i]) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: offsets not monotone");
+        if (P->patch_offsets[i + 1] < P->patch_offsets[i]) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: offsets not monotone", what);
         for (uint64_t q = P->patch_offsets[i]; q < P->patch_offsets[i + 1]; ++q) {
-            if (P->patch_ids[q] >= K) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth: patch id %llu out of range", (unsigned long long)P->patch_ids[q]);
+            if (P->patch_ids[q] >= K) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: patch id %llu out of range", what, (unsigned long long)P->patch_ids[q]);
             rev_off[P->patch_ids[q] + 1]++;
         }
     }
@@ -748,49 +851,51 @@ extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membr
     }
 
     // one blob: [in/out state | inputs | device-only work]
+    const size_t r = sizeof(R);
     Blob L;
-    const size_t o_head = L.take(K * 12), o_norm = L.take(K * 12), o_valid = L.take(K), o_coefs = L.take(K * 24),
-                 o_mean = L.take(K * 4), o_gauss = L.take(K * 4), o_pcurv = L.take(K * 8), o_pdirs = L.take(K * 24),
-                 o_area = L.take(K * 4), o_nvert = L.take(K * 4), o_neib = L.take(slots * 8), o_voro = L.take(slots * 12),
-                 o_fitted = L.take(E * 12);
+    const size_t o_head = L.take(K * 3 * r), o_norm = L.take(K * 3 * r), o_valid = L.take(K), o_coefs = L.take(K * 6 * r),
+                 o_mean = L.take(K * r), o_gauss = L.take(K * r), o_pcurv = L.take(K * 2 * r), o_pdirs = L.take(K * 6 * r),
+                 o_area = L.take(K * r), o_nvert = L.take(K * 4), o_neib = L.take(slots * 8), o_voro = L.take(slots * 3 * r),
+                 o_fitted = L.take(E * 3 * r);
     const size_t io_bytes = L.size;
     const size_t o_poff = L.take((K + 1) * 8), o_pids = L.take(E * 8), o_roff = L.take((K + 1) * 4), o_rent = L.take(E * 4),
                  o_rown = L.take(E * 4);
     const size_t up_bytes = L.size;
-    const size_t o_saved = L.take(K * 12), o_fh = L.take(K * 12), o_vwork = L.take(slots * 16), o_pwork = L.take(E * 16 + 16);
+    const size_t o_saved = L.take(K * 3 * r), o_fh = L.take(K * 3 * r), o_vwork = L.take(slots * sizeof(VertL)),
+                 o_pwork = L.take((E + 1) * sizeof(PtL));
     MH_TRY(c->m_partials.reserve(L.size));
     MH_TRY(ensure_pinned(c, up_bytes));
     char *h = (char *)c->h_pinned, *d = c->m_partials.as<char>();
-    auto put = [&](size_t off, const void *src, size_t bytes, bool zero_if_null = true) {
+    auto put = [&](size_t off, const void *src, size_t bytes) {
         if (src) std::memcpy(h + off, src, bytes);
-        else if (zero_if_null) std::memset(h + off, 0, bytes);
+        else std::memset(h + off, 0, bytes);
     };
-    put(o_head, S->head_markers, K * 12); put(o_norm, S->normals, K * 12); put(o_valid, S->valid, K);
-    put(o_coefs, S->quad_coefs, K * 24); put(o_mean, S->mean_curv, K * 4); put(o_gauss, S->gauss_curv, K * 4);
-    put(o_pcurv, S->princ_curvs, K * 8); put(o_pdirs, S->princ_dirs, K * 24); put(o_area, S->area, K * 4);
-    put(o_nvert, S->nvert, K * 4); put(o_neib, S->neib_ids, slots * 8); put(o_voro, S->voro_vertexes, slots * 12);
-    put(o_fitted, S->fitted_patch_points, E * 12);
+    put(o_head, S->head_markers, K * 3 * r); put(o_norm, S->normals, K * 3 * r); put(o_valid, S->valid, K);
+    put(o_coefs, S->quad_coefs, K * 6 * r); put(o_mean, S->mean_curv, K * r); put(o_gauss, S->gauss_curv, K * r);
+    put(o_pcurv, S->princ_curvs, K * 2 * r); put(o_pdirs, S->princ_dirs, K * 6 * r); put(o_area, S->area, K * r);
+    put(o_nvert, S->nvert, K * 4); put(o_neib, S->neib_ids, slots * 8); put(o_voro, S->voro_vertexes, slots * 3 * r);
+    put(o_fitted, S->fitted_patch_points, E * 3 * r);
     put(o_poff, P->patch_offsets, (K + 1) * 8); put(o_pids, P->patch_ids, E * 8);
     put(o_roff, rev_off.data(), (K + 1) * 4); put(o_rent, rev_entry.data(), E * 4); put(o_rown, rev_owner.data(), E * 4);
     {
         Prof span(c, 4);
         MH_HIP(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, c->stream));
-        MH_HIP(hipMemcpyAsync(d + o_saved, d + o_head, K * 12, hipMemcpyDeviceToDevice, c->stream));
-        SmoothDev A;
+        MH_HIP(hipMemcpyAsync(d + o_saved, d + o_head, K * 3 * r, hipMemcpyDeviceToDevice, c->stream));
+        SmoothDevT<R> A;
         A.K = (uint32_t)K;
         A.box = box;
-        A.saved = (const float *)(d + o_saved);
-        A.head = (float *)(d + o_head); A.normals = (float *)(d + o_norm); A.valid = (uint8_t *)(d + o_valid);
+        A.saved = (const R *)(d + o_saved);
+        A.head = (R *)(d + o_head); A.normals = (R *)(d + o_norm); A.valid = (uint8_t *)(d + o_valid);
         A.poff = (const uint64_t *)(d + o_poff); A.pids = (const uint64_t *)(d + o_pids);
-        A.coefs = (float *)(d + o_coefs); A.mean = (float *)(d + o_mean); A.gauss = (float *)(d + o_gauss);
-        A.pcurv = (float *)(d + o_pcurv); A.pdirs = (float *)(d + o_pdirs); A.area = (float *)(d + o_area);
-        A.nvert = (uint32_t *)(d + o_nvert); A.neib = (uint64_t *)(d + o_neib); A.voro = (float *)(d + o_voro);
-        A.fitted = (float *)(d + o_fitted); A.vwork = (float4 *)(d + o_vwork); A.pwork = (float4 *)(d + o_pwork);
+        A.coefs = (R *)(d + o_coefs); A.mean = (R *)(d + o_mean); A.gauss = (R *)(d + o_gauss);
+        A.pcurv = (R *)(d + o_pcurv); A.pdirs = (R *)(d + o_pdirs); A.area = (R *)(d + o_area);
+        A.nvert = (uint32_t *)(d + o_nvert); A.neib = (uint64_t *)(d + o_neib); A.voro = (R *)(d + o_voro);
+        A.fitted = (R *)(d + o_fitted); A.vwork = (VertL *)(d + o_vwork); A.pwork = (PtL *)(d + o_pwork);
         A.rev_off = (const uint32_t *)(d + o_roff); A.rev_entry = (const uint32_t *)(d + o_rent);
         A.rev_owner = (const uint32_t *)(d + o_rown);
         MH_TRY(launch_fit(c, A));
-        MH_HIP(hipMemcpyAsync(d + o_fh, d + o_head, K * 12, hipMemcpyDeviceToDevice, c->stream));
-        hipLaunchKernelGGL(k_membrane_average, dim3((uint32_t)((K + 3) / 4)), dim3(64), 0, c->stream, A, (const float *)(d + o_fh));
+        MH_HIP(hipMemcpyAsync(d + o_fh, d + o_head, K * 3 * r, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(k_membrane_average<R>, dim3((uint32_t)((K + 3) / 4)), dim3(64), 0, c->stream, A, (const R *)(d + o_fh));
         MH_HIP(hipGetLastError());
         MH_HIP(hipMemcpyAsync(h, d, io_bytes, hipMemcpyDeviceToHost, c->stream));
     }
@@ -798,14 +903,72 @@ extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membr
     auto get = [&](void *dst, size_t off, size_t bytes) {
         if (dst) std::memcpy(dst, h + off, bytes);
     };
-    get(S->head_markers, o_head, K * 12); get(S->normals, o_norm, K * 12); get(S->valid, o_valid, K);
-    get(S->quad_coefs, o_coefs, K * 24); get(S->mean_curv, o_mean, K * 4); get(S->gauss_curv, o_gauss, K * 4);
-    get(S->princ_curvs, o_pcurv, K * 8); get(S->princ_dirs, o_pdirs, K * 24); get(S->area, o_area, K * 4);
-    get(S->nvert, o_nvert, K * 4); get(S->neib_ids, o_neib, slots * 8); get(S->voro_vertexes, o_voro, slots * 12);
-    get(S->fitted_patch_points, o_fitted, E * 12);
+    get(S->head_markers, o_head, K * 3 * r); get(S->normals, o_norm, K * 3 * r); get(S->valid, o_valid, K);
+    get(S->quad_coefs, o_coefs, K * 6 * r); get(S->mean_curv, o_mean, K * r); get(S->gauss_curv, o_gauss, K * r);
+    get(S->princ_curvs, o_pcurv, K * 2 * r); get(S->princ_dirs, o_pdirs, K * 6 * r); get(S->area, o_area, K * r);
+    get(S->nvert, o_nvert, K * 4); get(S->neib_ids, o_neib, slots * 8); get(S->voro_vertexes, o_voro, slots * 3 * r);
+    get(S->fitted_patch_points, o_fitted, E * 3 * r);
     return MOLAR_HIP_OK;
 }
 
+// compute_initial_normals (lib.rs:456-505), host-only, the reference's loop order; `what` names the entry in error messages
+template <class R>
+int initial_normals(size_t K, const R *head, const R *tail, const uint64_t *poff, const uint64_t *pids, const uint8_t *valid,
+                    R *normals, const char *what) {
+    if (!head || !tail || !poff || !normals) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", what);
+    if (poff[K] && !pids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: patch_ids missing", what);
+    for (size_t i = 0; i < K; ++i) {
+        if (poff[i + 1] < poff[i]) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: offsets not monotone", what);
+        for (uint64_t q = poff[i]; q < poff[i + 1]; ++q)
+            if (pids[q] >= K) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: patch id %llu out of range", what, (unsigned long long)pids[q]);
+    }
+    struct V { R x, y, z; };
+    auto nrm = [](V a) { return std::sqrt((a.x * a.x + a.y * a.y) + a.z * a.z); };
+    auto unit = [&](V a) { const R n = nrm(a); return V{a.x / n, a.y / n, a.z / n}; };
+    // nalgebra Vector::angle with the two norms handed in: they are functions of one vector each, so computing
+    // them once per lipid instead of once per pair gives the same bits
+    const R half_pi = R(1.57079632679489661923);
+    // "angle <= FRAC_PI_2" (lib.rs:472-473, 494).  acos is only evaluated when the cosine is within 1e-6 of zero: acos is
+    // monotone, and outside that band it is more than 1e-6 away from pi/2, far beyond the spacing of either precision there
+    // (1.2e-7 in f32, 2.2e-16 in f64), so the comparison cannot depend on how acos rounds
+    auto within_half_pi = [&](V a, R n1, V b, R n2) {
+        if (n1 == R(0) || n2 == R(0)) return true;               // Vector::angle returns 0
+        R cc = ((a.x * b.x + a.y * b.y) + a.z * b.z) / (n1 * n2);
+        if (cc > R(1.0e-6)) return true;
+        if (cc < R(-1.0e-6)) return false;
+        cc = cc < R(-1) ? R(-1) : (cc > R(1) ? R(1) : cc);       // NaN falls through to acos like the reference
+        return std::acos(cc) <= half_pi;
+    };
+    std::vector<V> thv(K), nv(K);
+    std::vector<R> len(K);
+    auto ok = [&](size_t i) { return !valid || valid[i]; };
+    for (size_t i = 0; i < K; ++i) {
+        thv[i] = V{0, 0, 0};
+        nv[i] = V{normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]};
+        if (ok(i)) thv[i] = unit(V{head[3 * i] - tail[3 * i], head[3 * i + 1] - tail[3 * i + 1], head[3 * i + 2] - tail[3 * i + 2]});
+    }
+    for (int pass = 0; pass < 2; ++pass) {
+        const std::vector<V> &src = pass == 0 ? thv : nv;   // pass 2 reads normals already updated for l < i
+        for (size_t i = 0; i < K; ++i) len[i] = nrm(src[i]);
+        for (size_t i = 0; i < K; ++i) {
+            if (!ok(i)) continue;
+            const V self = src[i];
+            const R nself = len[i];
+            V sum{0, 0, 0};
+            for (uint64_t q = poff[i]; q < poff[i + 1]; ++q) {
+                const V o = src[pids[q]];
+                if (within_half_pi(o, len[pids[q]], self, nself)) { sum.x += o.x; sum.y += o.y; sum.z += o.z; }
+            }
+            sum.x += self.x; sum.y += self.y; sum.z += self.z;   // .chain(once(central))
+            nv[i] = unit(sum);
+            if (pass == 1) len[i] = nrm(nv[i]);                  // src aliases nv in pass 2: keep its norm current
+        }
+    }
+    for (size_t i = 0; i < K; ++i) {
+        normals[3 * i] = nv[i].x; normals[3 * i + 1] = nv[i].y; normals[3 * i + 2] = nv[i].z;
+    }
+    return MOLAR_HIP_OK;
+}
 
 // ================================================================ neighbour shells (host arithmetic)
 //
@@ -814,9 +977,6 @@ extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membr
 // neighbours of every member (so from n = 3 on a lipid is a member of its own set - the reference's HashSet picks it up on
 // the way back, and so does this).  The reference iterates a HashSet, whose order is unspecified; here members are in
 // ascending lipid id.  Graph bookkeeping over a few thousand short lists per frame: host loops, like the reference's.
-// (namespace mh: membrane_f64.hip walks the same shells for its smooth_curvature)
-
-namespace mh {
 
 // members of lipid i's n-th shell, ascending; `stamp` (K entries, values < 2 * (i + 1) on entry) marks membership
 void nth_shell_of(size_t i, size_t n_shells, const uint64_t *slot_off, const uint32_t *nvert, const uint64_t *neib, size_t K,
@@ -858,7 +1018,53 @@ int check_shell_args(size_t K, const uint8_t *valid, const uint64_t *patch_offse
     return 0;
 }
 
-}  // namespace mh
+// smooth_curvature (lib.rs:584-621): sums in R, in ascending member id, from the values before the call
+template <class R>
+int smooth_curvature(size_t K, const uint8_t *valid, const uint64_t *patch_offsets, const uint32_t *nvert, const uint64_t *neib_ids,
+                     size_t n_shells, R *mean_curv, R *gauss_curv, const char *what) {
+    MH_TRY(check_shell_args(K, valid, patch_offsets, nvert, neib_ids, what));
+    if (!mean_curv || !gauss_curv) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", what);
+    if (n_shells < 1) return MOLAR_HIP_OK;                         // lib.rs:585-587
+    const std::vector<R> mean(mean_curv, mean_curv + K), gauss(gauss_curv, gauss_curv + K);      // the values before smoothing (:589-590)
+    std::vector<uint32_t> stamp(K, 0u), members, frontier;
+    for (size_t i = 0; i < K; ++i) {
+        if (!valid[i]) continue;
+        nth_shell_of(i, n_shells, patch_offsets, nvert, neib_ids, K, stamp, members, frontier);
+        R m = R(0), g = R(0);
+        uint32_t n_valid = 0;
+        for (uint32_t id : members) {
+            if (!valid[id]) continue;
+            m += mean[id];
+            g += gauss[id];
+            ++n_valid;
+        }
+        mean_curv[i] = (mean[i] + m) / (R)(n_valid + 1u);
+        gauss_curv[i] = (gauss[i] + g) / (R)(n_valid + 1u);
+    }
+    return MOLAR_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" int molar_hip_membrane_smooth(molar_hip_ctx *c, const molar_hip_membrane_patches *P, const float *box9,
+                                         molar_hip_membrane_state *S) {
+    return membrane_smooth(c, P, box9, S, "membrane_smooth");
+}
+
+extern "C" int molar_hip_membrane_smooth_f64(molar_hip_ctx *c, const molar_hip_membrane_patches *P, const double *box9,
+                                             molar_hip_membrane_state_f64 *S) {
+    return membrane_smooth(c, P, box9, S, "membrane_smooth_f64");
+}
+
+extern "C" int molar_hip_membrane_initial_normals(size_t K, const float *head, const float *tail, const uint64_t *poff,
+                                                  const uint64_t *pids, const uint8_t *valid, float *normals) {
+    return initial_normals(K, head, tail, poff, pids, valid, normals, "initial_normals");
+}
+
+extern "C" int molar_hip_membrane_initial_normals_f64(size_t K, const double *head, const double *tail, const uint64_t *poff,
+                                                      const uint64_t *pids, const uint8_t *valid, double *normals) {
+    return initial_normals(K, head, tail, poff, pids, valid, normals, "initial_normals_f64");
+}
 
 extern "C" int molar_hip_membrane_nth_shell_patches(size_t K, const uint8_t *valid, const uint64_t *patch_offsets, const uint64_t *patch_ids,
                                                     const uint32_t *nvert, const uint64_t *neib_ids, size_t n_shells,
@@ -891,27 +1097,15 @@ extern "C" int molar_hip_membrane_nth_shell_patches(size_t K, const uint8_t *val
 
 extern "C" int molar_hip_membrane_smooth_curvature(size_t K, const uint8_t *valid, const uint64_t *patch_offsets, const uint32_t *nvert,
                                                    const uint64_t *neib_ids, size_t n_shells, float *mean_curv, float *gauss_curv) {
-    MH_TRY(check_shell_args(K, valid, patch_offsets, nvert, neib_ids, "membrane_smooth_curvature"));
-    if (!mean_curv || !gauss_curv) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "membrane_smooth_curvature: null argument");
-    if (n_shells < 1) return MOLAR_HIP_OK;                         // lib.rs:585-587
-    const std::vector<float> mean(mean_curv, mean_curv + K), gauss(gauss_curv, gauss_curv + K);      // the values before smoothing (:589-590)
-    std::vector<uint32_t> stamp(K, 0u), members, frontier;
-    for (size_t i = 0; i < K; ++i) {
-        if (!valid[i]) continue;
-        nth_shell_of(i, n_shells, patch_offsets, nvert, neib_ids, K, stamp, members, frontier);
-        float m = 0.0f, g = 0.0f;
-        uint32_t n_valid = 0;
-        for (uint32_t id : members) {
-            if (!valid[id]) continue;
-            m += mean[id];
-            g += gauss[id];
-            ++n_valid;
-        }
-        mean_curv[i] = (mean[i] + m) / (float)(n_valid + 1u);
-        gauss_curv[i] = (gauss[i] + g) / (float)(n_valid + 1u);
-    }
-    return MOLAR_HIP_OK;
+    return smooth_curvature(K, valid, patch_offsets, nvert, neib_ids, n_shells, mean_curv, gauss_curv, "membrane_smooth_curvature");
 }
+
+extern "C" int molar_hip_membrane_smooth_curvature_f64(size_t K, const uint8_t *valid, const uint64_t *patch_offsets,
+                                                       const uint32_t *nvert, const uint64_t *neib_ids, size_t n_shells,
+                                                       double *mean_curv, double *gauss_curv) {
+    return smooth_curvature(K, valid, patch_offsets, nvert, neib_ids, n_shells, mean_curv, gauss_curv, "membrane_smooth_curvature_f64");
+}
+
 
 // ================================================================ one whole frame of Membrane::compute on the stream
 //
@@ -1134,7 +1328,7 @@ __global__ __launch_bounds__(256) void k_normals_pass1(uint32_t K, const uint8_t
 // ids.  With ids laid out along a periodic lattice that chain is K/2 links long, and a link costs a GPU microseconds
 // (a dependency-driven kernel, 16 lanes per lipid, normals and flags in LDS: bit-identical, 10.3 ms for 4000 lipids)
 // where a CPU core takes 50 ns.  So this pass - and only this one - runs on the host, between two halves of the frame.
-// Same arithmetic as molar_hip_membrane_initial_normals (measure.hip).
+// Same arithmetic as molar_hip_membrane_initial_normals (initial_normals above).
 void normals_pass2_host(size_t K, const uint32_t *poff, const uint32_t *pids, const uint8_t *valid, const float *n1, float *nv,
                         std::vector<float> &len) {
     const float half_pi = 1.57079632679489661923f;

@@ -3,8 +3,6 @@
 // smoothing -> order, a single wait at the end).  Every pointer is device memory; nothing here synchronises.
 #pragma once
 
-#include <vector>
-
 #include "common.hpp"
 
 namespace mh {
@@ -47,12 +45,5 @@ int device_sort_pairs_u32(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *keys_in
                           uint32_t *vals_out, size_t n, int end_bit);
 int device_exclusive_sum_u32(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *in, uint32_t *out, size_t n);
 int device_exclusive_sum_u32_u64(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *in, unsigned long long *out, size_t n);
-
-// membrane.hip, host arithmetic shared with membrane_f64.hip: members of lipid i's n-th Voronoi neighbour shell, ascending
-// (`stamp`: K entries, values < i + 1 on entry), and the argument checks of the shell entries (`what` names the caller)
-void nth_shell_of(size_t i, size_t n_shells, const uint64_t *slot_off, const uint32_t *nvert, const uint64_t *neib, size_t K,
-                  std::vector<uint32_t> &stamp, std::vector<uint32_t> &members, std::vector<uint32_t> &frontier);
-int check_shell_args(size_t K, const uint8_t *valid, const uint64_t *patch_offsets, const uint32_t *nvert, const uint64_t *neib_ids,
-                     const char *what);
 
 }  // namespace mh

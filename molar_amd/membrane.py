@@ -257,45 +257,47 @@ class Membrane:
         return res
 
     def compute(self, xyz, box):
-        """One frame (Membrane::compute, lib.rs:410-454).  xyz: float32 [N,3] (numpy; unwrapped in place when
-        options.unwrap).  Returns a dict: markers, patch CSR, per-lipid state (valid, normals, curvatures, area,
-        Voronoi neighbours/vertices) and order: list over tails of [K, n_t-2]."""
+        """One frame (Membrane::compute, lib.rs:410-454).  xyz: float32 [N,3] (float64 for precision f64; numpy, unwrapped
+        in place when options.unwrap).  Returns a dict: markers, patch CSR, per-lipid state (valid, normals, curvatures,
+        area, Voronoi neighbours/vertices) and order: list over tails of [K, n_t-2]."""
         self._check_frame(xyz)
-        if self.precision == "f64":
-            return self._compute_f64(xyz, box)
         if self.fusable():
             return self.compute_end(self.compute_begin(xyz, box))
-        e, K, opt = self.eng, self.K, self.opt
-        pb = box if isinstance(box, api.PeriodicBox) else api.PeriodicBox.from_matrix(box)
+        # the staged loop: f32 through the engine, f64 through its _f64 entries (MeasureF64, search_f64)
+        e, K, opt, real = self.eng, self.K, self.opt, self.real
+        if self.precision == "f64":
+            if getattr(self, "_m64", None) is None:
+                self._m64 = api.MeasureF64(e)
+            meas = self._m64
+            pb = np.asarray(box.get_matrix() if isinstance(box, api.PeriodicBox) else box, np.float64)
+        else:
+            meas = e
+            pb = box if isinstance(box, api.PeriodicBox) else api.PeriodicBox.from_matrix(box)
         cst = self._constants(xyz)
         if opt.unwrap:                                                          # lipid_molecule.rs:75-76
-            e.unwrap_simple_batch(xyz, cst["lipid_idx"], self.lipid_off, pb)
-        mk = e.center_batch(xyz, cst["marker_idx"], self.marker_off, cst["masses"]).reshape(K, 3, 3)
+            meas.unwrap_simple_batch(xyz, cst["lipid_idx"], self.lipid_off, pb)
+        mk = meas.center_batch(xyz, cst["marker_idx"], self.marker_off, cst["masses"]).reshape(K, 3, 3)
         head, mid, tail = mk[:, 0].copy(), mk[:, 1].copy(), mk[:, 2].copy()
-        # compute_patches (lib.rs:539-558): search among the valid lipids' head markers, ids = lipid ids
-        vidx = np.flatnonzero(self.valid).astype(np.uint64)
-        n = e.search_count(api.SEARCH_SINGLE, opt.cutoff, head, idx1=vidx, box=pb, pbc=api.PBC_FULL, ids_local=False)
-        pairs, _ = e.search_fill(n)
-        patch_off, patch_ids = api.membrane_patches_from_pairs(pairs, K)
+        patch_off, patch_ids = api.membrane_patches_from_pairs(self._marker_pairs(head, pb), K)
         normals = api.membrane_initial_normals(head, tail, patch_off, patch_ids, valid=self.valid)
-        st = api.new_membrane_state(head, normals, self.valid, len(patch_ids))
+        st = api.new_membrane_state(head, normals, self.valid, len(patch_ids), dtype=real)
         it = 0
         while True:                                                             # lib.rs:417-432 (at least one pass)
             if opt.n_shells_patch > 0 and it == 0:
-                e.membrane_smooth(pb, st, patch_off, patch_ids)
+                meas.membrane_smooth(pb, st, patch_off, patch_ids)
                 # patches_from_nth_shell (lib.rs:562-583); the slots of neib_ids follow the patch lists they were made with
                 patch_off, patch_ids = api.membrane_nth_shell_patches(st["valid"], patch_off, patch_ids, st["nvert"], st["neib_ids"],
                                                                       opt.n_shells_patch)
-            e.membrane_smooth(pb, st, patch_off, patch_ids)
+            meas.membrane_smooth(pb, st, patch_off, patch_ids)
             it += 1
             if it >= opt.max_smooth_iter:
                 break
         self.valid[:] = st["valid"]
         # compute_order (lib.rs:435-443): one normal per lipid (or the global one), shared by its tails
-        nl = st["normals"] if opt.global_normal is None else np.tile(np.asarray(opt.global_normal, np.float32), (K, 1))
+        nl = st["normals"] if opt.global_normal is None else np.tile(np.asarray(opt.global_normal, real), (K, 1))
         nrm = np.repeat(nl, self.ntails, axis=0)
         noff = np.arange(K * self.ntails + 1, dtype=np.uint64)
-        flat = e.lipid_tail_order_csr(xyz, cst["tail_idx"], self.tail_off, opt.order_type, nrm, noff, cst["tail_bonds"])
+        flat = meas.lipid_tail_order_csr(xyz, cst["tail_idx"], self.tail_off, opt.order_type, nrm, noff, cst["tail_bonds"])
         per_lipid = sum(l - 2 for l in self.tail_lens)
         flat = flat.reshape(K, per_lipid)
         out, pos = [], 0
@@ -310,11 +312,23 @@ class Membrane:
                   "voro_vertexes", "fitted_patch_points"):
             res[k] = st[k]
         if self.groups:                                                         # lib.rs:448-451
-            d = (head - tail).astype(np.float32)
-            thv = d / np.sqrt((d * d).sum(1, dtype=np.float32))[:, None]        # tail_head_vec (lib.rs:459-461)
+            d = (head - tail).astype(real)
+            thv = d / np.sqrt((d * d).sum(1, dtype=real))[:, None]              # tail_head_vec (lib.rs:459-461)
             for g in self.groups.values():
                 g.frame_update(res, self.species_of_lipid, thv)
         return res
+
+    def _marker_pairs(self, head, pb):
+        """compute_patches (lib.rs:539-558): the pairs of the search among the valid lipids' head markers, ids = lipid ids,
+        as uint32 [n, 2] (the f64 search for precision f64)."""
+        e, opt = self.eng, self.opt
+        vidx = np.flatnonzero(self.valid).astype(np.uint64)
+        if self.precision == "f64":
+            i, j, _ = e.search_f64(api.SEARCH_SINGLE, opt.cutoff, head, idx1=vidx, box=pb, pbc=api.PBC_FULL, ids_local=False)
+            return np.stack([i, j], 1).astype(np.uint32)
+        n = e.search_count(api.SEARCH_SINGLE, opt.cutoff, head, idx1=vidx, box=pb, pbc=api.PBC_FULL, ids_local=False)
+        pairs, _ = e.search_fill(n)
+        return pairs
 
     def _check_frame(self, xyz):
         """A frame in the membrane's precision (float32 / float64, numpy or torch): never cast silently."""
@@ -322,57 +336,3 @@ class Membrane:
         want = "float64" if self.precision == "f64" else "float32"
         if dt != want:
             raise TypeError(f"a Membrane of precision {self.precision} takes {want} coordinates, not {dt}")
-
-    def _compute_f64(self, xyz, box):
-        """compute() in f64: the staged loop above through the engine's _f64 entries (unwrap, markers, marker search, patches,
-        initial normals, smoothing passes with the n-th shell options, tail order, curvature shells); float64 results."""
-        e, K, opt = self.eng, self.K, self.opt
-        if getattr(self, "_m64", None) is None:
-            self._m64 = api.MeasureF64(e)
-        m64 = self._m64
-        box = np.asarray(box.get_matrix() if isinstance(box, api.PeriodicBox) else box, np.float64)
-        cst = self._constants(xyz)
-        if opt.unwrap:                                                          # lipid_molecule.rs:75-76
-            m64.unwrap_simple_batch(xyz, cst["lipid_idx"], self.lipid_off, box)
-        mk = m64.center_batch(xyz, cst["marker_idx"], self.marker_off, cst["masses"]).reshape(K, 3, 3)
-        head, mid, tail = mk[:, 0].copy(), mk[:, 1].copy(), mk[:, 2].copy()
-        # compute_patches (lib.rs:539-558): the f64 search among the valid lipids' head markers, ids = lipid ids
-        vidx = np.flatnonzero(self.valid).astype(np.uint64)
-        i, j, _ = e.search_f64(api.SEARCH_SINGLE, opt.cutoff, head, idx1=vidx, box=box, pbc=api.PBC_FULL, ids_local=False)
-        patch_off, patch_ids = api.membrane_patches_from_pairs(np.stack([i, j], 1).astype(np.uint32), K)
-        normals = api.membrane_initial_normals(head, tail, patch_off, patch_ids, valid=self.valid)
-        st = api.new_membrane_state(head, normals, self.valid, len(patch_ids), dtype=np.float64)
-        it = 0
-        while True:                                                             # lib.rs:417-432 (at least one pass)
-            if opt.n_shells_patch > 0 and it == 0:
-                m64.membrane_smooth(box, st, patch_off, patch_ids)
-                patch_off, patch_ids = api.membrane_nth_shell_patches(st["valid"], patch_off, patch_ids, st["nvert"], st["neib_ids"],
-                                                                      opt.n_shells_patch)
-            m64.membrane_smooth(box, st, patch_off, patch_ids)
-            it += 1
-            if it >= opt.max_smooth_iter:
-                break
-        self.valid[:] = st["valid"]
-        # compute_order (lib.rs:435-443): one normal per lipid (or the global one), shared by its tails
-        nl = st["normals"] if opt.global_normal is None else np.tile(np.asarray(opt.global_normal, np.float64), (K, 1))
-        nrm = np.repeat(nl, self.ntails, axis=0)
-        noff = np.arange(K * self.ntails + 1, dtype=np.uint64)
-        flat = m64.lipid_tail_order_csr(xyz, cst["tail_idx"], self.tail_off, opt.order_type, nrm, noff, cst["tail_bonds"])
-        flat = flat.reshape(K, sum(l - 2 for l in self.tail_lens))
-        out, pos = [], 0
-        for l in self.tail_lens:
-            out.append(flat[:, pos:pos + l - 2].copy()); pos += l - 2
-        if opt.n_shells_smoothing > 0:              # smooth_curvature (lib.rs:584-621)
-            st["mean_curv"], st["gauss_curv"] = api.membrane_smooth_curvature(st["valid"], patch_off, st["nvert"], st["neib_ids"],
-                                                                              opt.n_shells_smoothing, st["mean_curv"], st["gauss_curv"])
-        res = dict(head=head, mid=mid, tail=tail, patch_off=patch_off, patch_ids=patch_ids, normals=st["normals"],
-                   initial_normals=normals, order=out, valid=st["valid"].copy(), smoothed_head=st["head_markers"])
-        for k in ("quad_coefs", "mean_curv", "gauss_curv", "princ_curvs", "princ_dirs", "area", "nvert", "neib_ids",
-                  "voro_vertexes", "fitted_patch_points"):
-            res[k] = st[k]
-        if self.groups:                                                         # lib.rs:448-451
-            d = head - tail
-            thv = d / np.sqrt((d * d).sum(1))[:, None]                          # tail_head_vec (lib.rs:459-461)
-            for g in self.groups.values():
-                g.frame_update(res, self.species_of_lipid, thv)
-        return res

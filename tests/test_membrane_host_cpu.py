@@ -108,6 +108,29 @@ def test_initial_normals_at_exactly_ninety_degrees():
     assert np.allclose(got[1], [s, 0, s], atol=1e-6)
 
 
+def test_initial_normals_reject_bad_arguments():
+    """The f32 twin of the f64 argument test: a null argument, an out-of-range id and non-monotone offsets are refused
+    before anything is read."""
+    from molar_amd import _lib
+    lib = _lib.load()
+    ERR_INVALID_ARGUMENT = 50
+    K = 3
+    head = np.zeros((K, 3), np.float32); tail = np.ones((K, 3), np.float32); out = np.zeros((K, 3), np.float32)
+    off = np.array([0, 1, 2, 3], np.uint64); ids = np.array([1, 2, 0], np.uint64)
+    P = lambda a: a.ctypes.data
+    assert lib.molar_hip_membrane_initial_normals(K, None, P(tail), P(off), P(ids), None, P(out)) == ERR_INVALID_ARGUMENT
+    assert "null" in _lib.last_error()
+    bad = np.array([1, 2, 7], np.uint64)
+    assert lib.molar_hip_membrane_initial_normals(K, P(head), P(tail), P(off), P(bad), None, P(out)) == ERR_INVALID_ARGUMENT
+    assert "out of range" in _lib.last_error()
+    with pytest.raises(MolarHipError):
+        api.membrane_initial_normals(head, tail, off, bad)
+    backwards = np.array([0, 2, 1, 3], np.uint64)
+    assert lib.molar_hip_membrane_initial_normals(K, P(head), P(tail), P(backwards), P(ids), None, P(out)) == ERR_INVALID_ARGUMENT
+    assert "monotone" in _lib.last_error()
+    assert not out.any()
+
+
 def random_neighbour_state(rng, K):
     """A Voronoi-like neighbour graph in the slotted layout of molar_hip_membrane_state: lipid i owns slots
     [patch_off[i] + 4 i, ...) of neib_ids and fills the first nvert[i]."""

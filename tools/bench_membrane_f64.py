@@ -2,7 +2,7 @@
 """The f64 membrane pass at C5 size (BASELINE.json configs[4]: build_bilayer(2000, 500_000), 4000 lipids, frames resident in
 HBM, one context): Membrane(precision="f64").compute (the staged loop, MolAR's `f64` feature) beside the f32 staged and
 chained forms in the same run, for the default options and the (n_shells_patch, n_shells_smoothing) = (2,0) and (3,2)
-shells.  Prints one JSON line per variant.  Kernel times (k_membrane_fit64 beside k_membrane_fit / _fit_lanes) come from a
+shells.  Prints one JSON line per variant.  Kernel times (k_membrane_fit<double> and k_membrane_average<double> beside their f32 instances and k_membrane_fit_lanes) come from a
 run under the tracer:
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python tools/bench_membrane_f64.py
 Usage: python tools/bench_membrane_f64.py   (FRAMES=20 timed frames per variant after two warm-up frames)"""
