@@ -312,6 +312,28 @@ int molar_hip_search_count_f64(molar_hip_ctx *ctx, const molar_hip_search_desc_f
 int molar_hip_search_fill_f64(molar_hip_ctx *ctx, uint64_t *i, uint64_t *j, double *dist);
 int molar_hip_search_fill_ids_f64(molar_hip_ctx *ctx, uint64_t *ids);
 int molar_hip_search_grid_dims_f64(molar_hip_ctx *ctx, uint64_t dims[3]);
+/* The consumer-fused histogram in f64 (molar_hip_search_histogram with every operation in double): the pairs and distances
+ * molar_hip_search_count_f64 + _fill_f64 report for the same request (kinds SINGLE, DOUBLE, DOUBLE_VDW; WITHIN is
+ * INVALID_ARGUMENT), each distance through the f64 Histogram1D::add_one (stats.rs:29-35): b = floor(n*(d-min)/(max-min)),
+ * kept if 0 <= b < n.  One pass, no pair list.  bins: uint64[nbins] in host or device memory, accumulated INTO; nbins in
+ * 1..8192 and finite min < max, else INVALID_ARGUMENT.  out_count (may be NULL): pairs within the cutoff, binned or not
+ * (= search_count_f64's count).  With device bins and out_count == NULL the call may return before the kernel ends
+ * (molar_hip_synchronize before reading the bins); otherwise it waits.  A histogram call invalidates the cached f64
+ * search: fill_f64 / fill_ids_f64 / grid_dims_f64 then return NO_SEARCH until the next search_count_f64. */
+int molar_hip_search_histogram_f64(molar_hip_ctx *ctx, const molar_hip_search_desc_f64 *desc, double hmin, double hmax,
+                                   size_t nbins, uint64_t *bins, uint64_t *out_count);
+/* The same for a block of frames: frame k at desc->xyz1 + k * xyz1_stride doubles (second set: xyz2 + k * xyz2_stride), its
+ * box at boxes9 + 9 k (NULL: desc->box9 for every frame).  The sums equal those of nframes calls of
+ * molar_hip_search_histogram_f64; the frames are walked one after the other.  With device bins the call may return before
+ * the last kernel ends. */
+int molar_hip_search_histogram_frames_f64(molar_hip_ctx *ctx, const molar_hip_search_desc_f64 *desc, size_t nframes,
+                                          size_t xyz1_stride, size_t xyz2_stride, const double *boxes9,
+                                          double hmin, double hmax, size_t nbins, uint64_t *bins);
+/* Host arithmetic, no GPU: the f64 twin of molar_hip_histogram_edges.  edges[b], b = 0..nbins (nbins + 1 doubles), is the
+ * smallest non-negative double d2 whose bin floor(n*(sqrt(d2)-min)/(max-min)) is >= b, found by bisection over the ordered
+ * bit patterns of the non-negative doubles with the formula itself, so "largest b with edges[b] <= d2" IS the formula.
+ * INVALID_ARGUMENT unless min < max, both finite (and max - min finite), and nbins > 0. */
+int molar_hip_histogram_edges_f64(double hmin, double hmax, size_t nbins, double *edges);
 
 /* ------------------------------------------------------------------ Measure (measure.rs) */
 

@@ -384,40 +384,7 @@ class Engine:
         Coordinates, indices and radii may be torch tensors in HBM (used in place); device_out=True leaves the result
         there too (int64 / int64 / float64 tensors); `out` = (i, j, d) device tensors of at least the result's length to fill
         instead of fresh ones (views of the result's length are returned)."""
-        def f64(a):
-            if a is None:
-                return None
-            if hasattr(a, "data_ptr"):          # a torch tensor in HBM is used in place (float64, contiguous)
-                if str(a.dtype) != "torch.float64" or not a.is_contiguous():
-                    raise TypeError("search_f64: device tensors must be contiguous float64")
-                return a
-            return np.ascontiguousarray(a, np.float64)
-
-        def addr(a):
-            return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
-        xyz1, xyz2, vdw1, vdw2 = f64(xyz1), f64(xyz2), f64(vdw1), f64(vdw2)
-        idx1 = idx1 if hasattr(idx1, "data_ptr") else _u64(idx1)       # (device index tensors: int64)
-        idx2 = idx2 if hasattr(idx2, "data_ptr") else _u64(idx2)
-        d = SearchDescF64()
-        d.kind = kind
-        d.cutoff = float(cutoff) if cutoff is not None else 0.0
-        keep = [xyz1, xyz2, vdw1, vdw2, idx1, idx2]
-        for name, arr in (("xyz1", xyz1), ("idx1", idx1), ("xyz2", xyz2), ("idx2", idx2), ("vdw1", vdw1), ("vdw2", vdw2)):
-            setattr(d, name, addr(arr))
-        d.natoms1 = 0 if xyz1 is None else xyz1.reshape(-1, 3).shape[0]
-        d.natoms2 = 0 if xyz2 is None else xyz2.reshape(-1, 3).shape[0]
-        d.n1 = 0 if idx1 is None else idx1.shape[0]
-        d.n2 = 0 if idx2 is None else idx2.shape[0]
-        d.ids_local = 1 if ids_local else 0
-        if box is not None:
-            b9 = np.ascontiguousarray(np.asarray(box, np.float64).T).reshape(9)      # column-major: columns a, b, c
-            keep.append(b9)
-            d.box9 = b9.ctypes.data
-            d.pbc = int(pbc)
-        if lower is not None:
-            lo, up = f64(lower), f64(upper)
-            keep += [lo, up]
-            d.lower3, d.upper3 = lo.ctypes.data, up.ctypes.data
+        d, keep = _search_desc_f64(kind, cutoff, xyz1, idx1, xyz2, idx2, box, pbc, vdw1, vdw2, ids_local, lower, upper)
         n = C.c_uint64()
         check(self.lib.molar_hip_search_count_f64(self.ctx, C.byref(d), C.byref(n)))
         n = int(n.value)
@@ -446,6 +413,77 @@ class Engine:
         i = np.empty(n, np.uint64); j = np.empty(n, np.uint64); dist = np.empty(n, np.float64)
         check(self.lib.molar_hip_search_fill_f64(self.ctx, i.ctypes.data, j.ctypes.data, dist.ctypes.data))
         return i, j, dist
+
+    def search_histogram_f64(self, kind, cutoff, hmin, hmax, nbins, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0,
+                             vdw1=None, vdw2=None, bins=None, want_count=True):
+        """molar_hip_search_histogram_f64: the fused histogram with every operation in double - the pairs and distances of
+        search_f64 for the same request, each through the f64 Histogram1D::add_one, no pair list.  Inputs as for search_f64
+        (float64 numpy or CUDA tensors, used in place; `box` a 3x3 matrix with the box vectors as columns).  `bins`
+        (uint64[nbins] numpy or an int64 CUDA tensor) is accumulated into.  Returns (bins, number_of_pairs); with device bins
+        and want_count=False the call may return before the GPU is done (count None): synchronize() before reading.  The
+        call invalidates the cached f64 search."""
+        d, keep = _search_desc_f64(kind, cutoff, xyz1, idx1, xyz2, idx2, box, pbc, vdw1, vdw2)
+        if bins is None:
+            bins = np.zeros(nbins, np.uint64)
+        ba, kb = _addr(bins)
+        cnt = C.c_uint64(0)
+        check(self.lib.molar_hip_search_histogram_f64(self.ctx, C.byref(d), float(hmin), float(hmax), int(nbins), ba,
+                                                      C.byref(cnt) if want_count else None))
+        self._keep = keep + [kb]
+        return bins, (int(cnt.value) if want_count else None)
+
+    def search_histogram_frames_f64(self, kind, cutoff, hmin, hmax, nbins, frames, idx1=None, box=None, pbc=0, bins=None,
+                                    frames2=None, idx2=None):
+        """molar_hip_search_histogram_frames_f64: `frames` = [nframes, natoms, 3] float64 (numpy, or a CUDA tensor - a window
+        of a larger buffer with a gap between frames is passed without a copy) through the f64 fused histogram; the same sums
+        as nframes calls of search_histogram_f64.  `box`: one 3x3 matrix for all frames or [nframes, 3, 3] (box vectors as
+        columns).  SEARCH_DOUBLE / _VDW: the second set is `idx2` of `frames2` (None: of the same frames).  With device bins
+        the call may return before the GPU is done: synchronize() before reading."""
+        def block(fr):
+            if _is_torch(fr) and fr.ndim == 3 and fr.stride(2) == 1 and fr.stride(1) == 3:
+                import torch
+                if fr.dtype != torch.float64:
+                    raise TypeError("search_histogram_frames_f64: frames must be float64")
+                return fr, fr.data_ptr(), fr, int(fr.stride(0))
+            if _is_torch(fr):
+                fr = _f64(fr)
+                return fr, fr.data_ptr(), fr, int(fr.shape[1]) * 3
+            fr = np.ascontiguousarray(fr, np.float64)
+            return fr, fr.ctypes.data, fr, int(fr.shape[1]) * 3
+        frames, fa, k1, stride = block(frames)
+        if frames.ndim != 3 or frames.shape[2] != 3:
+            raise ValueError("search_histogram_frames_f64: frames must be [nframes, natoms, 3]")
+        nframes = int(frames.shape[0])
+        two = kind in (SEARCH_DOUBLE, SEARCH_DOUBLE_VDW)
+        f2, stride2 = None, 0
+        if two:
+            f2, fa2, k2, stride2 = block(frames if frames2 is None else frames2)
+            if int(f2.shape[0]) != nframes:
+                raise ValueError("search_histogram_frames_f64: frames2 must have as many frames as frames")
+        boxes_ptr, box0 = None, None
+        keep = [k1]
+        if box is not None:
+            b = np.asarray(box.get_matrix() if isinstance(box, PeriodicBox) else box, np.float64)
+            if b.ndim == 3:
+                b9 = np.ascontiguousarray(np.transpose(b, (0, 2, 1))).reshape(nframes, 9)      # column-major per frame
+                boxes_ptr = b9.ctypes.data
+                keep.append(b9)
+                box0 = b[0]
+            else:
+                box0 = b.reshape(3, 3)
+        # the request of frame 0 (shapes, selections, box) - the library moves the coordinates on by the strides
+        d, k0 = _search_desc_f64(kind, cutoff, frames[0], idx1, f2[0] if two else None, idx2 if two else None, box0, pbc)
+        d.xyz1 = fa
+        if two:
+            d.xyz2 = fa2
+            keep.append(k2)
+        if bins is None:
+            bins = np.zeros(nbins, np.uint64)
+        ba, kb = _addr(bins)
+        check(self.lib.molar_hip_search_histogram_frames_f64(self.ctx, C.byref(d), nframes, stride, stride2, boxes_ptr,
+                                                             float(hmin), float(hmax), int(nbins), ba))
+        self._keep = keep + k0 + [kb]
+        return bins
 
     def grid_dims_f64(self):
         dims = (C.c_uint64 * 3)()
@@ -1325,6 +1363,55 @@ class MembranePlan:
         out, o = self._arrays(names, self.K, int(v.patch_entries))
         check(self.lib.molar_hip_membrane_frame_fetch(self.handle, int(ticket), C.byref(o)))
         return out
+
+
+def _search_desc_f64(kind, cutoff, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0, vdw1=None, vdw2=None, ids_local=False,
+                     lower=None, upper=None):
+    """(molar_hip_search_desc_f64, keepalive list) of an f64 request: float64 numpy arrays or contiguous CUDA tensors (used in
+    place), the box as a 3x3 matrix with the box vectors as columns."""
+    def f64(a):
+        if a is None:
+            return None
+        if hasattr(a, "data_ptr"):          # a torch tensor in HBM is used in place (float64, contiguous)
+            if str(a.dtype) != "torch.float64" or not a.is_contiguous():
+                raise TypeError("search_f64: device tensors must be contiguous float64")
+            return a
+        return np.ascontiguousarray(a, np.float64)
+
+    def addr(a):
+        return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+    xyz1, xyz2, vdw1, vdw2 = f64(xyz1), f64(xyz2), f64(vdw1), f64(vdw2)
+    idx1 = idx1 if hasattr(idx1, "data_ptr") else _u64(idx1)       # (device index tensors: int64)
+    idx2 = idx2 if hasattr(idx2, "data_ptr") else _u64(idx2)
+    d = SearchDescF64()
+    d.kind = kind
+    d.cutoff = float(cutoff) if cutoff is not None else 0.0
+    keep = [xyz1, xyz2, vdw1, vdw2, idx1, idx2]
+    for name, arr in (("xyz1", xyz1), ("idx1", idx1), ("xyz2", xyz2), ("idx2", idx2), ("vdw1", vdw1), ("vdw2", vdw2)):
+        setattr(d, name, addr(arr))
+    d.natoms1 = 0 if xyz1 is None else xyz1.reshape(-1, 3).shape[0]
+    d.natoms2 = 0 if xyz2 is None else xyz2.reshape(-1, 3).shape[0]
+    d.n1 = 0 if idx1 is None else idx1.shape[0]
+    d.n2 = 0 if idx2 is None else idx2.shape[0]
+    d.ids_local = 1 if ids_local else 0
+    if box is not None:
+        b9 = np.ascontiguousarray(np.asarray(box, np.float64).T).reshape(9)      # column-major: columns a, b, c
+        keep.append(b9)
+        d.box9 = b9.ctypes.data
+        d.pbc = int(pbc)
+    if lower is not None:
+        lo, up = f64(lower), f64(upper)
+        keep += [lo, up]
+        d.lower3, d.upper3 = lo.ctypes.data, up.ctypes.data
+    return d, keep
+
+
+def histogram_edges_f64(hmin, hmax, nbins):
+    """The f64 twin of histogram_edges: float64 [nbins + 1], edges[b] = the smallest d2 >= 0 whose f64 Histogram1D::add_one
+    bin is >= b (host arithmetic of the engine, no GPU)."""
+    e = np.zeros(max(int(nbins), 0) + 1, np.float64)
+    check(_lib.load().molar_hip_histogram_edges_f64(float(hmin), float(hmax), int(nbins), e.ctypes.data))
+    return e
 
 
 def histogram_edges(hmin, hmax, nbins):

@@ -18,10 +18,13 @@
 //     first to count, then, behind an exclusive scan of the slot counts, to write (i, j, sqrt(d2)) at its place of the
 //     reference's output order (plan order, then i-major / j-minor, :949-953);
 //   * records are 24-byte positions + 8-byte ids; results are (usize, usize, f64) columns or usize ids (within).
+//   * the fused histogram (molar_hip_search_histogram_f64) walks the same slots in one persistent kernel that bins every
+//     hit's d2 in LDS instead of writing it (hist64_kernel).
 // 1M atoms, rc 1.0 nm, 2.1e8 results, frame and result resident: see tools/bench_search_f64.py, profiles/r05_search_f64.jsonl.
 // tests/test_gpu_search_f64.py compares all eight drivers bit for bit with the f64 build of the CPU checker.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -49,6 +52,13 @@ struct molar_hip_search64_state {
     // device pipeline of the grid and the plan
     DevBuf in_xyz[2], in_idx[2], in_vdw[2];      // staging of host inputs
     DevBuf key_in, key_out, val_in, val_out, pos3, startA, startB, task_ns, task_first, cub_tmp, partial, flags;
+    // fused histogram (molar_hip_search_histogram_f64): bin edges of the last range, [bins of a host-bins call][pair count],
+    // the slot counter of the persistent kernel
+    DevBuf hedges, hsum, hnext;
+    std::vector<double> h_edges;
+    double edges_min = 0.0, edges_max = 0.0;
+    size_t edges_n = 0;
+    int occ_key = -1, occ_blocks = 0;    // workgroups per CU of the last (kernel, LDS size) launched
 };
 
 namespace {
@@ -619,6 +629,245 @@ inline dim3 grid_of(uint32_t n) {
     return dim3(gx, (n + gx - 1u) / gx);
 }
 
+// ---- the fused histogram in f64 (molar_hip_search_histogram_f64): search + Histogram1D::add_one (stats.rs:29-35) in ONE pass,
+// no count pass, no offsets, no pair list.
+//
+// The slots are those of the count and fill passes, and each is evaluated as run64 / pair64_kernel's FILL path evaluates it:
+// second cell in registers up to 256 atoms (chunk by chunk from memory beyond), the same row pruning, the same predicate for
+// plain, same-cell, vdW and wrapped entries, and for band-classified wrapped entries PeriodicBox::distance_squared for every
+// hit (the adjacent-image q2 only decides whether a pair is a hit).  So a binned d2 is exactly the d2 whose square root the
+// fill pass writes.  Instead of being written, a hit's d2 goes into the workgroup's histogram of 32-bit LDS counters: the
+// bin is the largest b with edges[b] <= d2 (histogram_edges64: the formula's own table over d2), found from an f32 estimate
+// of the bin corrected step by step against the edges.
+//
+// The kernel is persistent: a one-wave workgroup per slot, as the count and fill passes run, would have to flush nbins
+// counters per slot (5e4 slots a frame at 250k atoms).  Instead about (CUs x resident workgroups) workgroups of H64_WAVES
+// waves each hold one histogram; their waves take slots from one global counter (one atomic per slot) until none is left,
+// and the workgroup adds each non-zero counter to the caller's bins with one 64-bit atomic at the end.
+//
+// Counter overflow: a wave flushes the whole LDS histogram (exchange each counter with 0, add what it held to the bins) when
+// the hits it has added since its last flush pass `flush_at` (checked after every slot, and after every chunk in the chunk
+// loop).  Every counter then holds at most the sum over the waves of their hits since their own last flush, i.e. less than
+// H64_WAVES * (flush_at + 16384) < 2^32 (at most 16384 hits between two checks: a 64-row slot of <= 256 columns).
+constexpr int H64_WAVES = 8;
+constexpr uint32_t H64_FLUSH_AT = 0xFFFFFFFFu / (uint32_t)H64_WAVES - 16384u;
+constexpr size_t H64_EDGES_LDS = 40960;   // the edges join the counters in LDS while both fit in this (nbins <= 3412)
+
+struct Hist64 {
+    uint32_t *hist;                  // the workgroup's counters (LDS)
+    const double *edges;             // nbins + 1 edges: LDS copy or global memory
+    unsigned long long *bins;
+    uint32_t nbins;
+    float hmin, scale, hn;           // the f32 estimate: (sqrt(d2) - hmin) * scale, clamped to [0, n]
+};
+
+__device__ __forceinline__ void hist64_add(const Hist64 &H, double d2) {
+    float est = (__builtin_amdgcn_sqrtf((float)d2) - H.hmin) * H.scale;
+    est = __builtin_fminf(__builtin_fmaxf(est, 0.0f), H.hn);                // also sends a NaN to 0
+    int b = (int)est;
+    while (b < (int)H.nbins && H.edges[b + 1] <= d2) ++b;
+    while (b >= 0 && H.edges[b] > d2) --b;
+    if ((uint32_t)b < H.nbins) __hip_atomic_fetch_add(H.hist + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// the workgroup's counters into the bins by one wave, beside the others still counting
+__device__ __forceinline__ void hist64_flush(const Hist64 &H, uint32_t lane) {
+    for (uint32_t b = lane; b < H.nbins; b += 64u) {
+        const uint32_t v = __hip_atomic_exchange(H.hist + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (v) atomicAdd(H.bins + b, (unsigned long long)v);
+    }
+}
+
+// one slot whose second cell fits NCH chunks of 64 atoms (run64, FILL, with the hits binned): returns the slot's hits
+template <int KIND, int NCH>
+__device__ __forceinline__ uint32_t hist64_slot(const Params64 &P, const Slot64 &S, uint32_t lane, const Hist64 &H) {
+    const uint32_t wrap = S.flags & 7u;
+    const bool tri = (S.flags >> 8) & 1u;
+    constexpr bool VDW = KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW;
+    double bx[NCH], by[NCH], bz[NCH], bv[NCH];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+        const uint32_t j = (uint32_t)k * 64u + lane;
+        bx[k] = by[k] = bz[k] = bv[k] = 0.0;
+        if (j < S.n2) {
+            const size_t rb = (size_t)S.b0 + j;
+            bx[k] = P.posB[3 * rb]; by[k] = P.posB[3 * rb + 1]; bz[k] = P.posB[3 * rb + 2];
+            if (VDW) bv[k] = P.vdwB[rb];
+        }
+    }
+    const bool approx = P.approx_wrapped && P.use_box && wrap != 0u && !(P.box->nshift != 0 && wrap == MOLAR_HIP_PBC_FULL);
+    double cx[NCH], cy[NCH], cz[NCH];
+    double Sx = 0.0, Sy = 0.0, Sz = 0.0;
+    if (approx) {
+        for (int d = 0; d < 3; ++d) {
+            if (!((wrap >> d) & 1u)) continue;
+            const double sgn = ((S.flags >> (12 + d)) & 1u) ? 1.0 : -1.0;
+            Sx += sgn * P.box->m[3 * d];
+            Sy += sgn * P.box->m[3 * d + 1];
+            Sz += sgn * P.box->m[3 * d + 2];
+        }
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) { cx[k] = bx[k] + Sx; cy[k] = by[k] + Sy; cz[k] = bz[k] + Sz; }
+    }
+    double ax = 0.0, ay = 0.0, az = 0.0, av = 0.0;
+    if (lane < S.rows) {
+        const size_t ra = (size_t)S.a0 + S.i0 + lane;
+        ax = P.posA[3 * ra]; ay = P.posA[3 * ra + 1]; az = P.posA[3 * ra + 2];
+        if (VDW) av = P.vdwA[ra];
+    }
+    unsigned long long live;
+    {
+        bool need = lane < S.rows;
+        if (!tri && (wrap == 0u || !P.use_box || approx)) {                   // run64's row pruning
+            const double *bb = P.aabbB + 6 * (size_t)S.cb;
+            double px = ax, py = ay, pz = az, lim = P.cutoff2;
+            if (approx) {
+                px = ax - Sx;
+                py = ay - Sy;
+                pz = az - Sz;
+                lim = P.prune_limit2;
+            }
+            const double ex = fmax(fmax(bb[0] - px, px - bb[3]), 0.0), ey = fmax(fmax(bb[1] - py, py - bb[4]), 0.0),
+                         ez = fmax(fmax(bb[2] - pz, pz - bb[5]), 0.0);
+            need = need && !((ex * ex + ey * ey) + ez * ez > lim);
+        }
+        live = __builtin_amdgcn_ballot_w64(need);
+    }
+    uint32_t total = 0;
+    while (live) {
+        const uint32_t r = (uint32_t)__builtin_ctzll(live);
+        live &= live - 1ull;
+        const D3 a = D3{lane_bcast(ax, r), lane_bcast(ay, r), lane_bcast(az, r)};
+        const double vdw_a = VDW ? lane_bcast(av, r) : 0.0;
+        const uint32_t i = S.i0 + r;
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            if (tri && (uint32_t)k * 64u + 63u <= i) continue;                  // the whole chunk has j <= i (:443)
+            const uint32_t j = (uint32_t)k * 64u + lane;
+            bool hit = j < S.n2 && !(tri && j <= i);
+            double cut2 = P.cutoff2;
+            if (VDW) {
+                const double cut = (vdw_a + bv[k]) + 2.220446049250313e-16;    // :392, :423
+                cut2 = cut * cut;
+            }
+            double d2;
+            if (approx) {
+                const double ex = cx[k] - a.x, ey = cy[k] - a.y, ez = cz[k] - a.z;
+                const double q2 = (ex * ex + ey * ey) + ez * ez;
+                const bool sure = q2 < cut2 * P.band_lo, maybe = hit && q2 <= cut2 * P.band_hi;
+                d2 = q2;
+                if (__builtin_amdgcn_ballot_w64(maybe)) {                       // hits are binned with the reference's own d2
+                    if (maybe) d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
+                }
+                hit = maybe && (sure || d2 <= cut2);
+            } else {
+                d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
+                hit = hit && d2 <= cut2;
+            }
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+            if (!m) continue;
+            total += (uint32_t)__popcll(m);
+            if (hit) hist64_add(H, d2);
+        }
+    }
+    return total;
+}
+
+// second cells of more than 256 atoms: chunk by chunk from memory (pair64_kernel's generic loop)
+template <int KIND>
+__device__ __forceinline__ unsigned long long hist64_chunks(const Params64 &P, const Slot64 &S, uint32_t lane, const Hist64 &H,
+                                                            uint32_t &since_flush, uint32_t flush_at) {
+    const uint32_t wrap = S.flags & 7u;
+    const bool tri = (S.flags >> 8) & 1u;
+    unsigned long long total = 0;
+    for (uint32_t r = 0; r < S.rows; ++r) {
+        const uint32_t ra = S.a0 + S.i0 + r;
+        const D3 a = D3{P.posA[3 * ra], P.posA[3 * ra + 1], P.posA[3 * ra + 2]};
+        const double vdw_a = (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) ? P.vdwA[ra] : 0.0;
+        for (uint32_t j0 = 0; j0 < S.n2; j0 += 64u) {
+            const uint32_t j = j0 + lane;
+            bool hit = false;
+            double d2 = 0.0;
+            if (j < S.n2 && !(tri && j <= S.i0 + r)) {            // same cell: j in i+1..n (:443)
+                const uint32_t rb = S.b0 + j;
+                d2 = pair_d2(P, wrap, a, D3{P.posB[3 * rb], P.posB[3 * rb + 1], P.posB[3 * rb + 2]});
+                if (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) {
+                    const double cut = (vdw_a + P.vdwB[rb]) + 2.220446049250313e-16;        // :392, :423
+                    hit = d2 <= cut * cut;
+                } else {
+                    hit = d2 <= P.cutoff2;
+                }
+            }
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+            if (!m) continue;
+            const uint32_t cnt = (uint32_t)__popcll(m);
+            total += cnt;
+            if (hit) hist64_add(H, d2);
+            since_flush += cnt;
+            if (since_flush > flush_at) {
+                hist64_flush(H, lane);
+                since_flush = 0;
+            }
+        }
+    }
+    return total;
+}
+
+// EL: the edges are copied into LDS behind the counters (else read from global memory)
+template <int KIND, bool EL>
+__global__ void __launch_bounds__(64 * H64_WAVES) hist64_kernel(Params64 P, uint32_t *__restrict__ next_slot, const double *__restrict__ edges,
+                                                                uint32_t nbins, float hmin, float scale, uint32_t flush_at,
+                                                                unsigned long long *__restrict__ bins, unsigned long long *__restrict__ count) {
+    extern __shared__ double h64_lds[];
+    __shared__ unsigned long long wg_total;
+    uint32_t *hist = reinterpret_cast<uint32_t *>(h64_lds);
+    double *ledges = h64_lds + (nbins + 1u) / 2u;
+    for (uint32_t b = threadIdx.x; b < nbins; b += blockDim.x) hist[b] = 0u;
+    if (EL)
+        for (uint32_t b = threadIdx.x; b <= nbins; b += blockDim.x) ledges[b] = edges[b];
+    if (threadIdx.x == 0) wg_total = 0ull;
+    __syncthreads();
+    const Hist64 H{hist, EL ? ledges : edges, bins, nbins, hmin, scale, (float)nbins};
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t since_flush = 0;
+    unsigned long long total = 0;
+    for (;;) {
+        uint32_t s = 0;
+        if (lane == 0) s = atomicAdd(next_slot, 1u);
+        s = (uint32_t)__builtin_amdgcn_readlane((int)s, 0);
+        if (s >= P.nslots) break;
+        const Slot64 S = P.slots[s];
+        const uint32_t nch = (S.n2 + 63u) >> 6;
+        if (nch > 4u) {
+            total += hist64_chunks<KIND>(P, S, lane, H, since_flush, flush_at);
+            continue;
+        }
+        uint32_t t;
+        switch (nch) {
+            case 1: t = hist64_slot<KIND, 1>(P, S, lane, H); break;
+            case 2: t = hist64_slot<KIND, 2>(P, S, lane, H); break;
+            case 3: t = hist64_slot<KIND, 3>(P, S, lane, H); break;
+            default: t = hist64_slot<KIND, 4>(P, S, lane, H); break;
+        }
+        total += t;
+        since_flush += t;
+        if (since_flush > flush_at) {
+            hist64_flush(H, lane);
+            since_flush = 0;
+        }
+    }
+    if (lane == 0 && total) atomicAdd(&wg_total, total);
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < nbins; b += blockDim.x) {
+        const uint32_t v = hist[b];
+        if (v) atomicAdd(bins + b, (unsigned long long)v);
+    }
+    if (threadIdx.x == 0 && wg_total) atomicAdd(count, wg_total);
+}
+
+template <int KIND, bool EL>
+const void *hist64_fn() { return reinterpret_cast<const void *>(&hist64_kernel<KIND, EL>); }
+
 }  // namespace
 
 namespace mh {
@@ -690,8 +939,11 @@ static int build_grid64(molar_hip_ctx *c, molar_hip_search64_state &Z, const Set
     return 0;
 }
 
-int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, uint64_t *out_count) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_count_f64: null argument");
+// Everything of a search before its evaluation, shared by the count pass and the fused histogram: the sets on the device, the
+// box, the bounds, the grid dims, both grids, the cells' bounding boxes, the plan, its scan (read back: the number of slots),
+// the slot records and the classification of wrapped entries.  *P is the parameter block of the evaluation; *empty: nothing
+// to evaluate (no slot, or a vdW search with an empty set).
+static int prepare64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Params64 *P, bool *empty) {
     MH_HIP(hipSetDevice(c->device));
     if (!c->s64) c->s64 = new molar_hip_search64_state;
     molar_hip_search64_state &Z = *c->s64;
@@ -732,6 +984,7 @@ int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64
     Z.total = 0;
     Z.nslots = 0;
     Z.dims[0] = Z.dims[1] = Z.dims[2] = 1;
+    *empty = false;
     constexpr unsigned PARTS = 256;                        // workgroups of the reductions whose result the host needs
     MH_TRY(Z.partial.reserve((size_t)PARTS * 6 * 8 * 2));
     MH_TRY(Z.flags.reserve(64));
@@ -741,8 +994,7 @@ int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64
     double cutoff = q->cutoff;
     if (vdw) {
         if (S[0].nsel == 0 || S[1].nsel == 0) {        // the reference unwrap()s an empty max: nothing to report here
-            Z.have = true;
-            if (out_count) *out_count = 0;
+            *empty = true;
             return MOLAR_HIP_OK;
         }
         double mx[2];
@@ -843,19 +1095,14 @@ int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64
     Z.nslots = hs.nslots;
     Z.total = 0;
     if (Z.nslots == 0) {
-        Z.have = true;
-        if (out_count) *out_count = 0;
+        *empty = true;
         return MOLAR_HIP_OK;
     }
     MH_TRY(Z.slots.reserve((size_t)Z.nslots * sizeof(Slot64)));
     hipLaunchKernelGGL(slots64_kernel, dim3((unsigned)((ntasks + 255) / 256)), dim3(256), 0, c->stream, G, ntasks, mult, startA, startB,
                        Z.task_first.as<uint32_t>(), Z.slots.as<Slot64>());
-    // ---- count, offsets
     MH_TRY(Z.box.reserve(sizeof box));
     MH_HIP(hipMemcpyAsync(Z.box.p, &box, sizeof box, hipMemcpyHostToDevice, c->stream));
-    MH_TRY(Z.slot_cnt.reserve(((size_t)Z.nslots + 1) * 4));
-    MH_TRY(Z.slot_base.reserve(((size_t)Z.nslots + 1) * 8));
-    MH_HIP(hipMemsetAsync(Z.slot_cnt.as<uint32_t>() + Z.nslots, 0, 4, c->stream));
     const DevBuf &pB = two ? Z.posB : Z.posA, &iB = two ? Z.idB : Z.idA, &vB = two ? Z.vdwB : Z.vdwA;
     // Entries across the periodic boundary (search.hip, make_params, derives the same bound for f32): the reference evaluates
     // v = p2 - p1, f = inv v, f -= round(f), s = M f; the kernels classify with (b + S) - a.  With u = 2^-53, L the largest
@@ -896,10 +1143,28 @@ int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64
             Z.prune_limit2 = lim * lim;
         }
     }
-    Params64 P{Z.posA.as<double>(), pB.as<double>(), Z.vdwA.as<double>(), vB.as<double>(),
-               Z.idA.as<unsigned long long>(), iB.as<unsigned long long>(), Z.box.as<BoxD>(), Z.slots.as<Slot64>(), Z.nslots,
-               kind, use_box ? 1 : 0, cutoff * cutoff, Z.approx ? 1 : 0, Z.band_lo, Z.band_hi, (two ? Z.aabbB : Z.aabbA).as<double>(), Z.prune_limit2};
-    launch_pair64<false>(kind, grid_of(Z.nslots), c->stream, P, Z.slot_cnt.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr);
+    *P = Params64{Z.posA.as<double>(), pB.as<double>(), Z.vdwA.as<double>(), vB.as<double>(),
+                  Z.idA.as<unsigned long long>(), iB.as<unsigned long long>(), Z.box.as<BoxD>(), Z.slots.as<Slot64>(), Z.nslots,
+                  kind, use_box ? 1 : 0, cutoff * cutoff, Z.approx ? 1 : 0, Z.band_lo, Z.band_hi, (two ? Z.aabbB : Z.aabbA).as<double>(), Z.prune_limit2};
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_search_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, uint64_t *out_count) {
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_count_f64: null argument");
+    Params64 P{};
+    bool empty = false;
+    MH_TRY(prepare64(c, q, &P, &empty));
+    molar_hip_search64_state &Z = *c->s64;
+    if (empty) {
+        Z.have = true;
+        if (out_count) *out_count = 0;
+        return MOLAR_HIP_OK;
+    }
+    // ---- count, offsets
+    MH_TRY(Z.slot_cnt.reserve(((size_t)Z.nslots + 1) * 4));
+    MH_TRY(Z.slot_base.reserve(((size_t)Z.nslots + 1) * 8));
+    MH_HIP(hipMemsetAsync(Z.slot_cnt.as<uint32_t>() + Z.nslots, 0, 4, c->stream));
+    launch_pair64<false>(Z.kind, grid_of(Z.nslots), c->stream, P, Z.slot_cnt.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr);
     MH_HIP(hipGetLastError());
     MH_TRY(device_exclusive_sum_u32_u64(c, Z.cub_tmp, Z.slot_cnt.as<uint32_t>(), Z.slot_base.as<unsigned long long>(), (size_t)Z.nslots + 1));
     unsigned long long run = 0;
@@ -959,6 +1224,168 @@ int molar_hip_search_fill_ids_f64(molar_hip_ctx *c, uint64_t *ids) { return fill
 int molar_hip_search_grid_dims_f64(molar_hip_ctx *c, uint64_t dims[3]) {
     if (!c || !c->s64 || !c->s64->have || !dims) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached f64 search");
     for (int d = 0; d < 3; ++d) dims[d] = c->s64->dims[d];
+    return MOLAR_HIP_OK;
+}
+
+// The f64 twin of histogram_edges (search.hip): edges[b], b = 0..nbins, is the smallest non-negative double x whose bin
+// floor(n * (sqrt(x) - min) / (max - min)) is >= b, found by bisection over the bit patterns of the non-negative doubles
+// (ordered like the values) with the formula itself.  Each IEEE step of the formula is monotone, so the bin is a
+// non-decreasing function of x, and "the largest b with edges[b] <= x" IS the formula.  False unless min < max and both
+// and their difference are finite, and nbins > 0.
+static bool histogram_edges64(double hmin, double hmax, size_t nbins, double *edges) {
+    if (!(hmax > hmin) || !std::isfinite(hmin) || !std::isfinite(hmax) || !std::isfinite(hmax - hmin) || nbins == 0) return false;
+    const double hn = (double)nbins, range = hmax - hmin;
+    auto bin_of = [&](uint64_t bits) -> double {
+        double x;
+        std::memcpy(&x, &bits, 8);
+        volatile double d = std::sqrt(x);
+        volatile double t = d - hmin;
+        volatile double u = hn * t;
+        volatile double v = u / range;
+        return std::floor(v);
+    };
+    for (size_t b = 0; b <= nbins; ++b) {
+        uint64_t lo = 0u, hi = 0x7FF0000000000000ull;           // +0.0 .. +inf; bin_of(+inf) = +inf >= b
+        if (bin_of(lo) >= (double)b) {
+            hi = lo;
+        } else {
+            while (hi - lo > 1u) {                                // invariant: bin_of(lo) < b <= bin_of(hi)
+                const uint64_t mid = lo + (hi - lo) / 2u;
+                if (bin_of(mid) >= (double)b) hi = mid;
+                else lo = mid;
+            }
+        }
+        std::memcpy(&edges[b], &hi, 8);
+    }
+    return true;
+}
+
+int molar_hip_histogram_edges_f64(double hmin, double hmax, size_t nbins, double *edges) {
+    if (!edges) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "histogram_edges_f64: null argument");
+    if (!histogram_edges64(hmin, hmax, nbins, edges))
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "histogram_edges_f64: needs finite min < max and nbins > 0");
+    return MOLAR_HIP_OK;
+}
+
+// argument checks of the fused f64 histogram; the edges of (hmin, hmax, nbins) on the device (computed when the range changes)
+static int hist64_begin(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, double hmin, double hmax, size_t nbins, const void *bins) {
+    if (!c || !q || !bins) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_histogram_f64: null argument");
+    if (q->kind == MOLAR_HIP_SEARCH_WITHIN)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_histogram_f64: a within search has no distances");
+    if (q->kind < MOLAR_HIP_SEARCH_SINGLE || q->kind > MOLAR_HIP_SEARCH_DOUBLE_VDW)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_histogram_f64: unknown kind %d", (int)q->kind);
+    if (nbins == 0 || nbins > 8192) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_histogram_f64: nbins must be in 1..8192");
+    MH_HIP(hipSetDevice(c->device));
+    if (!c->s64) c->s64 = new molar_hip_search64_state;
+    molar_hip_search64_state &Z = *c->s64;
+    Z.have = false;                   // the histogram reuses the cached search's buffers: fill_f64 has nothing to fill after it
+    if (Z.edges_n == nbins && Z.edges_min == hmin && Z.edges_max == hmax) return 0;
+    Z.edges_n = 0;
+    Z.h_edges.resize(nbins + 1);
+    if (!histogram_edges64(hmin, hmax, nbins, Z.h_edges.data()))
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_histogram_f64: needs finite min < max");
+    MH_TRY(Z.hedges.reserve((nbins + 1) * 8));
+    MH_HIP(hipStreamSynchronize(c->stream));          // a kernel of an earlier call may still read the old table
+    MH_HIP(hipMemcpyAsync(Z.hedges.p, Z.h_edges.data(), (nbins + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    Z.edges_min = hmin;
+    Z.edges_max = hmax;
+    Z.edges_n = nbins;
+    return 0;
+}
+
+// one frame: the search's prologue, then hist64_kernel adding into bins / count (device memory)
+static int hist64_frame(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, size_t nbins, unsigned long long *bins,
+                        unsigned long long *count) {
+    Params64 P{};
+    bool empty = false;
+    MH_TRY(prepare64(c, q, &P, &empty));
+    molar_hip_search64_state &Z = *c->s64;
+    Z.have = false;
+    if (empty) return 0;
+    const bool el = (size_t)(nbins + 1) / 2 * 8 + (nbins + 1) * 8 <= H64_EDGES_LDS;
+    const size_t lds = (size_t)(nbins + 1) / 2 * 8 + (el ? (nbins + 1) * 8 : 0);
+    const void *fn = nullptr;
+    switch (Z.kind) {
+        case MOLAR_HIP_SEARCH_SINGLE: fn = el ? hist64_fn<MOLAR_HIP_SEARCH_SINGLE, true>() : hist64_fn<MOLAR_HIP_SEARCH_SINGLE, false>(); break;
+        case MOLAR_HIP_SEARCH_DOUBLE: fn = el ? hist64_fn<MOLAR_HIP_SEARCH_DOUBLE, true>() : hist64_fn<MOLAR_HIP_SEARCH_DOUBLE, false>(); break;
+        default: fn = el ? hist64_fn<MOLAR_HIP_SEARCH_DOUBLE_VDW, true>() : hist64_fn<MOLAR_HIP_SEARCH_DOUBLE_VDW, false>(); break;
+    }
+    // persistent grid: as many workgroups as are resident at once (occupancy of this kernel and LDS size, cached), no more
+    // than the slots need
+    const int key = (int)(Z.kind * 2 + (el ? 1 : 0)) | (int)(lds << 4);
+    if (Z.occ_key != key) {
+        int per_cu = 0;
+        MH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * H64_WAVES, lds));
+        Z.occ_blocks = per_cu > 0 ? per_cu : 1;
+        Z.occ_key = key;
+    }
+    const unsigned nwg = (unsigned)std::max<uint64_t>(1u, std::min<uint64_t>((uint64_t)Z.occ_blocks * c->num_cus,
+                                                                             ((uint64_t)Z.nslots + H64_WAVES - 1) / H64_WAVES));
+    MH_TRY(Z.hnext.reserve(4));
+    MH_HIP(hipMemsetAsync(Z.hnext.p, 0, 4, c->stream));
+    uint32_t flush_at = H64_FLUSH_AT;
+    if (const char *e = std::getenv("MOLAR_HIP_HIST64_FLUSH")) {      // tests: flush the LDS counters after fewer hits
+        const unsigned long v = std::strtoul(e, nullptr, 10);
+        if (v > 0 && v < flush_at) flush_at = (uint32_t)v;
+    }
+    const double range = Z.edges_max - Z.edges_min;
+    const float hmin = (float)Z.edges_min, scale = (float)((double)nbins / range);
+    uint32_t nb32 = (uint32_t)nbins;
+    void *args[] = {&P, &Z.hnext.p, &Z.hedges.p, &nb32, const_cast<float *>(&hmin), const_cast<float *>(&scale), &flush_at, &bins, &count};
+    MH_HIP(hipLaunchKernel(fn, dim3(nwg), dim3(64 * H64_WAVES), args, lds, c->stream));
+    return 0;
+}
+
+int molar_hip_search_histogram_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, double hmin, double hmax, size_t nbins,
+                                   uint64_t *bins, uint64_t *out_count) {
+    MH_TRY(hist64_begin(c, q, hmin, hmax, nbins, bins));
+    molar_hip_search64_state &Z = *c->s64;
+    const bool dev = is_device_ptr(bins);
+    // hsum: [bins of a call with host bins][the pair count]
+    MH_TRY(Z.hsum.reserve((nbins + 1) * 8));
+    unsigned long long *hsum = Z.hsum.as<unsigned long long>();
+    MH_HIP(hipMemsetAsync(dev ? hsum + nbins : hsum, 0, dev ? 8 : (nbins + 1) * 8, c->stream));
+    MH_TRY(hist64_frame(c, q, nbins, dev ? reinterpret_cast<unsigned long long *>(bins) : hsum, hsum + nbins));
+    MH_HIP(hipGetLastError());
+    if (dev && !out_count) return MOLAR_HIP_OK;      // the kernel may still run: molar_hip_synchronize before reading the bins
+    if (dev) {
+        unsigned long long tot = 0;
+        MH_HIP(hipMemcpyAsync(&tot, hsum + nbins, 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+        *out_count = tot;
+        return MOLAR_HIP_OK;
+    }
+    std::vector<unsigned long long> h(nbins + 1);
+    MH_HIP(hipMemcpyAsync(h.data(), hsum, (nbins + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < nbins; ++b) bins[b] += h[b];
+    if (out_count) *out_count = h[nbins];
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_search_histogram_frames_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, size_t nframes, size_t xyz1_stride,
+                                          size_t xyz2_stride, const double *boxes9, double hmin, double hmax, size_t nbins,
+                                          uint64_t *bins) {
+    MH_TRY(hist64_begin(c, q, hmin, hmax, nbins, bins));
+    molar_hip_search64_state &Z = *c->s64;
+    const bool dev = is_device_ptr(bins);
+    MH_TRY(Z.hsum.reserve((nbins + 1) * 8));
+    unsigned long long *hsum = Z.hsum.as<unsigned long long>();
+    MH_HIP(hipMemsetAsync(dev ? hsum + nbins : hsum, 0, dev ? 8 : (nbins + 1) * 8, c->stream));
+    for (size_t k = 0; k < nframes; ++k) {       // frame by frame: one slot-count read-back each
+        molar_hip_search_desc_f64 f = *q;
+        f.xyz1 = q->xyz1 ? q->xyz1 + k * xyz1_stride : nullptr;
+        f.xyz2 = q->xyz2 ? q->xyz2 + k * xyz2_stride : nullptr;
+        if (boxes9) f.box9 = boxes9 + 9 * k;
+        MH_TRY(hist64_frame(c, &f, nbins, dev ? reinterpret_cast<unsigned long long *>(bins) : hsum, hsum + nbins));
+        MH_HIP(hipGetLastError());
+    }
+    if (dev) return MOLAR_HIP_OK;                // molar_hip_synchronize before reading the bins
+    std::vector<unsigned long long> h(nbins);
+    MH_HIP(hipMemcpyAsync(h.data(), hsum, nbins * 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < nbins; ++b) bins[b] += h[b];
     return MOLAR_HIP_OK;
 }
 

@@ -452,6 +452,55 @@ impl Engine {
         })
     }
 
+    /// The fused radial distance histogram in f64: the pairs of `distance_search_single(_pbc)` with Float = f64, each
+    /// distance through the f64 `Histogram1D::add_one` (molar_membrane/src/stats.rs:29-35) over `bins.len()` bins of
+    /// [hmin, hmax), added into `bins`; no pair list.  Returns the number of pairs within the cutoff (binned or not).
+    pub fn histogram_single_f64(
+        &self, cutoff: f64, coords: &[[f64; 3]], index: Option<&[usize]>, box9: Option<&[f64; 9]>, pbc: u8, hmin: f64, hmax: f64,
+        bins: &mut [u64],
+    ) -> Result<u64, EngineError> {
+        check_index(index, coords.len(), "histogram_single_f64")?;
+        let (ip, n) = idx_ptr(index);
+        let d = MolarHipSearchDescF64 {
+            kind: SEARCH_SINGLE, cutoff, xyz1: coords.as_ptr() as *const f64, natoms1: coords.len(), idx1: ip, n1: n,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let mut count = 0u64;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.search_histogram_f64)(self.ctx, &d, hmin, hmax, bins.len(), bins.as_mut_ptr(), &mut count)
+        })?;
+        Ok(count)
+    }
+
+    /// The same for `distance_search_double(_pbc)` with Float = f64: pairs (atom of set 1, atom of set 2).
+    pub fn histogram_double_f64(
+        &self, cutoff: f64, coords1: &[[f64; 3]], index1: Option<&[usize]>, coords2: &[[f64; 3]], index2: Option<&[usize]>,
+        box9: Option<&[f64; 9]>, pbc: u8, hmin: f64, hmax: f64, bins: &mut [u64],
+    ) -> Result<u64, EngineError> {
+        check_index(index1, coords1.len(), "histogram_double_f64 (set 1)")?;
+        check_index(index2, coords2.len(), "histogram_double_f64 (set 2)")?;
+        let (i1, n1) = idx_ptr(index1);
+        let (i2, n2) = idx_ptr(index2);
+        let d = MolarHipSearchDescF64 {
+            kind: SEARCH_DOUBLE, cutoff, xyz1: coords1.as_ptr() as *const f64, natoms1: coords1.len(), idx1: i1, n1,
+            xyz2: coords2.as_ptr() as *const f64, natoms2: coords2.len(), idx2: i2, n2,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let mut count = 0u64;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.search_histogram_f64)(self.ctx, &d, hmin, hmax, bins.len(), bins.as_mut_ptr(), &mut count)
+        })?;
+        Ok(count)
+    }
+
+    /// The exact bin edges of the f64 histogram over the squared distance (host arithmetic, no GPU): `nbins + 1` values,
+    /// edges[b] = the smallest d2 >= 0 whose bin is >= b.
+    pub fn histogram_edges_f64(&self, hmin: f64, hmax: f64, nbins: usize) -> Result<Vec<f64>, EngineError> {
+        let mut e = vec![0f64; nbins + 1];
+        self.plugin.check(unsafe { (self.plugin.fns.histogram_edges_f64)(hmin, hmax, nbins, e.as_mut_ptr()) })?;
+        Ok(e)
+    }
+
     /// `Modify::unwrap_simple_dim` (modify.rs:40-54), in place
     pub fn unwrap_simple_dim(&self, coords: &mut [[f32; 3]], index: Option<&[usize]>, box9: &[f32; 9], dims: u8) -> Result<(), EngineError> {
         check_index(index, coords.len(), "unwrap_simple_dim")?;
