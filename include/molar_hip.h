@@ -201,7 +201,8 @@ int molar_hip_within_hold(molar_hip_ctx *ctx, int on);
  * without a pair has an empty list (the reference's map has no key for it).  Count-then-fill like the searches: the first
  * call runs the search (the request must be of kind MOLAR_HIP_SEARCH_SINGLE), builds the CSR in context-owned device memory
  * and returns rows and entries (= 2 x pairs, < 2^31: MOLAR_HIP_ERR_TOO_LARGE beyond); the second copies offsets[rows + 1] and
- * neigh[entries] to host or device memory. */
+ * neigh[entries] to host or device memory.  The CSR is uint64 in both precisions: molar_hip_search_connectivity_fill is also
+ * the fill call of molar_hip_search_connectivity_f64. */
 int molar_hip_search_connectivity(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, uint64_t *out_rows, uint64_t *out_entries);
 int molar_hip_search_connectivity_fill(molar_hip_ctx *ctx, uint64_t *offsets, uint64_t *neigh);
 /* Modify::unwrap_connectivity_dim (molar/src/modify.rs:72-131): neighbour search of the selection with local ids under
@@ -287,8 +288,10 @@ int molar_hip_histogram_edges(float hmin, float hmax, size_t nbins, float *edges
 /* ---- the drivers for MolAR built with its `f64` feature (Float = f64, aliases.rs:10-13): every operation in double -
  * cell assignment, the predicate d2 <= cutoff^2 and the distances - results as (usize, usize, f64) columns or usize ids.
  * Same request / count-then-fill convention as above.  Coordinates, index lists, radii and the result columns may be host or
- * device memory (device memory is used in place); grid and plan are built on the device.  The matrix-core count and the
- * pipelined resident forms exist for f32 only. */
+ * device memory (device memory is used in place); grid and plan are built on the device.  In f64 there are the eight drivers,
+ * the fused histogram, `within` as a set, SearchConnectivity and unwrap_connectivity (below).  Still f32 only: the matrix-core
+ * count, the resident and pipelined resident forms, the small-second-set `within` kernel and the grid hold
+ * (molar_hip_within_hold), and the chained membrane frame. */
 typedef struct {
     int32_t kind;
     double cutoff;
@@ -334,6 +337,35 @@ int molar_hip_search_histogram_frames_f64(molar_hip_ctx *ctx, const molar_hip_se
  * bit patterns of the non-negative doubles with the formula itself, so "largest b with edges[b] <= d2" IS the formula.
  * INVALID_ARGUMENT unless min < max, both finite (and max - min finite), and nbins > 0. */
 int molar_hip_histogram_edges_f64(double hmin, double hmax, size_t nbins, double *edges);
+/* `within` as the SET its callers keep, in f64: molar_hip_within_count / _fill with every operation in double.  The result is
+ * exactly sort + dedup of what molar_hip_search_count_f64 + _fill_ids_f64 return for the same request - same grid, same plan
+ * entries, same predicate per candidate (wrapped entries classified by the adjacent image and decided by
+ * PeriodicBox::distance_squared inside the band around the cutoff, as the stream's count pass does) - without the stream:
+ * one pass in which an atom stops looking at its first hit in ANY entry, the set out of a flag array in ascending order, one
+ * read-back (the count).  `desc` must be of kind MOLAR_HIP_SEARCH_WITHIN, else INVALID_ARGUMENT (non-periodic: lower3 /
+ * upper3 as for the stream form); ids are what the stream would carry (idx1 values, or 0..n1 with ids_local), 32-bit on the
+ * device (TOO_LARGE beyond).  ids: uint64[count], host or device, ascending, unique; with count == 0 the fill call has nothing
+ * to write and returns OK.  The count call invalidates the cached f64 search (fill_f64 / fill_ids_f64 / grid_dims_f64 return
+ * NO_SEARCH until the next search_count_f64); _fill_f64 without a count before it returns NO_SEARCH.  Not in f64: the kernel
+ * for small second sets walked from the inner selection's side and the grid hold (molar_hip_within_hold) - f32-only tunings;
+ * this form is correct for an inner selection of any size and walks every first-set cell for it. */
+int molar_hip_within_count_f64(molar_hip_ctx *ctx, const molar_hip_search_desc_f64 *desc, uint64_t *out_count);
+int molar_hip_within_fill_f64(molar_hip_ctx *ctx, uint64_t *ids);
+/* SearchConnectivity of the f64 single-selection search (molar_hip_search_connectivity with every operation of the search in
+ * double): runs the f64 search into context-owned device columns and builds the CSR on the device - entry 2p = (row i,
+ * neighbour j), entry 2p + 1 = (row j, neighbour i), one stable sort by row - in the reference's push order.  Kind SINGLE
+ * only (INVALID_ARGUMENT otherwise); rows = the selection's length for local ids, natoms for global ones; TOO_LARGE at
+ * >= 2^31 entries.  There is no _fill_f64: the CSR is uint64 in both precisions and lives in the same context fields, so the
+ * fill call is molar_hip_search_connectivity_fill. */
+int molar_hip_search_connectivity_f64(molar_hip_ctx *ctx, const molar_hip_search_desc_f64 *desc, uint64_t *out_rows,
+                                      uint64_t *out_entries);
+/* Modify::unwrap_connectivity_dim with Float = f64: the contract of molar_hip_unwrap_connectivity - search over the selection
+ * with local ids under FULL periodicity whatever pbc_dims, the reference's stack walk on the host (closest image over
+ * pbc_dims, in double), the same quirks (start atom not a member of its group, one-atom components give no group, members
+ * sorted), NO_PBC without a box.  xyz: double[natoms][3], host or device, modified in place. */
+int molar_hip_unwrap_connectivity_f64(molar_hip_ctx *ctx, double *xyz, size_t natoms, const uint64_t *idx, size_t n,
+                                      const double *box9, double cutoff, uint8_t pbc_dims, uint64_t *group_offsets,
+                                      uint64_t *group_ids, size_t *ngroups);
 
 /* ------------------------------------------------------------------ Measure (measure.rs) */
 
@@ -374,7 +406,7 @@ int molar_hip_fit_transform(molar_hip_ctx *ctx, const float *xyz1, size_t natoms
 /* ---- MolAR built with its `f64` feature (Float = f64: molar/src/aliases.rs:10-13, molar/Cargo.toml:56-60).
  * The Measure / Modify methods (centres, gyration, rmsd, fit, inertia, min_max, apply, translate, periodic centres and unwrap) on double-precision coordinates and masses, same argument meaning and
  * error codes as the f32 entries above; every per-atom term is formed and accumulated in f64 (two passes where the
- * reference has two: centre, then centred terms).  The search is f32 only. */
+ * reference has two: centre, then centred terms).  The f64 search entries are listed with the search above. */
 /* center_of_geometry :39-47, center_of_mass :60-75 (ERR_ZERO_MASS) */
 int molar_hip_center_of_geometry_f64(molar_hip_ctx *ctx, const double *xyz, size_t natoms, const uint64_t *idx,
                                      size_t n, double out[3]);

@@ -122,6 +122,10 @@ SYMBOLS = {
     "molar_hip_search_histogram_f64": (_I, [_P, _P, C.c_double, C.c_double, _SZ, _P, _P]),
     "molar_hip_search_histogram_frames_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, C.c_double, C.c_double, _SZ, _P]),
     "molar_hip_histogram_edges_f64": (_I, [C.c_double, C.c_double, _SZ, _P]),
+    "molar_hip_within_count_f64": (_I, [_P, _P, _P]),
+    "molar_hip_within_fill_f64": (_I, [_P, _P]),
+    "molar_hip_search_connectivity_f64": (_I, [_P, _P, _P, _P]),
+    "molar_hip_unwrap_connectivity_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P, C.c_double, _U8, _P, _P, _P]),
     "molar_hip_search_resident": (_I, [_P, _P, _P, _P, _P]),
     "molar_hip_search_fill_device": (_I, [_P, _P, _P]),
     "molar_hip_search_resident_planes": (_I, [_P, _I]),

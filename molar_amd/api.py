@@ -414,6 +414,37 @@ class Engine:
         check(self.lib.molar_hip_search_fill_f64(self.ctx, i.ctypes.data, j.ctypes.data, dist.ctypes.data))
         return i, j, dist
 
+    def within_set_f64(self, cutoff, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0, ids_local=False, lower=None,
+                       upper=None, device_out=None):
+        """`within` as the set its callers keep, every operation in double (molar_hip_within_count_f64 + _fill_f64): sorted,
+        de-duplicated ids of the atoms of set 1 with an atom of set 2 within the cutoff - np.unique of what
+        search_f64(SEARCH_WITHIN) returns, without the stream.  Returns a uint64 array (or, with `device_out` = a callable
+        that allocates a device int64 tensor of a given length, that tensor).  Invalidates the cached f64 search."""
+        d, keep = _search_desc_f64(SEARCH_WITHIN, cutoff, xyz1, idx1, xyz2, idx2, box, pbc, None, None, ids_local, lower, upper)
+        cnt = C.c_uint64(0)
+        check(self.lib.molar_hip_within_count_f64(self.ctx, C.byref(d), C.byref(cnt)))
+        n = int(cnt.value)
+        if device_out is not None:
+            out = device_out(n)
+            if n:
+                check(self.lib.molar_hip_within_fill_f64(self.ctx, out.data_ptr()))
+            return out
+        ids = np.empty(n, np.uint64)
+        check(self.lib.molar_hip_within_fill_f64(self.ctx, ids.ctypes.data))
+        return ids
+
+    def search_connectivity_f64(self, cutoff, xyz, idx=None, box=None, pbc=0, ids_local=True):
+        """SearchConnectivity::from_iter over the f64 single-selection search (molar_hip_search_connectivity_f64, filled by
+        molar_hip_search_connectivity_fill): CSR (offsets uint64[rows + 1], neigh uint64[2 * pairs]) with every list in the
+        reference's push order; rows = len(selection) for local ids, natoms for global ones."""
+        d, keep = _search_desc_f64(SEARCH_SINGLE, cutoff, xyz, idx, None, None, box, pbc, None, None, ids_local, None, None)
+        rows, ent = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.molar_hip_search_connectivity_f64(self.ctx, C.byref(d), C.byref(rows), C.byref(ent)))
+        off = np.empty(rows.value + 1, np.uint64)
+        nb = np.empty(max(ent.value, 1), np.uint64)
+        check(self.lib.molar_hip_search_connectivity_fill(self.ctx, off.ctypes.data, nb.ctypes.data))
+        return off, nb[:ent.value]
+
     def search_histogram_f64(self, kind, cutoff, hmin, hmax, nbins, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0,
                              vdw1=None, vdw2=None, bins=None, want_count=True):
         """molar_hip_search_histogram_f64: the fused histogram with every operation in double - the pairs and distances of
@@ -958,7 +989,7 @@ def _f64(x):
 class MeasureF64:
     """The Measure / Modify methods for MolAR's `f64` feature (Float = f64, molar/src/aliases.rs:10-13) on
     an Engine's context: float64 coordinates and masses (numpy or torch CUDA), float64 results.  Same argument meaning
-    as the Engine methods of the same name; the search exists in f32 only."""
+    as the Engine methods of the same name.  (The f64 search: Engine.search_f64, within_set_f64, search_connectivity_f64.)"""
 
     def __init__(self, engine: "Engine"):
         self.eng, self.lib, self.ctx = engine, engine.lib, engine.ctx
@@ -1044,6 +1075,23 @@ class MeasureF64:
             assert xyz.dtype == np.float64 and xyz.flags.c_contiguous, "unwrap_simple works in place"
         a = self._sel(xyz, idx); ba, kb = self._box9(box)
         check(self.lib.molar_hip_unwrap_simple_f64(self.ctx, *a[:4], ba, pbc_mask(dims)))
+
+    def unwrap_connectivity(self, xyz, box, cutoff, dims=PBC_FULL, idx=None):
+        """Modify::unwrap_connectivity_dim (modify.rs:72-131) in place with Float = f64 (molar_hip_unwrap_connectivity_f64):
+        f64 neighbour search with local ids on the GPU, adjacency in pair order, the reference's stack walk inside the
+        library.  Returns what Engine.unwrap_connectivity returns: the list of groups of LOCAL indices."""
+        if not _is_torch(xyz):
+            assert xyz.dtype == np.float64 and xyz.flags.c_contiguous, "unwrap_connectivity works in place"
+        if idx is not None and len(idx) == 0:      # (a NULL index means "all atoms" to the C ABI: never pass an empty one as NULL)
+            raise ValueError("unwrap_connectivity: empty selection")
+        xa, na, ia, n, k = self._sel(xyz, idx)
+        nsel = n if idx is not None else na
+        ba, kb = self._box9(box) if box is not None else (None, None)      # no box: the library's NO_PBC
+        goff = np.zeros(nsel + 1, np.uint64); gids = np.zeros(max(nsel, 1), np.uint64)
+        ng = C.c_size_t(0)
+        check(self.lib.molar_hip_unwrap_connectivity_f64(self.ctx, xa, na, ia, n, ba, float(cutoff), pbc_mask(dims), goff.ctypes.data,
+                                                         gids.ctypes.data, C.byref(ng)))
+        return [gids[int(goff[g]):int(goff[g + 1])].copy() for g in range(int(ng.value))]
 
     def fit_rmsd_batch(self, frames, mass, ref_xyz, idx=None, ref_idx=None, apply=True):
         """frames: float64 [F, natoms, 3] (numpy, modified in place if apply; or torch CUDA tensor).

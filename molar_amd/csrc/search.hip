@@ -21,11 +21,13 @@
 
 #include "boxmath.hpp"
 #include "common.hpp"
+#include "csr_kernels.hpp"
 #include "hoststream.hpp"
 #include <algorithm>
 
 #include "pair_kernels.hpp"
 #include "stages.hpp"
+#include "unwrap_walk.hpp"
 
 namespace mh {
 // pair_small.hip: count / fill kernels for frames of small cells, 64 / lanes_per_slot slots per wave
@@ -571,27 +573,6 @@ __global__ void __launch_bounds__(64) place_order_frames_kernel(const GridFrame 
 
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = 256 * SCAN_ITEMS;
-
-template <class T>
-__device__ __forceinline__ T block_exclusive_scan(T v, T *total) {
-    __shared__ T wave_sums[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (int)(blockDim.x >> 6);
-    T inc = v;
-    for (int off = 1; off < 64; off <<= 1) {
-        T o = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += o;
-    }
-    if (lane == 63) wave_sums[wave] = inc;
-    __syncthreads();
-    T base = 0, tot = 0;
-    for (int w = 0; w < nw; ++w) {
-        if (w < wave) base += wave_sums[w];
-        tot += wave_sums[w];
-    }
-    __syncthreads();
-    *total = tot;
-    return base + inc - v;
-}
 
 template <class TIn, class TOut>
 __global__ void __launch_bounds__(256) scan_tile_kernel(const TIn *in, TOut *out, TOut *block_sums, uint64_t n) {
@@ -2049,25 +2030,6 @@ __global__ void __launch_bounds__(256) conn_entries_kernel(const uint2 *__restri
     reinterpret_cast<uint2 *>(nb)[p] = make_uint2(ij.y, ij.x);
 }
 
-// off[r] = first sorted entry with row >= r, r = 0 .. nrows (off[nrows] = number of entries)
-__global__ void __launch_bounds__(256) conn_offsets_kernel(const uint32_t *__restrict__ row_sorted, unsigned long long nent, uint32_t nrows,
-                                                           unsigned long long *__restrict__ off) {
-    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
-    if (r > nrows) return;
-    unsigned long long lo = 0, hi = nent;
-    while (lo < hi) {
-        const unsigned long long mid = (lo + hi) >> 1;
-        if (row_sorted[mid] < r) lo = mid + 1;
-        else hi = mid;
-    }
-    off[r] = lo;
-}
-
-__global__ void __launch_bounds__(256) conn_widen_kernel(const uint32_t *__restrict__ nb_sorted, unsigned long long nent, unsigned long long *__restrict__ neigh) {
-    const unsigned long long e = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (e < nent) neigh[e] = nb_sorted[e];
-}
-
 // ================================================================= `within` as a set (selection/ast.rs:589-631)
 //
 // What a caller of distance_search_within(_pbc) keeps is the SET of first-set atoms with a second-set atom in range: the
@@ -2246,34 +2208,6 @@ __global__ void __launch_bounds__(64) within_flags_kernel(const SearchParams *__
         const unsigned long long found = full & ~live;
         if ((found >> lane) & 1ull) flags[__float_as_uint(a.w)] = 1u;
     }
-}
-
-// flags -> count per tile of 2048 (8 flags per thread)
-__global__ void __launch_bounds__(256) flag_tile_count_kernel(const uint8_t *__restrict__ flags, uint64_t n, uint32_t *__restrict__ tile_cnt) {
-    __shared__ uint32_t part[4];
-    const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 8u;
-    uint32_t v = 0;
-    for (uint32_t k = 0; k < 8u; ++k) v += (i + k < n && flags[i + k]) ? 1u : 0u;
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
-}
-
-// positions of the set flags, ascending, as u64
-__global__ void __launch_bounds__(256) flag_compact_kernel(const uint8_t *__restrict__ flags, uint64_t n, const unsigned long long *__restrict__ tile_off,
-                                                           unsigned long long *__restrict__ out) {
-    const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 8u;
-    uint32_t f[8], v = 0;
-    for (uint32_t k = 0; k < 8u; ++k) {
-        f[k] = (i + k < n && flags[i + k]) ? 1u : 0u;
-        v += f[k];
-    }
-    uint32_t tot;
-    uint32_t at = block_exclusive_scan<uint32_t>(v, &tot);
-    unsigned long long o = tile_off[blockIdx.x] + at;
-    for (uint32_t k = 0; k < 8u; ++k)
-        if (f[k]) out[o++] = i + k;
 }
 
 // the pinned ring is worth its host threads for results of some size that go to memory the runtime cannot DMA into
@@ -3339,52 +3273,8 @@ int molar_hip_unwrap_connectivity(molar_hip_ctx *c, float *xyz, size_t natoms, c
         MH_HIP(hipMemcpy(hidx.data(), idx, n * 8, hipMemcpyDeviceToHost));
     }
     const uint64_t *ix = hidx.empty() ? idx : hidx.data();
-    auto pos = [&](size_t k) -> float * { return h + 3 * (ix ? ix[k] : (uint64_t)k); };
-    // ---- the walk (:80-128)
-    std::vector<uint8_t> used(nsel, 0);
-    std::vector<uint32_t> todo, sel_vec;
-    todo.reserve(1024);
-    size_t ng = 0, nids = 0, first_unused = 0;
-    if (group_offsets) group_offsets[0] = 0;
-    auto emit = [&]() {
-        if (sel_vec.empty()) return;
-        std::sort(sel_vec.begin(), sel_vec.end());
-        if (group_ids) for (uint32_t v : sel_vec) group_ids[nids++] = v;
-        else nids += sel_vec.size();
-        ++ng;
-        if (group_offsets) group_offsets[ng] = nids;
-        sel_vec.clear();
-    };
-    todo.push_back(0);
-    used[0] = 1;
-    const uint32_t dims = pbc_dims & 7u;
-    for (;;) {
-        while (!todo.empty()) {
-            const uint32_t cc = todo.back();
-            todo.pop_back();
-            const float *pc = pos(cc);
-            const V3 p0 = v3(pc[0], pc[1], pc[2]);
-            for (uint64_t e = off[cc]; e < off[cc + 1]; ++e) {
-                const uint32_t ind = (uint32_t)adj[e];
-                if (used[ind]) continue;
-                float *pp = pos(ind);
-                const V3 r = closest_image(b, v3(pp[0], pp[1], pp[2]), p0, dims);
-                pp[0] = r.x; pp[1] = r.y; pp[2] = r.z;
-                todo.push_back(ind);
-                used[ind] = 1;
-                sel_vec.push_back(ind);
-            }
-        }
-        while (first_unused < nsel && used[first_unused]) ++first_unused;       // used.iter().find_position(false)
-        if (first_unused == nsel) {
-            emit();
-            break;
-        }
-        todo.push_back((uint32_t)first_unused);
-        used[first_unused] = 1;
-        emit();
-    }
-    if (ngroups) *ngroups = ng;
+    // ---- the walk (:80-128), one template with the f64 entry (unwrap_walk.hpp)
+    unwrap_walk<float, V3>(h, ix, nsel, b, pbc_dims & 7u, off.data(), adj.data(), group_offsets, group_ids, ngroups);
     if (dev) {
         MH_HIP(hipMemcpyAsync(xyz, hostcopy.data(), natoms * 12, hipMemcpyHostToDevice, c->stream));
         MH_HIP(hipStreamSynchronize(c->stream));

@@ -20,6 +20,13 @@
 //   * records are 24-byte positions + 8-byte ids; results are (usize, usize, f64) columns or usize ids (within).
 //   * the fused histogram (molar_hip_search_histogram_f64) walks the same slots in one persistent kernel that bins every
 //     hit's d2 in LDS instead of writing it (hist64_kernel).
+//   * `within` as a set (molar_hip_within_count_f64 / _fill_f64) needs no slots: the plan is inverted into per-cell partner
+//     lists and one wave per (first cell, 64-row block) walks them with a mask of the rows still looking; found rows set a flag,
+//     the ascending flagged ids are the set (within64_flags_kernel, csr_kernels.hpp).  Not here: the kernel for small second
+//     sets walked from the inner selection's side and the grid hold of the f32 form (search.hip) - tunings, f32 only.
+//   * SearchConnectivity (molar_hip_search_connectivity_f64) and unwrap_connectivity (molar_hip_unwrap_connectivity_f64): the
+//     single-selection search into the context's columns, the CSR by one stable sort as in f32 (filled by
+//     molar_hip_search_connectivity_fill), the stack walk on the host by the template both precisions use (unwrap_walk.hpp).
 // 1M atoms, rc 1.0 nm, 2.1e8 results, frame and result resident: see tools/bench_search_f64.py, profiles/r05_search_f64.jsonl.
 // tests/test_gpu_search_f64.py compares all eight drivers bit for bit with the f64 build of the CPU checker.
 #include <algorithm>
@@ -30,8 +37,10 @@
 
 #include "boxmath64.hpp"
 #include "common.hpp"
+#include "csr_kernels.hpp"
 #include "hoststream.hpp"
 #include "stages.hpp"
+#include "unwrap_walk.hpp"
 
 using namespace mh;
 
@@ -59,6 +68,11 @@ struct molar_hip_search64_state {
     double edges_min = 0.0, edges_max = 0.0;
     size_t edges_n = 0;
     int occ_key = -1, occ_blocks = 0;    // workgroups per CU of the last (kernel, LDS size) launched
+    // `within` as a set (molar_hip_within_count_f64 / _fill_f64): per first-set cell the second-set cells its plan entries
+    // meet, one flag byte per id, the flags counted per tile of 2048 and the scan of those counts
+    DevBuf w_part_cnt, w_part, w_flags, w_tile_cnt, w_tile_off, w_out;
+    uint64_t w_nflags = 0, w_total = 0;
+    bool have_within = false;
 };
 
 namespace {
@@ -868,6 +882,139 @@ __global__ void __launch_bounds__(64 * H64_WAVES) hist64_kernel(Params64 P, uint
 template <int KIND, bool EL>
 const void *hist64_fn() { return reinterpret_cast<const void *>(&hist64_kernel<KIND, EL>); }
 
+// ================================================================= `within` as a set in f64 (selection/ast.rs:589-631)
+//
+// What a caller of distance_search_within(_pbc) keeps is SortedSet::from_unsorted(stream) (selection_expr.rs:112): the set of
+// first-set atoms with a second-set atom in range.  The set needs no stream, no offsets and no second pass, and an atom that
+// has been found needs no further candidate in ANY of its plan entries (search.hip has the f32 form of the same idea):
+//  * within64_partners_kernel inverts the plan with plan_entry - the same wrap / drop rules, the same incomplete
+//    neighbourhoods of sheared boxes, both halves of every two-set entry - into per-first-cell lists of (second cell, flags);
+//  * within64_flags_kernel: one wave per (first-set cell, share of its 64-row blocks).  The wave loads its rows once (one per
+//    lane, as run64 does), keeps a mask of the rows still looking and walks the cell's partners: rows pruned against the
+//    partner's bounding box with run64's exact f64 lower bound, the partner's atoms 64 at a time in registers, the live rows
+//    handed round with v_readlane; a row leaves the mask at its first hit, the wave leaves the list when the mask is empty.
+//    Found rows set flags[id] (plain byte stores), id being what the stream would carry;
+//  * ascending flagged ids ARE the sorted, de-duplicated set: csr_kernels.hpp's tile counts and compaction.
+constexpr uint32_t W64_MAX_PART = 28;
+// every (mask, half) pair of the plan has exactly one first cell per origin cell, and origin -> first cell is one to one:
+// a cell is the first cell of at most 14 masks x 2 halves entries
+static_assert(W64_MAX_PART == 2u * sizeof(MASKS64) / sizeof(MASKS64[0]), "partner lists are sized for the plan's stencil");
+
+__global__ void __launch_bounds__(256) within64_partners_kernel(GridP G, uint64_t ntasks, const uint32_t *__restrict__ startA,
+                                                                const uint32_t *__restrict__ startB, uint32_t *__restrict__ part_cnt,
+                                                                uint2 *__restrict__ part) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (t >= ntasks) return;
+    const Entry64 e = plan_entry(G, t, 2u);
+    if (e.ca == 0xFFFFFFFFu) return;
+    if (startA[e.ca + 1] == startA[e.ca] || startB[e.cb + 1] == startB[e.cb]) return;
+    const uint32_t s = atomicAdd(&part_cnt[e.ca], 1u);
+    if (s < W64_MAX_PART) part[(size_t)e.ca * W64_MAX_PART + s] = make_uint2(e.cb, e.flags);
+}
+
+// The hit decision of one candidate as run64's count pass (FILL = false) makes it: row atom a against column atom b (`cand`:
+// the lane holds a column).  Entries classified by the adjacent image (`approx`; c = b + S): the plain distance to c decides
+// outside [band_lo, band_hi] * cutoff^2, PeriodicBox::distance_squared inside the band; every other entry: pair_d2.
+// (A copy, not a helper shared with run64 / hist64_slot: routing those two through a helper changed their ISA.)
+__device__ __forceinline__ bool within64_hit(const Params64 &P, uint32_t wrap, bool approx, bool cand, D3 a, D3 b, D3 c) {
+    const double cut2 = P.cutoff2;
+    if (approx) {
+        const double ex = c.x - a.x, ey = c.y - a.y, ez = c.z - a.z;
+        const double q2 = (ex * ex + ey * ey) + ez * ez;
+        const bool sure = q2 < cut2 * P.band_lo, maybe = cand && q2 <= cut2 * P.band_hi;
+        double d2 = q2;
+        if (__builtin_amdgcn_ballot_w64(maybe && !sure)) {
+            if (maybe && !sure) d2 = pair_d2(P, wrap, a, b);
+        }
+        return maybe && (sure || d2 <= cut2);
+    }
+    return cand && pair_d2(P, wrap, a, b) <= cut2;
+}
+
+__global__ void __launch_bounds__(64) within64_flags_kernel(Params64 P, const uint32_t *__restrict__ startA, const uint32_t *__restrict__ startB,
+                                                            const uint32_t *__restrict__ part_cnt, const uint2 *__restrict__ part,
+                                                            uint8_t *__restrict__ flags, uint32_t nsplit) {
+    const uint32_t lane = threadIdx.x, ca = blockIdx.x;
+    const uint32_t a0 = startA[ca], n1 = startA[ca + 1] - a0;
+    uint32_t np = part_cnt[ca];
+    if (n1 == 0u || np == 0u) return;
+    if (np > W64_MAX_PART) np = W64_MAX_PART;
+    for (uint32_t i0 = blockIdx.y * 64u; i0 < n1; i0 += nsplit * 64u) {
+        const uint32_t rows = n1 - i0 < 64u ? n1 - i0 : 64u;
+        double ax = 0.0, ay = 0.0, az = 0.0;
+        uint32_t aid = 0u;
+        if (lane < rows) {
+            const size_t ra = (size_t)a0 + i0 + lane;
+            ax = P.posA[3 * ra]; ay = P.posA[3 * ra + 1]; az = P.posA[3 * ra + 2];
+            aid = (uint32_t)P.idA[ra];
+        }
+        const unsigned long long full = __builtin_amdgcn_ballot_w64(lane < rows);
+        unsigned long long live = full;                      // rows still looking for a partner atom
+        for (uint32_t pi = 0; pi < np && live; ++pi) {
+            const uint2 e = part[(size_t)ca * W64_MAX_PART + pi];
+            const uint32_t cb = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x), fl = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
+            const uint32_t wrap = fl & 7u;
+            const uint32_t b0 = startB[cb], n2 = startB[cb + 1] - b0;
+            // b + S is the image of the second cell next to the first one (run64)
+            const bool approx = P.approx_wrapped && P.use_box && wrap != 0u && !(P.box->nshift != 0 && wrap == MOLAR_HIP_PBC_FULL);
+            double Sx = 0.0, Sy = 0.0, Sz = 0.0;
+            if (approx)
+                for (int d = 0; d < 3; ++d) {
+                    if (!((wrap >> d) & 1u)) continue;
+                    const double sgn = ((fl >> (12 + d)) & 1u) ? 1.0 : -1.0;
+                    Sx += sgn * P.box->m[3 * d];
+                    Sy += sgn * P.box->m[3 * d + 1];
+                    Sz += sgn * P.box->m[3 * d + 2];
+                }
+            unsigned long long cand = live;
+            if (wrap == 0u || !P.use_box || approx) {        // run64's row pruning: an f64 lower bound of every d2 of the row
+                const double *bb = P.aabbB + 6 * (size_t)cb;
+                double px = ax, py = ay, pz = az, lim = P.cutoff2;
+                if (approx) {
+                    px = ax - Sx;
+                    py = ay - Sy;
+                    pz = az - Sz;
+                    lim = P.prune_limit2;
+                }
+                const double ex = fmax(fmax(bb[0] - px, px - bb[3]), 0.0), ey = fmax(fmax(bb[1] - py, py - bb[4]), 0.0),
+                             ez = fmax(fmax(bb[2] - pz, pz - bb[5]), 0.0);
+                cand &= __builtin_amdgcn_ballot_w64(!((ex * ex + ey * ey) + ez * ez > lim));
+            }
+            for (uint32_t j0 = 0; j0 < n2 && cand; j0 += 64u) {
+                const bool inb = j0 + lane < n2;
+                double bx = 0.0, by = 0.0, bz = 0.0;
+                if (inb) {
+                    const size_t rb = (size_t)b0 + j0 + lane;
+                    bx = P.posB[3 * rb]; by = P.posB[3 * rb + 1]; bz = P.posB[3 * rb + 2];
+                }
+                const D3 b = D3{bx, by, bz}, cimg = D3{bx + Sx, by + Sy, bz + Sz};
+                unsigned long long rm = cand;
+                while (rm) {
+                    const uint32_t r = (uint32_t)__builtin_ctzll(rm);
+                    rm &= rm - 1ull;
+                    const D3 a = D3{lane_bcast(ax, r), lane_bcast(ay, r), lane_bcast(az, r)};
+                    if (__builtin_amdgcn_ballot_w64(within64_hit(P, wrap, approx, inb, a, b, cimg))) {   // the row's first hit (:287-290)
+                        live &= ~(1ull << r);
+                        cand &= ~(1ull << r);
+                    }
+                }
+            }
+        }
+        if (((full & ~live) >> lane) & 1ull) flags[aid] = 1u;
+    }
+}
+
+// SearchConnectivity::from_iter (connectivity.rs:19-35) over the f64 search's id columns: pair p pushes j onto i's list
+// (entry 2p), then i onto j's (entry 2p + 1) - conn_entries_kernel of search.hip for two uint64 columns
+__global__ void __launch_bounds__(256) conn64_entries_kernel(const unsigned long long *__restrict__ pi, const unsigned long long *__restrict__ pj,
+                                                             unsigned long long npairs, uint32_t *__restrict__ row, uint32_t *__restrict__ nb) {
+    const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (p >= npairs) return;
+    const uint32_t i = (uint32_t)pi[p], j = (uint32_t)pj[p];
+    reinterpret_cast<uint2 *>(row)[p] = make_uint2(i, j);
+    reinterpret_cast<uint2 *>(nb)[p] = make_uint2(j, i);
+}
+
 }  // namespace
 
 namespace mh {
@@ -876,7 +1023,8 @@ void search64_release(molar_hip_ctx *c) {
     molar_hip_search64_state &Z = *c->s64;
     for (DevBuf *b : {&Z.posA, &Z.idA, &Z.vdwA, &Z.posB, &Z.idB, &Z.vdwB, &Z.slots, &Z.slot_cnt, &Z.slot_base, &Z.box, &Z.out_i, &Z.out_j, &Z.out_d,
                       &Z.in_xyz[0], &Z.in_xyz[1], &Z.in_idx[0], &Z.in_idx[1], &Z.in_vdw[0], &Z.in_vdw[1], &Z.key_in, &Z.key_out, &Z.val_in,
-                      &Z.val_out, &Z.pos3, &Z.aabbA, &Z.aabbB, &Z.startA, &Z.startB, &Z.task_ns, &Z.task_first, &Z.cub_tmp, &Z.partial, &Z.flags})
+                      &Z.val_out, &Z.pos3, &Z.aabbA, &Z.aabbB, &Z.startA, &Z.startB, &Z.task_ns, &Z.task_first, &Z.cub_tmp, &Z.partial, &Z.flags, &Z.hedges, &Z.hsum, &Z.hnext, &Z.w_part_cnt, &Z.w_part, &Z.w_flags, &Z.w_tile_cnt,
+                      &Z.w_tile_off, &Z.w_out})
         b->release();
     delete c->s64;
     c->s64 = nullptr;
@@ -939,15 +1087,37 @@ static int build_grid64(molar_hip_ctx *c, molar_hip_search64_state &Z, const Set
     return 0;
 }
 
-// Everything of a search before its evaluation, shared by the count pass and the fused histogram: the sets on the device, the
-// box, the bounds, the grid dims, both grids, the cells' bounding boxes, the plan, its scan (read back: the number of slots),
-// the slot records and the classification of wrapped entries.  *P is the parameter block of the evaluation; *empty: nothing
-// to evaluate (no slot, or a vdW search with an empty set).
-static int prepare64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Params64 *P, bool *empty) {
+// What the first half of a search's prologue leaves for the second (prepare64) or for the partner lists of the set form
+struct Prep64 {
+    GridP G;
+    BoxD box;
+    double ext[3];
+    uint64_t dims[3];
+    double cutoff;
+    uint32_t mult;
+    bool two, vdw, use_box;
+    int *err_dev;                          // raised by the grid build: a selection index out of range
+    const uint32_t *startA, *startB;
+};
+
+// The parameter block of an evaluation from the cached state
+static Params64 params64(const molar_hip_search64_state &Z) {
+    const bool two = Z.kind != MOLAR_HIP_SEARCH_SINGLE;
+    const DevBuf &pB = two ? Z.posB : Z.posA, &iB = two ? Z.idB : Z.idA, &vB = two ? Z.vdwB : Z.vdwA;
+    return Params64{Z.posA.as<double>(), pB.as<double>(), Z.vdwA.as<double>(), vB.as<double>(),
+                    Z.idA.as<unsigned long long>(), iB.as<unsigned long long>(), Z.box.as<BoxD>(), Z.slots.as<Slot64>(), Z.nslots,
+                    Z.kind, Z.use_box ? 1 : 0, Z.cutoff * Z.cutoff, Z.approx ? 1 : 0, Z.band_lo, Z.band_hi, (two ? Z.aabbB : Z.aabbA).as<double>(), Z.prune_limit2};
+}
+
+// First half of the prologue, up to the point where the slot form and the set form part: the sets on the device, the box,
+// the bounds, the grid dims, both grids and the cells' bounding boxes.  Enqueues only (but for the vdW radii maximum and the
+// non-periodic bounding box, which the host needs for the grid).  *empty: a vdW search with an empty set.
+static int prepare64_grids(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Prep64 *R, bool *empty) {
     MH_HIP(hipSetDevice(c->device));
     if (!c->s64) c->s64 = new molar_hip_search64_state;
     molar_hip_search64_state &Z = *c->s64;
     Z.have = false;
+    Z.have_within = false;
     const int kind = q->kind;
     if (kind < MOLAR_HIP_SEARCH_SINGLE || kind > MOLAR_HIP_SEARCH_DOUBLE_VDW)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_count_f64: unknown kind %d", kind);
@@ -1080,37 +1250,33 @@ static int prepare64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Param
         hipLaunchKernelGGL(aabb64_kernel, dim3((G.ncells + 3u) / 4u), dim3(256), 0, c->stream, startB, G.ncells,
                            (two ? Z.posB : Z.posA).as<double>(), bb.as<double>());
     }
-    const uint64_t ntasks = (uint64_t)G.ncells * 14ull * mult;
-    MH_TRY(Z.task_ns.reserve((ntasks + 1) * 4));
-    MH_TRY(Z.task_first.reserve((ntasks + 1) * 4));
-    hipLaunchKernelGGL(plan64_kernel, dim3((unsigned)((ntasks + 1 + 255) / 256)), dim3(256), 0, c->stream, G, ntasks, mult, startA, startB,
-                       Z.task_ns.as<uint32_t>());
-    MH_TRY(device_exclusive_sum_u32(c, Z.cub_tmp, Z.task_ns.as<uint32_t>(), Z.task_first.as<uint32_t>(), ntasks + 1));
-    struct { uint32_t nslots; int err; } hs = {0, 0};
-    MH_HIP(hipMemcpyAsync(&hs.nslots, Z.task_first.as<uint32_t>() + ntasks, 4, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipMemcpyAsync(&hs.err, err_dev, 4, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    if (hs.err) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_f64: selection index out of range");
-    if (hs.nslots >= 0x7FFFFF00u) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_f64: plan too large");
-    Z.nslots = hs.nslots;
-    Z.total = 0;
-    if (Z.nslots == 0) {
-        *empty = true;
-        return MOLAR_HIP_OK;
-    }
-    MH_TRY(Z.slots.reserve((size_t)Z.nslots * sizeof(Slot64)));
-    hipLaunchKernelGGL(slots64_kernel, dim3((unsigned)((ntasks + 255) / 256)), dim3(256), 0, c->stream, G, ntasks, mult, startA, startB,
-                       Z.task_first.as<uint32_t>(), Z.slots.as<Slot64>());
-    MH_TRY(Z.box.reserve(sizeof box));
-    MH_HIP(hipMemcpyAsync(Z.box.p, &box, sizeof box, hipMemcpyHostToDevice, c->stream));
-    const DevBuf &pB = two ? Z.posB : Z.posA, &iB = two ? Z.idB : Z.idA, &vB = two ? Z.vdwB : Z.vdwA;
-    // Entries across the periodic boundary (search.hip, make_params, derives the same bound for f32): the reference evaluates
-    // v = p2 - p1, f = inv v, f -= round(f), s = M f; the kernels classify with (b + S) - a.  With u = 2^-53, L the largest
-    // |coordinate| the box allows and kappa = || |M| |M^-1| ||_inf the two difference vectors disagree by at most
-    // e = (4 kappa + 9) u L per component, d2 near cutoff^2 by 2 sqrt(3) e / rc relative to cutoff^2.  Outside a band of
-    // 1e-9 + four times that around cutoff^2 the plain distance to the adjacent image decides; inside it, and for every hit's
-    // distance, PeriodicBox::distance_squared itself.  Needs >= 4 cells along every periodic dimension (round(f_d) = +-1 for
-    // every pair of a wrapped entry that can be within the cutoff).
+    R->G = G;
+    R->box = box;
+    std::memcpy(R->ext, ext, sizeof ext);
+    std::memcpy(R->dims, dims, sizeof dims);
+    R->cutoff = cutoff;
+    R->mult = mult;
+    R->two = two;
+    R->vdw = vdw;
+    R->use_box = use_box;
+    R->err_dev = err_dev;
+    R->startA = startA;
+    R->startB = startB;
+    return MOLAR_HIP_OK;
+}
+
+// Entries across the periodic boundary (search.hip, make_params, derives the same bound for f32): the reference evaluates
+// v = p2 - p1, f = inv v, f -= round(f), s = M f; the kernels classify with (b + S) - a.  With u = 2^-53, L the largest
+// |coordinate| the box allows and kappa = || |M| |M^-1| ||_inf the two difference vectors disagree by at most
+// e = (4 kappa + 9) u L per component, d2 near cutoff^2 by 2 sqrt(3) e / rc relative to cutoff^2.  Outside a band of
+// 1e-9 + four times that around cutoff^2 the plain distance to the adjacent image decides; inside it, and for every hit's
+// distance, PeriodicBox::distance_squared itself.  Needs >= 4 cells along every periodic dimension (round(f_d) = +-1 for
+// every pair of a wrapped entry that can be within the cutoff).  Host arithmetic only.
+static void classify64(molar_hip_search64_state &Z, const Prep64 &R) {
+    const BoxD &box = R.box;
+    const double *ext = R.ext, cutoff = R.cutoff;
+    const uint64_t *dims = R.dims;
+    const bool use_box = R.use_box, vdw = R.vdw;
     Z.approx = false;
     Z.band_lo = Z.band_hi = 1.0;
     if (use_box) {
@@ -1143,9 +1309,46 @@ static int prepare64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Param
             Z.prune_limit2 = lim * lim;
         }
     }
-    *P = Params64{Z.posA.as<double>(), pB.as<double>(), Z.vdwA.as<double>(), vB.as<double>(),
-                  Z.idA.as<unsigned long long>(), iB.as<unsigned long long>(), Z.box.as<BoxD>(), Z.slots.as<Slot64>(), Z.nslots,
-                  kind, use_box ? 1 : 0, cutoff * cutoff, Z.approx ? 1 : 0, Z.band_lo, Z.band_hi, (two ? Z.aabbB : Z.aabbA).as<double>(), Z.prune_limit2};
+}
+
+// Everything of a search before its evaluation, shared by the count pass and the fused histogram: prepare64_grids, then the
+// plan, its scan (read back: the number of slots), the slot records and the classification of wrapped entries.  *P is the
+// parameter block of the evaluation; *empty: nothing to evaluate (no slot, or a vdW search with an empty set).
+static int prepare64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, Params64 *P, bool *empty) {
+    Prep64 R;
+    MH_TRY(prepare64_grids(c, q, &R, empty));
+    if (*empty) return MOLAR_HIP_OK;
+    molar_hip_search64_state &Z = *c->s64;
+    const GridP &G = R.G;
+    const BoxD &box = R.box;
+    const uint32_t mult = R.mult;
+    const uint32_t *startA = R.startA, *startB = R.startB;
+    int *err_dev = R.err_dev;
+    const uint64_t ntasks = (uint64_t)G.ncells * 14ull * mult;
+    MH_TRY(Z.task_ns.reserve((ntasks + 1) * 4));
+    MH_TRY(Z.task_first.reserve((ntasks + 1) * 4));
+    hipLaunchKernelGGL(plan64_kernel, dim3((unsigned)((ntasks + 1 + 255) / 256)), dim3(256), 0, c->stream, G, ntasks, mult, startA, startB,
+                       Z.task_ns.as<uint32_t>());
+    MH_TRY(device_exclusive_sum_u32(c, Z.cub_tmp, Z.task_ns.as<uint32_t>(), Z.task_first.as<uint32_t>(), ntasks + 1));
+    struct { uint32_t nslots; int err; } hs = {0, 0};
+    MH_HIP(hipMemcpyAsync(&hs.nslots, Z.task_first.as<uint32_t>() + ntasks, 4, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(&hs.err, err_dev, 4, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (hs.err) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_f64: selection index out of range");
+    if (hs.nslots >= 0x7FFFFF00u) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_f64: plan too large");
+    Z.nslots = hs.nslots;
+    Z.total = 0;
+    if (Z.nslots == 0) {
+        *empty = true;
+        return MOLAR_HIP_OK;
+    }
+    MH_TRY(Z.slots.reserve((size_t)Z.nslots * sizeof(Slot64)));
+    hipLaunchKernelGGL(slots64_kernel, dim3((unsigned)((ntasks + 255) / 256)), dim3(256), 0, c->stream, G, ntasks, mult, startA, startB,
+                       Z.task_first.as<uint32_t>(), Z.slots.as<Slot64>());
+    MH_TRY(Z.box.reserve(sizeof box));
+    MH_HIP(hipMemcpyAsync(Z.box.p, &box, sizeof box, hipMemcpyHostToDevice, c->stream));
+    classify64(Z, R);
+    *P = params64(Z);
     return MOLAR_HIP_OK;
 }
 
@@ -1196,11 +1399,7 @@ static int fill64(molar_hip_ctx *c, uint64_t *oi, uint64_t *oj, double *od, bool
         MH_TRY(dev(oj, Z.out_j, n * 8, &dj));
         MH_TRY(dev(od, Z.out_d, n * 8, &dd));
     }
-    const bool two = Z.kind != MOLAR_HIP_SEARCH_SINGLE;
-    const DevBuf &pB = two ? Z.posB : Z.posA, &iB = two ? Z.idB : Z.idA, &vB = two ? Z.vdwB : Z.vdwA;
-    Params64 P{Z.posA.as<double>(), pB.as<double>(), Z.vdwA.as<double>(), vB.as<double>(),
-               Z.idA.as<unsigned long long>(), iB.as<unsigned long long>(), Z.box.as<BoxD>(), Z.slots.as<Slot64>(), Z.nslots,
-               Z.kind, Z.use_box ? 1 : 0, Z.cutoff * Z.cutoff, Z.approx ? 1 : 0, Z.band_lo, Z.band_hi, (two ? Z.aabbB : Z.aabbA).as<double>(), Z.prune_limit2};
+    const Params64 P = params64(Z);
     launch_pair64<true>(Z.kind, grid_of(Z.nslots), c->stream, P, nullptr, Z.slot_base.as<unsigned long long>(),
                         static_cast<unsigned long long *>(di), static_cast<unsigned long long *>(dj), static_cast<double *>(dd));
     MH_HIP(hipGetLastError());
@@ -1386,6 +1585,181 @@ int molar_hip_search_histogram_frames_f64(molar_hip_ctx *c, const molar_hip_sear
     MH_HIP(hipMemcpyAsync(h.data(), hsum, nbins * 8, hipMemcpyDeviceToHost, c->stream));
     MH_HIP(hipStreamSynchronize(c->stream));
     for (size_t b = 0; b < nbins; ++b) bins[b] += h[b];
+    return MOLAR_HIP_OK;
+}
+
+// `within` as a set (see within64_flags_kernel): the prologue up to the grids, the partner lists, the flag pass, the flags
+// counted per tile and scanned - one read-back: the size of the set (with the grid build's error flag).
+int molar_hip_within_count_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, uint64_t *out_count) {
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within_count_f64: null argument");
+    if (q->kind != MOLAR_HIP_SEARCH_WITHIN)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within_count_f64: the request must be of kind MOLAR_HIP_SEARCH_WITHIN");
+    const size_t nsel1 = q->idx1 ? q->n1 : q->natoms1, nsel2 = q->idx2 ? q->n2 : q->natoms2;
+    const uint64_t nflags = q->ids_local ? nsel1 : (q->idx1 ? q->natoms1 : nsel1);       // the id range: one flag per id
+    if (nflags >= 0xFFFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "within_count_f64: ids of %llu atoms exceed 32 bits", (unsigned long long)nflags);
+    Prep64 R;
+    bool empty = false;
+    MH_TRY(prepare64_grids(c, q, &R, &empty));      // (the cached f64 search is gone: its buffers hold this request's grids)
+    molar_hip_search64_state &Z = *c->s64;
+    Z.w_nflags = nflags;
+    Z.w_total = 0;
+    if (out_count) *out_count = 0;
+    struct { unsigned long long total; int err; } hs = {0ull, 0};
+    if (nsel1 == 0 || nsel2 == 0 || nflags == 0) {
+        MH_HIP(hipMemcpyAsync(&hs.err, R.err_dev, 4, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+        if (hs.err) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_f64: selection index out of range");
+        Z.have_within = true;
+        return MOLAR_HIP_OK;
+    }
+    MH_TRY(Z.box.reserve(sizeof R.box));
+    MH_HIP(hipMemcpyAsync(Z.box.p, &R.box, sizeof R.box, hipMemcpyHostToDevice, c->stream));
+    classify64(Z, R);
+    const Params64 P = params64(Z);
+    const uint32_t ncells = R.G.ncells;
+    const uint64_t ntasks = (uint64_t)ncells * 14ull * 2ull, ntiles = (nflags + 2047) / 2048;
+    const size_t flag_bytes = (size_t)((nflags + 3) & ~(uint64_t)3);
+    MH_TRY(Z.w_flags.reserve(flag_bytes));
+    MH_TRY(Z.w_tile_cnt.reserve((ntiles + 1) * 4));
+    MH_TRY(Z.w_tile_off.reserve((ntiles + 1) * 8));
+    MH_TRY(Z.w_part_cnt.reserve((size_t)ncells * 4));
+    MH_TRY(Z.w_part.reserve((size_t)ncells * W64_MAX_PART * sizeof(uint2)));
+    MH_HIP(hipMemsetAsync(Z.w_flags.p, 0, flag_bytes, c->stream));
+    MH_HIP(hipMemsetAsync(Z.w_part_cnt.p, 0, (size_t)ncells * 4, c->stream));
+    MH_HIP(hipMemsetAsync(Z.w_tile_cnt.p, 0, (ntiles + 1) * 4, c->stream));
+    hipLaunchKernelGGL(within64_partners_kernel, dim3((unsigned)((ntasks + 255) / 256)), dim3(256), 0, c->stream, R.G, ntasks, R.startA, R.startB,
+                       Z.w_part_cnt.as<uint32_t>(), Z.w_part.as<uint2>());
+    // cells of many 64-row blocks get several waves (a share of the blocks each)
+    uint32_t nsplit = (uint32_t)(((uint64_t)nsel1 / 64u) / ncells) + 1u;
+    if (nsplit > 64u) nsplit = 64u;
+    hipLaunchKernelGGL(within64_flags_kernel, dim3(ncells, nsplit), dim3(64), 0, c->stream, P, R.startA, R.startB, Z.w_part_cnt.as<uint32_t>(),
+                       Z.w_part.as<uint2>(), Z.w_flags.as<uint8_t>(), nsplit);
+    hipLaunchKernelGGL(flag_tile_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, Z.w_flags.as<uint8_t>(), nflags,
+                       Z.w_tile_cnt.as<uint32_t>());
+    MH_HIP(hipGetLastError());
+    MH_TRY(device_exclusive_sum_u32_u64(c, Z.cub_tmp, Z.w_tile_cnt.as<uint32_t>(), Z.w_tile_off.as<unsigned long long>(), (size_t)ntiles + 1));
+    MH_HIP(hipMemcpyAsync(&hs.total, Z.w_tile_off.as<unsigned long long>() + ntiles, 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(&hs.err, R.err_dev, 4, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (hs.err) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_f64: selection index out of range");
+    Z.w_total = hs.total;
+    Z.have_within = true;
+    if (out_count) *out_count = hs.total;
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_within_fill_f64(molar_hip_ctx *c, uint64_t *ids) {
+    if (!c || !c->s64 || !c->s64->have_within)
+        return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached f64 within set: call molar_hip_within_count_f64 first");
+    molar_hip_search64_state &Z = *c->s64;
+    if (Z.w_total == 0) return MOLAR_HIP_OK;
+    if (!ids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within_fill_f64: null output");
+    MH_HIP(hipSetDevice(c->device));
+    const bool dev = is_device_ptr(ids);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(ids);
+    if (!dev) {
+        MH_TRY(Z.w_out.reserve((size_t)Z.w_total * 8));
+        dst = Z.w_out.as<unsigned long long>();
+    }
+    const uint64_t ntiles = (Z.w_nflags + 2047) / 2048;
+    hipLaunchKernelGGL(flag_compact_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, Z.w_flags.as<uint8_t>(), Z.w_nflags,
+                       Z.w_tile_off.as<unsigned long long>(), dst);
+    MH_HIP(hipGetLastError());
+    if (!dev) {
+        MH_HIP(hipMemcpyAsync(ids, dst, (size_t)Z.w_total * 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+    }
+    return MOLAR_HIP_OK;
+}
+
+// SearchConnectivity (connectivity.rs:8-60) of the f64 single-selection search: count, scan and fill into the context's own
+// columns, then the CSR on the device exactly as molar_hip_search_connectivity builds it - one stable sort of the entries by
+// row, offsets by bisection, neighbours widened - into the SAME context fields: molar_hip_search_connectivity_fill copies it out.
+int molar_hip_search_connectivity_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, uint64_t *out_rows, uint64_t *out_entries) {
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity_f64: null argument");
+    if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity_f64: ids of one selection index the lists - the request must be of kind MOLAR_HIP_SEARCH_SINGLE");
+    c->have_conn = false;
+    uint64_t npairs = 0;
+    MH_TRY(molar_hip_search_count_f64(c, q, &npairs));
+    const size_t nsel = q->idx1 ? q->n1 : q->natoms1;
+    const uint64_t nrows = q->ids_local ? nsel : (q->idx1 ? q->natoms1 : nsel);
+    if (nrows >= 0xFFFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity_f64: too many rows");
+    const uint64_t nent = 2ull * npairs;
+    if (nent >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity_f64: %llu list entries", (unsigned long long)nent);
+    MH_TRY(fill64(c, nullptr, nullptr, nullptr, false));          // (i, j, d) into the context's columns; nothing leaves the device
+    molar_hip_search64_state &Z = *c->s64;
+    MH_TRY(c->conn_off.reserve((nrows + 1) * 8));
+    MH_TRY(c->conn_ent.reserve((nent ? nent : 1) * 16));           // four u32 arrays: rows and neighbours, unsorted and sorted
+    MH_TRY(c->conn_neigh.reserve((nent ? nent : 1) * 8));
+    uint32_t *row_in = c->conn_ent.as<uint32_t>(), *nb_in = row_in + nent, *row_out = nb_in + nent, *nb_out = row_out + nent;
+    const unsigned nbP = (unsigned)((npairs + 255) / 256), nbE = (unsigned)((nent + 255) / 256);
+    if (nbP) {
+        hipLaunchKernelGGL(conn64_entries_kernel, dim3(nbP), dim3(256), 0, c->stream, Z.out_i.as<unsigned long long>(),
+                           Z.out_j.as<unsigned long long>(), (unsigned long long)npairs, row_in, nb_in);
+        int end_bit = 1;
+        while (end_bit < 32 && (nrows >> end_bit)) ++end_bit;
+        MH_TRY(device_sort_pairs_u32(c, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
+        hipLaunchKernelGGL(conn_widen_kernel, dim3(nbE), dim3(256), 0, c->stream, nb_out, (unsigned long long)nent, c->conn_neigh.as<unsigned long long>());
+    }
+    hipLaunchKernelGGL(conn_offsets_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, c->stream, row_out, (unsigned long long)nent,
+                       (uint32_t)nrows, c->conn_off.as<unsigned long long>());
+    MH_HIP(hipGetLastError());
+    c->conn_rows = nrows;
+    c->conn_entries = nent;
+    c->have_conn = true;
+    if (out_rows) *out_rows = nrows;
+    if (out_entries) *out_entries = nent;
+    return MOLAR_HIP_OK;
+}
+
+// Modify::unwrap_connectivity_dim (molar/src/modify.rs:72-131) with Float = f64: the neighbour search over the selection with
+// LOCAL ids under full PBC whatever `pbc_dims` (:77-78) and the CSR on the device (molar_hip_search_connectivity_f64), the
+// stack walk on the host with boxmath64.hpp's closest_image over pbc_dims (unwrap_walk.hpp: the same template as the f32 entry).
+int molar_hip_unwrap_connectivity_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double *box9,
+                                      double cutoff, uint8_t pbc_dims, uint64_t *group_offsets, uint64_t *group_ids, size_t *ngroups) {
+    if (!c || !xyz) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_connectivity_f64: null argument");
+    if (!box9) return fail(MOLAR_HIP_ERR_NO_PBC, "no periodic box");                               // require_box (:76)
+    const size_t nsel = idx ? n : natoms;
+    if (nsel == 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_connectivity_f64 of an empty selection");
+    if (nsel >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "unwrap_connectivity_f64: %zu atoms exceed the 32-bit local ids", nsel);
+    MH_HIP(hipSetDevice(c->device));
+    double hb[9];
+    MH_TRY(host_copy(c, box9, 9, hb));
+    BoxD b;
+    MH_TRY(box64_from_matrix(hb, &b));
+    molar_hip_search_desc_f64 q{};
+    q.kind = MOLAR_HIP_SEARCH_SINGLE;
+    q.cutoff = cutoff;
+    q.xyz1 = xyz; q.natoms1 = natoms; q.idx1 = idx; q.n1 = n;
+    q.ids_local = 1;
+    q.box9 = box9;
+    q.pbc = MOLAR_HIP_PBC_FULL;
+    uint64_t nrows = 0, nent = 0;
+    MH_TRY(molar_hip_search_connectivity_f64(c, &q, &nrows, &nent));
+    std::vector<uint64_t> off(nsel + 1, 0), adj((size_t)(nent ? nent : 1));
+    MH_TRY(molar_hip_search_connectivity_fill(c, off.data(), adj.data()));
+    // ---- the coordinates of the frame and the selection on the host
+    const bool dev = is_device_ptr(xyz);
+    std::vector<double> hostcopy;
+    double *h = xyz;
+    if (dev) {
+        hostcopy.resize(natoms * 3);
+        MH_HIP(hipMemcpyAsync(hostcopy.data(), xyz, natoms * 24, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+        h = hostcopy.data();
+    }
+    std::vector<uint64_t> hidx;
+    if (idx && is_device_ptr(idx)) {
+        hidx.resize(n);
+        MH_HIP(hipMemcpy(hidx.data(), idx, n * 8, hipMemcpyDeviceToHost));
+    }
+    const uint64_t *ix = hidx.empty() ? idx : hidx.data();
+    unwrap_walk<double, D3>(h, ix, nsel, b, pbc_dims & 7u, off.data(), adj.data(), group_offsets, group_ids, ngroups);
+    if (dev) {
+        MH_HIP(hipMemcpyAsync(xyz, hostcopy.data(), natoms * 24, hipMemcpyHostToDevice, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+    }
     return MOLAR_HIP_OK;
 }
 

@@ -386,7 +386,9 @@ impl Engine {
     }
 
     // ---- MolAR built with `f64` (Float = f64): the Measure / Modify methods on double-precision data
-    // (header: "MolAR built with its `f64` feature"); the periodic ones are bound in ffi.rs.  The search takes f32 only.
+    // (header: "MolAR built with its `f64` feature"); the periodic ones are bound in ffi.rs.  The f64 search
+    // is wrapped below as far as MolAR's own callers use it: the fused histogram, `within` as a set, SearchConnectivity and
+    // unwrap_connectivity (the raw f64 drivers are bound in ffi.rs).
 
     /// `Measure::center_of_mass` (:60-75), f64
     pub fn center_of_mass_f64(&self, coords: &[[f64; 3]], index: Option<&[usize]>, masses: &[f64]) -> Result<[f64; 3], EngineError> {
@@ -499,6 +501,76 @@ impl Engine {
         let mut e = vec![0f64; nbins + 1];
         self.plugin.check(unsafe { (self.plugin.fns.histogram_edges_f64)(hmin, hmax, nbins, e.as_mut_ptr()) })?;
         Ok(e)
+    }
+
+    /// `within <cutoff> [pbc] of <inner>` with Float = f64 as the selection keeps it: `SortedSet::from_unsorted` of the f64
+    /// stream, computed without the stream (molar_hip_within_count_f64 / _fill_f64).  `box9` = None: the non-periodic form,
+    /// which needs `bounds` = (lower, upper) as `distance_search_within` does.
+    pub fn within_set_f64(
+        &self, cutoff: f64, coords1: &[[f64; 3]], index1: Option<&[usize]>, coords2: &[[f64; 3]], index2: Option<&[usize]>,
+        box9: Option<&[f64; 9]>, pbc: u8, bounds: Option<(&[f64; 3], &[f64; 3])>,
+    ) -> Result<Vec<usize>, EngineError> {
+        check_index(index1, coords1.len(), "within_set_f64 (set 1)")?;
+        check_index(index2, coords2.len(), "within_set_f64 (set 2)")?;
+        let (i1, n1) = idx_ptr(index1);
+        let (i2, n2) = idx_ptr(index2);
+        let d = MolarHipSearchDescF64 {
+            kind: SEARCH_WITHIN, cutoff, xyz1: coords1.as_ptr() as *const f64, natoms1: coords1.len(), idx1: i1, n1,
+            xyz2: coords2.as_ptr() as *const f64, natoms2: coords2.len(), idx2: i2, n2,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc,
+            lower3: bounds.map_or(std::ptr::null(), |b| b.0.as_ptr()), upper3: bounds.map_or(std::ptr::null(), |b| b.1.as_ptr()),
+            ..Default::default()
+        };
+        let f = &self.plugin.fns;
+        let mut n = 0u64;
+        self.plugin.check(unsafe { (f.within_count_f64)(self.ctx, &d, &mut n) })?;
+        let mut ids = vec![0u64; n as usize];
+        if n > 0 {
+            self.plugin.check(unsafe { (f.within_fill_f64)(self.ctx, ids.as_mut_ptr()) })?;
+        }
+        Ok(ids.into_iter().map(|v| v as usize).collect())
+    }
+
+    /// `SearchConnectivity::from_iter(distance_search_single(_pbc)(..))` with Float = f64, built on the device: adjacency lists
+    /// in the reference's push order as CSR over local ids (`offsets[len + 1]`, `neigh[2 * pairs]`).  The CSR is u64 in both
+    /// precisions: the fill call is the f32 form's.
+    pub fn search_connectivity_f64(
+        &self, cutoff: f64, coords: &[[f64; 3]], index: Option<&[usize]>, box9: Option<&[f64; 9]>, pbc: u8,
+    ) -> Result<(Vec<usize>, Vec<usize>), EngineError> {
+        check_index(index, coords.len(), "search_connectivity_f64")?;
+        let (ip, n) = idx_ptr(index);
+        let d = MolarHipSearchDescF64 {
+            kind: SEARCH_SINGLE, cutoff, xyz1: coords.as_ptr() as *const f64, natoms1: coords.len(), idx1: ip, n1: n,
+            ids_local: 1, box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let f = &self.plugin.fns;
+        let (mut rows, mut entries) = (0u64, 0u64);
+        self.plugin.check(unsafe { (f.search_connectivity_f64)(self.ctx, &d, &mut rows, &mut entries) })?;
+        let mut off = vec![0u64; rows as usize + 1];
+        let mut nb = vec![0u64; entries as usize];
+        self.plugin.check(unsafe { (f.search_connectivity_fill)(self.ctx, off.as_mut_ptr(), if entries > 0 { nb.as_mut_ptr() } else { std::ptr::null_mut() }) })?;
+        Ok((off.into_iter().map(|v| v as usize).collect(), nb.into_iter().map(|v| v as usize).collect()))
+    }
+
+    /// `Modify::unwrap_connectivity_dim` (modify.rs:72-131) with Float = f64, in place: the f64 neighbour search with local ids
+    /// under full PBC on the GPU, the reference's stack walk inside the plugin.  Returns the groups of LOCAL indices the
+    /// reference returns as selections.
+    pub fn unwrap_connectivity_f64(
+        &self, coords: &mut [[f64; 3]], index: Option<&[usize]>, box9: &[f64; 9], cutoff: f64, dims: u8,
+    ) -> Result<Vec<Vec<usize>>, EngineError> {
+        check_index(index, coords.len(), "unwrap_connectivity_f64")?;
+        let (ip, n) = idx_ptr(index);
+        let nsel = index.map_or(coords.len(), |i| i.len());
+        let mut off = vec![0u64; nsel + 1];
+        let mut ids = vec![0u64; nsel.max(1)];
+        let mut ng = 0usize;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.unwrap_connectivity_f64)(
+                self.ctx, coords.as_mut_ptr() as *mut f64, coords.len(), ip, n, box9.as_ptr(), cutoff, dims, off.as_mut_ptr(),
+                ids.as_mut_ptr(), &mut ng,
+            )
+        })?;
+        Ok((0..ng).map(|g| ids[off[g] as usize..off[g + 1] as usize].iter().map(|&v| v as usize).collect()).collect())
     }
 
     /// `Modify::unwrap_simple_dim` (modify.rs:40-54), in place
