@@ -79,6 +79,18 @@ def _u64(x):
     return np.ascontiguousarray(x, dtype=np.uint64)
 
 
+_NO_ATOMS = np.zeros(1, np.uint64)[:0]      # an empty selection with an address
+
+
+def _sel(x):
+    """A selection for a search descriptor.  There a NULL index means "all atoms", and an empty torch tensor has no address
+    (data_ptr() == 0): an empty selection, device or host, is passed as an empty host array that has one."""
+    x = _u64(x)
+    if x is not None and x.shape[0] == 0:
+        return _NO_ATOMS
+    return x
+
+
 def pbc_mask(dims) -> int:
     """PbcDims::new (periodic_box.rs:101-107); None -> all False like the Python front-end."""
     if dims is None:
@@ -225,7 +237,7 @@ class Engine:
     # ------------------------------------------------------------ search
     def _search_desc(self, kind, cutoff, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0, vdw1=None,
                      vdw2=None, ids_local=False, lower=None, upper=None):
-        xyz1 = _f32(xyz1); xyz2 = _f32(xyz2); idx1 = _u64(idx1); idx2 = _u64(idx2)
+        xyz1 = _f32(xyz1); xyz2 = _f32(xyz2); idx1 = _sel(idx1); idx2 = _sel(idx2)
         vdw1 = _f32(vdw1); vdw2 = _f32(vdw2)
         d = SearchDesc()
         d.kind = kind
@@ -1429,8 +1441,7 @@ def _search_desc_f64(kind, cutoff, xyz1, idx1=None, xyz2=None, idx2=None, box=No
     def addr(a):
         return None if a is None else (a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
     xyz1, xyz2, vdw1, vdw2 = f64(xyz1), f64(xyz2), f64(vdw1), f64(vdw2)
-    idx1 = idx1 if hasattr(idx1, "data_ptr") else _u64(idx1)       # (device index tensors: int64)
-    idx2 = idx2 if hasattr(idx2, "data_ptr") else _u64(idx2)
+    idx1, idx2 = _sel(idx1), _sel(idx2)                            # (device index tensors: int64)
     d = SearchDescF64()
     d.kind = kind
     d.cutoff = float(cutoff) if cutoff is not None else 0.0
