@@ -270,64 +270,9 @@ int molar_hip_write_bandwidth(molar_hip_ctx *c, size_t bytes, int reps, float *g
 
 // ---------------------------------------------------------------- PeriodicBox constructors (host)
 
-// nalgebra try_inverse, 3x3 closed form (called at periodic_box.rs:167-169)
-static bool invert3(const float *m, float *o) {
-    const float a = m[0], d = m[1], g = m[2];   // column 0 : (0,0) (1,0) (2,0)
-    const float b = m[3], e = m[4], h = m[5];   // column 1
-    const float c = m[6], f = m[7], i = m[8];   // column 2
-    // row-major names: [a b c; d e f; g h i]
-    const float minor_bf = e * i - h * f;
-    const float minor_af = d * i - g * f;
-    const float minor_ae = d * h - g * e;
-    const float det = (a * minor_bf - b * minor_af) + c * minor_ae;
-    if (det == 0.0f) return false;
-    o[0] = minor_bf / det;             // (0,0)
-    o[3] = (c * h - i * b) / det;      // (0,1)
-    o[6] = (b * f - e * c) / det;      // (0,2)
-    o[1] = -minor_af / det;            // (1,0)
-    o[4] = (a * i - g * c) / det;      // (1,1)
-    o[7] = (c * d - f * a) / det;      // (1,2)
-    o[2] = minor_ae / det;             // (2,0)
-    o[5] = (b * g - h * a) / det;      // (2,1)
-    o[8] = (a * e - d * b) / det;      // (2,2)
-    return true;
-}
-
-static float len3(V3 v) { return std::sqrt(norm2(v)); }
-
 int molar_hip_box_from_matrix(const float m9[9], molar_hip_box *out) {
     if (!m9 || !out) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "box_from_matrix: null argument");
-    V3 col[3];
-    for (int k = 0; k < 3; ++k) {
-        col[k] = v3(m9[3 * k], m9[3 * k + 1], m9[3 * k + 2]);
-        if (len3(col[k]) == 0.0f) return fail(MOLAR_HIP_ERR_ZERO_LENGTH_VECTOR, "zero length box vector");
-    }
-    std::memcpy(out->m, m9, sizeof out->m);
-    if (!invert3(out->m, out->inv)) return fail(MOLAR_HIP_ERR_INVERSE_FAILED, "box matrix inverse failed");
-    out->nshift = 0;
-    // build_tric_corrections (periodic_box.rs:25-66)
-    const bool ortho = m9[3] == 0.f && m9[6] == 0.f && m9[1] == 0.f && m9[7] == 0.f && m9[2] == 0.f && m9[5] == 0.f;
-    if (ortho) return MOLAR_HIP_OK;
-    const V3 a = col[0], b = col[1], c = col[2];
-    const V3 na = v3(-a.x, -a.y, -a.z);
-    float longest = std::fmax(std::fmax(std::fmax(len3((a + b) + c), len3((a + b) - c)), len3((a - b) + c)),
-                              len3((na + b) + c));
-    const float half_diag = 0.5f * longest;
-    const float two = 2.0f * half_diag;
-    const float bound2 = two * two;
-    for (int i = -1; i <= 1; ++i)
-        for (int j = -1; j <= 1; ++j)
-            for (int k = -1; k <= 1; ++k) {
-                if (!i && !j && !k) continue;
-                const float fi = (float)i, fj = (float)j, fk = (float)k;
-                V3 s = (v3(fi * a.x, fi * a.y, fi * a.z) + v3(fj * b.x, fj * b.y, fj * b.z)) +
-                       v3(fk * c.x, fk * c.y, fk * c.z);
-                if (norm2(s) < bound2) {
-                    float *dst = out->shifts + 3 * out->nshift++;
-                    dst[0] = s.x; dst[1] = s.y; dst[2] = s.z;
-                }
-            }
-    return MOLAR_HIP_OK;
+    return box_from_matrix(m9, out);            // boxmath.hpp
 }
 
 int molar_hip_box_from_vectors_angles(float a, float b, float c, float alpha, float beta, float gamma,
@@ -363,7 +308,7 @@ void molar_hip_box_shortest_vector(const molar_hip_box *box, const float v[3], u
 }
 
 void molar_hip_box_extents(const molar_hip_box *box, float out[3]) {
-    for (int c = 0; c < 3; ++c) out[c] = len3(v3(box->m[3 * c], box->m[3 * c + 1], box->m[3 * c + 2]));
+    for (int c = 0; c < 3; ++c) out[c] = std::sqrt(norm2(v3(box->m[3 * c], box->m[3 * c + 1], box->m[3 * c + 2])));
 }
 
 void molar_hip_box_to_box_coords(const molar_hip_box *box, const float v[3], float out[3]) {

@@ -46,6 +46,13 @@ inline int fail(int code, const char *fmt, ...) {
         if (_rc) return _rc;  \
     } while (0)
 
+// first statement of an entry that takes a context
+#define MH_CTX(c)                                                                    \
+    do {                                                                             \
+        if (!(c)) return ::mh::fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context"); \
+        MH_HIP(hipSetDevice((c)->device));                                           \
+    } while (0)
+
 // ---------------------------------------------------------------- grow-only device buffer
 
 struct DevBuf {
@@ -342,6 +349,13 @@ inline int to_device(molar_hip_ctx *c, const T *src, size_t count, DevBuf &stage
     MH_TRY(stage.reserve(count * sizeof(T)));
     MH_HIP(hipMemcpyAsync(stage.p, src, count * sizeof(T), hipMemcpyHostToDevice, c->stream));
     *out = stage.as<T>();
+    return 0;
+}
+
+// CSR selections: offsets[nsel] = number of index entries; offsets may live on either side
+inline int csr_total(const uint64_t *offsets, size_t nsel, uint64_t *last) {
+    if (is_device_ptr(offsets)) MH_HIP(hipMemcpy(last, offsets + nsel, 8, hipMemcpyDeviceToHost));
+    else *last = offsets[nsel];
     return 0;
 }
 

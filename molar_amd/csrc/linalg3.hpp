@@ -1,6 +1,8 @@
-// linalg3.hpp — tiny dense kernels in double, usable from host code and from one GPU thread.
-//  * symmetric Jacobi eigensolver (N = 3 for the inertia tensor, N = 4 for Horn's key matrix)
+// linalg3.hpp — tiny dense kernels, usable from host code and from one GPU thread.
+//  * symmetric Jacobi eigensolver in double (N = 3 for the inertia tensor, N = 4 for Horn's key matrix)
 //  * optimal rotation from a 3x3 mass-weighted covariance via Horn's unit-quaternion method.
+//  * nalgebra's closed-form 3x3 inverse, Rodrigues' rotation and the finish of Measure::inertia / principal_transform,
+//    templates over the real type of the f32 and the f64 entries.
 //
 // The reference obtains the rotation as U diag(1,1,sign det(U V^T)) V^T from nalgebra's SVD
 // (molar/src/measure.rs:626-642).  For a non-degenerate covariance that rotation is the unique
@@ -11,13 +13,59 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <utility>
 
 namespace mh {
+
+// nalgebra try_inverse for 3x3 (closed form, column-major: m11 m21 m31 | m12 m22 m32 | m13 m23 m33).  A singular matrix
+// (det == 0) returns false and leaves `o` untouched, as try_inverse_mut leaves the matrix.
+template <class R>
+__host__ __device__ inline bool inverse3(const R *m, R *o) {
+    const R m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
+    const R mi1 = m22 * m33 - m32 * m23;
+    const R mi2 = m21 * m33 - m31 * m23;
+    const R mi3 = m21 * m32 - m31 * m22;
+    const R det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
+    if (det == R(0)) return false;
+    o[0] = mi1 / det;
+    o[3] = (m13 * m32 - m33 * m12) / det;
+    o[6] = (m12 * m23 - m22 * m13) / det;
+    o[1] = -mi2 / det;
+    o[4] = (m11 * m33 - m31 * m13) / det;
+    o[7] = (m13 * m21 - m23 * m11) / det;
+    o[2] = mi3 / det;
+    o[5] = (m12 * m31 - m32 * m11) / det;
+    o[8] = (m11 * m22 - m21 * m12) / det;
+    return true;
+}
+
+// nalgebra Rotation3::from_axis_angle (Rodrigues' formula on a unit axis), column-major
+template <class R>
+inline void rotation_from_axis_angle(const R *unit_axis3, R angle, R *R9) {
+    const R ux = unit_axis3[0], uy = unit_axis3[1], uz = unit_axis3[2];
+    const R sn = std::sin(angle), cs = std::cos(angle), k = R(1) - cs;
+    const R sqx = ux * ux, sqy = uy * uy, sqz = uz * uz;
+    const R rot[9] = {sqx + (R(1) - sqx) * cs, ux * uy * k + uz * sn, ux * uz * k - uy * sn,
+                      ux * uy * k - uz * sn, sqy + (R(1) - sqy) * cs, uy * uz * k + ux * sn,
+                      ux * uz * k + uy * sn, uy * uz * k - ux * sn, sqz + (R(1) - sqz) * cs};
+    for (int i = 0; i < 9; ++i) R9[i] = rot[i];
+}
+
+// do_principal_transform (measure.rs:646-649): Translation(cm) * Rotation(axes^-1) * Translation(-cm); a singular `axes`
+// stays as it is (try_inverse_mut)
+template <class R>
+inline void principal_transform_from(const R *axes9, const R *cm, R *R9, R *t3) {
+    if (!inverse3(axes9, R9))
+        for (int i = 0; i < 9; ++i) R9[i] = axes9[i];
+    for (int r = 0; r < 3; ++r) t3[r] = cm[r] + (((R9[r] * -cm[0]) + (R9[3 + r] * -cm[1])) + (R9[6 + r] * -cm[2]));
+}
+
+constexpr double JACOBI_TOL2 = 1e-26;      // jacobi_sym's default: ample for results stored in f32
 
 // Cyclic Jacobi on a symmetric NxN (row-major a[N*N], destroyed).  w = eigenvalues,
 // v = eigenvectors as COLUMNS (v[r*N+c]).
 template <int N>
-__host__ __device__ inline void jacobi_sym(double *a, double *w, double *v, double tol2 = 1e-26) {
+__host__ __device__ inline void jacobi_sym(double *a, double *w, double *v, double tol2 = JACOBI_TOL2) {
     // every loop over matrix indices is unrolled: on the GPU the two small matrices then live in registers (dynamic
     // indexing would put them in scratch memory, ~20 us per call for one lane)
 #pragma unroll
@@ -194,6 +242,35 @@ __host__ __device__ inline bool rotation_from_cov(const double *cov, double *R, 
     R[7] = 2.0 * (qy * qz - q0 * qx);
     R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
     return true;
+}
+
+// The finish of Measure::inertia (measure.rs:591-607) on the symmetric tensor T (stored in R, as the reference's Matrix3 is,
+// before the eigen solve): ascending moments; axes col0, col1 normalised in R, col2 = col0 x col1.  tol2: see jacobi_sym
+// (the f64 entries pass 1e-34).
+template <class R>
+inline void principal_axes(const R *T, double tol2, R *moments, R *axes9) {
+    double A[9], w[3], V[9];
+    for (int i = 0; i < 9; ++i) A[i] = T[i];
+    jacobi_sym<3>(A, w, V, tol2);
+    int ord[3] = {0, 1, 2};   // ascending moments (:594-601)
+    for (int a = 0; a < 2; ++a)
+        for (int q = a + 1; q < 3; ++q)
+            if (w[ord[q]] < w[ord[a]]) std::swap(ord[a], ord[q]);
+    for (int k = 0; k < 3; ++k) moments[k] = (R)w[ord[k]];
+    // col0, col1 normalised, col2 = col0 x col1 (:603-607)
+    R e[2][3];
+    for (int k = 0; k < 2; ++k) {
+        const R v[3] = {(R)V[0 * 3 + ord[k]], (R)V[1 * 3 + ord[k]], (R)V[2 * 3 + ord[k]]};
+        const R nn = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+        for (int d = 0; d < 3; ++d) e[k][d] = v[d] / nn;
+    }
+    const R c2[3] = {e[0][1] * e[1][2] - e[0][2] * e[1][1], e[0][2] * e[1][0] - e[0][0] * e[1][2],
+                     e[0][0] * e[1][1] - e[0][1] * e[1][0]};
+    for (int d = 0; d < 3; ++d) {
+        axes9[0 * 3 + d] = e[0][d];
+        axes9[1 * 3 + d] = e[1][d];
+        axes9[2 * 3 + d] = c2[d];
+    }
 }
 
 }  // namespace mh

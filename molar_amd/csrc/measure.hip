@@ -912,12 +912,6 @@ int central_onepass_host(molar_hip_ctx *c, const Sel &s, double r[8]) {
     return 0;
 }
 
-#define MH_CTX(c)                                                              \
-    do {                                                                       \
-        if (!(c)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context"); \
-        MH_HIP(hipSetDevice((c)->device));                                     \
-    } while (0)
-
 }  // namespace
 
 namespace mh {
@@ -1066,31 +1060,9 @@ int molar_hip_inertia(molar_hip_ctx *c, const float *xyz, size_t natoms, const u
     // symmetric tensor (:580-589); stored as f32 like the reference's Matrix3f before the eigen solve
     const float T00 = (float)r[2], T11 = (float)r[3], T22 = (float)r[4];
     const float T01 = (float)r[5], T02 = (float)r[6], T12 = (float)r[7];
-    if (tensor9) {
-        const float t[9] = {T00, T01, T02, T01, T11, T12, T02, T12, T22};
-        std::memcpy(tensor9, t, sizeof t);
-    }
-    double A[9] = {T00, T01, T02, T01, T11, T12, T02, T12, T22}, w[3], V[9];
-    jacobi_sym<3>(A, w, V);
-    int ord[3] = {0, 1, 2};   // ascending moments (:594-601)
-    for (int a = 0; a < 2; ++a)
-        for (int q = a + 1; q < 3; ++q)
-            if (w[ord[q]] < w[ord[a]]) std::swap(ord[a], ord[q]);
-    for (int k = 0; k < 3; ++k) moments[k] = (float)w[ord[k]];
-    // col0, col1 normalised, col2 = col0 x col1 (:603-607)
-    float e[2][3];
-    for (int k = 0; k < 2; ++k) {
-        float v[3] = {(float)V[0 * 3 + ord[k]], (float)V[1 * 3 + ord[k]], (float)V[2 * 3 + ord[k]]};
-        const float nn = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-        for (int d = 0; d < 3; ++d) e[k][d] = v[d] / nn;
-    }
-    const float c2[3] = {e[0][1] * e[1][2] - e[0][2] * e[1][1], e[0][2] * e[1][0] - e[0][0] * e[1][2],
-                         e[0][0] * e[1][1] - e[0][1] * e[1][0]};
-    for (int d = 0; d < 3; ++d) {
-        axes9[0 * 3 + d] = e[0][d];
-        axes9[1 * 3 + d] = e[1][d];
-        axes9[2 * 3 + d] = c2[d];
-    }
+    const float t[9] = {T00, T01, T02, T01, T11, T12, T02, T12, T22};
+    if (tensor9) std::memcpy(tensor9, t, sizeof t);
+    principal_axes(t, JACOBI_TOL2, moments, axes9);
     return MOLAR_HIP_OK;
 }
 
@@ -1425,13 +1397,6 @@ int molar_hip_fit_rmsd_batch(molar_hip_ctx *c, float *frames, size_t nframes, si
 
 // ---- CSR-batched entries (one wave per selection)
 
-// last offset = number of index entries; offsets may live on either side
-static int csr_total(const uint64_t *offsets, size_t nsel, uint64_t *last) {
-    if (is_device_ptr(offsets)) MH_HIP(hipMemcpy(last, offsets + nsel, 8, hipMemcpyDeviceToHost));
-    else *last = offsets[nsel];
-    return 0;
-}
-
 static int finish_batch(molar_hip_ctx *c, int *status, float *out, const float *d_out, size_t count, const char *what) {
     MH_HIP(hipGetLastError());
     int st = 0;
@@ -1573,13 +1538,8 @@ int molar_hip_translate(molar_hip_ctx *c, float *xyz, size_t natoms, const uint6
 int molar_hip_rotate(molar_hip_ctx *c, float *xyz, size_t natoms, const uint64_t *idx, size_t n, const float unit_axis3[3],
                      float angle) {
     if (!unit_axis3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "rotate: null axis");
-    // nalgebra Rotation3::from_axis_angle (Rodrigues' formula on a unit axis), f32, column-major
-    const float ux = unit_axis3[0], uy = unit_axis3[1], uz = unit_axis3[2];
-    const float sn = std::sin(angle), cs = std::cos(angle), k = 1.0f - cs;
-    const float sqx = ux * ux, sqy = uy * uy, sqz = uz * uz;
-    const float R[9] = {sqx + (1.0f - sqx) * cs, ux * uy * k + uz * sn, ux * uz * k - uy * sn,
-                        ux * uy * k - uz * sn, sqy + (1.0f - sqy) * cs, uy * uz * k + ux * sn,
-                        ux * uz * k + uy * sn, uy * uz * k - ux * sn, sqz + (1.0f - sqz) * cs};
+    float R[9];
+    rotation_from_axis_angle(unit_axis3, angle, R);
     const float t[3] = {0.f, 0.f, 0.f};
     return molar_hip_apply_transform(c, xyz, natoms, idx, n, R, t);     // p.coords = tr * p.coords (:28)
 }
@@ -1592,23 +1552,7 @@ int molar_hip_principal_transform(molar_hip_ctx *c, const float *xyz, size_t nat
     MH_TRY(molar_hip_inertia(c, xyz, natoms, idx, n, mass, box9, mom, axes, nullptr));
     if (box9) MH_TRY(molar_hip_center_of_mass_pbc(c, xyz, natoms, idx, n, mass, box9, MOLAR_HIP_PBC_FULL, cm));   // (:251)
     else MH_TRY(molar_hip_center_of_mass(c, xyz, natoms, idx, n, mass, cm));                                   // (:106)
-    // do_principal_transform (:646-649): Translation(cm) * Rotation(axes^-1) * Translation(-cm);
-    // try_inverse_mut leaves a singular matrix untouched (closed-form 3x3 inverse, nalgebra)
-    const float *m = axes;     // column-major: m11 m21 m31 | m12 m22 m32 | m13 m23 m33
-    const float m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
-    const float mi1 = m22 * m33 - m32 * m23, mi2 = m21 * m33 - m31 * m23, mi3 = m21 * m32 - m31 * m22;
-    const float det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
-    for (int i = 0; i < 9; ++i) R9[i] = axes[i];
-    if (det != 0.0f) {
-        const float inv[9] = {mi1 / det, -mi2 / det, mi3 / det,
-                              (m13 * m32 - m33 * m12) / det, (m11 * m33 - m31 * m13) / det, (m12 * m31 - m32 * m11) / det,
-                              (m12 * m23 - m22 * m13) / det, (m13 * m21 - m23 * m11) / det, (m11 * m22 - m21 * m12) / det};
-        for (int i = 0; i < 9; ++i) R9[i] = inv[i];
-    }
-    const V3 rv = mat_vec(R9, v3(-cm[0], -cm[1], -cm[2]));
-    t3[0] = cm[0] + rv.x;
-    t3[1] = cm[1] + rv.y;
-    t3[2] = cm[2] + rv.z;
+    principal_transform_from(axes, cm, R9, t3);
     return MOLAR_HIP_OK;
 }
 

@@ -8,13 +8,13 @@
 // accumulated per thread -> wave -> workgroup -> fixed-order total, so results agree with the reference's serial f64 sums
 // to ~1e-15 relative and do not depend on the launch shape.  These passes move 24-56 bytes per atom: HBM-bound like
 // their f32 counterparts (measure.hip); the periodic centres, gyration radius and unwrap_simple carry their own f64
-// PeriodicBox (boxmath64.hpp); the f64 search drivers are in search_f64.hip.
+// PeriodicBox (boxmath.hpp); the f64 search drivers are in search_f64.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "boxmath64.hpp"
+#include "boxmath.hpp"
 #include "common.hpp"
 #include "linalg3.hpp"
 
@@ -596,17 +596,11 @@ int rmsd64(molar_hip_ctx *c, const double *xyz1, size_t natoms1, const uint64_t 
 
 }  // namespace
 
-#define MH64_CTX(c)                                                                  \
-    do {                                                                             \
-        if (!(c)) return ::mh::fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context"); \
-        MH_HIP(hipSetDevice((c)->device));                                           \
-    } while (0)
-
 extern "C" {
 
 int molar_hip_center_of_geometry_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                      double out[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, nullptr, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
     return com64(c, s, false, out);
@@ -614,7 +608,7 @@ int molar_hip_center_of_geometry_f64(molar_hip_ctx *c, const double *xyz, size_t
 
 int molar_hip_center_of_mass_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                  const double *mass, double out[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "center_of_mass_f64: mass pointer is null");
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, mass, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
@@ -623,7 +617,7 @@ int molar_hip_center_of_mass_f64(molar_hip_ctx *c, const double *xyz, size_t nat
 
 int molar_hip_gyration_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                            const double *mass, double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "gyration_f64: mass pointer is null");
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, mass, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
@@ -638,14 +632,14 @@ int molar_hip_gyration_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, c
 
 int molar_hip_rmsd_f64(molar_hip_ctx *c, const double *xyz1, size_t natoms1, const uint64_t *idx1, size_t n1,
                        const double *xyz2, size_t natoms2, const uint64_t *idx2, size_t n2, double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     return rmsd64(c, xyz1, natoms1, idx1, n1, nullptr, xyz2, natoms2, idx2, n2, false, out);
 }
 
 int molar_hip_rmsd_mw_f64(molar_hip_ctx *c, const double *xyz1, size_t natoms1, const uint64_t *idx1, size_t n1,
                           const double *mass1, const double *xyz2, size_t natoms2, const uint64_t *idx2, size_t n2,
                           double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass1) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "rmsd_mw_f64: mass pointer is null");
     return rmsd64(c, xyz1, natoms1, idx1, n1, mass1, xyz2, natoms2, idx2, n2, true, out);
 }
@@ -653,7 +647,7 @@ int molar_hip_rmsd_mw_f64(molar_hip_ctx *c, const double *xyz1, size_t natoms1, 
 int molar_hip_fit_transform_f64(molar_hip_ctx *c, const double *xyz1, size_t natoms1, const uint64_t *idx1, size_t n1,
                                 const double *mass1, const double *xyz2, size_t natoms2, const uint64_t *idx2, size_t n2,
                                 const double *mass2, int at_origin, double R9[9], double t3[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass1 || (!at_origin && !mass2)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "fit_transform_f64: mass pointer is null");
     SelD s1, s2;
     MH_TRY(stage64(c, xyz1, natoms1, idx1, n1, mass1, c->m_xyz1, c->m_idx1, c->m_mass1, &s1));
@@ -679,7 +673,7 @@ int molar_hip_fit_transform_f64(molar_hip_ctx *c, const double *xyz1, size_t nat
 
 int molar_hip_min_max_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n, double lower[3],
                           double upper[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, nullptr, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
     const uint32_t nb = blocks64(c, s.n);
@@ -706,33 +700,12 @@ int molar_hip_min_max_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, co
 static void inertia64_finish(const double r[6], double moments[3], double axes9[9], double tensor9[9]) {
     const double T[9] = {r[0], r[3], r[4], r[3], r[1], r[5], r[4], r[5], r[2]};
     if (tensor9) std::memcpy(tensor9, T, sizeof T);
-    double A[9], w[3], V[9];
-    std::memcpy(A, T, sizeof A);
-    jacobi_sym<3>(A, w, V, 1e-34);
-    int ord[3] = {0, 1, 2};   // ascending moments (:594-601)
-    for (int a = 0; a < 2; ++a)
-        for (int q = a + 1; q < 3; ++q)
-            if (w[ord[q]] < w[ord[a]]) std::swap(ord[a], ord[q]);
-    for (int k = 0; k < 3; ++k) moments[k] = w[ord[k]];
-    // col0, col1 normalised, col2 = col0 x col1 (:603-607)
-    double e[2][3];
-    for (int k = 0; k < 2; ++k) {
-        const double v[3] = {V[0 * 3 + ord[k]], V[1 * 3 + ord[k]], V[2 * 3 + ord[k]]};
-        const double nn = std::sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-        for (int d = 0; d < 3; ++d) e[k][d] = v[d] / nn;
-    }
-    const double c2[3] = {e[0][1] * e[1][2] - e[0][2] * e[1][1], e[0][2] * e[1][0] - e[0][0] * e[1][2],
-                          e[0][0] * e[1][1] - e[0][1] * e[1][0]};
-    for (int d = 0; d < 3; ++d) {
-        axes9[0 * 3 + d] = e[0][d];
-        axes9[1 * 3 + d] = e[1][d];
-        axes9[2 * 3 + d] = c2[d];
-    }
+    principal_axes(T, 1e-34, moments, axes9);
 }
 
 int molar_hip_inertia_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                           const double *mass, double moments[3], double axes9[9], double tensor9[9]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "inertia_f64: mass pointer is null");
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, mass, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
@@ -746,7 +719,7 @@ int molar_hip_inertia_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, co
 }
 
 int molar_hip_translate_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double shift3[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!shift3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "translate_f64: null argument");
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, nullptr, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
@@ -762,7 +735,7 @@ int molar_hip_translate_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const 
 int molar_hip_fit_rmsd_batch_f64(molar_hip_ctx *c, double *frames, size_t nframes, size_t natoms, const uint64_t *idx, size_t n,
                                  const double *mass, const double *ref_xyz, size_t ref_natoms, const uint64_t *ref_idx,
                                  int apply, double *rmsd_out, double *R_out, double *t_out, double *com_out, double *gyr_out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!frames || !mass || !ref_xyz) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "fit_rmsd_batch_f64: null argument");
     if (nframes == 0) return MOLAR_HIP_OK;
     if (nframes > 65535) return fail(MOLAR_HIP_ERR_TOO_LARGE, "fit_rmsd_batch_f64: at most 65535 frames per call");
@@ -879,7 +852,7 @@ extern "C" {
 
 int molar_hip_center_of_geometry_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                          const double *box9, uint8_t pbc, double out[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));
     SelD s;
@@ -889,7 +862,7 @@ int molar_hip_center_of_geometry_pbc_f64(molar_hip_ctx *c, const double *xyz, si
 
 int molar_hip_center_of_mass_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                      const double *mass, const double *box9, uint8_t pbc, double out[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "center_of_mass_pbc_f64: mass pointer is null");
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));
@@ -900,7 +873,7 @@ int molar_hip_center_of_mass_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t
 
 int molar_hip_gyration_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                const double *mass, const double *box9, double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "gyration_pbc_f64: mass pointer is null");
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));
@@ -917,7 +890,7 @@ int molar_hip_gyration_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natom
 
 int molar_hip_unwrap_simple_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double *box9,
                                 uint8_t pbc) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (idx ? n == 0 : natoms == 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_simple_f64 of an empty selection");
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));
@@ -933,7 +906,7 @@ int molar_hip_unwrap_simple_f64(molar_hip_ctx *c, double *xyz, size_t natoms, co
 
 int molar_hip_inertia_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                               const double *mass, const double *box9, double moments[3], double axes9[9], double tensor9[9]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!mass) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "inertia_pbc_f64: mass pointer is null");
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));
@@ -950,7 +923,7 @@ int molar_hip_inertia_pbc_f64(molar_hip_ctx *c, const double *xyz, size_t natoms
 
 int molar_hip_apply_transform_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                   const double R9[9], const double t3[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!R9 || !t3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "apply_transform_f64: null argument");
     SelD s;
     MH_TRY(stage64(c, xyz, natoms, idx, n, nullptr, c->m_xyz1, c->m_idx1, c->m_mass1, &s));
@@ -968,7 +941,7 @@ int molar_hip_apply_transform_f64(molar_hip_ctx *c, double *xyz, size_t natoms, 
 int molar_hip_lipid_tail_order_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx,
                                    const uint64_t *tail_offsets, size_t ntails, int order_type, const double *normals,
                                    const uint64_t *normal_offsets, const uint8_t *bond_orders, double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!xyz || !idx || !tail_offsets || !normals || !normal_offsets || !out)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "lipid_tail_order_f64: null argument");
     if (order_type < 0 || order_type > 2) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "lipid_tail_order_f64: order_type %d", order_type);
@@ -1017,20 +990,15 @@ int molar_hip_lipid_tail_order_f64(molar_hip_ctx *c, const double *xyz, size_t n
 int molar_hip_rotate_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double unit_axis3[3],
                          double angle) {
     if (!unit_axis3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "rotate_f64: null axis");
-    // nalgebra Rotation3::from_axis_angle (Rodrigues' formula on a unit axis), column-major
-    const double ux = unit_axis3[0], uy = unit_axis3[1], uz = unit_axis3[2];
-    const double sn = std::sin(angle), cs = std::cos(angle), k = 1.0 - cs;
-    const double sqx = ux * ux, sqy = uy * uy, sqz = uz * uz;
-    const double R[9] = {sqx + (1.0 - sqx) * cs, ux * uy * k + uz * sn, ux * uz * k - uy * sn,
-                         ux * uy * k - uz * sn, sqy + (1.0 - sqy) * cs, uy * uz * k + ux * sn,
-                         ux * uz * k + uy * sn, uy * uz * k - ux * sn, sqz + (1.0 - sqz) * cs};
+    double R[9];
+    rotation_from_axis_angle(unit_axis3, angle, R);
     const double t[3] = {0.0, 0.0, 0.0};
     return molar_hip_apply_transform_f64(c, xyz, natoms, idx, n, R, t);     // p.coords = tr * p.coords (modify.rs:28)
 }
 
 int molar_hip_principal_transform_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                                       const double *mass, const double *box9, double R9[9], double t3[3]) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!R9 || !t3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "principal_transform_f64: null output");
     double mom[3], axes[9], cm[3];
     if (box9) {
@@ -1040,20 +1008,7 @@ int molar_hip_principal_transform_f64(molar_hip_ctx *c, const double *xyz, size_
         MH_TRY(molar_hip_inertia_f64(c, xyz, natoms, idx, n, mass, mom, axes, nullptr));
         MH_TRY(molar_hip_center_of_mass_f64(c, xyz, natoms, idx, n, mass, cm));                                // (:106)
     }
-    // do_principal_transform (:646-649): Translation(cm) * Rotation(axes^-1) * Translation(-cm);
-    // try_inverse_mut leaves a singular matrix untouched (closed-form 3x3 inverse, nalgebra)
-    const double *m = axes;
-    const double m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
-    const double mi1 = m22 * m33 - m32 * m23, mi2 = m21 * m33 - m31 * m23, mi3 = m21 * m32 - m31 * m22;
-    const double det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
-    for (int i = 0; i < 9; ++i) R9[i] = axes[i];
-    if (det != 0.0) {
-        const double inv[9] = {mi1 / det, -mi2 / det, mi3 / det,
-                               (m13 * m32 - m33 * m12) / det, (m11 * m33 - m31 * m13) / det, (m12 * m31 - m32 * m11) / det,
-                               (m12 * m23 - m22 * m13) / det, (m13 * m21 - m23 * m11) / det, (m11 * m22 - m21 * m12) / det};
-        for (int i = 0; i < 9; ++i) R9[i] = inv[i];
-    }
-    for (int r = 0; r < 3; ++r) t3[r] = cm[r] + (((R9[r] * -cm[0]) + (R9[3 + r] * -cm[1])) + (R9[6 + r] * -cm[2]));
+    principal_transform_from(axes, cm, R9, t3);
     return MOLAR_HIP_OK;
 }
 
@@ -1127,20 +1082,13 @@ __global__ void __launch_bounds__(256) k64_unwrap_batch(double *__restrict__ xyz
     }
 }
 
-// offsets[nsel] (host or device): the length of idx
-int csr_total(const uint64_t *offsets, size_t nsel, uint64_t *last) {
-    if (is_device_ptr(offsets)) MH_HIP(hipMemcpy(last, offsets + nsel, 8, hipMemcpyDeviceToHost));
-    else *last = offsets[nsel];
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int molar_hip_center_batch_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx,
                                const uint64_t *offsets, size_t nsel, const double *mass, double *out) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!xyz || !idx || !offsets || !out) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "center_batch_f64: null argument");
     if (nsel == 0) return MOLAR_HIP_OK;
     if (nsel >= 0xFFFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "center_batch_f64: %zu selections", nsel);
@@ -1171,7 +1119,7 @@ int molar_hip_center_batch_f64(molar_hip_ctx *c, const double *xyz, size_t natom
 
 int molar_hip_unwrap_simple_batch_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx,
                                       const uint64_t *offsets, size_t nsel, const double *box9, uint8_t pbc) {
-    MH64_CTX(c);
+    MH_CTX(c);
     if (!xyz || !idx || !offsets) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_simple_batch_f64: null argument");
     const BoxD *d_box;
     MH_TRY(box64_to_device(c, box9, &d_box));

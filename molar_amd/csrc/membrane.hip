@@ -23,7 +23,6 @@
 #include <cmath>
 
 #include "boxmath.hpp"
-#include "boxmath64.hpp"
 #include "common.hpp"
 #include "stages.hpp"
 
@@ -106,27 +105,6 @@ __device__ __forceinline__ typename Prec<R>::V vec(R x, R y, R z) { return typen
 template <class V>
 __device__ __forceinline__ V cross(V a, V b) {
     return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-// nalgebra try_inverse for 3x3 (closed form, column-major)
-template <class R>
-__device__ bool inverse3(const R *m, R *o) {
-    const R m11 = m[0], m21 = m[1], m31 = m[2], m12 = m[3], m22 = m[4], m32 = m[5], m13 = m[6], m23 = m[7], m33 = m[8];
-    const R mi1 = m22 * m33 - m32 * m23;
-    const R mi2 = m21 * m33 - m31 * m23;
-    const R mi3 = m21 * m32 - m31 * m22;
-    const R det = (m11 * mi1 - m12 * mi2) + m13 * mi3;
-    if (det == R(0)) return false;
-    o[0] = mi1 / det;
-    o[3] = (m13 * m32 - m33 * m12) / det;
-    o[6] = (m12 * m23 - m22 * m13) / det;
-    o[1] = -mi2 / det;
-    o[4] = (m11 * m33 - m31 * m13) / det;
-    o[7] = (m13 * m21 - m23 * m11) / det;
-    o[2] = mi3 / det;
-    o[5] = (m12 * m31 - m32 * m11) / det;
-    o[8] = (m11 * m22 - m21 * m12) / det;
-    return true;
 }
 
 // get_quad_coefs' solver (lib.rs:862): nalgebra Cholesky::new, then L y = b, L^T x = y.  a is column-major 6x6.

@@ -35,7 +35,7 @@
 #include <cstring>
 #include <vector>
 
-#include "boxmath64.hpp"
+#include "boxmath.hpp"
 #include "common.hpp"
 #include "csr_kernels.hpp"
 #include "hoststream.hpp"
@@ -88,12 +88,12 @@ __constant__ uint8_t MASKS64[14][6] = {
 };
 
 // Rust `as usize` / `as isize` on f64: saturating, NaN -> 0
-MH64_HD uint64_t as_usize(double x) {
+MH_HD uint64_t as_usize(double x) {
     if (!(x > 0.0)) return 0;
     if (x >= 18446744073709551615.0) return ~0ull;
     return (uint64_t)x;
 }
-MH64_HD int64_t as_isize(double x) {
+MH_HD int64_t as_isize(double x) {
     if (x != x) return 0;
     if (x >= 9223372036854775807.0) return INT64_MAX;
     if (x <= -9223372036854775808.0) return INT64_MIN;
@@ -405,13 +405,48 @@ __device__ __forceinline__ void fifo64_flush(Fifo64 &F, uint32_t count, uint32_t
     F.head += count;
 }
 
-template <bool FILL, int KIND, int NCH>
+// The fused histogram (hist64_kernel): a hit's d2 goes into the workgroup's 32-bit LDS counters, at the largest b with edges[b]
+// <= d2 (histogram_edges64: the formula's own table over d2), found from an f32 estimate corrected step by step against the edges.
+struct Hist64 {
+    uint32_t *hist;                  // the workgroup's counters (LDS)
+    const double *edges;             // nbins + 1 edges: LDS copy or global memory
+    unsigned long long *bins;
+    uint32_t nbins;
+    float hmin, scale, hn;           // the f32 estimate: (sqrt(d2) - hmin) * scale, clamped to [0, n]
+};
+
+__device__ __forceinline__ void hist64_add(const Hist64 &H, double d2) {
+    float est = (__builtin_amdgcn_sqrtf((float)d2) - H.hmin) * H.scale;
+    est = __builtin_fminf(__builtin_fmaxf(est, 0.0f), H.hn);                // also sends a NaN to 0
+    int b = (int)est;
+    while (b < (int)H.nbins && H.edges[b + 1] <= d2) ++b;
+    while (b >= 0 && H.edges[b] > d2) --b;
+    if ((uint32_t)b < H.nbins) __hip_atomic_fetch_add(H.hist + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// the workgroup's counters into the bins by one wave, beside the others still counting
+__device__ __forceinline__ void hist64_flush(const Hist64 &H, uint32_t lane) {
+    for (uint32_t b = lane; b < H.nbins; b += 64u) {
+        const uint32_t v = __hip_atomic_exchange(H.hist + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (v) atomicAdd(H.bins + b, (unsigned long long)v);
+    }
+}
+
+// What a slot's walk does with a hit: counts it, writes it - (i, j, sqrt(d2)), or the row's id for the within stream - or
+// bins its d2.  Writing and binning need the hit's exact d2: they decide every band-classified candidate inside the band's
+// upper edge by PeriodicBox::distance_squared, so a binned d2 is exactly the d2 whose square root the fill pass writes.
+// The arguments a mode does not use (F and the output columns when binning, H otherwise) are dead after inlining.
+enum { RUN_COUNT = 0, RUN_FILL = 1, RUN_HIST = 2 };
+
+template <int MODE, int KIND, int NCH>
 __device__ __forceinline__ uint32_t run64(const Params64 &P, const Slot64 &S, uint32_t lane, unsigned long long off,
                                           unsigned long long *__restrict__ out_i, unsigned long long *__restrict__ out_j,
-                                          double *__restrict__ out_d, Fifo64 F) {
+                                          double *__restrict__ out_d, Fifo64 F, const Hist64 &H) {
     const uint32_t wrap = S.flags & 7u;
     const bool tri = (S.flags >> 8) & 1u;
     constexpr bool VDW = KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW, WITHIN = KIND == MOLAR_HIP_SEARCH_WITHIN;
+    constexpr bool FILL = MODE == RUN_FILL, HIST = MODE == RUN_HIST, EXACT = FILL || HIST;
+    static_assert(!(HIST && WITHIN), "the histogram bins pairs; the within stream has none");
     double bx[NCH], by[NCH], bz[NCH], bv[NCH];
     unsigned long long bid[NCH];
 #pragma unroll
@@ -502,8 +537,8 @@ __device__ __forceinline__ uint32_t run64(const Params64 &P, const Slot64 &S, ui
                 const bool sure = q2 < cut2 * P.band_lo, maybe = hit && q2 <= cut2 * P.band_hi;
                 d2 = q2;
                 // hits carry the reference's own distance; candidates inside the band are decided by it
-                if (__builtin_amdgcn_ballot_w64(maybe && (FILL || !sure))) {
-                    if (maybe && (FILL || !sure)) d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
+                if (__builtin_amdgcn_ballot_w64(maybe && (EXACT || !sure))) {
+                    if (maybe && (EXACT || !sure)) d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
                 }
                 hit = maybe && (sure || d2 <= cut2);
             } else {
@@ -512,6 +547,11 @@ __device__ __forceinline__ uint32_t run64(const Params64 &P, const Slot64 &S, ui
             }
             if (WITHIN) {
                 any = any || hit;
+            } else if (HIST) {
+                const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+                if (!m) continue;
+                total += (uint32_t)__popcll(m);
+                if (hit) hist64_add(H, d2);
             } else if (!FILL) {
                 acc += hit ? 1u : 0u;
             } else {
@@ -540,13 +580,53 @@ __device__ __forceinline__ uint32_t run64(const Params64 &P, const Slot64 &S, ui
             total += 1;
         }
     }
-    if (!WITHIN && !FILL) {
+    if (MODE == RUN_COUNT && !WITHIN) {
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
         total = acc;
     }
     if (FILL && !WITHIN && F.tail != F.head) {
         __builtin_amdgcn_wave_barrier();
         fifo64_flush(F, F.tail - F.head, lane, off, out_i, out_j, out_d);
+    }
+    return total;
+}
+
+// second cells of more than 256 atoms: pair64_kernel's chunk loop with the hits binned (see there why it is a copy)
+template <int KIND>
+__device__ __forceinline__ unsigned long long hist64_chunks(const Params64 &P, const Slot64 &S, uint32_t lane, const Hist64 &H,
+                                                            uint32_t &since_flush, uint32_t flush_at) {
+    const uint32_t wrap = S.flags & 7u;
+    const bool tri = (S.flags >> 8) & 1u;
+    unsigned long long total = 0;
+    for (uint32_t r = 0; r < S.rows; ++r) {
+        const uint32_t ra = S.a0 + S.i0 + r;
+        const D3 a = D3{P.posA[3 * ra], P.posA[3 * ra + 1], P.posA[3 * ra + 2]};
+        const double vdw_a = (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) ? P.vdwA[ra] : 0.0;
+        for (uint32_t j0 = 0; j0 < S.n2; j0 += 64u) {
+            const uint32_t j = j0 + lane;
+            bool hit = false;
+            double d2 = 0.0;
+            if (j < S.n2 && !(tri && j <= S.i0 + r)) {            // same cell: j in i+1..n (:443)
+                const uint32_t rb = S.b0 + j;
+                d2 = pair_d2(P, wrap, a, D3{P.posB[3 * rb], P.posB[3 * rb + 1], P.posB[3 * rb + 2]});
+                if (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) {
+                    const double cut = (vdw_a + P.vdwB[rb]) + 2.220446049250313e-16;        // :392, :423
+                    hit = d2 <= cut * cut;
+                } else {
+                    hit = d2 <= P.cutoff2;
+                }
+            }
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
+            if (!m) continue;
+            const uint32_t cnt = (uint32_t)__popcll(m);
+            total += cnt;
+            if (hit) hist64_add(H, d2);
+            since_flush += cnt;
+            if (since_flush > flush_at) {
+                hist64_flush(H, lane);
+                since_flush = 0;
+            }
+        }
     }
     return total;
 }
@@ -564,23 +644,26 @@ __global__ void __launch_bounds__(64) pair64_kernel(Params64 P, uint32_t *__rest
     const bool tri = (S.flags >> 8) & 1u;
     unsigned long long off = FILL ? slot_base[s] : 0ull;
     const uint32_t nch = (S.n2 + 63u) >> 6;
+    constexpr int MODE = FILL ? RUN_FILL : RUN_COUNT;
     constexpr uint32_t QN = (FILL && KIND != MOLAR_HIP_SEARCH_WITHIN) ? FIFO64_CAP : 1u;
     __shared__ unsigned long long q_i[QN], q_j[QN];
     __shared__ double q_d[QN];
     if (nch <= 4u) {
         uint32_t t;
-        Fifo64 F{q_i, q_j, q_d, 0u, 0u, 64u};
+        const Hist64 H{};                              // binning only
+        const Fifo64 F{q_i, q_j, q_d, 0u, 0u, 64u};
         switch (nch) {
-            case 1: t = run64<FILL, KIND, 1>(P, S, lane, off, out_i, out_j, out_d, F); break;
-            case 2: t = run64<FILL, KIND, 2>(P, S, lane, off, out_i, out_j, out_d, F); break;
-            case 3: t = run64<FILL, KIND, 3>(P, S, lane, off, out_i, out_j, out_d, F); break;
-            default: t = run64<FILL, KIND, 4>(P, S, lane, off, out_i, out_j, out_d, F); break;
+            case 1: t = run64<MODE, KIND, 1>(P, S, lane, off, out_i, out_j, out_d, F, H); break;
+            case 2: t = run64<MODE, KIND, 2>(P, S, lane, off, out_i, out_j, out_d, F, H); break;
+            case 3: t = run64<MODE, KIND, 3>(P, S, lane, off, out_i, out_j, out_d, F, H); break;
+            default: t = run64<MODE, KIND, 4>(P, S, lane, off, out_i, out_j, out_d, F, H); break;
         }
         if (!FILL && lane == 0) slot_cnt[s] = t;
         return;
     }
-    // second cells of more than 256 atoms: chunk by chunk from memory
-    // rows are atoms of the first set's grid, columns atoms of the second set's (the same grid for SINGLE)
+    // Second cells of more than 256 atoms: chunk by chunk from memory; rows are atoms of the first set's grid, columns of the
+    // second set's (the same for SINGLE).  hist64_chunks is this loop with binning: as ONE function template the two reordered
+    // every pair64_kernel's scalar prologue (7-16 instructions more, one 20 fewer), which wants a timing before it is adopted.
     const double *pa = P.posA, *pb = P.posB;
     const unsigned long long *ia = P.idA, *ib = P.idB;
     const double *va = P.vdwA, *vb = P.vdwB;
@@ -646,13 +729,8 @@ inline dim3 grid_of(uint32_t n) {
 // ---- the fused histogram in f64 (molar_hip_search_histogram_f64): search + Histogram1D::add_one (stats.rs:29-35) in ONE pass,
 // no count pass, no offsets, no pair list.
 //
-// The slots are those of the count and fill passes, and each is evaluated as run64 / pair64_kernel's FILL path evaluates it:
-// second cell in registers up to 256 atoms (chunk by chunk from memory beyond), the same row pruning, the same predicate for
-// plain, same-cell, vdW and wrapped entries, and for band-classified wrapped entries PeriodicBox::distance_squared for every
-// hit (the adjacent-image q2 only decides whether a pair is a hit).  So a binned d2 is exactly the d2 whose square root the
-// fill pass writes.  Instead of being written, a hit's d2 goes into the workgroup's histogram of 32-bit LDS counters: the
-// bin is the largest b with edges[b] <= d2 (histogram_edges64: the formula's own table over d2), found from an f32 estimate
-// of the bin corrected step by step against the edges.
+// The slots are those of the count and fill passes, walked by the same run64 in its RUN_HIST mode: instead of being written,
+// a hit's d2 is binned (Hist64, hist64_add).  Second cells above 256 atoms: hist64_chunks, pair64_kernel's loop with binning.
 //
 // The kernel is persistent: a one-wave workgroup per slot, as the count and fill passes run, would have to flush nbins
 // counters per slot (5e4 slots a frame at 250k atoms).  Instead about (CUs x resident workgroups) workgroups of H64_WAVES
@@ -666,166 +744,6 @@ inline dim3 grid_of(uint32_t n) {
 constexpr int H64_WAVES = 8;
 constexpr uint32_t H64_FLUSH_AT = 0xFFFFFFFFu / (uint32_t)H64_WAVES - 16384u;
 constexpr size_t H64_EDGES_LDS = 40960;   // the edges join the counters in LDS while both fit in this (nbins <= 3412)
-
-struct Hist64 {
-    uint32_t *hist;                  // the workgroup's counters (LDS)
-    const double *edges;             // nbins + 1 edges: LDS copy or global memory
-    unsigned long long *bins;
-    uint32_t nbins;
-    float hmin, scale, hn;           // the f32 estimate: (sqrt(d2) - hmin) * scale, clamped to [0, n]
-};
-
-__device__ __forceinline__ void hist64_add(const Hist64 &H, double d2) {
-    float est = (__builtin_amdgcn_sqrtf((float)d2) - H.hmin) * H.scale;
-    est = __builtin_fminf(__builtin_fmaxf(est, 0.0f), H.hn);                // also sends a NaN to 0
-    int b = (int)est;
-    while (b < (int)H.nbins && H.edges[b + 1] <= d2) ++b;
-    while (b >= 0 && H.edges[b] > d2) --b;
-    if ((uint32_t)b < H.nbins) __hip_atomic_fetch_add(H.hist + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// the workgroup's counters into the bins by one wave, beside the others still counting
-__device__ __forceinline__ void hist64_flush(const Hist64 &H, uint32_t lane) {
-    for (uint32_t b = lane; b < H.nbins; b += 64u) {
-        const uint32_t v = __hip_atomic_exchange(H.hist + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (v) atomicAdd(H.bins + b, (unsigned long long)v);
-    }
-}
-
-// one slot whose second cell fits NCH chunks of 64 atoms (run64, FILL, with the hits binned): returns the slot's hits
-template <int KIND, int NCH>
-__device__ __forceinline__ uint32_t hist64_slot(const Params64 &P, const Slot64 &S, uint32_t lane, const Hist64 &H) {
-    const uint32_t wrap = S.flags & 7u;
-    const bool tri = (S.flags >> 8) & 1u;
-    constexpr bool VDW = KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW;
-    double bx[NCH], by[NCH], bz[NCH], bv[NCH];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) {
-        const uint32_t j = (uint32_t)k * 64u + lane;
-        bx[k] = by[k] = bz[k] = bv[k] = 0.0;
-        if (j < S.n2) {
-            const size_t rb = (size_t)S.b0 + j;
-            bx[k] = P.posB[3 * rb]; by[k] = P.posB[3 * rb + 1]; bz[k] = P.posB[3 * rb + 2];
-            if (VDW) bv[k] = P.vdwB[rb];
-        }
-    }
-    const bool approx = P.approx_wrapped && P.use_box && wrap != 0u && !(P.box->nshift != 0 && wrap == MOLAR_HIP_PBC_FULL);
-    double cx[NCH], cy[NCH], cz[NCH];
-    double Sx = 0.0, Sy = 0.0, Sz = 0.0;
-    if (approx) {
-        for (int d = 0; d < 3; ++d) {
-            if (!((wrap >> d) & 1u)) continue;
-            const double sgn = ((S.flags >> (12 + d)) & 1u) ? 1.0 : -1.0;
-            Sx += sgn * P.box->m[3 * d];
-            Sy += sgn * P.box->m[3 * d + 1];
-            Sz += sgn * P.box->m[3 * d + 2];
-        }
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) { cx[k] = bx[k] + Sx; cy[k] = by[k] + Sy; cz[k] = bz[k] + Sz; }
-    }
-    double ax = 0.0, ay = 0.0, az = 0.0, av = 0.0;
-    if (lane < S.rows) {
-        const size_t ra = (size_t)S.a0 + S.i0 + lane;
-        ax = P.posA[3 * ra]; ay = P.posA[3 * ra + 1]; az = P.posA[3 * ra + 2];
-        if (VDW) av = P.vdwA[ra];
-    }
-    unsigned long long live;
-    {
-        bool need = lane < S.rows;
-        if (!tri && (wrap == 0u || !P.use_box || approx)) {                   // run64's row pruning
-            const double *bb = P.aabbB + 6 * (size_t)S.cb;
-            double px = ax, py = ay, pz = az, lim = P.cutoff2;
-            if (approx) {
-                px = ax - Sx;
-                py = ay - Sy;
-                pz = az - Sz;
-                lim = P.prune_limit2;
-            }
-            const double ex = fmax(fmax(bb[0] - px, px - bb[3]), 0.0), ey = fmax(fmax(bb[1] - py, py - bb[4]), 0.0),
-                         ez = fmax(fmax(bb[2] - pz, pz - bb[5]), 0.0);
-            need = need && !((ex * ex + ey * ey) + ez * ez > lim);
-        }
-        live = __builtin_amdgcn_ballot_w64(need);
-    }
-    uint32_t total = 0;
-    while (live) {
-        const uint32_t r = (uint32_t)__builtin_ctzll(live);
-        live &= live - 1ull;
-        const D3 a = D3{lane_bcast(ax, r), lane_bcast(ay, r), lane_bcast(az, r)};
-        const double vdw_a = VDW ? lane_bcast(av, r) : 0.0;
-        const uint32_t i = S.i0 + r;
-#pragma unroll
-        for (int k = 0; k < NCH; ++k) {
-            if (tri && (uint32_t)k * 64u + 63u <= i) continue;                  // the whole chunk has j <= i (:443)
-            const uint32_t j = (uint32_t)k * 64u + lane;
-            bool hit = j < S.n2 && !(tri && j <= i);
-            double cut2 = P.cutoff2;
-            if (VDW) {
-                const double cut = (vdw_a + bv[k]) + 2.220446049250313e-16;    // :392, :423
-                cut2 = cut * cut;
-            }
-            double d2;
-            if (approx) {
-                const double ex = cx[k] - a.x, ey = cy[k] - a.y, ez = cz[k] - a.z;
-                const double q2 = (ex * ex + ey * ey) + ez * ez;
-                const bool sure = q2 < cut2 * P.band_lo, maybe = hit && q2 <= cut2 * P.band_hi;
-                d2 = q2;
-                if (__builtin_amdgcn_ballot_w64(maybe)) {                       // hits are binned with the reference's own d2
-                    if (maybe) d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
-                }
-                hit = maybe && (sure || d2 <= cut2);
-            } else {
-                d2 = pair_d2(P, wrap, a, D3{bx[k], by[k], bz[k]});
-                hit = hit && d2 <= cut2;
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-            if (!m) continue;
-            total += (uint32_t)__popcll(m);
-            if (hit) hist64_add(H, d2);
-        }
-    }
-    return total;
-}
-
-// second cells of more than 256 atoms: chunk by chunk from memory (pair64_kernel's generic loop)
-template <int KIND>
-__device__ __forceinline__ unsigned long long hist64_chunks(const Params64 &P, const Slot64 &S, uint32_t lane, const Hist64 &H,
-                                                            uint32_t &since_flush, uint32_t flush_at) {
-    const uint32_t wrap = S.flags & 7u;
-    const bool tri = (S.flags >> 8) & 1u;
-    unsigned long long total = 0;
-    for (uint32_t r = 0; r < S.rows; ++r) {
-        const uint32_t ra = S.a0 + S.i0 + r;
-        const D3 a = D3{P.posA[3 * ra], P.posA[3 * ra + 1], P.posA[3 * ra + 2]};
-        const double vdw_a = (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) ? P.vdwA[ra] : 0.0;
-        for (uint32_t j0 = 0; j0 < S.n2; j0 += 64u) {
-            const uint32_t j = j0 + lane;
-            bool hit = false;
-            double d2 = 0.0;
-            if (j < S.n2 && !(tri && j <= S.i0 + r)) {            // same cell: j in i+1..n (:443)
-                const uint32_t rb = S.b0 + j;
-                d2 = pair_d2(P, wrap, a, D3{P.posB[3 * rb], P.posB[3 * rb + 1], P.posB[3 * rb + 2]});
-                if (KIND == MOLAR_HIP_SEARCH_DOUBLE_VDW) {
-                    const double cut = (vdw_a + P.vdwB[rb]) + 2.220446049250313e-16;        // :392, :423
-                    hit = d2 <= cut * cut;
-                } else {
-                    hit = d2 <= P.cutoff2;
-                }
-            }
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(hit);
-            if (!m) continue;
-            const uint32_t cnt = (uint32_t)__popcll(m);
-            total += cnt;
-            if (hit) hist64_add(H, d2);
-            since_flush += cnt;
-            if (since_flush > flush_at) {
-                hist64_flush(H, lane);
-                since_flush = 0;
-            }
-        }
-    }
-    return total;
-}
 
 // EL: the edges are copied into LDS behind the counters (else read from global memory)
 template <int KIND, bool EL>
@@ -858,10 +776,10 @@ __global__ void __launch_bounds__(64 * H64_WAVES) hist64_kernel(Params64 P, uint
         }
         uint32_t t;
         switch (nch) {
-            case 1: t = hist64_slot<KIND, 1>(P, S, lane, H); break;
-            case 2: t = hist64_slot<KIND, 2>(P, S, lane, H); break;
-            case 3: t = hist64_slot<KIND, 3>(P, S, lane, H); break;
-            default: t = hist64_slot<KIND, 4>(P, S, lane, H); break;
+            case 1: t = run64<RUN_HIST, KIND, 1>(P, S, lane, 0ull, nullptr, nullptr, nullptr, Fifo64{}, H); break;
+            case 2: t = run64<RUN_HIST, KIND, 2>(P, S, lane, 0ull, nullptr, nullptr, nullptr, Fifo64{}, H); break;
+            case 3: t = run64<RUN_HIST, KIND, 3>(P, S, lane, 0ull, nullptr, nullptr, nullptr, Fifo64{}, H); break;
+            default: t = run64<RUN_HIST, KIND, 4>(P, S, lane, 0ull, nullptr, nullptr, nullptr, Fifo64{}, H); break;
         }
         total += t;
         since_flush += t;
@@ -915,7 +833,8 @@ __global__ void __launch_bounds__(256) within64_partners_kernel(GridP G, uint64_
 // The hit decision of one candidate as run64's count pass (FILL = false) makes it: row atom a against column atom b (`cand`:
 // the lane holds a column).  Entries classified by the adjacent image (`approx`; c = b + S): the plain distance to c decides
 // outside [band_lo, band_hi] * cutoff^2, PeriodicBox::distance_squared inside the band; every other entry: pair_d2.
-// (A copy, not a helper shared with run64 / hist64_slot: routing those two through a helper changed their ISA.)
+// (A copy, not a helper shared with run64: routing the two through one changed run64's ISA.  Tried twice; the second time, the
+// image shift and the pruning bound as two __forceinline__ helpers, by 60-100 instructions per pair and histogram kernel.)
 __device__ __forceinline__ bool within64_hit(const Params64 &P, uint32_t wrap, bool approx, bool cand, D3 a, D3 b, D3 c) {
     const double cut2 = P.cutoff2;
     if (approx) {
@@ -1033,22 +952,7 @@ void search64_release(molar_hip_ctx *c) {
 
 extern "C" {
 
-// one input array on the device: used in place if it is device memory, copied to `stage` otherwise
-static int to_device(molar_hip_ctx *c, const void *src, size_t bytes, DevBuf &stage, const void **out) {
-    if (!src || !bytes) {
-        *out = nullptr;
-        return 0;
-    }
-    if (is_device_ptr(src)) {
-        *out = src;
-        return 0;
-    }
-    MH_TRY(stage.reserve(bytes));
-    MH_HIP(hipMemcpyAsync(stage.p, src, bytes, hipMemcpyHostToDevice, c->stream));
-    *out = stage.p;
-    return 0;
-}
-
+// a small host-side input (a box, a corner) that may lie in device memory
 static int host_copy(molar_hip_ctx *c, const double *src, size_t count, double *dst) {
     if (is_device_ptr(src)) MH_HIP(hipMemcpy(dst, src, count * 8, hipMemcpyDeviceToHost));
     else std::memcpy(dst, src, count * 8);
@@ -1133,12 +1037,12 @@ static int prepare64_grids(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q,
         const size_t natoms = w ? q->natoms2 : q->natoms1, nidx = w ? q->n2 : q->n1;
         const size_t nsel = idx ? nidx : natoms;
         if (nsel >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_f64: %zu atoms exceed the 2^31 limit", nsel);
-        const void *dx, *di, *dv;
-        MH_TRY(to_device(c, xyz, natoms * 24, Z.in_xyz[w], &dx));
-        MH_TRY(to_device(c, idx, idx ? nsel * 8 : 0, Z.in_idx[w], &di));
-        MH_TRY(to_device(c, vd, vd ? nsel * 8 : 0, Z.in_vdw[w], &dv));
-        S[w] = SetIn{static_cast<const double *>(dx), static_cast<const unsigned long long *>(di), static_cast<const double *>(dv),
-                     (uint64_t)natoms, (uint32_t)nsel, (q->ids_local || vdw) ? 1 : 0};
+        const double *dx, *dv;             // in place if they are device memory, staged otherwise
+        const uint64_t *di;
+        MH_TRY(to_device(c, xyz, natoms * 3, Z.in_xyz[w], &dx));
+        MH_TRY(to_device(c, idx, idx ? nsel : 0, Z.in_idx[w], &di));
+        MH_TRY(to_device(c, vd, vd ? nsel : 0, Z.in_vdw[w], &dv));
+        S[w] = SetIn{dx, reinterpret_cast<const unsigned long long *>(di), dv, (uint64_t)natoms, (uint32_t)nsel, (q->ids_local || vdw) ? 1 : 0};
         if (vd && !is_device_ptr(vd)) hvdw[w] = vd;
     }
     BoxD box{};
@@ -1715,7 +1619,7 @@ int molar_hip_search_connectivity_f64(molar_hip_ctx *c, const molar_hip_search_d
 
 // Modify::unwrap_connectivity_dim (molar/src/modify.rs:72-131) with Float = f64: the neighbour search over the selection with
 // LOCAL ids under full PBC whatever `pbc_dims` (:77-78) and the CSR on the device (molar_hip_search_connectivity_f64), the
-// stack walk on the host with boxmath64.hpp's closest_image over pbc_dims (unwrap_walk.hpp: the same template as the f32 entry).
+// stack walk on the host with boxmath.hpp's closest_image over pbc_dims (unwrap_walk.hpp: the same template as the f32 entry).
 int molar_hip_unwrap_connectivity_f64(molar_hip_ctx *c, double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double *box9,
                                       double cutoff, uint8_t pbc_dims, uint64_t *group_offsets, uint64_t *group_ids, size_t *ngroups) {
     if (!c || !xyz) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_connectivity_f64: null argument");
