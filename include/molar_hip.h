@@ -433,6 +433,34 @@ int molar_hip_inertia_f64(molar_hip_ctx *ctx, const double *xyz, size_t natoms, 
                           const double *mass, double moments[3], double axes9[9], double tensor9[9]);
 int molar_hip_translate_f64(molar_hip_ctx *ctx, double *xyz, size_t natoms, const uint64_t *idx, size_t n,
                             const double shift3[3]);
+
+/* ---- Solvent-accessible surface area per atom (Measure::sasa, measure.rs:427; pymolar sel.sasa().areas / .total_area).
+ * The reference delegates to an analytic power-diagram crate; this library computes the same quantity by Shrake-Rupley,
+ * defined operation by operation so that the exposed-point counts are exact integers (Real = float, or double for _f64):
+ *   R_i = vdw_i + probe.  Points u_k, k < npoints: z = 1 - (2k+1)/npoints, r = sqrt(1 - z z), phi = k (pi (3 - sqrt 5)),
+ *   u_k = (r cos phi, r sin phi, z), computed on the host in double, then rounded to Real (molar_hip_sasa_points).
+ *   j != i is a neighbour of i iff (dx dx + dy dy) + dz dz < (R_i + R_j)(R_i + R_j), d = c_j - c_i (strict compare).
+ *   Point k of i is buried iff a neighbour j has (tx tx + ty ty) + tz tz < R_j R_j, t = R_i u_k - d.  No contraction.
+ *   exposed_i = points not buried; area_i = ((4 pi R_i^2) exposed_i) / npoints in double, rounded to Real;
+ *   total = sum of the areas in double (fixed order).
+ * An atom with a non-finite coordinate or radius or with R_i <= 0 gets exposed = 0, area = 0 and buries nothing.  No periodic
+ * box (the reference's sasa() takes none).  npoints in 1..4096, probe finite and >= 0, else ERR_INVALID_ARGUMENT.
+ * idx == NULL: atoms 0 .. n-1, all atoms when n is 0 (n > natoms: ERR_INVALID_ARGUMENT); an empty selection (idx != NULL,
+ * n == 0) is no error, its total is 0.  vdw: one radius per SELECTED atom, selection order.  Every pointer may be host
+ * or device memory; areas, exposed and total are optional (NULL). */
+int molar_hip_sasa_points(uint32_t npoints, float *out_xyz);
+int molar_hip_sasa_points_f64(uint32_t npoints, double *out_xyz);
+int molar_hip_sasa(molar_hip_ctx *ctx, const float *xyz, size_t natoms, const uint64_t *idx, size_t n, const float *vdw,
+                   float probe, uint32_t npoints, float *areas, uint32_t *exposed, double *total);
+int molar_hip_sasa_f64(molar_hip_ctx *ctx, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
+                       const double *vdw, double probe, uint32_t npoints, double *areas, uint32_t *exposed, double *total);
+/* the same over nframes frames, frame f at frames + f * frame_stride (floats, >= 3 natoms): every frame is enqueued behind the
+ * one before it and the call waits once; areas[nframes][n] (optional), totals[nframes]; frame by frame the results are
+ * those of molar_hip_sasa bit for bit */
+int molar_hip_sasa_frames(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                          const uint64_t *idx, size_t n, const float *vdw, float probe, uint32_t npoints, float *areas,
+                          double *totals);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -221,6 +221,10 @@ struct IsometryMatrix3 {                     // p -> R p + t
     Vector3f t;
 };
 enum class OrderType { Sz = 0, Scd = 1, ScdCorr = 2 };   // measure.rs:708-716
+struct Sasa {                                // measure.rs:427 (pymolar: sel.sasa().areas / .total_area)
+    std::vector<float> areas;                // per selected atom, selection order
+    double total_area = 0;
+};
 
 class System {                               // selection/system.rs: topology + current state
    public:
@@ -271,6 +275,17 @@ class SelBound {
         Pos lo, hi;
         check(molar_hip_min_max(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), &lo.x, &hi.x));
         return {lo, hi};
+    }
+    // Shrake-Rupley over `npoints` points per atom, radii vdw + probe (the definition: molar_hip.h, molar_hip_sasa)
+    Sasa sasa(Float probe = 0.14f, uint32_t npoints = 960) const {
+        if (sys_->top.vdw.size() != natoms()) throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "sasa: the topology has no vdW radii");
+        std::vector<Float> vdw(index_.size());
+        for (size_t k = 0; k < index_.size(); ++k) vdw[k] = sys_->top.vdw[index_[k]];
+        Sasa out;
+        out.areas.resize(index_.size());
+        check(molar_hip_sasa(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), vdw.data(), probe, npoints,
+                             out.areas.data(), nullptr, &out.total_area));
+        return out;
     }
     Pos center_of_geometry() const {
         Pos o;

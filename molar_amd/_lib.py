@@ -169,6 +169,11 @@ SYMBOLS = {
     "molar_hip_min_max_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "molar_hip_inertia_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
     "molar_hip_translate_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
+    "molar_hip_sasa_points": (_I, [C.c_uint32, _P]),
+    "molar_hip_sasa_points_f64": (_I, [C.c_uint32, _P]),
+    "molar_hip_sasa": (_I, [_P, _P, _SZ, _P, _SZ, _P, _F, C.c_uint32, _P, _P, _P]),
+    "molar_hip_sasa_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P, C.c_double, C.c_uint32, _P, _P, _P]),
+    "molar_hip_sasa_frames": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _F, C.c_uint32, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

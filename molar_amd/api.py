@@ -635,6 +635,35 @@ class Engine:
         self._keep = keep
         return bins
 
+    # ------------------------------------------------------------ surface area
+    def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
+        """Per-atom solvent-accessible surface area by Shrake-Rupley (molar_hip_sasa; the definition is in
+        include/molar_hip.h).  `vdw`: one radius per SELECTED atom, selection order.  Returns a `Sasa` (pymolar's
+        sel.sasa(): .areas, .total_area; .exposed with want_exposed).  torch CUDA inputs are read in place and give
+        torch CUDA results."""
+        return _sasa_call(self.lib.molar_hip_sasa, self.ctx, _f32(xyz), _f32(vdw), _sel(idx), C.c_float(probe), npoints, want_exposed,
+                          np.float32)
+
+    def sasa_frames(self, frames, vdw, idx=None, probe=0.14, npoints=960):
+        """molar_hip_sasa_frames over frames[F, natoms, 3] (numpy or torch CUDA): every frame is enqueued behind the one
+        before it, one wait.  Returns (areas[F, n], totals[F]); frame by frame they equal `sasa` bit for bit."""
+        frames = _f32(frames)
+        assert frames.ndim == 3 and frames.shape[2] == 3
+        F, natoms = frames.shape[0], frames.shape[1]
+        vdw = _f32(vdw); idx = _sel(idx)
+        n = natoms if idx is None else idx.shape[0]
+        assert vdw.shape[0] == n, "one radius per selected atom"
+        totals = np.zeros(F, np.float64)
+        if _is_torch(frames):
+            import torch
+            areas = torch.zeros((F, n), dtype=torch.float32, device=frames.device)
+        else:
+            areas = np.zeros((F, n), np.float32)
+        fa, k1 = _addr(frames); ia, k2 = _addr(idx); va, k3 = _addr(vdw); aa, k4 = _addr(areas)
+        check(self.lib.molar_hip_sasa_frames(self.ctx, fa, F, natoms * 3, natoms, ia, n, va, C.c_float(probe), npoints, aa,
+                                             totals.ctypes.data))
+        return areas, totals
+
     # ------------------------------------------------------------ measure
     def _sel_args(self, xyz, idx):
         xyz = _f32(xyz); idx = _u64(idx)
@@ -988,6 +1017,47 @@ class FitStream:
             pass
 
 
+class Sasa:
+    """Result of a surface-area call, with pymolar's getters: `areas` (per selected atom, nm^2), `total_area` (their
+    sum in double) and, when asked for, `exposed` (points of each atom that no neighbour buries)."""
+
+    def __init__(self, areas, total_area, exposed=None):
+        self.areas, self.total_area, self.exposed = areas, total_area, exposed
+
+
+def sasa_points(npoints, dtype=np.float32):
+    """The point table u_k[npoints, 3] of the surface-area calls (molar_hip_sasa_points / _f64); needs no GPU."""
+    real = np.dtype(dtype)
+    if real not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("sasa_points: dtype must be float32 or float64")
+    npoints = int(npoints) if 1 <= int(npoints) <= 0xFFFFFFFF else 0      # the library rejects it with its own message
+    out = np.zeros((max(npoints, 1), 3), real)
+    lib = _lib.load()
+    fn = lib.molar_hip_sasa_points if real == np.float32 else lib.molar_hip_sasa_points_f64
+    check(fn(npoints, out.ctypes.data))
+    return out
+
+
+def _sasa_call(fn, ctx, xyz, vdw, idx, probe, npoints, want_exposed, real):
+    """One frame through molar_hip_sasa / _f64: results live where the coordinates live."""
+    natoms = xyz.shape[0] if xyz.ndim == 2 else xyz.shape[0] // 3
+    n = natoms if idx is None else idx.shape[0]
+    assert vdw.shape[0] == n, "one radius per selected atom"
+    if not 1 <= int(npoints) <= 0xFFFFFFFF:
+        npoints = 0                                      # the library rejects it with its own message
+    total = C.c_double(0.0)
+    if _is_torch(xyz):
+        import torch
+        areas = torch.zeros(n, dtype=torch.float32 if real == np.float32 else torch.float64, device=xyz.device)
+        exposed = torch.zeros(n, dtype=torch.int32, device=xyz.device) if want_exposed else None
+    else:
+        areas = np.zeros(n, real)
+        exposed = np.zeros(n, np.uint32) if want_exposed else None
+    xa, k1 = _addr(xyz); ia, k2 = _addr(idx); va, k3 = _addr(vdw); aa, k4 = _addr(areas); ea, k5 = _addr(exposed)
+    check(fn(ctx, xa, natoms, ia, n, va, probe, int(npoints), aa if n else None, ea if n else None, C.byref(total)))
+    return Sasa(areas, float(total.value), exposed)
+
+
 def _f64(x):
     if x is None:
         return None
@@ -1127,6 +1197,11 @@ class MeasureF64:
                                                     1 if apply else 0, rm.ctypes.data, R.ctypes.data, t.ctypes.data,
                                                     com.ctypes.data, gy.ctypes.data))
         return dict(rmsd=rm, R=R.reshape(F, 3, 3).transpose(0, 2, 1).copy(), t=t, com=com, gyration=gy)
+
+    def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
+        """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""
+        return _sasa_call(self.lib.molar_hip_sasa_f64, self.ctx, _f64(xyz), _f64(vdw), _sel(idx), C.c_double(probe), npoints,
+                          want_exposed, np.float64)
 
     def min_max(self, xyz, idx=None):
         a = self._sel(xyz, idx)
@@ -1643,6 +1718,11 @@ class Sel:
 
     def min_max(self):
         return self.engine.min_max(self.state.coords, self.index)
+
+    def sasa(self, probe=0.14, npoints=960):
+        """Measure::sasa (measure.rs:427) / pymolar sel.sasa(): per-atom areas and their total, radii from the topology."""
+        vdw = self.top.vdw[self.index.astype(np.int64)]
+        return self.engine.sasa(self.state.coords, vdw, self.index, probe=probe, npoints=npoints)
 
     # measure.rs:100-109, 246-257, 646-649: T(cm) * inverse(axes) * T(-cm), returned as (R, t) of p -> R p + t
     def principal_transform(self):
