@@ -461,6 +461,38 @@ int molar_hip_sasa_frames(molar_hip_ctx *ctx, const float *frames, size_t nframe
                           const uint64_t *idx, size_t n, const float *vdw, float probe, uint32_t npoints, float *areas,
                           double *totals);
 
+/* ---- Per-atom volumes with the areas (Measure::sasa_vol, measure.rs:435; Sasa::volumes / total_volume, sasa.rs:92,97;
+ * pymolar sel.sasa_vol().volumes / .total_volume).  volume_i is the volume of atom i's ball inside its power cell (the
+ * points whose power distance |x - c_i|^2 - R_i^2 is smallest for i); the volumes add up to the volume of the union of the
+ * balls.  Evaluated on the point table of the areas: along u_k from c_i the ray stays inside the ball and the power cell on
+ * an interval [lo_k, hi_k], and the cone around u_k contributes (hi_k^3 - lo_k^3) / 3 times 4 pi / npoints.  Operation by
+ * operation (Real = float, or double for _f64; no contraction; R_i, u_k, the neighbour filter with
+ * dd = (dx dx + dy dy) + dz dz, d = c_j - c_i, and the atoms that take no part exactly as for molar_hip_sasa):
+ *   lo_k = 0, hi_k = R_i for every k.  Per neighbour j, in any order (only min and max are taken):
+ *     c = ((dd + R_i R_i) - R_j R_j) * 0.5;  a = (u_kx dx + u_ky dy) + u_kz dz;  t = c / a (IEEE division);
+ *     a > 0 and t < hi_k: hi_k = t;   a < 0 and t > lo_k: lo_k = t;   a == 0 and c < 0: hi_k = 0;
+ *     anything else (NaN, an infinite t that fails its compare) changes nothing.
+ *   hi_k = max(hi_k, lo_k): an empty interval contributes 0.
+ *   s_i = sum over k of (double)hi_k^3 - (double)lo_k^3, cubes and sum in double;
+ *   volume_i = ((4 pi / 3) s_i) / npoints in double, rounded to Real;  total_volume = sum of the volumes in double, in the
+ *   fixed order of the areas' total.
+ * A non-neighbour's radical plane never enters ball i, so the filter changes nothing but the work.  An atom that takes no
+ * part gets volume 0 and cuts nobody.  Coincident atoms of equal radius (a == 0 and c == 0 for every k)
+ * each keep their full ball: there the volumes add up to more than the union.  exposed, areas and total are those of
+ * molar_hip_sasa on the same input bit for bit.  Arguments, checks and errors as for the three calls above; every output
+ * pointer is optional. */
+int molar_hip_sasa_vol(molar_hip_ctx *ctx, const float *xyz, size_t natoms, const uint64_t *idx, size_t n, const float *vdw,
+                       float probe, uint32_t npoints, float *areas, uint32_t *exposed, double *total, float *volumes,
+                       double *total_volume);
+int molar_hip_sasa_vol_f64(molar_hip_ctx *ctx, const double *xyz, size_t natoms, const uint64_t *idx, size_t n,
+                           const double *vdw, double probe, uint32_t npoints, double *areas, uint32_t *exposed, double *total,
+                           double *volumes, double *total_volume);
+/* frames as in molar_hip_sasa_frames: areas[nframes][n], totals[nframes], volumes[nframes][n], total_volumes[nframes]; frame
+ * by frame the results are those of molar_hip_sasa_vol bit for bit */
+int molar_hip_sasa_vol_frames(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                              const uint64_t *idx, size_t n, const float *vdw, float probe, uint32_t npoints, float *areas,
+                              double *totals, float *volumes, double *total_volumes);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -221,9 +221,11 @@ struct IsometryMatrix3 {                     // p -> R p + t
     Vector3f t;
 };
 enum class OrderType { Sz = 0, Scd = 1, ScdCorr = 2 };   // measure.rs:708-716
-struct Sasa {                                // measure.rs:427 (pymolar: sel.sasa().areas / .total_area)
+struct Sasa {                                // measure.rs:427,435 (pymolar: sel.sasa().areas / .total_area / .volumes / .total_volume)
     std::vector<float> areas;                // per selected atom, selection order
     double total_area = 0;
+    std::vector<float> volumes;              // sasa_vol() only: each ball inside its power cell; empty after sasa()
+    double total_volume = 0;
 };
 
 class System {                               // selection/system.rs: topology + current state
@@ -277,16 +279,9 @@ class SelBound {
         return {lo, hi};
     }
     // Shrake-Rupley over `npoints` points per atom, radii vdw + probe (the definition: molar_hip.h, molar_hip_sasa)
-    Sasa sasa(Float probe = 0.14f, uint32_t npoints = 960) const {
-        if (sys_->top.vdw.size() != natoms()) throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "sasa: the topology has no vdW radii");
-        std::vector<Float> vdw(index_.size());
-        for (size_t k = 0; k < index_.size(); ++k) vdw[k] = sys_->top.vdw[index_[k]];
-        Sasa out;
-        out.areas.resize(index_.size());
-        check(molar_hip_sasa(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), vdw.data(), probe, npoints,
-                             out.areas.data(), nullptr, &out.total_area));
-        return out;
-    }
+    Sasa sasa(Float probe = 0.14f, uint32_t npoints = 960) const { return sasa_call("sasa", probe, npoints, false); }
+    // the same with the per-atom volumes (Measure::sasa_vol; the definition: molar_hip.h, molar_hip_sasa_vol)
+    Sasa sasa_vol(Float probe = 0.14f, uint32_t npoints = 960) const { return sasa_call("sasa_vol", probe, npoints, true); }
     Pos center_of_geometry() const {
         Pos o;
         check(molar_hip_center_of_geometry(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), &o.x));
@@ -409,6 +404,24 @@ class SelBound {
     IsometryMatrix3 principal_transform_pbc() const { return principal(require_box().colmajor9()); }
 
    private:
+    // sasa() and sasa_vol(): the radii of the selected atoms, then molar_hip_sasa or molar_hip_sasa_vol
+    Sasa sasa_call(const char *who, Float probe, uint32_t npoints, bool with_volumes) const {
+        if (sys_->top.vdw.size() != natoms())
+            throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, std::string(who) + ": the topology has no vdW radii");
+        std::vector<Float> vdw(index_.size());
+        for (size_t k = 0; k < index_.size(); ++k) vdw[k] = sys_->top.vdw[index_[k]];
+        Sasa out;
+        out.areas.resize(index_.size());
+        if (with_volumes) {
+            out.volumes.resize(index_.size());
+            check(molar_hip_sasa_vol(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), vdw.data(), probe, npoints,
+                                     out.areas.data(), nullptr, &out.total_area, out.volumes.data(), &out.total_volume));
+        } else {
+            check(molar_hip_sasa(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), vdw.data(), probe, npoints,
+                                 out.areas.data(), nullptr, &out.total_area));
+        }
+        return out;
+    }
     IsometryMatrix3 principal(const Float *box9) const {
         IsometryMatrix3 tr;
         check(molar_hip_principal_transform(ctx(), coords_ptr(), natoms(), index_.data(), index_.size(), masses(), box9,

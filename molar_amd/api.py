@@ -647,22 +647,44 @@ class Engine:
     def sasa_frames(self, frames, vdw, idx=None, probe=0.14, npoints=960):
         """molar_hip_sasa_frames over frames[F, natoms, 3] (numpy or torch CUDA): every frame is enqueued behind the one
         before it, one wait.  Returns (areas[F, n], totals[F]); frame by frame they equal `sasa` bit for bit."""
+        return self._sasa_frames(frames, vdw, idx, probe, npoints, False)
+
+    def sasa_vol(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
+        """`sasa` with the per-atom volumes (molar_hip_sasa_vol; Measure::sasa_vol, pymolar sel.sasa_vol()): the returned
+        `Sasa` also has .volumes (each atom's ball inside its power cell, nm^3) and .total_volume (the union of the balls).
+        Areas and exposed counts are those of `sasa` bit for bit."""
+        return _sasa_call(self.lib.molar_hip_sasa_vol, self.ctx, _f32(xyz), _f32(vdw), _sel(idx), C.c_float(probe), npoints, want_exposed,
+                          np.float32, want_volumes=True)
+
+    def sasa_vol_frames(self, frames, vdw, idx=None, probe=0.14, npoints=960):
+        """molar_hip_sasa_vol_frames over frames[F, natoms, 3] (numpy or torch CUDA), queued like `sasa_frames`.  Returns
+        (areas[F, n], totals[F], volumes[F, n], total_volumes[F]); frame by frame they equal `sasa_vol` bit for bit."""
+        return self._sasa_frames(frames, vdw, idx, probe, npoints, True)
+
+    def _sasa_frames(self, frames, vdw, idx, probe, npoints, want_volumes):
         frames = _f32(frames)
         assert frames.ndim == 3 and frames.shape[2] == 3
         F, natoms = frames.shape[0], frames.shape[1]
         vdw = _f32(vdw); idx = _sel(idx)
         n = natoms if idx is None else idx.shape[0]
         assert vdw.shape[0] == n, "one radius per selected atom"
-        totals = np.zeros(F, np.float64)
-        if _is_torch(frames):
-            import torch
-            areas = torch.zeros((F, n), dtype=torch.float32, device=frames.device)
-        else:
-            areas = np.zeros((F, n), np.float32)
+
+        def per_atom():
+            if _is_torch(frames):
+                import torch
+                return torch.zeros((F, n), dtype=torch.float32, device=frames.device)
+            return np.zeros((F, n), np.float32)
+        areas, totals = per_atom(), np.zeros(F, np.float64)
         fa, k1 = _addr(frames); ia, k2 = _addr(idx); va, k3 = _addr(vdw); aa, k4 = _addr(areas)
-        check(self.lib.molar_hip_sasa_frames(self.ctx, fa, F, natoms * 3, natoms, ia, n, va, C.c_float(probe), npoints, aa,
-                                             totals.ctypes.data))
-        return areas, totals
+        if not want_volumes:
+            check(self.lib.molar_hip_sasa_frames(self.ctx, fa, F, natoms * 3, natoms, ia, n, va, C.c_float(probe), npoints, aa,
+                                                 totals.ctypes.data))
+            return areas, totals
+        volumes, vtotals = per_atom(), np.zeros(F, np.float64)
+        oa, k5 = _addr(volumes)
+        check(self.lib.molar_hip_sasa_vol_frames(self.ctx, fa, F, natoms * 3, natoms, ia, n, va, C.c_float(probe), npoints, aa,
+                                                 totals.ctypes.data, oa, vtotals.ctypes.data))
+        return areas, totals, volumes, vtotals
 
     # ------------------------------------------------------------ measure
     def _sel_args(self, xyz, idx):
@@ -1019,10 +1041,12 @@ class FitStream:
 
 class Sasa:
     """Result of a surface-area call, with pymolar's getters: `areas` (per selected atom, nm^2), `total_area` (their
-    sum in double) and, when asked for, `exposed` (points of each atom that no neighbour buries)."""
+    sum in double) and, when asked for, `exposed` (points of each atom that no neighbour buries).  After a `sasa_vol`
+    call also `volumes` (per selected atom, nm^3) and `total_volume`; both are None when not computed."""
 
-    def __init__(self, areas, total_area, exposed=None):
+    def __init__(self, areas, total_area, exposed=None, volumes=None, total_volume=None):
         self.areas, self.total_area, self.exposed = areas, total_area, exposed
+        self.volumes, self.total_volume = volumes, total_volume
 
 
 def sasa_points(npoints, dtype=np.float32):
@@ -1038,8 +1062,9 @@ def sasa_points(npoints, dtype=np.float32):
     return out
 
 
-def _sasa_call(fn, ctx, xyz, vdw, idx, probe, npoints, want_exposed, real):
-    """One frame through molar_hip_sasa / _f64: results live where the coordinates live."""
+def _sasa_call(fn, ctx, xyz, vdw, idx, probe, npoints, want_exposed, real, want_volumes=False):
+    """One frame through molar_hip_sasa / _f64 or, with want_volumes, molar_hip_sasa_vol / _f64: results live where the
+    coordinates live."""
     natoms = xyz.shape[0] if xyz.ndim == 2 else xyz.shape[0] // 3
     n = natoms if idx is None else idx.shape[0]
     assert vdw.shape[0] == n, "one radius per selected atom"
@@ -1054,8 +1079,15 @@ def _sasa_call(fn, ctx, xyz, vdw, idx, probe, npoints, want_exposed, real):
         areas = np.zeros(n, real)
         exposed = np.zeros(n, np.uint32) if want_exposed else None
     xa, k1 = _addr(xyz); ia, k2 = _addr(idx); va, k3 = _addr(vdw); aa, k4 = _addr(areas); ea, k5 = _addr(exposed)
-    check(fn(ctx, xa, natoms, ia, n, va, probe, int(npoints), aa if n else None, ea if n else None, C.byref(total)))
-    return Sasa(areas, float(total.value), exposed)
+    if not want_volumes:
+        check(fn(ctx, xa, natoms, ia, n, va, probe, int(npoints), aa if n else None, ea if n else None, C.byref(total)))
+        return Sasa(areas, float(total.value), exposed)
+    volumes = areas.clone() if _is_torch(xyz) else areas.copy()            # zeros of the same kind
+    total_volume = C.c_double(0.0)
+    oa, k6 = _addr(volumes)
+    check(fn(ctx, xa, natoms, ia, n, va, probe, int(npoints), aa if n else None, ea if n else None, C.byref(total), oa if n else None,
+             C.byref(total_volume)))
+    return Sasa(areas, float(total.value), exposed, volumes, float(total_volume.value))
 
 
 def _f64(x):
@@ -1202,6 +1234,11 @@ class MeasureF64:
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""
         return _sasa_call(self.lib.molar_hip_sasa_f64, self.ctx, _f64(xyz), _f64(vdw), _sel(idx), C.c_double(probe), npoints,
                           want_exposed, np.float64)
+
+    def sasa_vol(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
+        """Engine.sasa_vol on float64 coordinates and radii (molar_hip_sasa_vol_f64): compares, cuts and division in f64."""
+        return _sasa_call(self.lib.molar_hip_sasa_vol_f64, self.ctx, _f64(xyz), _f64(vdw), _sel(idx), C.c_double(probe), npoints,
+                          want_exposed, np.float64, want_volumes=True)
 
     def min_max(self, xyz, idx=None):
         a = self._sel(xyz, idx)
@@ -1723,6 +1760,11 @@ class Sel:
         """Measure::sasa (measure.rs:427) / pymolar sel.sasa(): per-atom areas and their total, radii from the topology."""
         vdw = self.top.vdw[self.index.astype(np.int64)]
         return self.engine.sasa(self.state.coords, vdw, self.index, probe=probe, npoints=npoints)
+
+    def sasa_vol(self, probe=0.14, npoints=960):
+        """Measure::sasa_vol (measure.rs:435) / pymolar sel.sasa_vol(): areas, volumes and their totals."""
+        vdw = self.top.vdw[self.index.astype(np.int64)]
+        return self.engine.sasa_vol(self.state.coords, vdw, self.index, probe=probe, npoints=npoints)
 
     # measure.rs:100-109, 246-257, 646-649: T(cm) * inverse(axes) * T(-cm), returned as (R, t) of p -> R p + t
     def principal_transform(self):

@@ -29,7 +29,8 @@ struct molar_hip_sasa_state {
     DevBuf cell_count, cell_start;                   // u32 [cap + 2]
     DevBuf rec;                                      // {x, y, z, R} per atom in cell order
     DevBuf partials, totals;                         // double per workgroup; double per frame
-    DevBuf out_areas, out_exposed;                   // results of calls whose destinations are host memory
+    DevBuf vpartials, vtotals;                       // the same for the volumes
+    DevBuf out_areas, out_exposed, out_volumes;      // results of calls whose destinations are host memory
 };
 
 namespace {
@@ -38,6 +39,7 @@ constexpr uint32_t SASA_WAVES = 4;                   // atoms per workgroup
 constexpr uint32_t SASA_CHUNK = 256;                 // neighbour entries a wave holds in LDS between two point passes
 constexpr uint32_t SASA_MAX_POINTS = 4096;           // 64 lanes x 64 mask bits
 constexpr uint32_t AXIS_CAP = 1024;                  // cells per axis
+constexpr int SASA_VOL_Q = 4;                        // points per lane whose intervals the volume variant holds in registers
 
 struct GridP {
     double lo[3];
@@ -253,18 +255,55 @@ __device__ __forceinline__ void sasa_points_pass(typename Real4T<Real>::type *ch
     }
 }
 
+// The volume variant's point work: a batch of SASA_VOL_Q points of the lane (directions u, surface points a = R_i u, the
+// rays' intervals [lo, hi]) against the `count` entries of the chunk.  Per entry the radical plane's offset c once, then
+// per point the burial compare of the areas (bit q of `bur`) and the cut of the ray's interval at t = c / (u . d); the
+// definition's three cases.
 template <class Real>
+struct SasaVolBatch {
+    Real u[SASA_VOL_Q][3], a[SASA_VOL_Q][3], lo[SASA_VOL_Q], hi[SASA_VOL_Q];
+    uint32_t bur;
+};
+
+template <class Real>
+__device__ __forceinline__ void sasa_vol_pass(const typename Real4T<Real>::type *chunk, uint32_t count, Real Ri2, uint32_t live, SasaVolBatch<Real> &B) {
+    for (uint32_t e = 0; e < count; ++e) {
+        const typename Real4T<Real>::type nb = chunk[e];            // one address for the whole wave: LDS broadcasts
+        const Real dd = (nb.x * nb.x + nb.y * nb.y) + nb.z * nb.z;
+        const Real c = ((dd + Ri2) - nb.w) * (Real)0.5;
+#pragma unroll
+        for (int q = 0; q < SASA_VOL_Q; ++q) {
+            if ((uint32_t)q >= live) break;                           // wave-uniform: slots past the table's last q do no work
+            B.bur |= (uint32_t)sasa_buries<Real>(nb, B.a[q][0], B.a[q][1], B.a[q][2]) << q;
+            const Real al = (B.u[q][0] * nb.x + B.u[q][1] * nb.y) + B.u[q][2] * nb.z;
+            const Real t = c / al;
+            // selects, no branches: the lanes of a wave take different cases at every entry
+            const Real hi = B.hi[q], lo = B.lo[q];
+            B.hi[q] = ((al > (Real)0) & (t < hi)) ? t : (((al == (Real)0) & (c < (Real)0)) ? (Real)0 : hi);
+            B.lo[q] = ((al < (Real)0) & (t > lo)) ? t : lo;
+        }
+    }
+}
+
+// One wave per atom.  WithVol = false: the exposed-point counts and areas.  WithVol = true: the same counts and areas (the
+// same compares, so the same bits) and the volume of the atom's ball inside its power cell.  The volume variant cannot
+// leave when every point is buried (a buried point still carries volume) and cannot keep the intervals of 64 points per
+// lane, so it takes the points in batches of SASA_VOL_Q per lane with their intervals in registers, each batch against
+// every neighbour: the chunk is read again per batch, and the cells are walked again per batch only for an atom whose
+// neighbours overflowed the chunk.
+template <class Real, bool WithVol>
 __global__ void __launch_bounds__(64 * SASA_WAVES) sasa_kernel(const typename Real4T<Real>::type *__restrict__ rec, const uint32_t *__restrict__ key_sorted,
                                                                const uint32_t *__restrict__ val_sorted, const uint32_t *__restrict__ cell_start,
                                                                const GridP *__restrict__ Gp, uint32_t cap, uint32_t n, const Real *__restrict__ table,
                                                                uint32_t npoints, Real *__restrict__ areas, uint32_t *__restrict__ exposed,
-                                                               double *__restrict__ partials) {
+                                                               double *__restrict__ partials, Real *__restrict__ volumes,
+                                                               double *__restrict__ vpartials) {
     using R4 = typename Real4T<Real>::type;
     __shared__ R4 chunks[SASA_WAVES][SASA_CHUNK + 4];           // + the pad of sasa_points_pass
     __shared__ double wave_area[SASA_WAVES];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t s = blockIdx.x * SASA_WAVES + wave;
-    double area_d = 0.0;
+    double area_d = 0.0, vol_d = 0.0;
     // wave-uniform: the atoms that take part come first in cell order
     if (s < n && key_sorted[s] < cap) {
         R4 *chunk = chunks[wave];
@@ -273,60 +312,110 @@ __global__ void __launch_bounds__(64 * SASA_WAVES) sasa_kernel(const typename Re
         const uint32_t cx = cell % dx, cy = (cell / dx) % dy, cz = cell / (dx * dy);
         const R4 me = rec[s];
         const Real Ri = me.w;
-        const uint32_t nq = (npoints + 63u) / 64u;
         // points this lane owns: lane + 64 q < npoints
         const uint32_t mine = npoints > lane ? (npoints - lane + 63u) / 64u : 0u;
         const unsigned long long full = mine >= 64u ? ~0ull : ((1ull << mine) - 1ull);
         unsigned long long buried = 0ull;
-        uint32_t count = 0;
-        bool done = false;
-        const uint32_t x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < dx ? cx + 1u : dx - 1u;
-        for (uint32_t zz = (cz > 0u ? cz - 1u : 0u); zz <= (cz + 1u < dz ? cz + 1u : dz - 1u) && !done; ++zz) {
-            for (uint32_t yy = (cy > 0u ? cy - 1u : 0u); yy <= (cy + 1u < dy ? cy + 1u : dy - 1u) && !done; ++yy) {
-                const uint32_t row = (zz * dy + yy) * dx;
-                const uint32_t t0 = cell_start[row + x0], t1 = cell_start[row + x1 + 1u];      // cells of one row are contiguous
-                for (uint32_t base = t0; base < t1; base += 64u) {
-                    if (count + 64u > SASA_CHUNK) {
-                        __builtin_amdgcn_wave_barrier();
-                        sasa_points_pass<Real>(chunk, count, table, npoints, lane, Ri, buried);
-                        __builtin_amdgcn_wave_barrier();
-                        count = 0;
-                        if (__all(buried == full)) {
-                            done = true;
-                            break;
+        double vsum = 0.0;
+        // One nest for both variants.  The area variant runs it once and leaves when every point is buried; the volume variant
+        // runs the part from the batch's set-up to its sums once per batch of points, the walk over the cells again only
+        // while the neighbours do not fit the chunk (`fits`: later batches read the chunk as the first walk left it).
+        const Real Ri2 = Ri * Ri;
+        uint32_t count = 0, q0 = 0;
+        bool done = false, fits = false;
+        do {
+            SasaVolBatch<Real> B;
+            uint32_t flushes = 0u;
+            const uint32_t live = min((uint32_t)SASA_VOL_Q, (npoints + 63u) / 64u - q0);      // slots of this batch that hold points
+            if constexpr (WithVol) {
+#pragma unroll
+                for (int q = 0; q < SASA_VOL_Q; ++q) {
+                    const uint32_t p = lane + 64u * (q0 + (uint32_t)q);
+#pragma unroll
+                    for (int d = 0; d < 3; ++d) {
+                        B.u[q][d] = p < npoints ? table[3u * p + (uint32_t)d] : (Real)0;
+                        B.a[q][d] = Ri * B.u[q][d];
+                    }
+                    B.lo[q] = (Real)0;
+                    B.hi[q] = Ri;
+                }
+                B.bur = 0u;
+                // a batch that walks the cells starts with an empty chunk; once the first walk has shown that every neighbour
+                // fits (`fits`), no later batch walks: `count` and the chunk's entries stay as that walk left them
+                if (!fits) count = 0;
+                __builtin_amdgcn_wave_barrier();
+            }
+            const uint32_t x0 = cx > 0u ? cx - 1u : 0u, x1 = cx + 1u < dx ? cx + 1u : dx - 1u;
+            for (uint32_t zz = (cz > 0u ? cz - 1u : 0u); zz <= (cz + 1u < dz ? cz + 1u : dz - 1u) && !done && !fits; ++zz) {
+                for (uint32_t yy = (cy > 0u ? cy - 1u : 0u); yy <= (cy + 1u < dy ? cy + 1u : dy - 1u) && !done; ++yy) {
+                    const uint32_t row = (zz * dy + yy) * dx;
+                    const uint32_t t0 = cell_start[row + x0], t1 = cell_start[row + x1 + 1u];      // cells of one row are contiguous
+                    for (uint32_t base = t0; base < t1; base += 64u) {
+                        if (count + 64u > SASA_CHUNK) {
+                            __builtin_amdgcn_wave_barrier();
+                            if constexpr (WithVol) {
+                                sasa_vol_pass<Real>(chunk, count, Ri2, live, B);
+                                ++flushes;
+                            } else {
+                                sasa_points_pass<Real>(chunk, count, table, npoints, lane, Ri, buried);
+                            }
+                            __builtin_amdgcn_wave_barrier();
+                            count = 0;
+                            if constexpr (!WithVol) {
+                                if (__all(buried == full)) {
+                                    done = true;
+                                    break;
+                                }
+                            }
                         }
+                        const uint32_t t = base + lane;
+                        bool hit = false;
+                        R4 ent;
+                        ent.x = ent.y = ent.z = ent.w = (Real)0;
+                        if (t < t1 && t != s) {
+                            const R4 o = rec[t];
+                            const Real ddx = o.x - me.x, ddy = o.y - me.y, ddz = o.z - me.z;
+                            const Real d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
+                            const Real lim = Ri + o.w;
+                            hit = d2 < lim * lim;
+                            ent.x = ddx;
+                            ent.y = ddy;
+                            ent.z = ddz;
+                            ent.w = o.w * o.w;
+                        }
+                        const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
+                        if (hit) {
+                            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                            chunk[count + rank] = ent;
+                        }
+                        count += (uint32_t)__builtin_popcountll(mask);
                     }
-                    const uint32_t t = base + lane;
-                    bool hit = false;
-                    R4 ent;
-                    ent.x = ent.y = ent.z = ent.w = (Real)0;
-                    if (t < t1 && t != s) {
-                        const R4 o = rec[t];
-                        const Real ddx = o.x - me.x, ddy = o.y - me.y, ddz = o.z - me.z;
-                        const Real d2 = (ddx * ddx + ddy * ddy) + ddz * ddz;
-                        const Real lim = Ri + o.w;
-                        hit = d2 < lim * lim;
-                        ent.x = ddx;
-                        ent.y = ddy;
-                        ent.z = ddz;
-                        ent.w = o.w * o.w;
-                    }
-                    const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
-                    if (hit) {
-                        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-                        chunk[count + rank] = ent;
-                    }
-                    count += (uint32_t)__builtin_popcountll(mask);
                 }
             }
-        }
-        if (!done && count) {
-            __builtin_amdgcn_wave_barrier();
-            sasa_points_pass<Real>(chunk, count, table, npoints, lane, Ri, buried);
-        }
-        (void)nq;
+            if (!done && count) {
+                __builtin_amdgcn_wave_barrier();
+                if constexpr (WithVol)
+                    sasa_vol_pass<Real>(chunk, count, Ri2, live, B);
+                else
+                    sasa_points_pass<Real>(chunk, count, table, npoints, lane, Ri, buried);
+            }
+            if constexpr (WithVol) {
+                if (q0 == 0u) fits = flushes == 0u;
+#pragma unroll
+                for (int q = 0; q < SASA_VOL_Q; ++q) {
+                    // a point past the table has u = 0: its interval stays [0, R_i] or becomes [0, 0], its bit falls outside `full`
+                    const bool own = lane + 64u * (q0 + (uint32_t)q) < npoints;
+                    const double h = (double)(B.hi[q] < B.lo[q] ? B.lo[q] : B.hi[q]), l = (double)B.lo[q];
+                    vsum += own ? (h * h) * h - (l * l) * l : 0.0;
+                    buried |= (unsigned long long)((B.bur >> q) & 1u) << (q0 + (uint32_t)q);
+                }
+                q0 += (uint32_t)SASA_VOL_Q;
+            }
+        } while (WithVol && q0 * 64u < npoints);
         uint32_t ex = mine - (uint32_t)__builtin_popcountll(buried & full);
         for (int off = 32; off > 0; off >>= 1) ex += (uint32_t)__shfl_xor((int)ex, off, 64);
+        if constexpr (WithVol)
+            for (int off = 32; off > 0; off >>= 1) vsum += __shfl_xor(vsum, off, 64);
         if (lane == 0) {
             const double Rd = (double)Ri;
             const Real a = (Real)((((4.0 * 3.14159265358979323846) * (Rd * Rd)) * (double)ex) / (double)npoints);
@@ -334,10 +423,29 @@ __global__ void __launch_bounds__(64 * SASA_WAVES) sasa_kernel(const typename Re
             areas[k] = a;
             if (exposed) exposed[k] = ex;
             area_d = (double)a;
+            if constexpr (WithVol) {
+                const Real v = (Real)(((((4.0 * 3.14159265358979323846) / 3.0) * vsum)) / (double)npoints);
+                volumes[k] = v;
+                vol_d = (double)v;
+            }
         }
+    } else if constexpr (WithVol) {
+        // an atom that takes no part: its area and count were zeroed with the records
+        if (s < n && lane == 0) volumes[val_sorted[s]] = (Real)0;
     }
     if (lane == 0) wave_area[wave] = area_d;
-    __syncthreads();
+    if constexpr (WithVol) {
+        __shared__ double wave_vol[SASA_WAVES];
+        if (lane == 0) wave_vol[wave] = vol_d;
+        __syncthreads();
+        if (threadIdx.x == 64) {
+            double sum = 0.0;
+            for (uint32_t w = 0; w < SASA_WAVES; ++w) sum += wave_vol[w];
+            vpartials[blockIdx.x] = sum;
+        }
+    } else {
+        __syncthreads();
+    }
     if (threadIdx.x == 0) {
         double sum = 0.0;
         for (uint32_t w = 0; w < SASA_WAVES; ++w) sum += wave_area[w];
@@ -416,7 +524,8 @@ int copy_out(molar_hip_ctx *c, void *dst, const void *src_dev, size_t bytes) {
 
 template <class Real>
 int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nframes, size_t frame_stride, size_t natoms, const uint64_t *idx,
-             size_t n, const Real *vdw, Real probe, uint32_t npoints, Real *areas, uint32_t *exposed, double *totals) {
+             size_t n, const Real *vdw, Real probe, uint32_t npoints, Real *areas, uint32_t *exposed, double *totals, bool with_vol = false,
+             Real *volumes = nullptr, double *vtotals = nullptr) {
     MH_CTX(c);
     MH_TRY(check_npoints(who, npoints));
     if (!(probe >= (Real)0) || !std::isfinite(probe)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: probe radius %g is negative or not finite", who, (double)probe);
@@ -428,9 +537,11 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
     if (!c->sasa) c->sasa = new molar_hip_sasa_state;
     molar_hip_sasa_state &Z = *c->sasa;
     MH_TRY(Z.totals.reserve(nframes * 8 + 8));
+    if (with_vol) MH_TRY(Z.vtotals.reserve(nframes * 8 + 8));
     if (nsel == 0) {
         MH_HIP(hipMemsetAsync(Z.totals.p, 0, nframes * 8, c->stream));
         MH_TRY(copy_out(c, totals, Z.totals.p, nframes * 8));
+        if (with_vol) MH_TRY(copy_out(c, vtotals, Z.totals.p, nframes * 8));
         MH_HIP(hipStreamSynchronize(c->stream));
         return MOLAR_HIP_OK;
     }
@@ -462,7 +573,9 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
     MH_TRY(Z.rec.reserve((size_t)ns * 4 * sizeof(Real)));
     // the workgroups' partial areas, and behind them the levels of their sum
     const uint32_t nlevel1 = (nblocks + SUM_SPAN - 1u) / SUM_SPAN;
-    MH_TRY(Z.partials.reserve(((size_t)nblocks + nlevel1 + nlevel1 / SUM_SPAN + 4) * 8));
+    const size_t partials_bytes = ((size_t)nblocks + nlevel1 + nlevel1 / SUM_SPAN + 4) * 8;
+    MH_TRY(Z.partials.reserve(partials_bytes));
+    if (with_vol) MH_TRY(Z.vpartials.reserve(partials_bytes));
     // results: straight into device destinations, through the state's buffers otherwise
     const bool areas_dev = areas && is_device_ptr(areas), exposed_dev = exposed && is_device_ptr(exposed);
     Real *d_areas = areas;
@@ -474,6 +587,12 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
     if (exposed && !exposed_dev) {
         MH_TRY(Z.out_exposed.reserve((size_t)ns * 4));
         d_exposed = Z.out_exposed.as<uint32_t>();
+    }
+    const bool volumes_dev = volumes && is_device_ptr(volumes);
+    Real *d_volumes = volumes;
+    if (with_vol && !volumes_dev) {
+        MH_TRY(Z.out_volumes.reserve((volumes ? nframes : 1) * (size_t)ns * sizeof(Real)));
+        d_volumes = Z.out_volumes.as<Real>();
     }
     MH_HIP(hipMemsetAsync(Z.err.p, 0, 4, c->stream));
     using R4 = typename Real4T<Real>::type;
@@ -492,15 +611,25 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
         MH_TRY(device_exclusive_sum_u32(c, Z.cub_tmp, Z.cell_count.as<uint32_t>(), Z.cell_start.as<uint32_t>(), (size_t)cap + 2));
         hipLaunchKernelGGL(sasa_gather_kernel<Real>, dim3(nb256), dim3(256), 0, c->stream, S, cap, Z.key_out.as<uint32_t>(), Z.val_out.as<uint32_t>(),
                            Z.rec.as<R4>(), fa, d_exposed);
-        hipLaunchKernelGGL(sasa_kernel<Real>, dim3(nblocks), dim3(64 * SASA_WAVES), 0, c->stream, Z.rec.as<R4>(), Z.key_out.as<uint32_t>(),
-                           Z.val_out.as<uint32_t>(), Z.cell_start.as<uint32_t>(), Z.gridp.as<GridP>(), cap, ns, table, npoints, fa, d_exposed,
-                           Z.partials.as<double>());
-        {
-            const double *src = Z.partials.as<double>();
-            double *level = Z.partials.as<double>() + nblocks;
+        if (with_vol) {
+            Real *fv = volumes ? d_volumes + f * (size_t)ns : d_volumes;
+            hipLaunchKernelGGL((sasa_kernel<Real, true>), dim3(nblocks), dim3(64 * SASA_WAVES), 0, c->stream, Z.rec.as<R4>(), Z.key_out.as<uint32_t>(),
+                               Z.val_out.as<uint32_t>(), Z.cell_start.as<uint32_t>(), Z.gridp.as<GridP>(), cap, ns, table, npoints, fa, d_exposed,
+                               Z.partials.as<double>(), fv, Z.vpartials.as<double>());
+        } else {
+            hipLaunchKernelGGL((sasa_kernel<Real, false>), dim3(nblocks), dim3(64 * SASA_WAVES), 0, c->stream, Z.rec.as<R4>(), Z.key_out.as<uint32_t>(),
+                               Z.val_out.as<uint32_t>(), Z.cell_start.as<uint32_t>(), Z.gridp.as<GridP>(), cap, ns, table, npoints, fa, d_exposed,
+                               Z.partials.as<double>(), (Real *)nullptr, (double *)nullptr);
+        }
+        // the areas' total, then the volumes': the same levels over each array of partial sums
+        for (int pass = 0; pass < (with_vol ? 2 : 1); ++pass) {
+            DevBuf &P = pass ? Z.vpartials : Z.partials;
+            DevBuf &T = pass ? Z.vtotals : Z.totals;
+            const double *src = P.as<double>();
+            double *level = P.as<double>() + nblocks;
             for (uint32_t cnt = nblocks;;) {
                 const uint32_t nb = (cnt + SUM_SPAN - 1u) / SUM_SPAN;
-                double *dst = nb == 1u ? Z.totals.as<double>() + f : level;
+                double *dst = nb == 1u ? T.as<double>() + f : level;
                 hipLaunchKernelGGL(sasa_sum_kernel, dim3(nb), dim3(256), 0, c->stream, src, cnt, dst);
                 if (nb == 1u) break;
                 src = dst;
@@ -513,6 +642,10 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
     if (areas && !areas_dev) MH_TRY(copy_out(c, areas, d_areas, nframes * (size_t)ns * sizeof(Real)));
     if (exposed && !exposed_dev) MH_TRY(copy_out(c, exposed, d_exposed, (size_t)ns * 4));
     MH_TRY(copy_out(c, totals, Z.totals.p, nframes * 8));
+    if (with_vol) {
+        if (volumes && !volumes_dev) MH_TRY(copy_out(c, volumes, d_volumes, nframes * (size_t)ns * sizeof(Real)));
+        MH_TRY(copy_out(c, vtotals, Z.vtotals.p, nframes * 8));
+    }
     MH_TRY(ensure_pinned(c, 8));
     MH_HIP(hipMemcpyAsync(c->h_pinned, Z.err.p, 4, hipMemcpyDeviceToHost, c->stream));
     MH_HIP(hipStreamSynchronize(c->stream));
@@ -537,7 +670,8 @@ void sasa_release(molar_hip_ctx *c) {
     if (!c->sasa) return;
     molar_hip_sasa_state &Z = *c->sasa;
     for (DevBuf *b : {&Z.in_xyz, &Z.in_idx, &Z.in_vdw, &Z.table[0], &Z.table[1], &Z.bounds, &Z.gridp, &Z.err, &Z.key_in, &Z.key_out, &Z.val_in, &Z.val_out,
-                      &Z.cub_tmp, &Z.cell_count, &Z.cell_start, &Z.rec, &Z.partials, &Z.totals, &Z.out_areas, &Z.out_exposed})
+                      &Z.cub_tmp, &Z.cell_count, &Z.cell_start, &Z.rec, &Z.partials, &Z.totals, &Z.vpartials, &Z.vtotals, &Z.out_areas, &Z.out_exposed,
+                      &Z.out_volumes})
         b->release();
     delete c->sasa;
     c->sasa = nullptr;
@@ -563,6 +697,23 @@ int molar_hip_sasa_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const
 int molar_hip_sasa_frames(molar_hip_ctx *c, const float *frames, size_t nframes, size_t frame_stride, size_t natoms, const uint64_t *idx,
                           size_t n, const float *vdw, float probe, uint32_t npoints, float *areas, double *totals) {
     return sasa_run<float>(c, "sasa_frames", frames, nframes, frame_stride, natoms, idx, n, vdw, probe, npoints, areas, nullptr, totals);
+}
+
+int molar_hip_sasa_vol(molar_hip_ctx *c, const float *xyz, size_t natoms, const uint64_t *idx, size_t n, const float *vdw, float probe,
+                       uint32_t npoints, float *areas, uint32_t *exposed, double *total, float *volumes, double *total_volume) {
+    return sasa_run<float>(c, "sasa_vol", xyz, 1, 0, natoms, idx, n, vdw, probe, npoints, areas, exposed, total, true, volumes, total_volume);
+}
+
+int molar_hip_sasa_vol_f64(molar_hip_ctx *c, const double *xyz, size_t natoms, const uint64_t *idx, size_t n, const double *vdw, double probe,
+                           uint32_t npoints, double *areas, uint32_t *exposed, double *total, double *volumes, double *total_volume) {
+    return sasa_run<double>(c, "sasa_vol_f64", xyz, 1, 0, natoms, idx, n, vdw, probe, npoints, areas, exposed, total, true, volumes, total_volume);
+}
+
+int molar_hip_sasa_vol_frames(molar_hip_ctx *c, const float *frames, size_t nframes, size_t frame_stride, size_t natoms, const uint64_t *idx,
+                              size_t n, const float *vdw, float probe, uint32_t npoints, float *areas, double *totals, float *volumes,
+                              double *total_volumes) {
+    return sasa_run<float>(c, "sasa_vol_frames", frames, nframes, frame_stride, natoms, idx, n, vdw, probe, npoints, areas, nullptr, totals, true,
+                           volumes, total_volumes);
 }
 
 }  // extern "C"

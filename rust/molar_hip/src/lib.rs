@@ -142,6 +142,16 @@ impl Drop for Engine {
     }
 }
 
+/// What `Engine::sasa` and `Engine::sasa_vol` return: the reference's `Sasa` (sasa.rs:82-97), per selected atom in selection
+/// order; `volumes` is empty and `total_volume` 0 after `sasa`.
+#[derive(Debug, Clone)]
+pub struct Sasa {
+    pub areas: Vec<f32>,
+    pub total_area: f64,
+    pub volumes: Vec<f32>,
+    pub total_volume: f64,
+}
+
 fn idx_ptr(idx: Option<&[usize]>) -> (*const u64, usize) {
     // usize == u64 on every target MolAR supports (aliases.rs); the engine reads u64
     match idx {
@@ -330,6 +340,47 @@ impl Engine {
         self.plugin.check(unsafe {
             (self.plugin.fns.center_of_mass)(self.ctx, coords.as_ptr() as *const f32, coords.len(), ip, n, masses.as_ptr(), out.as_mut_ptr())
         })?;
+        Ok(out)
+    }
+
+    /// `Measure::sasa` (:427) through molar_hip_sasa: Shrake-Rupley areas over `npoints` points per atom, radii `vdw + probe`;
+    /// `vdw` holds one radius per SELECTED atom in selection order.  `volumes` stays empty.
+    pub fn sasa(&self, coords: &[[f32; 3]], index: Option<&[usize]>, vdw: &[f32], probe: f32, npoints: u32) -> Result<Sasa, EngineError> {
+        self.sasa_call("sasa", coords, index, vdw, probe, npoints, false)
+    }
+
+    /// `Measure::sasa_vol` (:435; `Sasa::volumes / total_volume`, sasa.rs:92,97) through molar_hip_sasa_vol: the areas of
+    /// `sasa` and the volume of each ball inside its power cell.
+    pub fn sasa_vol(&self, coords: &[[f32; 3]], index: Option<&[usize]>, vdw: &[f32], probe: f32, npoints: u32) -> Result<Sasa, EngineError> {
+        self.sasa_call("sasa_vol", coords, index, vdw, probe, npoints, true)
+    }
+
+    #[allow(clippy::too_many_arguments)]
+    fn sasa_call(
+        &self, what: &str, coords: &[[f32; 3]], index: Option<&[usize]>, vdw: &[f32], probe: f32, npoints: u32, with_volumes: bool,
+    ) -> Result<Sasa, EngineError> {
+        check_index(index, coords.len(), what)?;
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { coords.len() };
+        if vdw.len() != nsel {
+            return Err(EngineError::Sizes(format!("{what}: {} radii for {nsel} selected atoms", vdw.len())));
+        }
+        let mut out = Sasa { areas: vec![0f32; nsel], total_area: 0.0, volumes: vec![0f32; if with_volumes { nsel } else { 0 }], total_volume: 0.0 };
+        if index.is_none() && nsel == 0 {
+            return Ok(out); // to the C call, no index and n == 0 would mean "all atoms"
+        }
+        let xyz = coords.as_ptr() as *const f32;
+        if with_volumes {
+            self.plugin.check(unsafe {
+                (self.plugin.fns.sasa_vol)(self.ctx, xyz, coords.len(), ip, nsel, vdw.as_ptr(), probe, npoints, out.areas.as_mut_ptr(),
+                                           std::ptr::null_mut(), &mut out.total_area, out.volumes.as_mut_ptr(), &mut out.total_volume)
+            })?;
+        } else {
+            self.plugin.check(unsafe {
+                (self.plugin.fns.sasa)(self.ctx, xyz, coords.len(), ip, nsel, vdw.as_ptr(), probe, npoints, out.areas.as_mut_ptr(),
+                                       std::ptr::null_mut(), &mut out.total_area)
+            })?;
+        }
         Ok(out)
     }
 

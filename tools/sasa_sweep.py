@@ -9,8 +9,15 @@ Milliseconds per frame from HIP events on one stream shared by the engine and to
 best of --reps repetitions.  Also the relative difference of the total area at 96, 192 and 960 points against 3840 points on
 the 100k blob (the convergence of Shrake-Rupley towards the exact union-of-spheres area).  Writes a text table.
 
-    python tools/sasa_sweep.py [--out profiles/sasa.txt] [--reps 20] [--sizes 100000,1000000] [--fused-only]"""
+--vol times the volume call (Engine.sasa_vol, molar_hip_sasa_vol) beside the area call on the same shapes, and with
+--base-lib also the area call of another build of the library (the commit before the volumes, say) in the same process on
+the same stream, the three taking turns; it checks that the volume call's areas are those of the area call and prints the
+total volume and the number of atoms with an empty power cell.
+
+    python tools/sasa_sweep.py [--out profiles/sasa.txt] [--reps 20] [--sizes 100000,1000000] [--fused-only]
+    python tools/sasa_sweep.py --vol [--vol-only] [--base-lib other/libmolar_hip.so] [--out profiles/sasa_vol.txt]"""
 import argparse
+import ctypes as C
 import math
 import os
 import sys
@@ -46,14 +53,80 @@ def timed(fn, reps, stream):
     return float(np.median(ms)), float(np.min(ms))
 
 
+_base = {}          # path -> (library, context)
+
+
+def base_area_call(path, stream, dxyz, dvdw, n, npoints):
+    """molar_hip_sasa of the library at `path` on device arrays; returns (call, areas tensor)"""
+    import torch
+    if path not in _base:
+        lib = C.CDLL(path)
+        lib.molar_hip_create.restype = C.c_void_p
+        lib.molar_hip_create.argtypes = [C.c_int]
+        lib.molar_hip_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+        lib.molar_hip_sasa.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]
+        ctx = lib.molar_hip_create(0)
+        assert ctx and lib.molar_hip_set_stream(ctx, C.c_void_p(stream.cuda_stream)) == 0
+        _base[path] = (lib, ctx)
+    lib, ctx = _base[path]
+    areas = torch.zeros(n, dtype=torch.float32, device="cuda")
+    exposed = torch.zeros(n, dtype=torch.int32, device="cuda")
+    total = C.c_double(0.0)
+
+    def call():
+        rc = lib.molar_hip_sasa(ctx, dxyz.data_ptr(), n, None, n, dvdw.data_ptr(), PROBE, npoints, areas.data_ptr(), exposed.data_ptr(), C.byref(total))
+        assert rc == 0, rc
+    return call, areas
+
+
+def volume_leg(args, eng, stream, say):
+    import torch
+    say(f"{'atoms':>8} {'points':>6} {'area ms':>18} {'volume ms':>18} {'volume / area':>13} {'base area ms':>18} {'total nm^3':>12} {'empty cells':>11}")
+    for n in [int(x) for x in args.sizes.split(",")]:
+        xyz, vdw = blob(n, 21)
+        dxyz, dvdw = torch.from_numpy(xyz).cuda(), torch.from_numpy(vdw).cuda()
+        stream.synchronize()
+        for npoints in [int(x) for x in args.points.split(",")]:
+            res = {}
+
+            def area():
+                res["a"] = eng.sasa(dxyz, dvdw, probe=PROBE, npoints=npoints, want_exposed=True)
+
+            def volume():
+                res["v"] = eng.sasa_vol(dxyz, dvdw, probe=PROBE, npoints=npoints, want_exposed=True)
+            v_med, v_best = timed(volume, args.reps, stream)
+            if args.vol_only:
+                say(f"{n:>8} {npoints:>6} {'':>18} {v_med:>10.3f} ({v_best:.3f})")
+                continue
+            a_med, a_best = timed(area, args.reps, stream)
+            base = f"{'-':>18}"
+            if args.base_lib:
+                call, b_areas = base_area_call(args.base_lib, stream, dxyz, dvdw, n, npoints)
+                b_med, b_best = timed(call, args.reps, stream)
+                a2_med, a2_best = timed(area, args.reps, stream)              # again, after the other build: the spread of the area call
+                base = f"{b_med:>10.3f} ({b_best:.3f})"
+                assert torch.equal(b_areas, res["a"].areas), "the area call's results changed"
+                say(f"#   area call once more after the base build's: {a2_med:.3f} ({a2_best:.3f})")
+            assert torch.equal(res["v"].areas, res["a"].areas) and torch.equal(res["v"].exposed, res["a"].exposed)
+            empty = int((res["v"].volumes == 0).sum())
+            say(f"{n:>8} {npoints:>6} {a_med:>10.3f} ({a_best:.3f}) {v_med:>10.3f} ({v_best:.3f}) {v_med / a_med:>13.1f} {base} "
+                f"{res['v'].total_volume:>12.3f} {empty:>11}")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sasa.txt"))
+    ap.add_argument("--out", default=None, help="default: profiles/sasa.txt, profiles/sasa_vol.txt with --vol")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--sizes", default="100000,1000000")
     ap.add_argument("--points", default="96,960")
     ap.add_argument("--fused-only", action="store_true", help="the fused call alone (kernel traces)")
+    ap.add_argument("--vol", action="store_true", help="the volume call beside the area call")
+    ap.add_argument("--vol-only", action="store_true", help="with --vol: the volume call alone (kernel traces)")
+    ap.add_argument("--base-lib", default=None, help="with --vol: another build of libmolar_hip.so whose area call is timed in the same run")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sasa_vol.txt" if args.vol else "sasa.txt")
     import torch
     from molar_amd import api, build
     build.build_library()
@@ -69,6 +142,10 @@ def main():
         f"{args.reps} repetitions after a warm-up, HIP events; ms per frame as median (best)")
     with torch.cuda.stream(stream):
         eng = api.Engine(0, stream=stream.cuda_stream)
+        if args.vol:
+            volume_leg(args, eng, stream, say)
+            out.close()
+            return
         say(f"{'atoms':>8} {'points':>6} {'fused ms':>18} {'composition ms':>20} {'search ms':>16} {'pairs':>11} {'speed-up':>8} "
             f"{'exposed differ':>14}")
         for n in [int(x) for x in args.sizes.split(",")]:
