@@ -285,13 +285,47 @@ int molar_hip_search_histogram_frames(molar_hip_ctx *ctx, const molar_hip_search
  * itself, so "largest b with edges[b] <= d2" IS the formula.  INVALID_ARGUMENT unless min < max, both finite. */
 int molar_hip_histogram_edges(float hmin, float hmax, size_t nbins, float *edges);
 
+/* The second fused consumer: contact counts.  Never materialises pairs.  Let L be the list the search described by `desc`
+ * emits, ids taken as POSITIONS IN THE SELECTION (desc->ids_local has no effect here).  L includes the reference's
+ * duplicates - the same-cell cross pairs of the two-set search, and repeated cell pairs when a periodic dimension has two
+ * cells or fewer - and the counts inherit them (the occupancy of the frames form is immune: it records "non-zero").
+ *   *out_count = |L|.
+ *   SINGLE: deg1[p] += entries with p as first OR second member (the length of SearchConnectivity's list of p); deg2 must be
+ *           NULL; map is ngroups1 x ngroups1, row-major, and an entry (a, b) adds 1 at [min(g1[a], g1[b])][max(..)]: only the
+ *           upper triangle with the diagonal is used (which member of a single-set entry comes first follows the plan).
+ *   DOUBLE: deg1[p] += entries with first member p, deg2[p] += entries with second member p; map is ngroups1 x ngroups2 and
+ *           [g1[a]][g2[b]] += 1.
+ * Every output is uint64, accumulated INTO, host or device memory, and may be NULL (all NULL: the call only counts).
+ * Atoms the reference drops (outside a non-periodic dimension of the grid) get 0.  With every requested output in device
+ * memory and out_count == NULL the call returns without waiting (molar_hip_synchronize before reading) - except that labels
+ * in DEVICE memory are checked on the device first, one 4-byte read-back per call; labels in host memory are checked on the
+ * host.  INVALID_ARGUMENT: kinds WITHIN and DOUBLE_VDW, deg2 with SINGLE, a map without labels, a label >= ngroups (nothing
+ * at all is added to any output then).  TOO_LARGE: ngroups1 * ngroups2 > 2^24 (the map is dense).  f32 only.  The call
+ * works on a search state of its own: a cached search of the context (count -> fill, a held `within` grid) stays valid. */
+typedef struct {
+    const uint32_t *group1;   /* label per SELECTED atom of set 1, length n1 (host or device) */
+    size_t ngroups1;
+    const uint32_t *group2;   /* DOUBLE: labels of set 2, length n2; SINGLE: ignored */
+    size_t ngroups2;
+} molar_hip_contact_groups;
+
+int molar_hip_search_contacts(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const molar_hip_contact_groups *groups /* may be NULL */,
+                              uint64_t *deg1, uint64_t *deg2, uint64_t *map, uint64_t *out_count);
+/* The same for a block of a trajectory (frames laid out as for molar_hip_search_histogram_frames): the sums are those of
+ * nframes single calls, and occupancy[r][c] (uint32, the map's shape, accumulated INTO, host or device, may be asked for
+ * without `map`) += 1 for every frame whose own contribution to map[r][c] is non-zero (a frame's own map is kept in 32 bits:
+ * one frame may add fewer than 2^32 entries to one group pair).  Labels are checked once for the block.  The frames are walked one after the other; with every requested output in device memory the call does not wait. */
+int molar_hip_search_contacts_frames(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const molar_hip_contact_groups *groups,
+                                     size_t nframes, size_t xyz1_stride, size_t xyz2_stride, const float *boxes9,
+                                     uint64_t *deg1, uint64_t *deg2, uint64_t *map, uint32_t *occupancy);
+
 /* ---- the drivers for MolAR built with its `f64` feature (Float = f64, aliases.rs:10-13): every operation in double -
  * cell assignment, the predicate d2 <= cutoff^2 and the distances - results as (usize, usize, f64) columns or usize ids.
  * Same request / count-then-fill convention as above.  Coordinates, index lists, radii and the result columns may be host or
  * device memory (device memory is used in place); grid and plan are built on the device.  In f64 there are the eight drivers,
  * the fused histogram, `within` as a set, SearchConnectivity and unwrap_connectivity (below).  Still f32 only: the matrix-core
  * count, the resident and pipelined resident forms, the small-second-set `within` kernel and the grid hold
- * (molar_hip_within_hold), and the chained membrane frame. */
+ * (molar_hip_within_hold), the fused contact counts (molar_hip_search_contacts), and the chained membrane frame. */
 typedef struct {
     int32_t kind;
     double cutoff;

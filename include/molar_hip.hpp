@@ -679,6 +679,95 @@ class Histogram1D {
     std::vector<uint64_t> counts_;
 };
 
+// Contact counts over frames, with the engine's second fused consumer as a feed (molar_hip_search_contacts / _frames; the
+// definition is in molar_hip.h): per-atom contact counts, a group x group contact matrix and the number of frames in which
+// each group pair was in contact - what a caller folds out of distance_search's list (coordination numbers, residue
+// contact maps, contact occupancy), without the list.  Ids are positions in the selections.  labels1 / labels2: one group
+// label per selected atom (labels2 empty: a single-selection map, ngroups1 x ngroups1, upper triangle).  Everything is an
+// integer and sums exactly over frames and ranks.  The counts include the reference list's duplicates (same-cell cross
+// pairs of the two-selection search, repeated cell pairs of grids with two cells or fewer along a periodic dimension);
+// the occupancy does not see them.
+struct ContactMap {
+    std::vector<uint32_t> labels1, labels2;
+    usize ngroups1 = 0, ngroups2 = 0;
+    std::vector<uint64_t> deg1, deg2;         // per selected atom (single selection: deg1 counts both members, deg2 stays empty)
+    std::vector<uint64_t> map;                // ngroups1 x (ngroups2 or ngroups1), row-major
+    std::vector<uint32_t> occupancy;          // same shape: frames with at least one contact
+    uint64_t frames = 0;                      // frames added so far
+
+    ContactMap(std::vector<uint32_t> l1, usize g1, std::vector<uint32_t> l2 = {}, usize g2 = 0)
+        : labels1(std::move(l1)), labels2(std::move(l2)), ngroups1(g1), ngroups2(g2) {}
+    usize cols() const { return labels2.empty() ? ngroups1 : ngroups2; }
+    uint64_t at(usize r, usize c) const { return map[r * cols() + c]; }
+    uint64_t entries() const {                // entries of all the lists so far: every entry is in deg1 once (single selection: twice)
+        uint64_t n = 0;
+        for (uint64_t v : deg1) n += v;
+        return labels2.empty() ? n / 2 : n;
+    }
+
+    // one frame: distance_search_single(_pbc) of `s1`, or distance_search_double(_pbc) of `s1` against `s2`
+    void add_frame(Float cutoff, const SelBound &s1, const SelBound *s2, const PeriodicBox *pbox, PbcDims pbc_dims) {
+        const molar_hip_search_desc d = detail::desc(s2 ? MOLAR_HIP_SEARCH_DOUBLE : MOLAR_HIP_SEARCH_SINGLE, cutoff, s1, s2, true, pbox, pbc_dims);
+        size(s1.len(), s2 ? s2->len() : 0);
+        const molar_hip_contact_groups g = groups();
+        check(molar_hip_search_contacts_frames(s1.ctx(), &d, &g, 1, 0, 0, nullptr, deg1.data(), s2 ? deg2.data() : nullptr, map.data(), occupancy.data()));
+        frames += 1;
+    }
+    // a block of a trajectory in memory: frame k at frames + k * natoms * 3 floats, its box at boxes9 + 9 k (column-major), the
+    // selection `index` (empty: all atoms) of every frame against itself (distance_search_single_pbc per frame)
+    void add_trajectory_single_pbc(Engine &eng, const float *frames_xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                                   const std::vector<usize> &index, PbcDims pbc_dims);
+    // ... and selection index1 against index2 (distance_search_double_pbc per frame)
+    void add_trajectory_double_pbc(Engine &eng, const float *frames_xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                                   const std::vector<usize> &index1, const std::vector<usize> &index2, PbcDims pbc_dims);
+    void merge(const ContactMap &o) {
+        if (o.map.size() != map.size() || o.deg1.size() != deg1.size() || o.deg2.size() != deg2.size())
+            throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "ContactMap::merge: different shape");
+        for (size_t k = 0; k < map.size(); ++k) { map[k] += o.map[k]; occupancy[k] += o.occupancy[k]; }
+        for (size_t k = 0; k < deg1.size(); ++k) deg1[k] += o.deg1[k];
+        for (size_t k = 0; k < deg2.size(); ++k) deg2[k] += o.deg2[k];
+        frames += o.frames;
+    }
+
+  private:
+    void size(size_t n1, size_t n2) {
+        if (labels1.size() != n1 || (n2 && labels2.size() != n2))
+            throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "ContactMap: one label per selected atom is needed");
+        if (deg1.size() != n1) deg1.assign(n1, 0);
+        if (deg2.size() != n2) deg2.assign(n2, 0);
+        if (map.size() != ngroups1 * cols()) { map.assign(ngroups1 * cols(), 0); occupancy.assign(ngroups1 * cols(), 0); }
+    }
+    molar_hip_contact_groups groups() const {
+        molar_hip_contact_groups g{};
+        g.group1 = labels1.data(); g.ngroups1 = ngroups1;
+        g.group2 = labels2.empty() ? nullptr : labels2.data(); g.ngroups2 = ngroups2;
+        return g;
+    }
+    void trajectory(Engine &eng, int kind, const float *xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                    const std::vector<usize> &i1, const std::vector<usize> *i2, PbcDims pbc_dims) {
+        molar_hip_search_desc d{};
+        d.kind = kind;
+        d.cutoff = cutoff;
+        d.xyz1 = xyz; d.natoms1 = natoms; d.idx1 = i1.empty() ? nullptr : i1.data(); d.n1 = i1.size();
+        if (i2) { d.xyz2 = xyz; d.natoms2 = natoms; d.idx2 = i2->empty() ? nullptr : i2->data(); d.n2 = i2->size(); }
+        d.box9 = boxes9;
+        d.pbc = pbc_dims.raw();
+        size(i1.empty() ? natoms : i1.size(), i2 ? (i2->empty() ? natoms : i2->size()) : 0);
+        const molar_hip_contact_groups g = groups();
+        check(molar_hip_search_contacts_frames(eng.ctx(), &d, &g, nframes, natoms * 3, natoms * 3, boxes9, deg1.data(), i2 ? deg2.data() : nullptr,
+                                               map.data(), occupancy.data()));
+        frames += nframes;
+    }
+};
+inline void ContactMap::add_trajectory_single_pbc(Engine &eng, const float *frames_xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                                                  const std::vector<usize> &index, PbcDims pbc_dims) {
+    trajectory(eng, MOLAR_HIP_SEARCH_SINGLE, frames_xyz, nframes, natoms, boxes9, cutoff, index, nullptr, pbc_dims);
+}
+inline void ContactMap::add_trajectory_double_pbc(Engine &eng, const float *frames_xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                                                  const std::vector<usize> &index1, const std::vector<usize> &index2, PbcDims pbc_dims) {
+    trajectory(eng, MOLAR_HIP_SEARCH_DOUBLE, frames_xyz, nframes, natoms, boxes9, cutoff, index1, &index2, pbc_dims);
+}
+
 // ids: the reference takes an iterator; the two uses are the selection's own indices
 // (sel.iter_index(), ids_local = false) and 0..n (modify.rs:78, ids_local = true).
 template <class T>

@@ -42,6 +42,11 @@ class SearchDesc(C.Structure):
     ]
 
 
+class ContactGroups(C.Structure):
+    """molar_hip_contact_groups: one label per selected atom of each set, and the number of groups per side."""
+    _fields_ = [("group1", C.c_void_p), ("ngroups1", C.c_size_t), ("group2", C.c_void_p), ("ngroups2", C.c_size_t)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -134,6 +139,8 @@ SYMBOLS = {
     "molar_hip_search_histogram": (_I, [_P, _P, _F, _F, _SZ, _P, _P]),
     "molar_hip_search_histogram_frames": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _F, _F, _SZ, _P]),
     "molar_hip_histogram_edges": (_I, [_F, _F, _SZ, _P]),
+    "molar_hip_search_contacts": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_search_contacts_frames": (_I, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_min_max": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "molar_hip_center_of_geometry": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
     "molar_hip_center_of_mass": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),

@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (MEMBRANE_ARRAYS, Box, MembraneDesc, MembraneOut, MembraneView, MolarHipError, SearchDesc, SearchDescF64,
+from ._lib import (MEMBRANE_ARRAYS, Box, ContactGroups, MembraneDesc, MembraneOut, MembraneView, MolarHipError, SearchDesc, SearchDescF64,
                    check)
 
 PBC_FULL = 7
@@ -77,6 +77,18 @@ def _u64(x):
             return x.contiguous()     # non-negative int64 has the same bits as uint64
         raise TypeError("index tensors must be int64")
     return np.ascontiguousarray(x, dtype=np.uint64)
+
+
+def _u32(x):
+    """Group labels: numpy uint32, or a torch int32 tensor (non-negative int32 has the same bits as uint32)."""
+    if x is None:
+        return None
+    if _is_torch(x):
+        import torch
+        if x.dtype == torch.int32:
+            return x.contiguous()
+        raise TypeError("label tensors must be int32")
+    return np.ascontiguousarray(x, dtype=np.uint32)
 
 
 _NO_ATOMS = np.zeros(1, np.uint64)[:0]      # an empty selection with an address
@@ -635,6 +647,133 @@ class Engine:
         self._keep = keep
         return bins
 
+    # ------------------------------------------------------------ contact counts
+    def _contacts_desc(self, kind, cutoff, xyz1, idx1, xyz2, idx2, pbc):
+        d = SearchDesc()
+        d.kind = kind
+        d.cutoff = float(cutoff)
+        keep = []
+        for name, arr in (("xyz1", xyz1), ("idx1", idx1), ("xyz2", xyz2), ("idx2", idx2)):
+            a, k = _addr(arr)
+            setattr(d, name, a)
+            keep.append(k)
+        d.natoms1 = 0 if xyz1 is None else xyz1.shape[-2]
+        d.natoms2 = 0 if xyz2 is None else xyz2.shape[-2]
+        d.n1 = 0 if idx1 is None else idx1.shape[0]
+        d.n2 = 0 if idx2 is None else idx2.shape[0]
+        d.pbc = pbc_mask(pbc)
+        return d, keep
+
+    @staticmethod
+    def _contacts_out(arr, want, shape, like, dtype64=True):
+        """An output of the contacts calls: the caller's array, or zeros (a CUDA tensor when the coordinates are one)."""
+        if arr is not None or not want:
+            return arr
+        if _is_torch(like):
+            import torch
+            return torch.zeros(shape, dtype=torch.int64 if dtype64 else torch.int32, device=like.device)
+        return np.zeros(shape, np.uint64 if dtype64 else np.uint32)
+
+    def search_contacts(self, kind, cutoff, xyz1, idx1=None, xyz2=None, idx2=None, box=None, pbc=0, group1=None, ngroups1=0,
+                        group2=None, ngroups2=0, deg1=None, deg2=None, cmap=None, want_deg=True, want_map=None, want_count=True):
+        """molar_hip_search_contacts: per-atom contact counts and the group x group contact matrix of the pair list, fused
+        into the pair loop (no pair is written).  `group1` / `group2`: one label per SELECTED atom.  deg1 / deg2 / cmap
+        (uint64 numpy or int64 CUDA tensors) are accumulated into; missing ones are made as zeros when wanted (want_map
+        defaults to "labels were given"), CUDA tensors when xyz1 is one.  SINGLE: deg1 counts both members, deg2 stays
+        None and only the upper triangle of cmap is used.  The counts include the reference list's duplicates
+        (include/molar_hip.h).  Returns a `Contacts`; with every output on the device and want_count=False the call does
+        not wait (synchronize() before reading)."""
+        xyz1 = _f32(xyz1); xyz2 = _f32(xyz2); idx1 = _u64(idx1); idx2 = _u64(idx2)
+        group1 = _u32(group1); group2 = _u32(group2)
+        two = kind == SEARCH_DOUBLE
+        d, keep = self._contacts_desc(kind, cutoff, xyz1, idx1, xyz2, idx2, pbc)
+        if box is not None:
+            ba, kb = self._box9(box)
+            keep.append(kb)
+            d.box9 = ba
+        n1 = d.n1 if idx1 is not None else d.natoms1
+        n2 = d.n2 if idx2 is not None else d.natoms2
+        if want_map is None:
+            want_map = group1 is not None
+        deg1 = self._contacts_out(deg1, want_deg, (n1,), xyz1)
+        deg2 = self._contacts_out(deg2, want_deg and two, (n2,), xyz1)
+        cmap = self._contacts_out(cmap, want_map, (int(ngroups1), int(ngroups2) if two else int(ngroups1)), xyz1)
+        g = ContactGroups()
+        (g.group1, k1), (g.group2, k2) = _addr(group1), _addr(group2)
+        g.ngroups1, g.ngroups2 = int(ngroups1), int(ngroups2)
+        keep += [k1, k2]
+        cnt = C.c_uint64(0)
+        check(self.lib.molar_hip_search_contacts(self.ctx, C.byref(d), C.byref(g) if group1 is not None else None, _addr(deg1)[0],
+                                                 _addr(deg2)[0], _addr(cmap)[0], C.byref(cnt) if want_count else None))
+        self._keep = keep
+        return Contacts(int(cnt.value) if want_count else None, deg1, deg2, cmap)
+
+    def search_contacts_frames(self, kind, cutoff, frames, idx1=None, box=None, pbc=0, frames2=None, idx2=None, group1=None, ngroups1=0,
+                               group2=None, ngroups2=0, deg1=None, deg2=None, cmap=None, occupancy=None, want_deg=True, want_map=None,
+                               want_occupancy=None):
+        """molar_hip_search_contacts_frames: `frames` = [nframes, natoms, 3] float32 (numpy or a CUDA tensor, frames may have a
+        gap between them) through search_contacts - the same sums as nframes calls - plus `occupancy` (uint32 / int32, the
+        map's shape): the number of frames in which each group pair was in contact.  `box`: one 3x3 matrix or
+        [nframes, 3, 3].  SEARCH_DOUBLE: the second set is `idx2` of `frames2` (None: of the same frames).  Returns a
+        `Contacts` with count None; synchronize() before reading device outputs."""
+        def block(fr):
+            stride = None
+            if _is_torch(fr) and fr.ndim == 3 and fr.stride(2) == 1 and fr.stride(1) == 3:
+                import torch
+                assert fr.dtype == torch.float32
+                stride = int(fr.stride(0))
+                fa, k = fr.data_ptr(), fr
+            else:
+                fr = _f32(fr)
+                fa, k = _addr(fr)
+            assert fr.ndim == 3 and fr.shape[2] == 3
+            return fr, fa, k, (int(fr.shape[1]) * 3 if stride is None else stride)
+        frames, fa, k1, stride = block(frames)
+        idx1 = _u64(idx1); idx2 = _u64(idx2)
+        group1 = _u32(group1); group2 = _u32(group2)
+        nframes = int(frames.shape[0])
+        two = kind == SEARCH_DOUBLE
+        f2, fa2, k3, stride2 = (None, None, None, 0)
+        if kind != SEARCH_SINGLE:
+            f2, fa2, k3, stride2 = block(frames if frames2 is None else frames2)
+            assert int(f2.shape[0]) == nframes
+        d, keep = self._contacts_desc(kind, cutoff, None, idx1, None, idx2, pbc)
+        d.xyz1, d.xyz2 = fa, fa2
+        d.natoms1 = int(frames.shape[1])
+        d.natoms2 = 0 if f2 is None else int(f2.shape[1])
+        keep += [k1, k3]
+        boxes_ptr = None
+        if box is not None:
+            b = np.asarray(box.get_matrix() if isinstance(box, PeriodicBox) else box, np.float32)
+            if b.ndim == 3:
+                b9 = np.ascontiguousarray(np.transpose(b, (0, 2, 1))).reshape(nframes, 9)      # column-major per frame
+                boxes_ptr = b9.ctypes.data
+                d.box9 = boxes_ptr
+            else:
+                b9 = np.ascontiguousarray(b.reshape(3, 3).T).reshape(9)
+                d.box9 = b9.ctypes.data
+            keep.append(b9)
+        n1 = d.n1 if idx1 is not None else d.natoms1
+        n2 = d.n2 if idx2 is not None else d.natoms2
+        if want_map is None:
+            want_map = group1 is not None
+        if want_occupancy is None:
+            want_occupancy = group1 is not None
+        shape = (int(ngroups1), int(ngroups2) if two else int(ngroups1))
+        deg1 = self._contacts_out(deg1, want_deg, (n1,), frames)
+        deg2 = self._contacts_out(deg2, want_deg and two, (n2,), frames)
+        cmap = self._contacts_out(cmap, want_map, shape, frames)
+        occupancy = self._contacts_out(occupancy, want_occupancy, shape, frames, dtype64=False)
+        g = ContactGroups()
+        (g.group1, g1k), (g.group2, g2k) = _addr(group1), _addr(group2)
+        g.ngroups1, g.ngroups2 = int(ngroups1), int(ngroups2)
+        keep += [g1k, g2k]
+        check(self.lib.molar_hip_search_contacts_frames(self.ctx, C.byref(d), C.byref(g) if group1 is not None else None, nframes, stride,
+                                                        stride2, boxes_ptr, _addr(deg1)[0], _addr(deg2)[0], _addr(cmap)[0],
+                                                        _addr(occupancy)[0]))
+        self._keep = keep
+        return Contacts(None, deg1, deg2, cmap, occupancy)
+
     # ------------------------------------------------------------ surface area
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Per-atom solvent-accessible surface area by Shrake-Rupley (molar_hip_sasa; the definition is in
@@ -1037,6 +1176,16 @@ class FitStream:
             self.close()
         except Exception:
             pass
+
+
+class Contacts:
+    """Result of a contacts call: `count` (entries of the pair list, None when not asked for), `deg1` / `deg2` (per
+    selected atom; deg2 is None for a single-set search, whose deg1 counts both members), `map` (group x group, upper
+    triangle for a single-set search) and, from the frames form, `occupancy` (frames in which a group pair was in
+    contact)."""
+
+    def __init__(self, count, deg1, deg2, cmap, occupancy=None):
+        self.count, self.deg1, self.deg2, self.map, self.occupancy = count, deg1, deg2, cmap, occupancy
 
 
 class Sasa:
@@ -1852,6 +2001,26 @@ def distance_search(cutoff, data1: Sel, data2: Sel | None = None, dims=None):
         n = eng.search_count(SEARCH_SINGLE, cutoff, data1.state.coords, data1.index, box=box, pbc=pbc)
     i, j, d = eng.search_fill_usize(n)
     return np.stack([i, j], 1), d
+
+
+def contacts(cutoff, sel1: Sel, sel2: Sel | None = None, dims=None, groups1=None, groups2=None):
+    """Contact counts of what distance_search(cutoff, sel1, sel2, dims) lists, without the list (same dispatch: any
+    periodic dim -> the _pbc driver, two selections -> DOUBLE).  `groups1` / `groups2`: one label per selected atom
+    (e.g. the residue number); the map has max(label) + 1 groups per side.  Returns a `Contacts` whose ids are positions
+    in the selections."""
+    eng = sel1.engine
+    pbc = pbc_mask(dims)
+    box = sel1.require_box() if pbc else None
+    g1 = None if groups1 is None else np.ascontiguousarray(groups1, np.uint32)
+    g2 = None if groups2 is None else np.ascontiguousarray(groups2, np.uint32)
+    ng1 = 0 if g1 is None else int(g1.max()) + 1
+    if sel2 is not None:
+        if (g1 is None) != (g2 is None):
+            raise ValueError("contacts: labels are needed for both selections or for none")
+        ng2 = 0 if g2 is None else int(g2.max()) + 1
+        return eng.search_contacts(SEARCH_DOUBLE, cutoff, sel1.state.coords, sel1.index, sel2.state.coords, sel2.index, box=box, pbc=pbc,
+                                   group1=g1, ngroups1=ng1, group2=g2, ngroups2=ng2)
+    return eng.search_contacts(SEARCH_SINGLE, cutoff, sel1.state.coords, sel1.index, box=box, pbc=pbc, group1=g1, ngroups1=ng1)
 
 
 def fit_transform(sel1: Sel, sel2: Sel):

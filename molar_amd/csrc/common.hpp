@@ -283,6 +283,13 @@ struct molar_hip_ctx {
     molar_hip_ctx *aux = nullptr;
     mh::DevBuf xh_win[2], xh_bins;
 
+    // molar_hip_search_contacts: a second context on THIS context's stream holds the grid, plan and slot records of the contacts
+    // calls, so the cached search of this one (count -> fill, a held `within` grid) is not disturbed; the buffers below live in it:
+    // staged labels, 64-bit accumulators of outputs that go to host memory [count | deg1 | deg2 | map], the per-frame 32-bit map
+    // of the frames form and the occupancy of a host caller
+    molar_hip_ctx *contacts = nullptr;
+    mh::DevBuf ct_g1, ct_g2, ct_acc, ct_frame, ct_occ;
+
     // ---- profiling (HIP events on `stream`)
     bool profiling = false;
     bool profile_frames = false;   // molar_hip_profile_enable(ctx, 2): ONE span (class 5) around count + offsets + fill of a resident search, none inside

@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "pair_kernels.hpp"
+#include "contact_kernels.hpp"
 #include "stages.hpp"
 #include "unwrap_walk.hpp"
 
@@ -3030,6 +3031,230 @@ int molar_hip_search_histogram_frames(molar_hip_ctx *c, const molar_hip_search_d
         f += (size_t)W;
     }
     return MOLAR_HIP_OK;
+}
+
+}  // extern "C"
+
+// ================================================================= fused contact counts (contact_kernels.hpp, pair_k9.hip)
+//
+// molar_hip_search_contacts / _frames.  The grid, the REGULAR plan and its slot records are those of the count pass
+// (prepare_search with ids_local forced on, so the id an atom carries is its position in the selection); contact_kernel walks
+// the slot list once and adds degrees, map and |L| on chip-summed portions.  All of it runs on a second context that shares
+// this context's stream (molar_hip_ctx::contacts): nothing the caller has cached here - a counted search waiting for its fill,
+// a held `within` grid, the histogram's grid generations - is touched.
+// Outputs in device memory are added into directly; outputs in host memory go through zeroed 64-bit accumulators that are
+// read back and added on the host at the end of the call (of the block, in the frames form).
+// Occupancy (frames form): the kernel adds the frame's map into ONE 32-bit scratch matrix of ngroups1 * ngroups2 words; behind
+// the frame's kernel contact_fold_kernel adds it into the map, counts its non-zero entries into the occupancy and clears it.
+// The frames are walked one after the other on one stream, so the fold of frame k is ordered in front of the kernel of
+// frame k + 1 and one scratch (4 bytes per map entry, 64 MiB at the 2^24 cap) serves the whole block.
+namespace {
+
+__global__ void __launch_bounds__(256) contact_check_labels_kernel(const uint32_t *__restrict__ g, size_t n, uint32_t ngroups, uint32_t *__restrict__ flag) {
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u)
+        if (g[i] >= ngroups) *flag = 1u;
+}
+
+__global__ void __launch_bounds__(256) contact_fold_kernel(uint32_t *__restrict__ frame, size_t n, unsigned long long *__restrict__ map,
+                                                           uint32_t *__restrict__ occ) {
+    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+        const uint32_t v = frame[i];
+        if (v) {
+            if (map) map[i] += v;
+            if (occ) occ[i] += 1u;
+            frame[i] = 0u;
+        }
+    }
+}
+
+struct ContactCall {
+    molar_hip_ctx *s = nullptr;        // the contacts context
+    bool two = false;
+    size_t n1 = 0, n2 = 0, nmap = 0;
+    const uint32_t *g1 = nullptr, *g2 = nullptr;                 // device labels (NULL: no map, no occupancy)
+    size_t ng2 = 0;
+    uint64_t *h_deg1 = nullptr, *h_deg2 = nullptr, *h_map = nullptr;   // caller's HOST outputs (added at the end)
+    uint32_t *h_occ = nullptr;
+    unsigned long long *t_count = nullptr, *t_deg1 = nullptr, *t_deg2 = nullptr, *t_map = nullptr;   // what the kernels add into
+    uint32_t *t_frame = nullptr, *t_occ = nullptr;
+};
+
+constexpr size_t CONTACT_MAP_MAX = (size_t)1 << 24;
+
+// labels of one set: checked (on the host when they are host memory, else by a kernel and a 4-byte read-back), then device-readable
+int contact_labels(molar_hip_ctx *s, const uint32_t *g, size_t n, size_t ngroups, DevBuf &stage, const uint32_t **out, const char *who) {
+    const uint32_t ng = (uint32_t)ngroups;
+    if (!is_device_ptr(g)) {
+        for (size_t i = 0; i < n; ++i)
+            if (g[i] >= ng)
+                return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: label %u of atom %zu is not below ngroups = %zu", who, g[i], i, ngroups);
+        return to_device(s, g, n, stage, out);
+    }
+    *out = g;
+    if (n == 0) return 0;
+    MH_TRY(s->hist.reserve(64));
+    uint32_t *flag = s->hist.as<uint32_t>();
+    MH_HIP(hipMemsetAsync(flag, 0, 4, s->stream));
+    const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
+    hipLaunchKernelGGL(contact_check_labels_kernel, dim3(nb), dim3(256), 0, s->stream, g, n, ng, flag);
+    MH_HIP(hipGetLastError());
+    uint32_t bad = 0;
+    MH_TRY(read_back(s, &bad, flag, 4));
+    if (bad) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = %zu", who, ngroups);
+    return 0;
+}
+
+int contacts_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
+                   uint64_t *map, uint32_t *occ, ContactCall &K, const char *who) {
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (q->kind != MOLAR_HIP_SEARCH_SINGLE && q->kind != MOLAR_HIP_SEARCH_DOUBLE)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: only the SINGLE and DOUBLE kinds have contact counts (got kind %d)", who, q->kind);
+    K.two = q->kind == MOLAR_HIP_SEARCH_DOUBLE;
+    if (!K.two && deg2) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: deg2 must be NULL for a single-set search (deg1 counts both members)", who);
+    if (!q->xyz1 || (K.two && !q->xyz2)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: xyz pointer is null");
+    K.n1 = q->idx1 ? q->n1 : q->natoms1;
+    K.n2 = K.two ? (q->idx2 ? q->n2 : q->natoms2) : 0;
+    const bool want_map = map != nullptr || occ != nullptr;
+    size_t G1 = 0, G2 = 0;
+    if (want_map) {
+        if (!groups || !groups->group1 || (K.two && !groups->group2))
+            return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a map or an occupancy needs group labels", who);
+        G1 = groups->ngroups1;
+        G2 = K.two ? groups->ngroups2 : G1;
+        if (G1 > CONTACT_MAP_MAX || G2 > CONTACT_MAP_MAX || G1 * G2 > CONTACT_MAP_MAX)
+            return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: the map is dense, ngroups1 * ngroups2 may be 2^24 at most (got %zu x %zu)", who, G1, G2);
+        if ((G1 == 0 && K.n1 != 0) || (G2 == 0 && (K.two ? K.n2 : K.n1) != 0))
+            return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = 0", who);
+    }
+    K.nmap = G1 * G2;
+    K.ng2 = G2;
+    MH_HIP(hipSetDevice(c->device));
+    if (!c->contacts) {
+        molar_hip_ctx *s = molar_hip_create(c->device);
+        if (!s) return MOLAR_HIP_ERR_HIP;
+        (void)hipStreamDestroy(s->stream);
+        s->own_stream = false;
+        c->contacts = s;
+    }
+    molar_hip_ctx *s = K.s = c->contacts;
+    s->stream = c->stream;
+    if (want_map && K.nmap) {
+        MH_TRY(contact_labels(s, groups->group1, K.n1, G1, s->ct_g1, &K.g1, who));
+        if (K.two) MH_TRY(contact_labels(s, groups->group2, K.n2, G2, s->ct_g2, &K.g2, who));
+        else K.g2 = K.g1;
+    }
+    // ---- where the sums go
+    const bool d1 = deg1 && !is_device_ptr(deg1), d2 = deg2 && !is_device_ptr(deg2), dm = map && !is_device_ptr(map);
+    const size_t words = 1 + (d1 ? K.n1 : 0) + (d2 ? K.n2 : 0) + (dm ? K.nmap : 0);
+    MH_TRY(s->ct_acc.reserve(words * 8));
+    MH_HIP(hipMemsetAsync(s->ct_acc.p, 0, words * 8, s->stream));
+    unsigned long long *w = s->ct_acc.as<unsigned long long>();
+    K.t_count = w;
+    w += 1;
+    K.t_deg1 = reinterpret_cast<unsigned long long *>(deg1);
+    K.t_deg2 = reinterpret_cast<unsigned long long *>(deg2);
+    K.t_map = reinterpret_cast<unsigned long long *>(map);
+    if (d1) { K.h_deg1 = deg1; K.t_deg1 = w; w += K.n1; }
+    if (d2) { K.h_deg2 = deg2; K.t_deg2 = w; w += K.n2; }
+    if (dm) { K.h_map = map; K.t_map = w; w += K.nmap; }
+    if (occ && K.nmap) {
+        MH_TRY(s->ct_frame.reserve(K.nmap * 4));
+        MH_HIP(hipMemsetAsync(s->ct_frame.p, 0, K.nmap * 4, s->stream));
+        K.t_frame = s->ct_frame.as<uint32_t>();
+        K.t_occ = occ;
+        if (!is_device_ptr(occ)) {
+            MH_TRY(s->ct_occ.reserve(K.nmap * 4));
+            MH_HIP(hipMemsetAsync(s->ct_occ.p, 0, K.nmap * 4, s->stream));
+            K.h_occ = occ;
+            K.t_occ = s->ct_occ.as<uint32_t>();
+        }
+    }
+    return 0;
+}
+
+// one frame: grid, plan, the contact kernel and (frames form with occupancy) the fold - enqueued, nothing waited for beyond what
+// prepare_search itself needs (the bounding box of a non-periodic request is read back)
+int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
+    if (K.n1 == 0 || (K.two && K.n2 == 0)) return 0;
+    molar_hip_ctx *s = K.s;
+    molar_hip_search_desc qq = *q;
+    qq.ids_local = 1;                       // ids are positions in the selection, whatever the caller's list would carry
+    MH_TRY(prepare_search(s, &qq, /*size_masks=*/false));      // (the plan kernel leaves the parameter block in s->params)
+    s->params_fresh = false;
+    if (s->nslots_bound == 0) return 0;
+    ContactArgs A{};
+    A.g1 = K.g1;
+    A.g2 = K.g2;
+    A.ng2 = (uint32_t)K.ng2;
+    A.deg1 = K.t_deg1;
+    A.deg2 = K.two ? K.t_deg2 : K.t_deg1;
+    A.map = K.t_frame ? nullptr : K.t_map;
+    A.map32 = K.t_frame;
+    if (!A.map && !A.map32) A.g1 = A.g2 = nullptr;
+    A.count = K.t_count;
+    {
+        Prof prof(s, 3);
+        launch_contacts(s->kind, (unsigned)s->num_cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)s->nslots_bound, A);
+        MH_HIP(hipGetLastError());
+    }
+    if (K.t_frame) {
+        const unsigned nb = (unsigned)std::min<size_t>((K.nmap + 255) / 256, (size_t)s->num_cus * 16);
+        hipLaunchKernelGGL(contact_fold_kernel, dim3(nb), dim3(256), 0, s->stream, K.t_frame, K.nmap, K.t_map, K.t_occ);
+        MH_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int contacts_end(ContactCall &K, uint64_t *out_count) {
+    molar_hip_ctx *s = K.s;
+    auto add_back = [&](uint64_t *dst, const unsigned long long *src, size_t n) -> int {
+        if (!dst || n == 0) return 0;
+        std::vector<unsigned long long> h(n);
+        MH_TRY(read_back(s, h.data(), src, n * 8));
+        for (size_t i = 0; i < n; ++i) dst[i] += h[i];
+        return 0;
+    };
+    MH_TRY(add_back(K.h_deg1, K.t_deg1, K.n1));
+    MH_TRY(add_back(K.h_deg2, K.t_deg2, K.n2));
+    MH_TRY(add_back(K.h_map, K.t_map, K.nmap));
+    if (K.h_occ && K.nmap) {
+        std::vector<uint32_t> h(K.nmap);
+        MH_TRY(read_back(s, h.data(), K.t_occ, K.nmap * 4));
+        for (size_t i = 0; i < K.nmap; ++i) K.h_occ[i] += h[i];
+    }
+    if (out_count) {
+        unsigned long long tot = 0;
+        MH_TRY(read_back(s, &tot, K.t_count, 8));
+        *out_count = tot;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int molar_hip_search_contacts(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
+                              uint64_t *map, uint64_t *out_count) {
+    ContactCall K;
+    MH_TRY(contacts_begin(c, q, groups, deg1, deg2, map, nullptr, K, "search_contacts"));
+    MH_TRY(contacts_frame(K, q));
+    return contacts_end(K, out_count);
+}
+
+int molar_hip_search_contacts_frames(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, size_t nframes,
+                                     size_t xyz1_stride, size_t xyz2_stride, const float *boxes9, uint64_t *deg1, uint64_t *deg2, uint64_t *map,
+                                     uint32_t *occupancy) {
+    ContactCall K;
+    MH_TRY(contacts_begin(c, q, groups, deg1, deg2, map, occupancy, K, "search_contacts_frames"));
+    for (size_t f = 0; f < nframes; ++f) {
+        molar_hip_search_desc qf = *q;
+        qf.xyz1 = q->xyz1 + f * xyz1_stride;
+        if (q->xyz2) qf.xyz2 = q->xyz2 + f * xyz2_stride;
+        if (boxes9) qf.box9 = boxes9 + 9 * f;
+        MH_TRY(contacts_frame(K, &qf));
+    }
+    return contacts_end(K, nullptr);
 }
 
 int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uint64_t *out_count) {

@@ -172,6 +172,37 @@ fn check_index(index: Option<&[usize]>, natoms: usize, what: &str) -> Result<(),
     Ok(())
 }
 
+// Contact counts: the engine adds into `deg*` at every selected position and into `map` at every pair of labels, so the
+// slices must cover exactly that (labels2 None: a single-set request, the map is ngroups1 x ngroups1).
+#[allow(clippy::too_many_arguments)]
+fn check_contact_outputs(
+    what: &str, nsel1: usize, deg1: Option<&[u64]>, labels1: Option<(&[u32], usize)>, labels2: Option<(&[u32], usize)>, nsel2: usize,
+    deg2: Option<&[u64]>, map: Option<&[u64]>,
+) -> Result<Option<MolarHipContactGroups>, EngineError> {
+    if deg1.is_some_and(|d| d.len() != nsel1) || deg2.is_some_and(|d| d.len() != nsel2) {
+        return Err(EngineError::Sizes(format!("{what}: a degree array must have one entry per selected atom")));
+    }
+    let Some((l1, g1)) = labels1 else {
+        if map.is_some() {
+            return Err(EngineError::Sizes(format!("{what}: a map needs labels")));
+        }
+        return Ok(None);
+    };
+    let (l2, g2) = labels2.unwrap_or((l1, g1));
+    if l1.len() != nsel1 || (labels2.is_some() && l2.len() != nsel2) {
+        return Err(EngineError::Sizes(format!("{what}: one label per selected atom is needed")));
+    }
+    if l1.iter().any(|&l| l as usize >= g1) || l2.iter().any(|&l| l as usize >= g2) {
+        return Err(EngineError::Sizes(format!("{what}: a label is not below the number of groups")));
+    }
+    if map.is_some_and(|m| Some(m.len()) != g1.checked_mul(g2)) {
+        return Err(EngineError::Sizes(format!("{what}: the map must have ngroups1 x ngroups2 = {g1} x {g2} entries")));
+    }
+    Ok(Some(MolarHipContactGroups {
+        group1: l1.as_ptr(), ngroups1: g1, group2: if labels2.is_some() { l2.as_ptr() } else { std::ptr::null() }, ngroups2: if labels2.is_some() { g2 } else { 0 },
+    }))
+}
+
 fn check_column(len: usize, natoms: usize, what: &str) -> Result<(), EngineError> {
     // per-atom columns (masses) are gathered through the index: they must cover the whole frame
     if len < natoms {
@@ -503,6 +534,62 @@ impl Engine {
         self.plugin.check(unsafe {
             (self.plugin.fns.apply_transform_f64)(self.ctx, coords.as_mut_ptr() as *mut f64, coords.len(), ip, n, r.as_ptr(), t.as_ptr())
         })
+    }
+
+    /// Contact counts of `distance_search_single(_pbc)` (f32) without the list (`molar_hip_search_contacts`): `deg[p]` += the
+    /// entries with selected atom `p` (a position in the selection) as either member, and, with `labels` (one per selected
+    /// atom, each below `ngroups`), `map[min(g_a, g_b) * ngroups + max(g_a, g_b)]` += 1 per entry (a, b).  Both are added
+    /// into; the counts include the reference list's duplicates (header).  Returns the number of entries.
+    pub fn contacts_single(
+        &self, cutoff: f32, coords: &[[f32; 3]], index: Option<&[usize]>, box9: Option<&[f32; 9]>, pbc: u8, deg: Option<&mut [u64]>,
+        labels: Option<(&[u32], usize)>, map: Option<&mut [u64]>,
+    ) -> Result<u64, EngineError> {
+        check_index(index, coords.len(), "contacts_single")?;
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { coords.len() };
+        let g = check_contact_outputs("contacts_single", nsel, deg.as_deref(), labels, None, 0, None, map.as_deref())?;
+        let d = MolarHipSearchDesc {
+            kind: SEARCH_SINGLE, cutoff, xyz1: coords.as_ptr() as *const f32, natoms1: coords.len(), idx1: ip, n1: n,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let mut count = 0u64;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.search_contacts)(self.ctx, &d, g.as_ref().map_or(std::ptr::null(), |g| g as *const MolarHipContactGroups),
+                                              deg.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()), std::ptr::null_mut(),
+                                              map.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()), &mut count)
+        })?;
+        Ok(count)
+    }
+
+    /// The same for `distance_search_double(_pbc)`: `deg1[p]` += entries with first member `p`, `deg2[p]` += entries with
+    /// second member `p`, `map[g1_a * ngroups2 + g2_b]` += 1.
+    pub fn contacts_double(
+        &self, cutoff: f32, coords1: &[[f32; 3]], index1: Option<&[usize]>, coords2: &[[f32; 3]], index2: Option<&[usize]>,
+        box9: Option<&[f32; 9]>, pbc: u8, deg1: Option<&mut [u64]>, deg2: Option<&mut [u64]>, labels1: Option<(&[u32], usize)>,
+        labels2: Option<(&[u32], usize)>, map: Option<&mut [u64]>,
+    ) -> Result<u64, EngineError> {
+        check_index(index1, coords1.len(), "contacts_double (set 1)")?;
+        check_index(index2, coords2.len(), "contacts_double (set 2)")?;
+        let (i1, n1) = idx_ptr(index1);
+        let (i2, n2) = idx_ptr(index2);
+        let nsel1 = if index1.is_some() { n1 } else { coords1.len() };
+        let nsel2 = if index2.is_some() { n2 } else { coords2.len() };
+        if labels1.is_some() != labels2.is_some() {
+            return Err(EngineError::Sizes("contacts_double: labels are needed for both sets or for none".into()));
+        }
+        let g = check_contact_outputs("contacts_double", nsel1, deg1.as_deref(), labels1, labels2, nsel2, deg2.as_deref(), map.as_deref())?;
+        let d = MolarHipSearchDesc {
+            kind: SEARCH_DOUBLE, cutoff, xyz1: coords1.as_ptr() as *const f32, natoms1: coords1.len(), idx1: i1, n1,
+            xyz2: coords2.as_ptr() as *const f32, natoms2: coords2.len(), idx2: i2, n2,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let mut count = 0u64;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.search_contacts)(self.ctx, &d, g.as_ref().map_or(std::ptr::null(), |g| g as *const MolarHipContactGroups),
+                                              deg1.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()), deg2.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()),
+                                              map.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()), &mut count)
+        })?;
+        Ok(count)
     }
 
     /// The fused radial distance histogram in f64: the pairs of `distance_search_single(_pbc)` with Float = f64, each

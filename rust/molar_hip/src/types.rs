@@ -61,6 +61,22 @@ impl Default for MolarHipSearchDesc {
     }
 }
 
+/// `molar_hip_contact_groups`: group labels of the contact-count calls, one per SELECTED atom of each set.
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct MolarHipContactGroups {
+    pub group1: *const u32,
+    pub ngroups1: usize,
+    pub group2: *const u32,
+    pub ngroups2: usize,
+}
+
+impl Default for MolarHipContactGroups {
+    fn default() -> Self {
+        unsafe { std::mem::zeroed() }
+    }
+}
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]

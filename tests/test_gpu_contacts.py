@@ -1,0 +1,415 @@
+"""The fused contact counts (molar_hip_search_contacts / _frames, contact_kernels.hpp) against the ORACLE's pair list folded
+by numpy (tests/contacts_ref.py).  Everything is an integer and compared with np.array_equal: no tolerances.  The list keeps
+the reference's duplicates (same-cell cross pairs of the two-set search, repeated cell pairs of tiny periodic grids), and
+so do the counts."""
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import contacts_ref as cr  # noqa: E402
+
+from molar_amd import synth  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+INVALID_ARGUMENT, TOO_LARGE = 50, 51       # MOLAR_HIP_ERR_*
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from molar_amd import build
+    from molar_amd.api import Engine
+    build.build_library()
+    return Engine(0)
+
+
+def api():
+    import molar_amd.api as a
+    return a
+
+
+def default_labels(n):
+    """pos // 3; frames of more than 12 288 selected atoms: pos // ceil(n / 4096), so the map stays below the 2^24 cap"""
+    k = 3 if n <= 12288 else math.ceil(n / 4096)
+    g = (np.arange(n) // k).astype(np.uint32)
+    return g, int(g.max()) + 1
+
+
+_REFS = {}
+
+
+def ref_single(orc32, boxname, n, cutoff, pbc, frame_no=0, stride=1):
+    """(pos, box, oracle list with local ids) of one single-set case; computed once per module"""
+    key = ("s", boxname, n, cutoff, pbc, frame_no, stride)
+    if key not in _REFS:
+        if boxname is None:
+            box = None
+            pos = synth.frame(n, synth.box_ortho(n), frame_no)
+            sel = pos[::stride]
+            ref = orc32.search_single(cutoff, sel, nthreads=8)
+        else:
+            box = getattr(synth, boxname)(n)
+            pos = synth.frame(n, box, frame_no)
+            sel = pos[::stride]
+            ref = orc32.search_single_pbc(cutoff, sel, orc32.box_from_matrix(box), pbc, nthreads=8)
+        _REFS[key] = (pos, box, ref)
+    return _REFS[key]
+
+
+def check_single(c, ref, n, g=None, G=0, times=1):
+    count, deg, m = cr.single(ref, n, g, G)
+    if c.count is not None:
+        assert c.count == count
+    if c.deg1 is not None:
+        assert np.array_equal(np.asarray(c.deg1, np.uint64), times * deg)
+        assert int(np.asarray(c.deg1).sum()) == 2 * times * count
+    assert c.deg2 is None
+    if g is not None and c.map is not None:
+        assert np.array_equal(np.asarray(c.map, np.uint64), times * m)
+    return count, deg, m
+
+
+# ---------------------------------------------------------------- 1. every class of plan entry, SINGLE
+
+@pytest.mark.parametrize("boxname,n,cutoff,pbc", [
+    ("box_ortho", 4000, 0.45, 7),
+    ("box_a", 20000, 0.8, 7),          # band-classified wrapped entries, triclinic corner entries
+    ("box_b", 6000, 0.5, 7),           # hexagonal prism: the reference's incomplete grid
+    ("box_a", 3000, 0.5, 1),           # partial pbc on a triclinic box: no band classification, dropped atoms
+    ("box_ortho", 3000, 0.5, 3),       # z not periodic
+    (None, 5000, 0.6, 0),              # no box
+    ("box_a", 30000, 2.1, 7),          # grid (2, 2, 3): duplicates of the small grid, cells against their own image, second cells of ~900 atoms
+])
+def test_single_entry_classes(eng, orc32, boxname, n, cutoff, pbc):
+    a = api()
+    pos, box, ref = ref_single(orc32, boxname, n, cutoff, pbc)
+    g, G = default_labels(n)
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=pbc, group1=g, ngroups1=G)
+    count, _, m = check_single(c, ref, n, g, G)
+    assert count > 0 and int(m.sum()) == count
+    if (boxname, n) == ("box_a", 30000):
+        assert ref["dims"] == (2, 2, 3)
+
+
+# ---------------------------------------------------------------- 2. DOUBLE
+
+@pytest.mark.parametrize("with_box", [True, False])
+def test_double_overlapping_selections(eng, orc32, with_box):
+    a = api()
+    n = 6000
+    box = synth.box_a(n)
+    pos = synth.frame(n, box)
+    idx1, idx2 = np.arange(0, 3000, dtype=np.uint64), np.arange(2000, 6000, dtype=np.uint64)
+    p1, p2 = pos[:3000], pos[2000:]
+    if with_box:
+        ref = orc32.search_double_pbc(0.5, p1, p2, orc32.box_from_matrix(box), 7, nthreads=4)
+    else:
+        ref = orc32.search_double(0.5, p1, p2, nthreads=4)
+    g1, G1 = default_labels(3000)
+    g2, G2 = cr.ragged_labels(4000)
+    count, deg1, deg2, m = cr.double(ref, 3000, 4000, g1, G1, g2, G2)
+    assert count > 0
+    c = eng.search_contacts(a.SEARCH_DOUBLE, 0.5, pos, idx1, pos, idx2, box=box if with_box else None, pbc=7 if with_box else 0,
+                            group1=g1, ngroups1=G1, group2=g2, ngroups2=G2)
+    assert c.count == count
+    assert np.array_equal(c.deg1, deg1) and np.array_equal(c.deg2, deg2)
+    assert c.map.shape == (G1, G2) and np.array_equal(c.map, m)
+    assert int(c.deg1.sum()) == int(c.deg2.sum()) == int(c.map.sum()) == count
+
+
+# ---------------------------------------------------------------- 3. label patterns
+
+def test_label_patterns(eng, orc32):
+    a = api()
+    n, cutoff = 20000, 0.8
+    pos, box, ref = ref_single(orc32, "box_a", n, cutoff, 7)
+    # one group: the one entry is |L|
+    g = np.zeros(n, np.uint32)
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=1, want_deg=False)
+    assert c.deg1 is None and c.map.shape == (1, 1) and int(c.map[0, 0]) == c.count == len(ref["i"])
+    # ragged groups of 1..40 atoms
+    g, G = cr.ragged_labels(n)
+    check_single(eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G), ref, n, g, G)
+    # no locality at all: the pos // 5 labels, permuted
+    g, G = default_labels(n)
+    g = np.random.default_rng(11).permutation(g)
+    check_single(eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G), ref, n, g, G)
+
+
+def test_one_group_per_atom(eng, orc32):
+    a = api()
+    n = 3000
+    pos, box, ref = ref_single(orc32, "box_a", n, 0.5, 7)
+    g = np.arange(n, dtype=np.uint32)
+    c = eng.search_contacts(a.SEARCH_SINGLE, 0.5, pos, box=box, pbc=7, group1=g, ngroups1=n)
+    assert c.map.shape == (n, n)
+    check_single(c, ref, n, g, n)
+
+
+def test_strided_selection(eng, orc32):
+    a = api()
+    n, cutoff = 20000, 0.8
+    pos, box, ref = ref_single(orc32, "box_a", n, cutoff, 7, stride=2)
+    idx = np.arange(0, n, 2, dtype=np.uint64)
+    g, G = default_labels(len(idx))
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, idx, box=box, pbc=7, group1=g, ngroups1=G)
+    check_single(c, ref, len(idx), g, G)
+
+
+# ---------------------------------------------------------------- 4. call forms
+
+def test_call_forms(eng, orc32):
+    import torch
+    a = api()
+    n, cutoff = 6000, 0.5
+    pos, box, ref = ref_single(orc32, "box_a", n, cutoff, 7)
+    g, G = default_labels(n)
+    count, deg, m = cr.single(ref, n, g, G)
+    # host arrays, twice into the same arrays
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G)
+    check_single(c, ref, n, g, G)
+    c2 = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G, deg1=c.deg1, cmap=c.map)
+    assert c2.deg1 is c.deg1 and c2.map is c.map
+    check_single(c2, ref, n, g, G, times=2)
+    # degrees only (no labels), map only, count only
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7)
+    assert c.map is None and c.count == count and np.array_equal(c.deg1, deg)
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G, want_deg=False)
+    assert c.deg1 is None and np.array_equal(c.map, m)
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, want_deg=False, want_map=False)
+    assert c.deg1 is None and c.map is None and c.count == count
+    # device tensors in and out, no count: the call does not wait
+    dpos = torch.from_numpy(pos).cuda()
+    dg = torch.from_numpy(g.astype(np.int32)).cuda()
+    ddeg = torch.full((n,), 5, dtype=torch.int64, device="cuda")
+    dmap = torch.zeros((G, G), dtype=torch.int64, device="cuda")
+    for _ in range(2):
+        c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, dpos, box=box, pbc=7, group1=dg, ngroups1=G, deg1=ddeg, cmap=dmap, want_count=False)
+    assert c.count is None
+    eng.synchronize()
+    assert np.array_equal(ddeg.cpu().numpy().astype(np.uint64), 2 * deg + 5)
+    assert np.array_equal(dmap.cpu().numpy().astype(np.uint64), 2 * m)
+    # device coordinates, outputs made by the call: CUDA tensors
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, dpos, box=box, pbc=7, group1=dg, ngroups1=G)
+    assert c.deg1.is_cuda and c.map.is_cuda and c.count == count
+    assert np.array_equal(c.deg1.cpu().numpy().astype(np.uint64), deg) and np.array_equal(c.map.cpu().numpy().astype(np.uint64), m)
+
+
+def test_module_level_contacts(orc32):
+    a = api()
+    n = 6000
+    pos, box, ref = ref_single(orc32, "box_a", n, 0.5, 7)
+    top = a.Topology(np.ones(n, np.float32))
+    st = a.State(pos.copy(), a.PeriodicBox.from_matrix(box))
+    g, G = default_labels(n)
+    c = a.contacts(0.5, a.Sel(top, st), dims=[True, True, True], groups1=g)
+    check_single(c, ref, n, g, G)
+    s1, s2 = a.Sel(top, st, np.arange(0, 3000)), a.Sel(top, st, np.arange(2000, 6000))
+    refd = orc32.search_double(0.5, pos[:3000], pos[2000:], nthreads=4)
+    c = a.contacts(0.5, s1, s2)
+    count, deg1, deg2, _ = cr.double(refd, 3000, 4000)
+    assert c.count == count and np.array_equal(c.deg1, deg1) and np.array_equal(c.deg2, deg2) and c.map is None
+
+
+# ---------------------------------------------------------------- 5. frames
+
+FR_N, FR_CUT, FR_NF = 6000, 0.5, 17
+
+
+@pytest.fixture(scope="module")
+def frames_ref(orc32):
+    """17 frames of box_a / 6000 at 0.5, labels pos // 3: per-frame folds of the oracle's lists"""
+    box = synth.box_a(FR_N)
+    ob = orc32.box_from_matrix(box)
+    g, G = default_labels(FR_N)
+    frames = np.stack([synth.frame(FR_N, box, f) for f in range(FR_NF)])
+    folds = [cr.single(orc32.search_single_pbc(FR_CUT, frames[f], ob, 7, nthreads=8), FR_N, g, G) for f in range(FR_NF)]
+    return box, frames, g, G, folds
+
+
+def expect_frames(folds, sel):
+    deg = sum(folds[f][1] for f in sel)
+    m = sum(folds[f][2] for f in sel)
+    occ = cr.occupancy([folds[f][2] for f in sel])
+    return deg, m, occ
+
+
+def test_frames_device_host_and_strided(eng, frames_ref):
+    import torch
+    a = api()
+    box, frames, g, G, folds = frames_ref
+    deg, m, occ = expect_frames(folds, range(FR_NF))
+    # checked on the CPU for this shape: some group pairs touch in some frames only, others in all of them
+    assert np.any((occ > 0) & (occ < FR_NF)) and np.any(occ == FR_NF)
+    # device memory, contiguous
+    dfr = torch.from_numpy(frames).cuda()
+    dg = torch.from_numpy(g.astype(np.int32)).cuda()
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, dfr, box=box, pbc=7, group1=dg, ngroups1=G)
+    eng.synchronize()
+    assert c.occupancy.dtype == torch.int32
+    assert np.array_equal(c.deg1.cpu().numpy().astype(np.uint64), deg)
+    assert np.array_equal(c.map.cpu().numpy().astype(np.uint64), m)
+    assert np.array_equal(c.occupancy.cpu().numpy().astype(np.uint32), occ)
+    # device memory, a gap between the frames
+    store = torch.zeros((FR_NF, FR_N + 37, 3), dtype=torch.float32, device="cuda")
+    store[:, :FR_N] = dfr
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, store[:, :FR_N], box=box, pbc=7, group1=dg, ngroups1=G)
+    eng.synchronize()
+    assert np.array_equal(c.deg1.cpu().numpy().astype(np.uint64), deg)
+    assert np.array_equal(c.map.cpu().numpy().astype(np.uint64), m)
+    assert np.array_equal(c.occupancy.cpu().numpy().astype(np.uint32), occ)
+    # host memory; occupancy without a map, accumulated into a caller's array
+    occ0 = np.full((G, G), 2, np.uint32)
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, frames, box=box, pbc=7, group1=g, ngroups1=G, want_map=False, occupancy=occ0)
+    assert c.map is None and c.occupancy is occ0
+    assert np.array_equal(c.deg1, deg) and np.array_equal(occ0, occ + 2)
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, frames, box=box, pbc=7, group1=g, ngroups1=G)
+    assert np.array_equal(c.deg1, deg) and np.array_equal(c.map, m) and np.array_equal(c.occupancy, occ)
+
+
+def test_frames_one_frame_and_per_frame_boxes(eng, orc32, frames_ref):
+    a = api()
+    box, frames, g, G, folds = frames_ref
+    deg, m, occ = expect_frames(folds, [3])
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, frames[3:4], box=box, pbc=7, group1=g, ngroups1=G)
+    assert np.array_equal(c.deg1, deg) and np.array_equal(c.map, m) and np.array_equal(c.occupancy, occ)
+    # every frame in a box of its own (scaled, with its coordinates)
+    scales = np.array([1.0, 1.03, 0.97, 1.05], np.float32)
+    boxes = np.stack([box * s for s in scales]).astype(np.float32)
+    fr = np.stack([(frames[k] * scales[k]).astype(np.float32) for k in range(4)])
+    per = [cr.single(orc32.search_single_pbc(FR_CUT, fr[k], orc32.box_from_matrix(boxes[k]), 7, nthreads=8), FR_N, g, G) for k in range(4)]
+    deg, m, occ = expect_frames(per, range(4))
+    c = eng.search_contacts_frames(a.SEARCH_SINGLE, FR_CUT, fr, box=boxes, pbc=7, group1=g, ngroups1=G)
+    assert np.array_equal(c.deg1, deg) and np.array_equal(c.map, m) and np.array_equal(c.occupancy, occ)
+
+
+def test_frames_double_with_its_own_second_set(eng, orc32, frames_ref):
+    import torch
+    a = api()
+    box, frames, g, G, _ = frames_ref
+    nf, n2 = 5, 2500
+    ob = orc32.box_from_matrix(box)
+    fr2 = np.stack([synth.frame(n2, box, 40 + f) for f in range(nf)])
+    idx1 = np.arange(0, FR_N, 2, dtype=np.uint64)
+    g1, G1 = default_labels(len(idx1))
+    g2, G2 = cr.ragged_labels(n2)
+    per = [cr.double(orc32.search_double_pbc(FR_CUT, frames[f][::2], fr2[f], ob, 7, nthreads=8), len(idx1), n2, g1, G1, g2, G2) for f in range(nf)]
+    deg1, deg2, m = sum(p[1] for p in per), sum(p[2] for p in per), sum(p[3] for p in per)
+    occ = cr.occupancy([p[3] for p in per])
+    assert np.any((occ > 0) & (occ < nf))
+    for dev in (False, True):
+        f1, f2, i1 = frames[:nf], fr2, idx1
+        l1, l2 = g1, g2
+        if dev:
+            f1, f2 = torch.from_numpy(np.ascontiguousarray(f1)).cuda(), torch.from_numpy(f2).cuda()
+            i1 = torch.from_numpy(idx1.astype(np.int64)).cuda()
+            l1, l2 = torch.from_numpy(g1.astype(np.int32)).cuda(), torch.from_numpy(g2.astype(np.int32)).cuda()
+        c = eng.search_contacts_frames(a.SEARCH_DOUBLE, FR_CUT, f1, idx1=i1, box=box, pbc=7, frames2=f2, group1=l1, ngroups1=G1,
+                                       group2=l2, ngroups2=G2)
+        eng.synchronize()
+        got = [np.asarray(x.cpu().numpy() if dev else x) for x in (c.deg1, c.deg2, c.map, c.occupancy)]
+        assert np.array_equal(got[0].astype(np.uint64), deg1) and np.array_equal(got[1].astype(np.uint64), deg2)
+        assert np.array_equal(got[2].astype(np.uint64), m) and np.array_equal(got[3].astype(np.uint32), occ)
+
+
+# ---------------------------------------------------------------- 6. refusals
+
+def test_refusals(eng):
+    import ctypes as C
+    a = api()
+    from molar_amd._lib import ContactGroups, MolarHipError
+    n = 3000
+    box = synth.box_a(n)
+    pos = synth.frame(n, box)
+    g, G = default_labels(n)
+
+    def code(fn):
+        with pytest.raises(MolarHipError) as e:
+            fn()
+        return e.value.code
+
+    radii = np.full(n, 0.15, np.float32)
+    assert code(lambda: eng.search_contacts(a.SEARCH_WITHIN, 0.5, pos, None, pos, None, box=box, pbc=7)) == INVALID_ARGUMENT
+    d, keep = eng._search_desc(a.SEARCH_DOUBLE_VDW, None, pos, None, pos, None, box, 7, radii, radii, False, None, None)
+    cnt = C.c_uint64(0)
+    assert eng.lib.molar_hip_search_contacts(eng.ctx, C.byref(d), None, None, None, None, C.byref(cnt)) == INVALID_ARGUMENT
+    # deg2 with SINGLE
+    assert code(lambda: eng.search_contacts(a.SEARCH_SINGLE, 0.5, pos, box=box, pbc=7, deg2=np.zeros(n, np.uint64))) == INVALID_ARGUMENT
+    # a map / an occupancy without labels
+    assert code(lambda: eng.search_contacts(a.SEARCH_SINGLE, 0.5, pos, box=box, pbc=7, cmap=np.zeros((G, G), np.uint64))) == INVALID_ARGUMENT
+    assert code(lambda: eng.search_contacts_frames(a.SEARCH_SINGLE, 0.5, pos[None], box=box, pbc=7,
+                                                   occupancy=np.zeros((G, G), np.uint32))) == INVALID_ARGUMENT
+    assert code(lambda: eng.search_contacts(a.SEARCH_DOUBLE, 0.5, pos, None, pos, None, box=box, pbc=7, group1=g, ngroups1=G,
+                                            cmap=np.zeros((G, G), np.uint64))) == INVALID_ARGUMENT          # no labels for set 2
+    # a dense map of more than 2^24 entries
+    d, keep = eng._search_desc(a.SEARCH_SINGLE, 0.5, pos, None, None, None, box, 7, None, None, False, None, None)
+    gg = ContactGroups()
+    gg.group1, gg.ngroups1 = g.ctypes.data, 4097
+    one = np.zeros(1, np.uint64)
+    assert eng.lib.molar_hip_search_contacts(eng.ctx, C.byref(d), C.byref(gg), None, None, one.ctypes.data, None) == TOO_LARGE
+    # a label >= ngroups, host and device labels, single and frames form: nothing at all is added
+    import torch
+    bad = g.copy()
+    bad[n - 7] = G
+    for labels in (bad, torch.from_numpy(bad.astype(np.int32)).cuda()):
+        deg = np.arange(1, n + 1, dtype=np.uint64)
+        m = np.full((G, G), 3, np.uint64)
+        occ = np.full((G, G), 9, np.uint32)
+        deg0, m0, occ0 = deg.copy(), m.copy(), occ.copy()
+        assert code(lambda: eng.search_contacts(a.SEARCH_SINGLE, 0.5, pos, box=box, pbc=7, group1=labels, ngroups1=G, deg1=deg, cmap=m)) == INVALID_ARGUMENT
+        assert code(lambda: eng.search_contacts_frames(a.SEARCH_SINGLE, 0.5, pos[None], box=box, pbc=7, group1=labels, ngroups1=G, deg1=deg,
+                                                       cmap=m, occupancy=occ)) == INVALID_ARGUMENT
+        assert np.array_equal(deg, deg0) and np.array_equal(m, m0) and np.array_equal(occ, occ0)
+    ddeg = torch.arange(1, n + 1, dtype=torch.int64, device="cuda")
+    dm = torch.full((G, G), 3, dtype=torch.int64, device="cuda")
+    assert code(lambda: eng.search_contacts(a.SEARCH_SINGLE, 0.5, torch.from_numpy(pos).cuda(), box=box, pbc=7,
+                                            group1=torch.from_numpy(bad.astype(np.int32)).cuda(), ngroups1=G, deg1=ddeg, cmap=dm)) == INVALID_ARGUMENT
+    eng.synchronize()
+    assert np.array_equal(ddeg.cpu().numpy(), np.arange(1, n + 1)) and bool((dm == 3).all())
+    # ... and the context still works
+    c = eng.search_contacts(a.SEARCH_SINGLE, 0.5, pos, box=box, pbc=7, group1=g, ngroups1=G)
+    assert int(c.map.sum()) == c.count > 0
+
+
+# ---------------------------------------------------------------- 7. neighbours on the context
+
+def test_neighbours_on_the_context(eng, orc32):
+    a = api()
+    n, cutoff = 6000, 0.5
+    pos, box, ref = ref_single(orc32, "box_a", n, cutoff, 7)
+    g, G = default_labels(n)
+    other = synth.frame(4000, synth.box_ortho(4000))          # the contacts calls in between work on another system
+    og, oG = default_labels(4000)
+    oref = orc32.search_single_pbc(0.45, other, orc32.box_from_matrix(synth.box_ortho(4000)), 7, nthreads=4)
+
+    def contacts_other():
+        c = eng.search_contacts(a.SEARCH_SINGLE, 0.45, other, box=synth.box_ortho(4000), pbc=7, group1=og, ngroups1=oG)
+        check_single(c, oref, 4000, og, oG)
+
+    # between search_count and search_fill: the counted search is still the cached one
+    cnt = eng.search_count(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7)
+    contacts_other()
+    pairs, dist = eng.search_fill(cnt)
+    assert cnt == len(ref["i"])
+    assert np.array_equal(pairs[:, 0].astype(np.uint64), ref["i"]) and np.array_equal(pairs[:, 1].astype(np.uint64), ref["j"])
+    assert np.array_equal(dist, ref["d"])
+    # between two histogram calls
+    nb = 50
+    want = orc32.histogram_add(0.0, cutoff, nb, ref["d"]).astype(np.uint64)
+    bins, c1 = eng.search_histogram(a.SEARCH_SINGLE, cutoff, 0.0, cutoff, nb, pos, box=box, pbc=7)
+    contacts_other()
+    bins, c2 = eng.search_histogram(a.SEARCH_SINGLE, cutoff, 0.0, cutoff, nb, pos, box=box, pbc=7, bins=bins)
+    assert c1 == c2 == len(ref["i"]) and np.array_equal(bins, 2 * want)
+    # after a within_set
+    idx2 = np.arange(0, 300, dtype=np.uint64)
+    wref = np.unique(orc32.search_within_pbc(cutoff, pos, pos[:300], orc32.box_from_matrix(box), 7)["i"])
+    ids = eng.within_set(cutoff, pos, None, pos, idx2, box=box, pbc=7)
+    assert np.array_equal(ids, wref)
+    c = eng.search_contacts(a.SEARCH_SINGLE, cutoff, pos, box=box, pbc=7, group1=g, ngroups1=G)
+    check_single(c, ref, n, g, G)
+    ids = eng.within_set(cutoff, pos, None, pos, idx2, box=box, pbc=7)
+    assert np.array_equal(ids, wref)
