@@ -527,6 +527,47 @@ int molar_hip_sasa_vol_frames(molar_hip_ctx *ctx, const float *frames, size_t nf
                               const uint64_t *idx, size_t n, const float *vdw, float probe, uint32_t npoints, float *areas,
                               double *totals, float *volumes, double *total_volumes);
 
+/* ---- All-pairs minimum RMSD over the frames of a block, or of one block against another: out[a][b] is the rmsd_mw of frame
+ * a after the mass-weighted fit_transform onto frame b (measure.rs:507-522 with :538-558; with unit masses the fit followed by
+ * rmsd, :485-504), for every pair at once from one Gram product on the f64 matrix cores instead of one fit_rmsd_batch call per
+ * reference frame.  Frame f of a block is at frames + f * frame_stride (elements, >= 3 natoms, as for molar_hip_sasa_frames).
+ * Operation by operation (Real = float, or double for _f64; everything below is formed and accumulated in double from the
+ * exact inputs, only the result is rounded to Real):
+ *   selection idx[0..n), shared by all frames; idx == NULL: atoms 0 .. n-1.  w_k = mass[idx[k]] (mass: one per ATOM, >= 0);
+ *   mass == NULL: w_k = 1.  W = sum_k w_k.
+ *   fit != 0:  c_f = sum_k w_k p_f,k / W,  x_f,k = p_f,k - c_f,  q_f,k = sqrt(w_k) x_f,k,  G_f = sum_k |q_f,k|^2,
+ *     C_ab = sum_k q_a,k q_b,k^T (3x3),  lambda = largest eigenvalue of Horn's 4x4 matrix of C_ab (the maximum of
+ *     sum_k w_k (R x_a,k) . x_b,k over PROPER rotations R: a mirror image does not give 0),
+ *     out[a][b] = sqrt(max(0, (G_a + G_b) - 2 lambda) / W).
+ *   fit == 0:  no superposition, out[a][b] = sqrt(sum_k w_k |p_a,k - p_b,k|^2 / W), by the same route with trace(C_ab) in
+ *     place of lambda and ONE origin in place of the centres: c_0 of the first block (if that frame holds a non-finite
+ *     coordinate, the first finite centre of the first block).
+ *   All sums have a fixed order that depends on the sizes alone (no floating-point atomics): the same call gives the same bits.
+ *   The products of the Gram matrix are the matrix cores' (v_mfma_f64_16x16x4_f64), so results are bounded, not fixed
+ *   bit for bit:  |out^2 - exact^2| <= (3 n + 16) 2^-53 (G_a + G_b) / W + 4 eps exact^2, eps = 2^-24 (2^-53 for _f64).
+ * frames2 == NULL (symmetric form): out is [nframes1][ld] over the pairs of block 1; only pairs with b >= a are computed and
+ *   each is stored twice, so out[a][b] == out[b][a] bit for bit, and out[a][a] is exactly 0.  nframes2 / frame_stride2 are
+ *   not read.
+ * frames2 != NULL (rectangular form): block 1 against block 2, out is [nframes1][ld] with nframes2 columns used (the rest of a
+ *   row is not touched); both blocks share natoms, idx and mass.  frames2 == frames1 is still the rectangular form.
+ * frames, idx, mass and out may each be host or device memory.  A device `out` is written on the context's stream and not
+ * waited for (the call itself waits once, early, for the 16 bytes that decide its status).
+ * Errors: n == 0 or ld below the column count: ERR_SIZES; W == 0: ERR_ZERO_MASS; an index not below natoms, n > natoms without
+ * an index, a stride below 3 natoms: ERR_INVALID_ARGUMENT; a workspace that cannot be allocated: ERR_TOO_LARGE with the byte
+ * count in molar_hip_last_error().  nframes1 == 0 (or nframes2 == 0 in the rectangular form) is a successful no-op.  A frame
+ * with a non-finite selected coordinate gives NaN in its row and column (its diagonal entry included) and leaves every other
+ * entry as it would be without that frame; the status stays MOLAR_HIP_OK.
+ * molar_hip_rmsd_matrix_plan is a pure host function: the bytes of device workspace such a call allocates (kept by the
+ * context and reused; staging of host-memory arguments not included; never smaller for a larger argument) and the number of
+ * workgroups the atom dimension is split over (1: the finish is fused into the Gram kernel).  nframes2 == 0: symmetric. */
+int molar_hip_rmsd_matrix_plan(size_t nframes1, size_t nframes2, size_t n, size_t *workspace_bytes, uint32_t *ksplits);
+int molar_hip_rmsd_matrix(molar_hip_ctx *ctx, const float *frames1, size_t nframes1, size_t frame_stride1,
+                          const float *frames2, size_t nframes2, size_t frame_stride2, size_t natoms, const uint64_t *idx,
+                          size_t n, const float *mass, int fit, float *out, size_t ld);
+int molar_hip_rmsd_matrix_f64(molar_hip_ctx *ctx, const double *frames1, size_t nframes1, size_t frame_stride1,
+                              const double *frames2, size_t nframes2, size_t frame_stride2, size_t natoms,
+                              const uint64_t *idx, size_t n, const double *mass, int fit, double *out, size_t ld);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

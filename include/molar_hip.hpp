@@ -459,6 +459,35 @@ inline IsometryMatrix3 fit_transform_at_origin(const SelBound &s1, const SelBoun
     return tr;
 }
 
+// All-pairs minimum RMSD over trajectory frames (molar_hip_rmsd_matrix; the definition: molar_hip.h): rmsd_mw after the
+// mass-weighted fit_transform of every frame onto every other one, for the selection's atoms and masses.  `frames` holds
+// whole frames one after the other (sel.natoms() positions each).  One block: the symmetric [F][F] matrix, row by row,
+// exactly symmetric with a zero diagonal.  Two blocks: [F1][F2] of the first against the second.  fit = false: no
+// superposition; mass_weighted = false: unit weights (the fit followed by rmsd).
+inline std::vector<Float> rmsd_matrix(const SelBound &sel, const std::vector<Pos> &frames, const std::vector<Pos> *frames2 = nullptr,
+                                      bool fit = true, bool mass_weighted = true) {
+    const size_t natoms = sel.natoms();
+    if (natoms == 0 || frames.size() % natoms || (frames2 && frames2->size() % natoms))
+        throw MolarError(MOLAR_HIP_ERR_SIZES, "rmsd_matrix: a block is not a whole number of frames");
+    const size_t F1 = frames.size() / natoms, F2 = frames2 ? frames2->size() / natoms : 0, cols = frames2 ? F2 : F1;
+    std::vector<Float> out(F1 * cols);
+    if (out.empty()) return out;
+    check(molar_hip_rmsd_matrix(sel.ctx(), &frames[0].x, F1, natoms * 3, frames2 ? &(*frames2)[0].x : nullptr, F2, natoms * 3, natoms,
+                                sel.get_index_slice().data(), sel.len(), mass_weighted ? sel.masses() : nullptr, fit ? 1 : 0, out.data(), cols));
+    return out;
+}
+// the same on f64 frames and masses (MolAR's f64 feature): molar_hip_rmsd_matrix_f64; mass: one per atom, or null; an empty
+// index means every atom
+inline std::vector<double> rmsd_matrix_f64(Engine &eng, const double *frames, size_t nframes, const double *frames2, size_t nframes2,
+                                           size_t natoms, const std::vector<usize> &index, const double *mass, bool fit = true) {
+    const size_t cols = frames2 ? nframes2 : nframes;
+    std::vector<double> out(nframes * cols);
+    if (out.empty()) return out;
+    check(molar_hip_rmsd_matrix_f64(eng.ctx(), frames, nframes, natoms * 3, frames2, nframes2, natoms * 3, natoms,
+                                    index.empty() ? nullptr : index.data(), index.empty() ? natoms : index.size(), mass, fit ? 1 : 0, out.data(), cols));
+    return out;
+}
+
 // The per-frame fit of an AnalysisTask whose States live in host memory (analysis_task.rs:245-252 hands them over frame by frame),
 // at the rate the SELECTION crosses the link: molar_hip_fit_stream_*.  Built on the selection and the reference once;
 //     auto t1 = fs.begin(state_k1.coords);  FitRecord r = fs.end(t0);      // up to three frames in flight

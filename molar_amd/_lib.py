@@ -184,6 +184,9 @@ SYMBOLS = {
     "molar_hip_sasa_vol": (_I, [_P, _P, _SZ, _P, _SZ, _P, _F, C.c_uint32, _P, _P, _P, _P, _P]),
     "molar_hip_sasa_vol_f64": (_I, [_P, _P, _SZ, _P, _SZ, _P, C.c_double, C.c_uint32, _P, _P, _P, _P, _P]),
     "molar_hip_sasa_vol_frames": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _F, C.c_uint32, _P, _P, _P, _P]),
+    "molar_hip_rmsd_matrix_plan": (_I, [_SZ, _SZ, _SZ, _P, _P]),
+    "molar_hip_rmsd_matrix": (_I, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _I, _P, _SZ]),
+    "molar_hip_rmsd_matrix_f64": (_I, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _I, _P, _SZ]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

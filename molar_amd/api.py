@@ -1130,6 +1130,17 @@ class Engine:
                                                 com.ctypes.data, gy.ctypes.data))
         return dict(rmsd=rm, R=R.reshape(F, 3, 3).transpose(0, 2, 1).copy(), t=t, com=com, gyration=gy)
 
+    def rmsd_matrix(self, frames, idx=None, mass=None, frames2=None, fit=True, out=None):
+        """All-pairs minimum RMSD (molar_hip_rmsd_matrix): frames [F, natoms, 3] float32, numpy or torch CUDA (rows may be
+        strided: frames[::2] or a wider last-but-one stride are read in place).  out[a][b] = mass-weighted RMSD of frame a
+        fitted onto frame b (`mass`: one per atom, None: unit weights; `idx`: the selection, None: every atom; fit=False: no
+        superposition).  frames2=None: the symmetric [F, F] matrix, exactly symmetric with a zero diagonal; otherwise
+        [F, F2] of `frames` against `frames2`.  numpy in, numpy out; torch CUDA in, torch CUDA out, written on the ENGINE's
+        stream and not waited for: `Engine.synchronize()` before torch reads it (the call waits for torch's current stream
+        first, and for its own kernels only when it had to copy an argument to make it contiguous).
+        `out`: an optional [F, >= columns] destination of the same kind."""
+        return _rmsd_matrix_call(self.lib, self.lib.molar_hip_rmsd_matrix, self.ctx, frames, idx, mass, frames2, fit, out, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -1237,6 +1248,86 @@ def _sasa_call(fn, ctx, xyz, vdw, idx, probe, npoints, want_exposed, real, want_
     check(fn(ctx, xa, natoms, ia, n, va, probe, int(npoints), aa if n else None, ea if n else None, C.byref(total), oa if n else None,
              C.byref(total_volume)))
     return Sasa(areas, float(total.value), exposed, volumes, float(total_volume.value))
+
+
+def rmsd_matrix_plan(nframes1, nframes2, n):
+    """(workspace_bytes, ksplits) of an rmsd_matrix call of these sizes (molar_hip_rmsd_matrix_plan; nframes2 = 0: the
+    symmetric form).  A host function: no GPU is needed."""
+    ws, ks = C.c_size_t(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_rmsd_matrix_plan(int(nframes1), int(nframes2), int(n), C.addressof(ws), C.addressof(ks)))
+    return int(ws.value), int(ks.value)
+
+
+def _frame_block(x, real):
+    """(array, F, natoms, frame stride in elements) of frames [F, natoms, 3]; read in place when each frame is contiguous."""
+    if _is_torch(x):
+        import torch
+        assert x.dtype == (torch.float32 if real == np.float32 else torch.float64) and x.ndim == 3 and x.shape[2] == 3
+        inner = x.stride(2) == 1 and x.stride(1) == 3              # each frame contiguous (a single frame too: a transposed view is not)
+        ok = inner and (x.shape[0] <= 1 or x.stride(0) >= 3 * x.shape[1])
+        if not ok:
+            x = x.contiguous()
+        stride = x.stride(0) if x.shape[0] > 1 else 3 * x.shape[1]
+        return x, x.shape[0], x.shape[1], stride
+    x = np.asarray(x)
+    assert x.ndim == 3 and x.shape[2] == 3
+    e = np.dtype(real).itemsize
+    ok = x.dtype == real and (x.shape[0] <= 1 or (x.strides[2] == e and x.strides[1] == 3 * e and x.strides[0] >= 3 * e * x.shape[1]
+                                                  and x.strides[0] % e == 0))
+    if not ok or (x.shape[0] <= 1 and not x.flags.c_contiguous):
+        x = np.ascontiguousarray(x, dtype=real)
+    stride = x.strides[0] // e if x.shape[0] > 1 else 3 * x.shape[1]
+    return x, x.shape[0], x.shape[1], stride
+
+
+def _rmsd_matrix_call(lib, fn, ctx, frames, idx, mass, frames2, fit, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr1, F1, natoms, st1 = _frame_block(frames, real)
+    dev = _is_torch(fr1)
+    fr2, F2, st2 = None, 0, 0
+    if frames2 is not None:
+        fr2, F2, natoms2, st2 = _frame_block(frames2, real)
+        assert natoms2 == natoms and _is_torch(fr2) == dev, "both blocks have the same atoms and live on the same side"
+    cols = F1 if fr2 is None else F2
+    idx_in, mass_in = idx, mass
+    idx = _u64(idx); mass = conv(mass)
+    n = natoms if idx is None else idx.shape[0]
+    if mass is not None:
+        assert mass.shape[0] == natoms, "one mass per atom"
+    if out is None:
+        if dev:
+            import torch
+            out = torch.zeros((F1, cols), dtype=fr1.dtype, device=fr1.device)
+        else:
+            out = np.zeros((F1, cols), real)
+    else:
+        assert _is_torch(out) == dev and out.ndim == 2 and out.shape[0] >= F1
+        if dev:
+            assert out.dtype == fr1.dtype and (out.shape[1] == 0 or out.stride(1) == 1)
+        else:
+            assert out.dtype == real and (out.shape[1] == 0 or out.strides[1] == out.itemsize)
+    if dev:
+        ld = out.stride(0) if out.shape[0] > 1 else out.shape[1]
+        oa = out.data_ptr()
+    else:
+        ld = out.strides[0] // out.itemsize if out.shape[0] > 1 else out.shape[1]
+        oa = out.ctypes.data
+    if F1 > 0 and cols > 0 and out.shape[1] < cols:
+        ld = out.shape[1]                       # too narrow: the library reports it
+    a1 = fr1.data_ptr() if dev else fr1.ctypes.data
+    a2 = None if fr2 is None else (fr2.data_ptr() if dev else fr2.ctypes.data)
+    if fr2 is not None and not a2:
+        a2 = a1                                 # an empty second block still means the rectangular form
+    ia, k1 = _addr(idx); ma, k2 = _addr(mass)
+    if dev:
+        # torch made `out` and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, a1, F1, st1, a2, F2, st2, natoms, ia, n, ma, 1 if fit else 0, oa, ld))
+    if dev and (fr1 is not frames or fr2 is not frames2 or idx is not idx_in or mass is not mass_in):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return out
 
 
 def _f64(x):
@@ -1378,6 +1469,10 @@ class MeasureF64:
                                                     1 if apply else 0, rm.ctypes.data, R.ctypes.data, t.ctypes.data,
                                                     com.ctypes.data, gy.ctypes.data))
         return dict(rmsd=rm, R=R.reshape(F, 3, 3).transpose(0, 2, 1).copy(), t=t, com=com, gyration=gy)
+
+    def rmsd_matrix(self, frames, idx=None, mass=None, frames2=None, fit=True, out=None):
+        """Engine.rmsd_matrix on float64 frames and masses (molar_hip_rmsd_matrix_f64): float64 results."""
+        return _rmsd_matrix_call(self.lib, self.lib.molar_hip_rmsd_matrix_f64, self.ctx, frames, idx, mass, frames2, fit, out, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

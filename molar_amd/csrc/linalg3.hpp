@@ -198,6 +198,105 @@ __host__ __device__ inline bool horn_dominant_eigenvector(const double *K, doubl
     return res <= 1e-20 * f2 * best;
 }
 
+// Horn's key matrix of S[a][b] = sum w x1[a] x2[b] (row-major S[a*3+b]); its largest eigenvalue is the maximum of
+// sum w (R x1) . x2 over proper rotations R, the same for S and for its transpose.
+__host__ __device__ inline void horn_matrix(const double *S, double *K) {
+    const double Sxx = S[0], Sxy = S[1], Sxz = S[2], Syx = S[3], Syy = S[4], Syz = S[5], Szx = S[6], Szy = S[7], Szz = S[8];
+    const double Nm[16] = {(Sxx + Syy) + Szz, Syz - Szy,         Szx - Sxz,          Sxy - Syx,
+                           Syz - Szy,         (Sxx - Syy) - Szz, Sxy + Syx,          Szx + Sxz,
+                           Szx - Sxz,         Sxy + Syx,         (Syy - Sxx) - Szz,  Syz + Szy,
+                           Sxy - Syx,         Szx + Sxz,         Syz + Szy,          (Szz - Sxx) - Syy};
+#pragma unroll
+    for (int i = 0; i < 16; ++i) K[i] = Nm[i];
+}
+
+// s + a b with the rounding errors of the product and of the sum collected in `err` (Ogita, Rump and Oishi's Dot2): the
+// explicit fma gives the product's error exactly, and -ffp-contract=off keeps the rest as written
+__host__ __device__ inline void dot2_step(double a, double b, double &s, double &err) {
+    const double p = a * b, e = fma(a, b, -p);
+    const double t = s + p, z = t - s;
+    err += ((s - (t - z)) + (p - z)) + e;
+    s = t;
+}
+
+// Rayleigh quotient v^T K v / v^T v of a symmetric 4x4 in twice the working precision: for an eigenvector good to d it
+// is the eigenvalue to d^2 |K| plus a few 2^-53 of the eigenvalue itself, whatever the other eigenvalues are
+__host__ __device__ inline double rayleigh4(const double *K, double v0, double v1, double v2, double v3) {
+    const double v[4] = {v0, v1, v2, v3};
+    double num = 0.0, nerr = 0.0, den = 0.0, derr = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double y = 0.0, yerr = 0.0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dot2_step(K[i * 4 + j], v[j], y, yerr);
+        dot2_step(v[i], y, num, nerr);
+        nerr += v[i] * yerr;
+        dot2_step(v[i], v[i], den, derr);
+    }
+    return (num + nerr) / (den + derr);
+}
+
+// Largest eigenvalue of Horn's symmetric, traceless 4x4 matrix K, for callers that need no rotation: the
+// Newton iteration of horn_dominant_eigenvector on the characteristic polynomial, accepted only where the root is well
+// conditioned.  A rounding error e in the polynomial's value moves the root by e / P'(l), and both the coefficients and
+// Horner's scheme carry a few 2^-53 of M = l^4 + |c2| l^2 + |c1| l + |c0|: the root is taken when M <= 2 l P'(l), which
+// keeps it within a few 2^-53 of l (an isotropic covariance has M = 0.84 l P').  Multiple or close roots (planar and
+// collinear selections, a mirror image) fail that test or the iteration itself and go to Jacobi sweeps at f64 working
+// precision for the eigenvector, whatever the gaps.
+__host__ __device__ inline double horn_lambda_max(const double *K) {
+    double K2[16], f2 = 0.0, t3 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s += K[i * 4 + k] * K[k * 4 + j];
+            K2[i * 4 + j] = s;
+        }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        f2 += K[i] * K[i];
+        t3 += K2[i] * K[i];
+    }
+    if (f2 == 0.0) return 0.0;
+    if (f2 > 0.0 && f2 <= 1.7976931348623157e308) {
+        const double det = K[0] * minor3(K, 1, 2, 3, 1, 2, 3) - K[1] * minor3(K, 1, 2, 3, 0, 2, 3) +
+                           K[2] * minor3(K, 1, 2, 3, 0, 1, 3) - K[3] * minor3(K, 1, 2, 3, 0, 1, 2);
+        const double c2 = -0.5 * f2, c1 = -t3 / 3.0, c0 = det;
+        double l = sqrt(f2);
+        for (int it = 0; it < 60; ++it) {
+            const double l2 = l * l;
+            const double P = (l2 + c2) * l2 + (c1 * l + c0);
+            const double dP = (4.0 * l2 + 2.0 * c2) * l + c1;
+            if (!(dP > 0.0)) break;                   // at or beyond a multiple root
+            const double step = P / dP;
+            l -= step;
+            if (fabs(step) <= 1e-15 * fabs(l)) {
+                const double m2 = l * l;
+                const double M = (m2 + fabs(c2)) * m2 + (fabs(c1) * l + fabs(c0));
+                const double dQ = (4.0 * m2 + 2.0 * c2) * l + c1;
+                if (M <= 2.0 * l * dQ) return l;
+                break;
+            }
+        }
+    }
+    // Jacobi's own eigenvalues carry the roundings of every rotation (up to a hundred 2^-53 |K| were seen on two-atom
+    // frames); its eigenvector is good to about as much, and the Rayleigh quotient on the untouched matrix squares that
+    double A[16], w[4], v[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) A[i] = K[i];
+    jacobi_sym<4>(A, w, v, 1e-34);
+    double wb = w[0], q0 = v[0], q1 = v[4], q2 = v[8], q3 = v[12];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+        if (w[i] > wb) {
+            wb = w[i];
+            q0 = v[0 * 4 + i]; q1 = v[1 * 4 + i]; q2 = v[2 * 4 + i]; q3 = v[3 * 4 + i];
+        }
+    return rayleigh4(K, q0, q1, q2, q3);
+}
+
 // cov(r,c) = sum m * q2[r] * q1[c]  (measure.rs:621-623), column-major cov[c*3+r].
 // Writes R (column-major) with q2 ~ R q1.  Returns false if cov holds a non-finite entry (NaN or +-inf: the callers
 // report MOLAR_HIP_ERR_SVD) or if no unit quaternion comes out of the eigen-solve.

@@ -756,6 +756,51 @@ impl Engine {
         })?;
         Ok(out)
     }
+
+    /// All-pairs minimum RMSD through molar_hip_rmsd_matrix: `rmsd_mw` after the mass-weighted `fit_transform`
+    /// (measure.rs:507-522 with :538-558) of every frame of `frames` onto every other one (`frames2` None: the symmetric
+    /// matrix, exactly symmetric with a zero diagonal) or onto every frame of `frames2`.  A block holds its frames one after the
+    /// other, `natoms` positions each; `masses` None: unit weights; `fit` false: no superposition.  Returns the matrix row by
+    /// row, `frames.len() / natoms` rows.
+    #[allow(clippy::too_many_arguments)]
+    pub fn rmsd_matrix(
+        &self, frames: &[[f32; 3]], frames2: Option<&[[f32; 3]]>, natoms: usize, index: Option<&[usize]>, masses: Option<&[f32]>, fit: bool,
+    ) -> Result<Vec<f32>, EngineError> {
+        check_index(index, natoms, "rmsd_matrix")?;
+        if natoms == 0 || frames.len() % natoms != 0 || frames2.is_some_and(|f| f.len() % natoms != 0) {
+            return Err(EngineError::Sizes(format!("rmsd_matrix: a block is not a whole number of frames of {natoms} atoms")));
+        }
+        if let Some(m) = masses {
+            check_column(m.len(), natoms, "rmsd_matrix: masses")?;
+        }
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { natoms };
+        if nsel == 0 {
+            return Err(EngineError::Sizes("rmsd_matrix: empty selection".into()));
+        }
+        let f1 = frames.len() / natoms;
+        let f2 = frames2.map_or(0, |f| f.len() / natoms);
+        let cols = if frames2.is_some() { f2 } else { f1 };
+        let mut out = vec![0f32; f1 * cols];
+        if out.is_empty() {
+            return Ok(out);
+        }
+        let p2 = frames2.map_or(std::ptr::null(), |f| f.as_ptr() as *const f32);
+        let mp = masses.map_or(std::ptr::null(), |m| m.as_ptr());
+        self.plugin.check(unsafe {
+            (self.plugin.fns.rmsd_matrix)(self.ctx, frames.as_ptr() as *const f32, f1, natoms * 3, p2, f2, natoms * 3, natoms, ip, nsel, mp,
+                                          fit as i32, out.as_mut_ptr(), cols)
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and the number of splits of the atom dimension an `rmsd_matrix` call of these sizes uses
+    /// (molar_hip_rmsd_matrix_plan, a host function; `nframes2` 0: the symmetric form).
+    pub fn rmsd_matrix_plan(&self, nframes1: usize, nframes2: usize, n: usize) -> Result<(usize, u32), EngineError> {
+        let (mut ws, mut ks) = (0usize, 0u32);
+        self.plugin.check(unsafe { (self.plugin.fns.rmsd_matrix_plan)(nframes1, nframes2, n, &mut ws, &mut ks) })?;
+        Ok((ws, ks))
+    }
 }
 
 /// What one frame of a streamed fit returns: `fit_transform` (measure.rs:507-522) as (R column-major, t), and RMSD / centre of
