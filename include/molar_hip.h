@@ -568,6 +568,55 @@ int molar_hip_rmsd_matrix_f64(molar_hip_ctx *ctx, const double *frames1, size_t 
                               const double *frames2, size_t nframes2, size_t frame_stride2, size_t natoms,
                               const uint64_t *idx, size_t n, const double *mass, int fit, double *out, size_t ld);
 
+/* ---- Fluctuations of a block of trajectory frames about their mean structure: the mean, the per-atom RMSF and the 3n x 3n
+ * positional covariance (the input of a principal-component analysis), after an optional mass-weighted fit of every frame
+ * onto a reference, in one call instead of fit_rmsd_batch(apply) on a copy of the block followed by reductions.  Frame f is
+ * at frames + f * frame_stride (elements, >= 3 natoms), as for molar_hip_rmsd_matrix.  Operation by operation (Real = float,
+ * or double for _f64; everything below is formed and accumulated in double from the exact inputs, only the results are
+ * rounded to Real; F = nframes):
+ *   selection idx[0..n), shared by all frames; idx == NULL: atoms 0 .. n-1.  w_k = mass[idx[k]] (mass: one per ATOM, >= 0);
+ *   mass == NULL: w_k = 1.  W = sum_k w_k.  c_f = sum_k w_k x_f,k / W.
+ *   reference r_k: ref[k] (the selected atoms packed, [n][3]); ref == NULL: x_0,k.  c_ref = sum_k w_k r_k / W, y_k = r_k - c_ref.
+ *   fit != 0:  R_f = the proper rotation that minimises sum_k w_k |R (x_f,k - c_f) - y_k|^2: the dominant eigenvector of
+ *     Horn's 4x4 matrix of S_f = sum_k w_k (x_f,k - c_f) y_k^T by Jacobi sweeps at f64 working precision, as a rotation
+ *     matrix, followed by one Newton step R <- R + R (I - R^T R) / 2 (R^T R = I to a few 2^-53).  z_f,k = R_f (x_f,k - c_f) + c_ref;  t_f = c_ref - R_f c_f, so that p' = R p + t is fit_rmsd_batch's convention.
+ *     Where the optimal rotation is not unique (n < 3, collinear selections) any optimal proper rotation is a correct answer.
+ *   fit == 0:  z_f,k = x_f,k.  Internally every frame is taken about ONE origin, c_0 (if frame 0 holds a non-finite coordinate,
+ *     the first finite c_f), so that the cancellation below happens at the scale of the structure.
+ *   mean_k = (1/F) sum_f z_f,k;  rmsf_k = sqrt((1/F) sum_f |z_f,k - mean_k|^2);
+ *   cov[3k+d][3l+e] = (1/F) sum_f (z_f,k,d - mean_k,d) (z_f,l,e - mean_l,e):  two passes - the mean is finished first and
+ *     the deviations are taken about it, never E[z z] - m m.  Unweighted, in nm and nm^2 (the mass-weighted covariance is a
+ *     row and column scaling).  Atoms of zero weight still get their mean, rmsf and covariance.
+ *   iterations = I > 0 (fit != 0 only; ignored otherwise): after a pass its mean, kept in f64 on the device, becomes the
+ *     reference and the frames are fitted again: 1 + I passes, the outputs are those of the last one.
+ *   fit_out[f] = {R_f (9, column-major), t_f (3), sqrt(sum_k w_k |z_f,k - r_k|^2 / W)} against the reference of the last
+ *     pass, the distance by the Gram route (sum w |x - c_f|^2 + sum w |y|^2 - 2 sum w (R x) . y).  fit == 0: R = I, t = 0 and
+ *     the distance of the frame as it stands.
+ *   cov is computed on the f64 matrix cores (v_mfma_f64_16x16x4_f64, K = frames) for the tiles on and above the diagonal and
+ *     every entry is stored twice: cov[i][j] == cov[j][i] bit for bit.  cov is [3n][ld], ld >= 3n; the rest of a row is not
+ *     touched.
+ *   All sums have a fixed order that depends on the sizes alone (no floating-point atomics): the same call gives the same bits.
+ * Every output (mean [n][3], rmsf [n], cov, fit_out [nframes][13]) may be NULL and is then not computed; frames, idx, mass,
+ * ref and every output may each be host or device memory.  Device outputs are written on the context's stream and not waited
+ * for (the call itself waits once, early, for the 16 bytes that decide its status).
+ * Errors: n == 0, or cov != NULL with ld below 3n: ERR_SIZES; W == 0: ERR_ZERO_MASS; an index not below natoms, n > natoms
+ * without an index, a stride below 3 natoms (with more than one frame: the stride of a single frame is not read, as for
+ * molar_hip_rmsd_matrix), iterations < 0: ERR_INVALID_ARGUMENT; a workspace or a covariance that cannot be allocated, more
+ * than 65535 * 4096 selected atoms, a covariance of more than 65532 * 16 coordinates: ERR_TOO_LARGE with the byte count in molar_hip_last_error().  nframes == 0 is a successful no-op.  A frame with a
+ * non-finite selected coordinate gives NaN in its own fit_out row and in every entry of mean, rmsf and cov that it enters
+ * (with a fit: all of them); the status stays MOLAR_HIP_OK and nothing is read back for it.
+ * molar_hip_fluct_plan is a pure host function: the bytes of device workspace such a call allocates (kept by the context,
+ * grows only; staging of host-memory arguments not included; never smaller for a larger argument, and never larger without
+ * the covariance than with it) and the number of workgroups the frames of the covariance are split over (1: the scaling and
+ * the mirrored store are fused into the covariance kernel; always 1 with want_cov == 0). */
+int molar_hip_fluct_plan(size_t nframes, size_t n, int want_cov, size_t *workspace_bytes, uint32_t *ksplits);
+int molar_hip_fluct(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                    const uint64_t *idx, size_t n, const float *mass, const float *ref, int fit, int iterations, float *mean,
+                    float *rmsf, float *cov, size_t ld, float *fit_out);
+int molar_hip_fluct_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                        const uint64_t *idx, size_t n, const double *mass, const double *ref, int fit, int iterations,
+                        double *mean, double *rmsf, double *cov, size_t ld, double *fit_out);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

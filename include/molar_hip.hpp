@@ -488,6 +488,54 @@ inline std::vector<double> rmsd_matrix_f64(Engine &eng, const double *frames, si
     return out;
 }
 
+// Fluctuations of a block of frames about their mean structure (molar_hip_fluct; the definition: molar_hip.h): the mean, the
+// per-atom RMSF and, on request, the 3n x 3n positional covariance after the mass-weighted fit of every frame of `frames`
+// (whole frames one after the other, sel.natoms() positions each) onto `ref` (the selected atoms, sel.len() positions; null:
+// frame 0), iterated `iterations` times onto the mean.  fit = false: the frames as they stand; mass_weighted = false: unit
+// weights.  `fit` of the result holds, per frame, R (9, column-major), t (3) and the RMSD to the last reference.
+template <class Real>
+struct FluctuationsOf {
+    std::vector<Real> mean;       // [n][3]
+    std::vector<Real> rmsf;       // [n]
+    std::vector<Real> cov;        // [3n][3n], empty unless asked for
+    std::vector<Real> fit;        // [F][13], empty unless asked for
+};
+using Fluctuations = FluctuationsOf<Float>;
+inline Fluctuations fluctuations(const SelBound &sel, const std::vector<Pos> &frames, const std::vector<Pos> *ref = nullptr, bool fit = true,
+                                 int iterations = 0, bool want_cov = false, bool want_fit = false, bool mass_weighted = true) {
+    const size_t natoms = sel.natoms(), n = sel.len();
+    if (natoms == 0 || frames.size() % natoms) throw MolarError(MOLAR_HIP_ERR_SIZES, "fluctuations: the block is not a whole number of frames");
+    if (ref && ref->size() != n) throw MolarError(MOLAR_HIP_ERR_SIZES, "fluctuations: the reference holds one position per selected atom");
+    const size_t F = frames.size() / natoms;
+    Fluctuations out;
+    if (F == 0) return out;
+    out.mean.resize(3 * n);
+    out.rmsf.resize(n);
+    if (want_cov) out.cov.resize(9 * n * n);
+    if (want_fit) out.fit.resize(13 * F);
+    check(molar_hip_fluct(sel.ctx(), &frames[0].x, F, natoms * 3, natoms, sel.get_index_slice().data(), n, mass_weighted ? sel.masses() : nullptr,
+                          ref ? &(*ref)[0].x : nullptr, fit ? 1 : 0, iterations, out.mean.data(), out.rmsf.data(), want_cov ? out.cov.data() : nullptr,
+                          3 * n, want_fit ? out.fit.data() : nullptr));
+    return out;
+}
+// the same on f64 frames, masses and reference (MolAR's f64 feature): molar_hip_fluct_f64; mass: one per atom, or null; ref: the
+// selected atoms packed, or null; an empty index means every atom
+inline FluctuationsOf<double> fluctuations_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const std::vector<usize> &index,
+                                               const double *mass, const double *ref = nullptr, bool fit = true, int iterations = 0,
+                                               bool want_cov = false, bool want_fit = false) {
+    const size_t n = index.empty() ? natoms : index.size();
+    FluctuationsOf<double> out;
+    if (nframes == 0) return out;
+    out.mean.resize(3 * n);
+    out.rmsf.resize(n);
+    if (want_cov) out.cov.resize(9 * n * n);
+    if (want_fit) out.fit.resize(13 * nframes);
+    check(molar_hip_fluct_f64(eng.ctx(), frames, nframes, natoms * 3, natoms, index.empty() ? nullptr : index.data(), n, mass, ref, fit ? 1 : 0,
+                              iterations, out.mean.data(), out.rmsf.data(), want_cov ? out.cov.data() : nullptr, 3 * n,
+                              want_fit ? out.fit.data() : nullptr));
+    return out;
+}
+
 // The per-frame fit of an AnalysisTask whose States live in host memory (analysis_task.rs:245-252 hands them over frame by frame),
 // at the rate the SELECTION crosses the link: molar_hip_fit_stream_*.  Built on the selection and the reference once;
 //     auto t1 = fs.begin(state_k1.coords);  FitRecord r = fs.end(t0);      // up to three frames in flight

@@ -187,6 +187,9 @@ SYMBOLS = {
     "molar_hip_rmsd_matrix_plan": (_I, [_SZ, _SZ, _SZ, _P, _P]),
     "molar_hip_rmsd_matrix": (_I, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _I, _P, _SZ]),
     "molar_hip_rmsd_matrix_f64": (_I, [_P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _I, _P, _SZ]),
+    "molar_hip_fluct_plan": (_I, [_SZ, _SZ, _I, _P, _P]),
+    "molar_hip_fluct": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "molar_hip_fluct_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

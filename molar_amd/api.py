@@ -11,6 +11,7 @@ Arrays may be numpy (host) or torch CUDA tensors (device-resident, used in place
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import numpy as np
@@ -1141,6 +1142,18 @@ class Engine:
         `out`: an optional [F, >= columns] destination of the same kind."""
         return _rmsd_matrix_call(self.lib, self.lib.molar_hip_rmsd_matrix, self.ctx, frames, idx, mass, frames2, fit, out, np.float32)
 
+    def fluctuations(self, frames, idx=None, mass=None, ref=None, fit=True, iterations=0, cov=False, fit_out=False, out=None):
+        """Mean structure, per-atom RMSF and (cov=True) the 3n x 3n positional covariance of frames [F, natoms, 3] float32 about
+        their mean, after the mass-weighted fit of every frame onto `ref` ([n, 3], the selected atoms; None: frame 0) - with
+        iterations=I the mean of a pass becomes the reference of the next, 1 + I passes (molar_hip_fluct; the definition:
+        molar_hip.h).  `mass`: one per atom, None: unit weights; `idx`: the selection, None: every atom; fit=False: the frames
+        as they stand.  Statistics are unweighted, two-pass and formed in float64.  fit_out=True also returns, per frame,
+        R (9, column-major), t (3) and the weighted RMSD to the reference of the last pass.  Returns
+        Fluctuations(mean [n, 3], rmsf [n], cov [3n, 3n] or None, fit [F, 13] or None): numpy in, numpy out; torch CUDA in,
+        torch CUDA out, written on the ENGINE's stream and not waited for (`Engine.synchronize()` before torch reads them).
+        `out`: an optional Fluctuations (or 4-tuple) of destinations of the same kind; None entries are allocated."""
+        return _fluct_call(self.lib, self.lib.molar_hip_fluct, self.ctx, frames, idx, mass, ref, fit, iterations, cov, fit_out, out, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -1258,6 +1271,14 @@ def rmsd_matrix_plan(nframes1, nframes2, n):
     return int(ws.value), int(ks.value)
 
 
+def fluct_plan(nframes, n, want_cov=True):
+    """(workspace_bytes, ksplits) of a fluctuations call of these sizes (molar_hip_fluct_plan).  A host function: no GPU is
+    needed."""
+    ws, ks = C.c_size_t(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_fluct_plan(int(nframes), int(n), 1 if want_cov else 0, C.addressof(ws), C.addressof(ks)))
+    return int(ws.value), int(ks.value)
+
+
 def _frame_block(x, real):
     """(array, F, natoms, frame stride in elements) of frames [F, natoms, 3]; read in place when each frame is contiguous."""
     if _is_torch(x):
@@ -1328,6 +1349,50 @@ def _rmsd_matrix_call(lib, fn, ctx, frames, idx, mass, frames2, fit, out, real):
         # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
         check(lib.molar_hip_synchronize(ctx))
     return out
+
+
+Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
+
+
+def _fluct_call(lib, fn, ctx, frames, idx, mass, ref, fit, iterations, cov, fit_out, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    idx_in, mass_in, ref_in = idx, mass, ref
+    idx = _u64(idx); mass = conv(mass); ref = conv(ref)
+    n = natoms if idx is None else idx.shape[0]
+    if mass is not None:
+        assert mass.shape[0] == natoms, "one mass per atom"
+    if ref is not None:
+        assert tuple(ref.shape) == (n, 3), "ref holds the selected atoms, [n, 3]"
+    want = (True, True, bool(cov), bool(fit_out))
+    shapes = ((n, 3), (n,), (3 * n, 3 * n), (F, 13))
+    given = tuple(out) if out is not None else (None,) * 4
+    res = []
+    for w, shape, g in zip(want, shapes, given):
+        if not w:
+            res.append(None)
+        elif g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape
+            assert (g.dtype == fr.dtype and g.is_contiguous()) if dev else (g.dtype == real and g.flags.c_contiguous)
+            res.append(g)
+        elif dev:
+            import torch
+            res.append(torch.zeros(shape, dtype=fr.dtype, device=fr.device))
+        else:
+            res.append(np.zeros(shape, real))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ia, k1 = _addr(idx); ma, k2 = _addr(mass); ra, k3 = _addr(ref)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ia, n, ma, ra, 1 if fit else 0, int(iterations), addr[0], addr[1], addr[2], 3 * n, addr[3]))
+    if dev and (fr is not frames or idx is not idx_in or mass is not mass_in or ref is not ref_in):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return Fluctuations(*res)
 
 
 def _f64(x):
@@ -1473,6 +1538,10 @@ class MeasureF64:
     def rmsd_matrix(self, frames, idx=None, mass=None, frames2=None, fit=True, out=None):
         """Engine.rmsd_matrix on float64 frames and masses (molar_hip_rmsd_matrix_f64): float64 results."""
         return _rmsd_matrix_call(self.lib, self.lib.molar_hip_rmsd_matrix_f64, self.ctx, frames, idx, mass, frames2, fit, out, np.float64)
+
+    def fluctuations(self, frames, idx=None, mass=None, ref=None, fit=True, iterations=0, cov=False, fit_out=False, out=None):
+        """Engine.fluctuations on float64 frames, masses and reference (molar_hip_fluct_f64): float64 results."""
+        return _fluct_call(self.lib, self.lib.molar_hip_fluct_f64, self.ctx, frames, idx, mass, ref, fit, iterations, cov, fit_out, out, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

@@ -122,6 +122,7 @@ struct GridSet {
 struct molar_hip_search64_state;        // the cached f64 search (search_f64.hip)
 struct molar_hip_sasa_state;            // point tables, grid and scratch of the surface-area calls (sasa.hip)
 struct molar_hip_rmsd_matrix_state;     // packed operands, partial covariances and staging of the all-pairs RMSD (rmsd_matrix.hip)
+struct molar_hip_fluct_state;           // fits, packed deviations, partial covariances and staging of the fluctuations (fluct.hip)
 
 // frames per launch of molar_hip_search_histogram_frames (search.hip, hist_frames_group)
 #ifndef MH_HIST_BATCH
@@ -140,6 +141,7 @@ struct molar_hip_ctx {
     molar_hip_search64_state *s64 = nullptr;      // created by the first molar_hip_search_count_f64
     molar_hip_sasa_state *sasa = nullptr;         // created by the first molar_hip_sasa*
     molar_hip_rmsd_matrix_state *rmsdm = nullptr; // created by the first molar_hip_rmsd_matrix*
+    molar_hip_fluct_state *fluct = nullptr;       // created by the first molar_hip_fluct*
     // ring of pinned chunks for large results that go to pageable host memory (hoststream.hpp), allocated on first use
     void *ring[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

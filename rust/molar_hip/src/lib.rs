@@ -801,6 +801,76 @@ impl Engine {
         self.plugin.check(unsafe { (self.plugin.fns.rmsd_matrix_plan)(nframes1, nframes2, n, &mut ws, &mut ks) })?;
         Ok((ws, ks))
     }
+
+    /// Fluctuations of a block of frames about their mean structure through molar_hip_fluct (the definition: molar_hip.h): the
+    /// mean, the per-atom RMSF and, with `want_cov`, the 3n x 3n positional covariance after the mass-weighted fit of every
+    /// frame onto `reference` (one position per SELECTED atom; None: frame 0), iterated `iterations` times onto the mean.
+    /// `frames` holds whole frames one after the other, `natoms` positions each; `masses` None: unit weights; `fit` false: the
+    /// frames as they stand.  With `want_fit` the result also holds, per frame, R (9, column-major), t (3) and the RMSD to
+    /// the last reference.
+    #[allow(clippy::too_many_arguments)]
+    pub fn fluctuations(
+        &self, frames: &[[f32; 3]], natoms: usize, index: Option<&[usize]>, masses: Option<&[f32]>, reference: Option<&[[f32; 3]]>, fit: bool,
+        iterations: u32, want_cov: bool, want_fit: bool,
+    ) -> Result<Fluctuations, EngineError> {
+        check_index(index, natoms, "fluctuations")?;
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("fluctuations: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        if let Some(m) = masses {
+            check_column(m.len(), natoms, "fluctuations: masses")?;
+        }
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { natoms };
+        if nsel == 0 {
+            return Err(EngineError::Sizes("fluctuations: empty selection".into()));
+        }
+        if let Some(r) = reference {
+            if r.len() != nsel {
+                return Err(EngineError::Sizes(format!("fluctuations: a reference of {} positions for {nsel} selected atoms", r.len())));
+            }
+        }
+        if iterations > i32::MAX as u32 {
+            return Err(EngineError::Sizes("fluctuations: too many iterations".into()));
+        }
+        let nframes = frames.len() / natoms;
+        let mut out = Fluctuations {
+            mean: vec![[0f32; 3]; nsel],
+            rmsf: vec![0f32; nsel],
+            cov: if want_cov { vec![0f32; 9 * nsel * nsel] } else { Vec::new() },
+            fit: if want_fit { vec![[0f32; 13]; nframes] } else { Vec::new() },
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        let mp = masses.map_or(std::ptr::null(), |m| m.as_ptr());
+        let rp = reference.map_or(std::ptr::null(), |r| r.as_ptr() as *const f32);
+        let cp = if want_cov { out.cov.as_mut_ptr() } else { std::ptr::null_mut() };
+        let fp = if want_fit { out.fit.as_mut_ptr() as *mut f32 } else { std::ptr::null_mut() };
+        self.plugin.check(unsafe {
+            (self.plugin.fns.fluct)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, ip, nsel, mp, rp, fit as i32,
+                                    iterations as i32, out.mean.as_mut_ptr() as *mut f32, out.rmsf.as_mut_ptr(), cp, 3 * nsel, fp)
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and the number of splits of the frame dimension a `fluctuations` call of these sizes uses
+    /// (molar_hip_fluct_plan, a host function).
+    pub fn fluct_plan(&self, nframes: usize, n: usize, want_cov: bool) -> Result<(usize, u32), EngineError> {
+        let (mut ws, mut ks) = (0usize, 0u32);
+        self.plugin.check(unsafe { (self.plugin.fns.fluct_plan)(nframes, n, want_cov as i32, &mut ws, &mut ks) })?;
+        Ok((ws, ks))
+    }
+}
+
+/// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless
+/// asked for) and per frame {R column-major, t, rmsd} (empty unless asked for).
+#[derive(Debug, Clone, Default)]
+pub struct Fluctuations {
+    pub mean: Vec<[f32; 3]>,
+    pub rmsf: Vec<f32>,
+    pub cov: Vec<f32>,
+    pub fit: Vec<[f32; 13]>,
 }
 
 /// What one frame of a streamed fit returns: `fit_transform` (measure.rs:507-522) as (R column-major, t), and RMSD / centre of
