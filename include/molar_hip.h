@@ -988,9 +988,10 @@ int molar_hip_rmsd_batch(molar_hip_ctx *ctx, const float *xyz1, size_t natoms1, 
                          float *out);
 
 /* fit_transform (measure.rs:507-522) of every selection of frame 1 onto its counterpart in frame 2 (idx2 NULL: same
- * atoms, mass2 NULL: mass1); apply != 0 moves the selections of xyz1 in place (modify.rs:32-36).  Any output may be
- * NULL: R_out[nsel][9] column-major, t_out[nsel][3], and of the FITTED selection rmsd_out[nsel] (unweighted, :485-504),
- * com_out[nsel][3], gyr_out[nsel]. */
+ * atoms; mass2 NULL or mass1: the column mass1 read through idx2, selection 2's own masses - INVALID_ARGUMENT if idx2
+ * differs from idx1 and frame 2 has more atoms than that column); apply != 0 moves the selections of xyz1 in place
+ * (modify.rs:32-36).  Any output may be NULL: R_out[nsel][9] column-major, t_out[nsel][3], and of the FITTED selection
+ * rmsd_out[nsel] (unweighted, :485-504), com_out[nsel][3], gyr_out[nsel]. */
 int molar_hip_fit_batch(molar_hip_ctx *ctx, float *xyz1, size_t natoms1, const uint64_t *idx1, const float *mass1,
                         const float *xyz2, size_t natoms2, const uint64_t *idx2, const float *mass2,
                         const uint64_t *offsets, size_t nsel, int apply, float *R_out, float *t_out, float *rmsd_out,

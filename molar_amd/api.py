@@ -1065,8 +1065,9 @@ class Engine:
 
     def fit_batch(self, xyz1, mass1, xyz2, idx, offsets, idx2=None, mass2=None, apply=False):
         """fit_transform (measure.rs:507-522) of each selection of frame 1 onto its counterpart in frame 2; `apply`
-        moves the selections of xyz1 in place.  Returns dict(R[K,3,3], t[K,3], rmsd[K], com[K,3], gyration[K]); the last
-        three describe the fitted selections."""
+        moves the selections of xyz1 in place.  mass2=None (or mass1 itself): one mass column, read through idx2 for the
+        second selection's centre (MolarHipError 50 if idx2 differs from idx and frame 2 has more atoms than that column).
+        Returns dict(R[K,3,3], t[K,3], rmsd[K], com[K,3], gyration[K]); the last three describe the fitted selections."""
         if apply and not _is_torch(xyz1):
             assert xyz1.dtype == np.float32 and xyz1.flags.c_contiguous, "apply works in place"
         xyz1 = _f32(xyz1); xyz2 = _f32(xyz2); idx = _u64(idx); idx2 = _u64(idx2); offsets = _u64(offsets)

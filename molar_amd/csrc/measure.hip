@@ -1480,7 +1480,14 @@ int molar_hip_fit_batch(molar_hip_ctx *c, float *xyz1, size_t natoms1, const uin
     MH_TRY(c->m_partials.reserve((nsel + 1) * 8));
     MH_TRY(to_device(c, offsets, nsel + 1, c->m_partials, &d_off));
     MH_TRY(to_device(c, mass1, natoms1, c->m_mass1, &m1));
-    if (mass2 && mass2 != mass1) MH_TRY(to_device(c, mass2, natoms2, c->m_mass2, &m2));
+    if (mass2 && mass2 != mass1) {
+        MH_TRY(to_device(c, mass2, natoms2, c->m_mass2, &m2));
+    } else if (i2 != i1) {
+        // one mass column for both frames: selection 2's own masses are that column read through idx2 (cm2, measure.rs:512);
+        // a NULL m2 makes the kernel take mass1[idx1[q]], which is the same number only when idx2 is idx1
+        if (natoms2 > natoms1) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "fit_batch: frame 2 has more atoms than the mass column; pass mass2");
+        m2 = m1;
+    }
     MH_TRY(c->m_out.reserve(nsel * 18 * 4));
     float *o = c->m_out.as<float>();
     hipLaunchKernelGGL(k_fit_csr, dim3((unsigned)((nsel + 3) / 4)), dim3(256), 0, c->stream, const_cast<float *>(d1), d2, i1, i2,
