@@ -163,7 +163,6 @@ molar_hip_ctx *molar_hip_create(int device) {
     c->env_no_mfma_wrapped = std::getenv("MOLAR_HIP_NO_MFMA_WRAPPED") != nullptr;
     c->env_no_tile_sum = std::getenv("MOLAR_HIP_NO_TILE_SUM") != nullptr;
     c->env_host_grid_wait = std::getenv("MOLAR_HIP_HOST_GRID_WAIT") != nullptr;
-    c->env_grid_late = std::getenv("MOLAR_HIP_GRID_LATE") != nullptr;
     c->env_no_bin_tile = std::getenv("MOLAR_HIP_NO_BIN_TILE") != nullptr;
 #endif
 #ifdef MOLAR_HIP_DEBUG_KNOBS
@@ -222,7 +221,6 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     for (auto &t : c->tickets)
         if (t.done) (void)hipEventDestroy(t.done);
     if (c->grid_done) (void)hipEventDestroy(c->grid_done);
-    if (c->count_done) (void)hipEventDestroy(c->count_done);
     for (auto e : c->gen_free)
         if (e) (void)hipEventDestroy(e);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);

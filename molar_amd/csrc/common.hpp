@@ -161,9 +161,10 @@ struct molar_hip_ctx {
     // the next frame on `side_stream` while the pair kernels of the frame before it still read theirs.
     mh::GridSet set_store[2][2];
     mh::GridSet *set = set_store[0];     // the generation the cached search refers to (set[0], set[1]: first / second set)
+    // What ONE request asks of the shared helpers (plan or not, side stream, output capacity ...) is not kept here: it travels
+    // down the call chain as a SearchCall argument (search.hip).
     hipStream_t side_stream = nullptr;   // grid build of a pipelined search (created on first use, highest priority)
     hipEvent_t grid_done = nullptr;
-    bool want_side = false;              // set by _begin / the asynchronous histogram call around their enqueue
     bool env_no_side = false;            // MOLAR_HIP_NO_SIDE_STREAM, read once in molar_hip_create
     bool env_no_mfma = false;            // MOLAR_HIP_NO_MFMA_COUNT: count pass of plain entries on the vector ALUs (A/B runs)
     bool env_no_mfma_wrapped = false;    // MOLAR_HIP_NO_MFMA_WRAPPED: count pass of wrapped entries on the vector ALUs (A/B runs)
@@ -172,16 +173,12 @@ struct molar_hip_ctx {
     uint32_t env_debug_skip = 0;         // MOLAR_HIP_DEBUG_SKIP (builds with -DMOLAR_HIP_DEBUG_KNOBS only), read once
     uint32_t env_debug_launch = 0, dbg_launches = 0;   // MOLAR_HIP_DEBUG_LAUNCH (same builds): which histogram launch records its wave times
     hipEvent_t gen_free[2] = {nullptr, nullptr};   // recorded on the main stream behind the last asynchronous reader of
-                                                   // a grid generation (histogram calls that do not wait)
-    hipEvent_t side_wait = nullptr;      // what the side stream has to wait for before it rebuilds the generation
-    hipEvent_t side_wait2 = nullptr;     // ... and a second event (the count pass of the frame in flight, see count_done)
-    hipEvent_t count_done = nullptr;     // recorded behind the count pass of every pipelined search (molar_hip_search_resident_begin)
-    bool count_done_set = false;
-    bool record_count_done = false;      // set around the enqueue of a pipelined search
-    bool env_grid_late = false;          // MOLAR_HIP_GRID_LATE: the next frame's grid waits for the count pass of the frame in flight (A/B runs)
+                                                   // a grid generation (histogram calls that do not wait): what the side
+                                                   // stream waits for before it rebuilds the generation
     bool env_no_bin_tile = false;        // MOLAR_HIP_NO_BIN_TILE: the grid's binning with one global atomic per atom (A/B runs)
     int hist_gen = 0;                    // generation of the last asynchronous histogram call
-    bool on_side = false;                // launches currently go to side_stream (scans then use scan_tmp_side)
+    bool on_side = false;                // `stream` is side_stream for the grid build in hand (scans then use scan_tmp_side); set
+                                         // and restored together with `stream` by one scope guard in prepare_search
     mh::DevBuf scan_tmp_side;
     uint64_t nslots_bound = 0; // host-side upper bound of the slot count (sizes the launches)
     mh::DevBuf params;         // SearchParams block read by the pair kernels
@@ -191,10 +188,8 @@ struct molar_hip_ctx {
     mh::DevBuf slot_cnt;       // u32 per slot (+1): results of the slot
     mh::DevBuf slot_base;      // u64 per slot (+1): output offset (last = grand total)
     mh::DevBuf tile_sum;       // u64 per tile of 256 slots: results of the tile (tile_sums_kernel -> slot_offsets_kernel)
-    unsigned long long plan_out_cap = ~0ull;   // resident searches: the output capacity the plan kernel writes into the parameter block
     bool params_fresh = false;                 // the plan kernel of this search left a parameter block the count pass can use as it is
     unsigned long long params_fresh_cap = 0;   // ... written with this output capacity
-    unsigned long long *sizes_dev = nullptr;   // resident searches: device-side address of the pinned 16 bytes the kernels write the two sizes to
     mh::DevBuf scan_tmp;       // block sums for the scans
     mh::DevBuf sort_tmp, sort_tmp_side;   // scratch of the device sort (devsort.hip), per stream
     mh::DevBuf scan_state;     // ticket + tile descriptors of the single-pass scans (zeroed by the plan kernel)
@@ -213,8 +208,8 @@ struct molar_hip_ctx {
         molar_hip_search_desc desc{};
     } tickets[2];
     int next_ticket = 0;
-    bool resident_no_dist = false;          // molar_hip_search_resident_planes: the resident searches fill the (i, j) plane only
-    bool grid_drop_nonfinite = false;       // the grid being built leaves atoms with a non-finite coordinate out (search_resident_enqueue)
+    bool resident_no_dist = false;          // molar_hip_search_resident_planes: the resident calls of the C ABI fill the (i, j) plane only
+                                            // (a setting of the caller's: internal users that want the plane alone say so by argument)
     unsigned long long search_serial = 0;   // counts resident searches enqueued on this context
     // Resident searches launch their count and fill passes over the slots the plan of the SEARCH BEFORE came to (+ 3 % + 512)
     // instead of the host's bound (14 N / 64 + entries: 13 % above the real count on the headline frame - 3.7e4 workgroups per
@@ -222,7 +217,6 @@ struct molar_hip_ctx {
     // search that needed more slots than were launched is repeated with the bound where its sizes are read.
     unsigned long long trim_real = 0, trim_ntasks = 0;   // slots of the last resident search whose sizes were read, and its plan
     int trim_kind = -1;
-    uint32_t slot_launch = 0;               // slots the passes of the resident search being enqueued launch (0: the bound)
     void *h_sizes = nullptr;                // pinned: 32 bytes of result sizes per ticket (total, history units, slots, occupied cells)
     // Occupied cells of the two sets' grids as the last finished search of this shape found them (the grid build counts them, the
     // offsets kernel hands them to the host with the sizes): small_cell_lanes() judges a frame by its atoms per OCCUPIED cell when it
@@ -248,7 +242,6 @@ struct molar_hip_ctx {
     hipEvent_t hb_pin_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool hb_pin_used[4] = {false, false, false, false};
     unsigned hb_pin_next = 0;
-    bool hist_plan_now = false;           // set around prepare_search by the fused histogram of the fixed-cutoff kinds
     mh::DevBuf hist_edges;     // f32[nbins + 1]: smallest d2 that reaches each bin (hist_kernel), for the cached (min, max, nbins)
     float edges_min = 0.f, edges_max = 0.f;
     size_t edges_nbins = 0;    // 0: no table cached
@@ -277,7 +270,6 @@ struct molar_hip_ctx {
     mh::DevBuf w_flags, w_part_cnt, w_part, w_tile_cnt, w_tile_off;
     uint64_t within_nflags = 0, within_total = 0;
     bool have_within = false;
-    bool skip_plan = false;    // set around prepare_search by callers that do not walk slots
     mh::DevBuf task_mu;        // u32 per task (+1): 64-word hit-history units of the task's slots
     mh::DevBuf task_moff;      // u64 per task (+1): exclusive scan of task_mu
     mh::DevBuf maskbuf;        // hit bits recorded by the count pass, replayed by the fill pass

@@ -1225,8 +1225,52 @@ static bool records_hit_history(const molar_hip_ctx *c) {
     return (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE) && small_cell_lanes(c) == 0;
 }
 
+// What ONE request asks of the helpers below (prepare_search, build_grid, the plan, launch_pairs), beyond its descriptor.  It
+// lives on the caller's stack and goes down the call chain by reference; the context holds only what outlasts a request.
+struct SearchCall {
+    bool plan = true;              // prepare_search enqueues the plan (false: the caller walks cells, or plans inside launch_pairs)
+    bool within_set = false;       // the request is molar_hip_within_count's: its first set's grid may be held (molar_hip_within_hold)
+    bool hist_plan = false;        // fused histogram of the fixed-cutoff kinds: grid and slot bound for hist_plan_kernel
+    bool size_masks = true;        // count -> fill pair: read the plan's sizes back and size the hit-history buffer exactly
+    bool side = false;             // the grid may be built on the side stream (pipelined searches, asynchronous histograms) ...
+    hipEvent_t side_wait = nullptr;            // ... which first waits for this (the last reader of the grid generation)
+    unsigned long long out_cap = ~0ull;        // resident searches: the output capacity in the parameter block (plan kernel, pair passes)
+    unsigned long long *sizes_dev = nullptr;   // resident searches: device-side address of the pinned sizes the kernels write
+    bool drop_nonfinite = false;   // the grid leaves atoms with a non-finite coordinate out (stages.hpp, search_resident_enqueue)
+    uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
+};
+
+// restores a field of the context on every exit from the scope
+template <class T>
+struct Restore {
+    T &ref;
+    const T old;
+    explicit Restore(T &r) : ref(r), old(r) {}
+    ~Restore() { ref = old; }
+    Restore(const Restore &) = delete;
+};
+// launches go to the side stream while one of these lives (c->stream and c->on_side move together)
+struct OnSideStream {
+    Restore<hipStream_t> stream;
+    Restore<bool> on_side;
+    explicit OnSideStream(molar_hip_ctx *c) : stream(c->stream), on_side(c->on_side) {
+        c->stream = c->side_stream;
+        c->on_side = true;
+    }
+};
+
+// the side stream (highest priority) and the event its grid builds end with, created on first use
+static int ensure_side_stream(molar_hip_ctx *c) {
+    if (c->side_stream) return 0;
+    int lo = 0, hi = 0;
+    MH_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    MH_HIP(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, hi));
+    MH_HIP(hipEventCreateWithFlags(&c->grid_done, hipEventDisableTiming));
+    return 0;
+}
+
 // what the grid kernels take of the request (the context's cached search) and of a set
-static BinParams grid_bin_params(const molar_hip_ctx *c, const GridSet &S) {
+static BinParams grid_bin_params(const molar_hip_ctx *c, const GridSet &S, bool drop_nonfinite) {
     BinParams P{};
     P.xyz = S.d_xyz;
     P.idx = S.d_idx;
@@ -1236,7 +1280,7 @@ static BinParams grid_bin_params(const molar_hip_ctx *c, const GridSet &S) {
     P.dz = c->dims[2];
     P.pbc = c->pbc;
     P.use_box = c->use_box ? 1u : 0u;
-    P.drop_nonfinite = c->grid_drop_nonfinite ? 1u : 0u;
+    P.drop_nonfinite = drop_nonfinite ? 1u : 0u;
     for (int d = 0; d < 3; ++d) {
         P.lower[d] = c->lower[d];
         P.upper[d] = c->upper[d];
@@ -1265,25 +1309,13 @@ static int grid_reserve(GridSet &S, uint32_t ncells) {
     return 0;
 }
 
-int build_grid(molar_hip_ctx *c, GridSet &S, int ids_local) {
+int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_local) {
     Prof prof(c, 0);
     const uint32_t ncells = c->dims[0] * c->dims[1] * c->dims[2];
-    const BinParams P = grid_bin_params(c, S);
-    MH_TRY(S.key.reserve((size_t)(S.n ? S.n : 1) * 4));
-    MH_TRY(S.cell_count.reserve((size_t)(ncells + 1 + OCC_WORDS) * 4));      // cell starts, then the occupied-cell counters
-    MH_TRY(S.cursor.reserve((size_t)(S.n ? S.n : 1) * 4));   // arrival order of each atom in its cell
-    MH_TRY(S.tmp_key.reserve((size_t)(S.n ? S.n : 1) * 4));
-    MH_TRY(S.sorted.reserve((size_t)(S.n ? S.n : 1) * sizeof(float4)));
-    if (S.d_vdw) MH_TRY(S.sorted_vdw.reserve((size_t)(S.n ? S.n : 1) * 4));
-    MH_TRY(S.aabb.reserve((size_t)ncells * 2 * sizeof(float4)));
-    MH_TRY(S.perm.reserve((size_t)(S.n ? S.n : 1) * 16));
-    MH_TRY(S.chunk_aabb.reserve(((size_t)S.n / 64 + ncells + 1) * 2 * sizeof(float4)));
-    MH_TRY(S.h16.reserve((size_t)(S.n ? S.n : 1) * 16));
-    MH_TRY(S.cell_org.reserve((size_t)(ncells + 1) * 16));
-    // one counter per 128-byte line while that stays small (<= 64 MB) and cells are crowded
+    const BinParams P = grid_bin_params(c, S, call.drop_nonfinite);
+    MH_TRY(grid_reserve(S, ncells));
     const uint32_t pad_shift = grid_pad_shift(S.n, ncells);
     const size_t npad = pad_shift ? ((size_t)ncells << pad_shift) : 0;
-    if (pad_shift) MH_TRY(S.cnt_pad.reserve(npad * 4));
     {
         const size_t nz = (size_t)ncells + 1 + npad;
         // workgroup size: one wave on the side stream (see place_order_kernel), four otherwise
@@ -1331,7 +1363,7 @@ int build_grid(molar_hip_ctx *c, GridSet &S, int ids_local) {
                            S.cell_count.as<uint32_t>(), S.cursor.as<uint32_t>(), S.tmp_key.as<uint32_t>());
         // (the spatial order serves the regular count pass and the fused histogram; pair_small.hip reads the placed records only)
         const int want_order = ((c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE) &&
-                                (c->hist_plan_now || small_cell_lanes(c) == 0)) ? 1 : 0;
+                                (call.hist_plan || small_cell_lanes(c) == 0)) ? 1 : 0;
         if (!want_order && !by_sort && (uint64_t)S.n < 16ull * ncells)
             hipLaunchKernelGGL(place_small_kernel, dim3((unsigned)(((uint64_t)ncells * 16u + bs - 1u) / bs)), dim3(bs), 0, c->stream, P, ncells,
                                ids_local, S.cell_count.as<uint32_t>(), S.tmp_key.as<uint32_t>(), S.d_vdw, S.sorted.as<float4>(),
@@ -1485,31 +1517,44 @@ SearchParams make_params(molar_hip_ctx *c) {
     return P;
 }
 
+// where the fill pass writes (count pass: nothing) and, for the fused histogram, what the distances are added into
+struct PairOut {
+    uint2 *pairs = nullptr;
+    float *dist = nullptr;
+    uint32_t *ids = nullptr;       // `within` in its stream form
+};
+struct HistTarget {
+    uint32_t nbins = 0;            // 0: not a histogram launch
+    float min = 0.f, max = 0.f;
+    unsigned long long *bins = nullptr;
+    unsigned long long *total = nullptr;
+};
+
+// of `call`: out_cap and slot_launch
 template <bool FILL>
-int launch_pairs(molar_hip_ctx *c, uint2 *pairs, float *dist, uint32_t *ids, uint32_t hist_nbins = 0, float hmin = 0.f,
-                 float hmax = 0.f, unsigned long long *hist_bins = nullptr, unsigned long long out_cap = ~0ull,
-                 bool params_resident = false, unsigned long long *hist_total = nullptr) {
+int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, const HistTarget &hist = HistTarget{},
+                 bool params_resident = false) {
     // the fill pass writes two (i, j) pairs / two distances per lane and instruction (fifo_flush_wide): naturally aligned
     // dwordx4 / dwordx2 stores relative to these bases (include/molar_hip.h states the requirement for caller-owned outputs)
-    if (FILL && (((uintptr_t)pairs & 15u) || ((uintptr_t)dist & 7u)))
+    if (FILL && (((uintptr_t)out.pairs & 15u) || ((uintptr_t)out.dist & 7u)))
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search fill: device outputs must be aligned to 16 bytes (pairs) and 8 bytes (distances)");
     Prof prof(c, FILL ? 3 : 1);
     SearchParams P = make_params(c);
     if (P.nblocks == 0) return 0;
-    P.out_cap = out_cap;
-    P.hist_nbins = hist_nbins;
-    P.hist_min = hmin;
-    P.hist_max = hmax;
-    P.hist_bins = hist_bins;
-    P.hist_total = hist_total;
+    P.out_cap = call.out_cap;
+    P.hist_nbins = hist.nbins;
+    P.hist_min = hist.min;
+    P.hist_max = hist.max;
+    P.hist_bins = hist.bins;
+    P.hist_total = hist.total;
     size_t dyn_lds = 0;
     P.hist_lean = 0u;
     P.hist_big = 0u;
     P.hist_edges = nullptr;
     P.hist_nslots = nullptr;
     P.hist_scale = 0.f;
-    if (hist_nbins) {
-        dyn_lds = (size_t)hist_nbins * 4;
+    if (hist.nbins) {
+        dyn_lds = (size_t)hist.nbins * 4;
         const uint32_t wpb = (uint32_t)waves_per_block(MODE_HIST);
         P.nblocks = (P.nblocks + wpb - 1u) / wpb;
         const uint32_t cap = (uint32_t)c->num_cus * 8u;
@@ -1522,9 +1567,9 @@ int launch_pairs(molar_hip_ctx *c, uint2 *pairs, float *dist, uint32_t *ids, uin
             const uint64_t nb_set = c->kind == MOLAR_HIP_SEARCH_SINGLE ? c->set[0].n : c->set[1].n;
             P.hist_big = (P.hist_lean && nb_set > 384ull * ncells) ? 1u : 0u;
         }
-        if (P.hist_lean && c->edges_nbins == hist_nbins && c->edges_min == hmin && c->edges_max == hmax) {
+        if (P.hist_lean && c->edges_nbins == hist.nbins && c->edges_min == hist.min && c->edges_max == hist.max) {
             P.hist_edges = c->hist_edges.as<float>();
-            P.hist_scale = (float)hist_nbins / (hmax - hmin);
+            P.hist_scale = (float)hist.nbins / (hist.max - hist.min);
         }
 #ifdef MOLAR_HIP_DEBUG_KNOBS
         // 16 words per wave of hist_kernel; MOLAR_HIP_DEBUG_LAUNCH=n: only the n-th histogram launch of the context records
@@ -1539,19 +1584,18 @@ int launch_pairs(molar_hip_ctx *c, uint2 *pairs, float *dist, uint32_t *ids, uin
     // (a kernel argument, not a copy from pageable memory: the latter makes the host wait for the stream to drain,
     // which would serialise the begin/end pipelining of molar_hip_search_resident_begin)
     // (params_fresh: the plan kernel of this search has already written exactly this block - resident searches)
-    // (compared with the capacity the plan kernel was given: resident_enqueue has reset plan_out_cap by now - comparing with
-    // that made every resident search upload the block again, 8.6 us on the critical stream of every frame, until round 4)
-    const bool plan_wrote = c->params_fresh && !FILL && !hist_nbins && out_cap == c->params_fresh_cap;
+    // (written with the same output capacity: the plan kernel and this pass read it from the same SearchCall)
+    const bool plan_wrote = c->params_fresh && !FILL && !hist.nbins && call.out_cap == c->params_fresh_cap;
     c->params_fresh = false;
     if (!params_resident && !plan_wrote && !P.hist_lean)
         hipLaunchKernelGGL(upload_params_kernel, dim3(1), dim3(256), 0, c->stream, P, c->params.as<SearchParams>());
     const SearchParams *dP = c->params.as<SearchParams>();
     const SlotDesc *tf = c->slot_desc.as<SlotDesc>();
     uint32_t st = (uint32_t)c->nslots_bound;
-    if (c->slot_launch && !hist_nbins && c->slot_launch < st) P.nblocks = st = c->slot_launch;      // resident searches, see common.hpp
+    if (call.slot_launch && !hist.nbins && call.slot_launch < st) P.nblocks = st = call.slot_launch;      // resident searches, see common.hpp
     uint32_t *sc = c->slot_cnt.as<uint32_t>();
     auto *sb = c->slot_base.as<unsigned long long>();
-    const int mode = !FILL ? MODE_COUNT : (hist_nbins ? MODE_HIST : MODE_FILL);
+    const int mode = !FILL ? MODE_COUNT : (hist.nbins ? MODE_HIST : MODE_FILL);
     if (P.hist_lean) {
         // fused histogram of the fixed-cutoff kinds: one-kernel plan (which also writes the parameter block), the lean kernel on
         // its list, the generic kernel on the list of what the lean one cannot do (triclinic corner entries, oversized cells)
@@ -1568,37 +1612,37 @@ int launch_pairs(molar_hip_ctx *c, uint2 *pairs, float *dist, uint32_t *ids, uin
     }
     // frames of large cells (more than 448 atoms per cell of the second set on average, i.e. cells above 512 are common): the
     // instances with 128 registers per lane and up to 16 chunks of the second cell resident
-    if (!hist_nbins && !ids && (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE)) {
+    if (!hist.nbins && !out.ids && (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE)) {
         // (per occupied cell where the last search of this shape has counted them, like small_cell_lanes: a slab in a mostly empty box)
         const int sb_set = c->kind == MOLAR_HIP_SEARCH_SINGLE ? 0 : 1;
         const uint64_t all_cells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
         const uint64_t ncells = c->occ_use[sb_set] ? std::min<uint64_t>(c->occ_use[sb_set], all_cells) : all_cells;
         const uint64_t nb_set = c->set[sb_set].n;
         if (nb_set > 1000ull * ncells) {       // cells above 1024 atoms are the rule: 256 registers per lane, up to 2048 atoms resident (pair_k7.hip)
-            launch_pair_huge(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, pairs, dist);
+            launch_pair_huge(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
             MH_HIP(hipGetLastError());
             return 0;
         }
         if (nb_set > 448ull * ncells) {
-            launch_pair_wide(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, pairs, dist);
+            launch_pair_wide(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
             MH_HIP(hipGetLastError());
             return 0;
         }
     }
     // frames of small cells (contact / hydrogen-bond cutoffs): several slots per wave, pair_small.hip
-    if (!hist_nbins && !ids) {
+    if (!hist.nbins && !out.ids) {
         const int lanes = small_cell_lanes(c);
         if (lanes) {
-            launch_pair_small(mode, lanes, c->stream, dP, tf, st, sc, sb, pairs, dist);
+            launch_pair_small(mode, lanes, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
             MH_HIP(hipGetLastError());
             return 0;
         }
     }
     switch (c->kind) {
-        case MOLAR_HIP_SEARCH_SINGLE: launch_pair_single(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, pairs, dist, ids); break;
-        case MOLAR_HIP_SEARCH_DOUBLE: launch_pair_double(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, pairs, dist, ids); break;
-        case MOLAR_HIP_SEARCH_WITHIN: launch_pair_within(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, pairs, dist, ids); break;
-        default: launch_pair_vdw(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, pairs, dist, ids); break;
+        case MOLAR_HIP_SEARCH_SINGLE: launch_pair_single(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
+        case MOLAR_HIP_SEARCH_DOUBLE: launch_pair_double(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
+        case MOLAR_HIP_SEARCH_WITHIN: launch_pair_within(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
+        default: launch_pair_vdw(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
     }
     MH_HIP(hipGetLastError());
     return 0;
@@ -1703,7 +1747,7 @@ int device_fmax2(molar_hip_ctx *c, const float *d_v1, uint32_t n1, const float *
 
 // Second half of the plan, for the kernels that walk slots (count / fill / histogram): slot index of every plan entry and
 // (fast kinds) its first hit-history unit by one single-pass scan over both, then one record per slot.
-int enqueue_plan_slots(molar_hip_ctx *c) {
+int enqueue_plan_slots(molar_hip_ctx *c, unsigned long long *sizes_dev) {
     const uint32_t fast_kind = records_hit_history(c) ? 1u : 0u;
     const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
     if (c->ntasks + 1 > (1ull << 18)) {
@@ -1719,7 +1763,7 @@ int enqueue_plan_slots(molar_hip_ctx *c) {
     const unsigned nbs = (unsigned)((c->ntasks + c->nslots_bound + 1 + pbs - 1) / pbs);
     hipLaunchKernelGGL(slotmap_kernel, dim3(nbs), dim3(pbs), 0, c->stream, c->ntasks, c->task_nb.as<uint32_t>(),
                        c->task_desc.as<TaskDesc>(), fast_kind ? c->task_moff.as<unsigned long long>() : nullptr,
-                       c->slot_desc.as<SlotDesc>(), c->nslots_bound, c->sizes_dev);
+                       c->slot_desc.as<SlotDesc>(), c->nslots_bound, sizes_dev);
     MH_HIP(hipGetLastError());
     return 0;
 }
@@ -1749,7 +1793,7 @@ int size_plan(molar_hip_ctx *c) {
     return 0;
 }
 
-int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_masks = true) {
+int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call) {
     if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: null argument");
     if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
     MH_HIP(hipSetDevice(c->device));
@@ -1762,7 +1806,7 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
     if (c->use_box) MH_TRY(molar_hip_box_from_matrix(q->box9, &c->box));
     // molar_hip_within_hold: consecutive `within` requests against the SAME first set (same pointers and sizes, same box, same
     // grid) reuse its staged coordinates and its grid; anything else that stages or bins set 0 ends the hold's validity
-    const bool may_hold = c->within_hold && q->kind == MOLAR_HIP_SEARCH_WITHIN && c->skip_plan;
+    const bool may_hold = c->within_hold && q->kind == MOLAR_HIP_SEARCH_WITHIN && call.within_set;
     // A first set in HOST memory is staged, so the hold would serve a copy: a fingerprint of the caller's array (its two ends and
     // 512 atoms spread over it) tells an array updated in place, or a new one that the allocator put at the old address, from the
     // one that was staged.  Device memory is read in place by the grid build; there the caller's promise is all there is.
@@ -1855,13 +1899,13 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
     // entries wrapping in all three dims of a triclinic box use 2-row (<= 1024 rows) or 8-row slots: <= 28 tasks of <= 512 slots
     c->nslots_bound += 28ull * 512ull;
     // (the one-kernel plan of the fused histogram cuts same-cell entries into 32-row slots: one such entry per cell)
-    if (c->hist_plan_now) c->nslots_bound += ((uint64_t)c->set[0].n + 31ull) / 32ull + ncells;
+    if (call.hist_plan) c->nslots_bound += ((uint64_t)c->set[0].n + 31ull) / 32ull + ncells;
     if (c->ntasks >= 0xFFFFFFF0ull || c->nslots_bound >= 0xFFFFFFF0ull || c->ntasks + c->nslots_bound >= 0xFFFFFF00ull)
         return fail(MOLAR_HIP_ERR_TOO_LARGE, "search plan too large (%llu entries)", (unsigned long long)c->ntasks);
     MH_TRY(c->task_nb.reserve((c->ntasks + 1) * 4));
     MH_TRY(c->task_desc.reserve((c->ntasks + 1) * sizeof(TaskDesc)));
     MH_TRY(c->slot_desc.reserve((c->nslots_bound + 1) * sizeof(SlotDesc)));
-    if (c->hist_plan_now) MH_TRY(c->slot_desc_rest.reserve((c->nslots_bound + 1) * sizeof(SlotDesc)));
+    if (call.hist_plan) MH_TRY(c->slot_desc_rest.reserve((c->nslots_bound + 1) * sizeof(SlotDesc)));
     MH_TRY(c->slot_cnt.reserve((c->nslots_bound + 1) * 4));
     MH_TRY(c->slot_base.reserve((c->nslots_bound + 1) * 8));
     MH_TRY(c->params.reserve(sizeof(SearchParams)));
@@ -1877,8 +1921,8 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
         // kernel also writes the parameter block the count and fill passes read, output capacity included.
         SearchParams *params_dst = nullptr;
         c->params_fresh = false;
-        if (!size_masks) {
-            P.out_cap = c->plan_out_cap;
+        if (!call.size_masks) {
+            P.out_cap = call.out_cap;
             params_dst = c->params.as<SearchParams>();
             c->params_fresh = true;
             c->params_fresh_cap = P.out_cap;
@@ -1902,7 +1946,7 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
             unsigned long long *gt = ngroups ? lmoff + (c->ntasks + 1) : nullptr;
             if (ngroups) hipLaunchKernelGGL(plan_groups_kernel, dim3(ngroups), dim3(64), 0, c->stream, ntiles, tt, gt);
             hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, c->ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
-                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), c->nslots_bound, c->sizes_dev, gt);
+                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), c->nslots_bound, call.sizes_dev, gt);
             MH_HIP(hipGetLastError());
             return 0;
         }
@@ -1924,33 +1968,23 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
                 break;
         }
         MH_HIP(hipGetLastError());
-        return enqueue_plan_slots(c);
+        return enqueue_plan_slots(c, call.sizes_dev);
     };
     // Pipelined search on a context that owns its stream, inputs already in device memory: the grid build goes to the
     // side stream.  It touches only this generation's GridSet (last read by the search two frames back, which has been
     // ended) and its own scan scratch, so it needs to wait for nothing and overlaps the pair kernels of the frame in
     // front of it; the plan and the pair kernels of THIS search wait for it on the main stream.
-    const bool side = c->want_side && c->own_stream && c->use_box && !vdw && c->set[0].d_xyz == q->xyz1 &&
+    const bool side = call.side && c->own_stream && c->use_box && !vdw && c->set[0].d_xyz == q->xyz1 &&
                       c->set[0].d_idx == q->idx1 && (!two || (c->set[1].d_xyz == q->xyz2 && c->set[1].d_idx == q->idx2));
     if (side) {
-        if (!c->side_stream) {
-            int lo = 0, hi = 0;
-            MH_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            MH_HIP(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, hi));
-            MH_HIP(hipEventCreateWithFlags(&c->grid_done, hipEventDisableTiming));
+        MH_TRY(ensure_side_stream(c));
+        if (call.side_wait) MH_HIP(hipStreamWaitEvent(c->side_stream, call.side_wait, 0));
+        {
+            OnSideStream on_side(c);
+            if (!reuse0) MH_TRY(build_grid(c, call, c->set[0], q->ids_local || vdw));
+            if (two) MH_TRY(build_grid(c, call, c->set[1], q->ids_local || vdw));
+            MH_HIP(hipEventRecord(c->grid_done, c->side_stream));
         }
-        if (c->side_wait) MH_HIP(hipStreamWaitEvent(c->side_stream, c->side_wait, 0));
-        if (c->side_wait2) MH_HIP(hipStreamWaitEvent(c->side_stream, c->side_wait2, 0));
-        hipStream_t main_stream = c->stream;
-        c->stream = c->side_stream;
-        c->on_side = true;
-        int rc = reuse0 ? 0 : build_grid(c, c->set[0], q->ids_local || vdw);
-        if (!rc && two) rc = build_grid(c, c->set[1], q->ids_local || vdw);
-        hipError_t e = rc ? hipSuccess : hipEventRecord(c->grid_done, c->side_stream);
-        c->stream = main_stream;
-        c->on_side = false;
-        MH_TRY(rc);
-        MH_HIP(e);
         // The plan and the pair kernels of this search need the grid.  A wait command on the main stream costs that stream
         // ~25 us in front of the plan kernel even when the grid has long been finished (cross-queue barrier packet); the
         // host waiting for the side stream instead costs nothing there: the frame in flight still has its fill pass
@@ -1958,8 +1992,8 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
         if (c->env_host_grid_wait) MH_HIP(hipEventSynchronize(c->grid_done));
         else MH_HIP(hipStreamWaitEvent(c->stream, c->grid_done, 0));
     } else {
-        if (!reuse0) MH_TRY(build_grid(c, c->set[0], q->ids_local || vdw));
-        if (two) MH_TRY(build_grid(c, c->set[1], q->ids_local || vdw));
+        if (!reuse0) MH_TRY(build_grid(c, call, c->set[0], q->ids_local || vdw));
+        if (two) MH_TRY(build_grid(c, call, c->set[1], q->ids_local || vdw));
     }
     if (may_hold && !reuse0) {        // this grid of set 0 is the one later `within` requests may reuse
         c->hold_valid = true;
@@ -1974,11 +2008,11 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, bool size_m
     // of their buffers, one-wave workgroups: bit-identical, not faster; the fill pass of the frame in flight is stretched by
     // more than the main stream gains, 1.03 -> 1.06-1.12 ms.  Whatever shares the chip with the fill pass costs it at least
     // its own stand-alone duration.)
-    if (!c->skip_plan) MH_TRY(enqueue_plan());
+    if (call.plan) MH_TRY(enqueue_plan());
     // hit-history buffer of the count -> fill pair: sized exactly (one small read-back; the fused histogram
     // mode does not use it, but sizing it here keeps a later count/fill on the same cached search valid)
     c->mask_units = 0;
-    if (size_masks && !c->skip_plan) MH_TRY(size_plan(c));
+    if (call.size_masks && call.plan) MH_TRY(size_plan(c));
     return 0;
 }
 
@@ -2224,12 +2258,13 @@ bool ring_pays(size_t link_bytes, const void *a, const void *b = nullptr, const 
 extern "C" {
 
 int molar_hip_search_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uint64_t *out_count) {
-    MH_TRY(prepare_search(c, q));
+    SearchCall call;
+    MH_TRY(prepare_search(c, q, call));
     if (c->have_search) {   // degenerate (empty vdw input)
         if (out_count) *out_count = 0;
         return MOLAR_HIP_OK;
     }
-    MH_TRY(launch_pairs<false>(c, nullptr, nullptr, nullptr));
+    MH_TRY(launch_pairs<false>(c, call, PairOut{}));
     MH_TRY(finish_count(c));
     if (out_count) *out_count = c->total;
     return MOLAR_HIP_OK;
@@ -2276,7 +2311,7 @@ static int fill_common(molar_hip_ctx *c, uint2 *d_pairs, float *d_dist, uint32_t
         MH_TRY(c->out_dist.reserve((size_t)c->total * 4));
         d = c->out_dist.as<float>();
     }
-    MH_TRY(launch_pairs<true>(c, p, d, d_ids));
+    MH_TRY(launch_pairs<true>(c, SearchCall{}, PairOut{p, d, d_ids}));
     if (via_p) MH_HIP(hipMemcpyAsync(d_pairs, p, (size_t)c->total * 8, hipMemcpyDeviceToDevice, c->stream));
     if (via_d) MH_HIP(hipMemcpyAsync(d_dist, d, (size_t)c->total * 4, hipMemcpyDeviceToDevice, c->stream));
     return 0;
@@ -2333,9 +2368,10 @@ int molar_hip_search_fill_device(molar_hip_ctx *c, const uint32_t **d_pairs, con
 // Enqueue one whole resident search (grid, plan, count, offset scan, fill into outP/outD against their present
 // capacity) and the async read-back of its two sizes into `sizes` (pinned, 16 bytes).  No host wait.
 // (struct ResidentLaunch: stages.hpp)
-
+// pairs_only: the fill pass writes the (i, j) plane alone; trim: launch the passes over what the plan of the search before came
+// to (common.hpp, trim_real) where that is known.  Of `call` the caller sets side, side_wait and drop_nonfinite; the rest is set here.
 static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD,
-                            void *sizes, ResidentLaunch *L) {
+                            void *sizes, ResidentLaunch *L, bool pairs_only, bool trim = true, SearchCall call = SearchCall{}) {
     if (q && q->kind == MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within search yields ids: use molar_hip_search_count + fill_ids");
     const unsigned long long a = outP.cap / 8u, b = outD.cap / 4u;
@@ -2347,12 +2383,10 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
         (void)hipGetLastError();
         sizes_dev = nullptr;
     }
-    c->plan_out_cap = cap0;
-    c->sizes_dev = (unsigned long long *)sizes_dev;
-    const int prc = prepare_search(c, q, /*size_masks=*/false);
-    c->plan_out_cap = ~0ull;
-    c->sizes_dev = nullptr;
-    MH_TRY(prc);
+    call.size_masks = false;
+    call.out_cap = cap0;
+    call.sizes_dev = (unsigned long long *)sizes_dev;
+    MH_TRY(prepare_search(c, q, call));
     ++c->search_serial;
     *L = ResidentLaunch{};
     L->degenerate = c->have_search;
@@ -2363,27 +2397,19 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
     // slots the two passes are launched over: what the plan of the search before came to, with a margin (common.hpp, trim_real)
     L->launched = c->nslots_bound;
     L->ntasks = c->ntasks;
-    if (c->trim_real && c->trim_ntasks == c->ntasks && c->trim_kind == c->kind) {
+    if (trim && c->trim_real && c->trim_ntasks == c->ntasks && c->trim_kind == c->kind) {
         const unsigned long long want = c->trim_real + c->trim_real / 32u + 512ull;
         if (want < L->launched) L->launched = want;
     }
-    c->slot_launch = (uint32_t)L->launched;
-    struct SlotLaunchReset {
-        molar_hip_ctx *c;
-        ~SlotLaunchReset() { c->slot_launch = 0u; }
-    } slot_launch_reset{c};
+    call.slot_launch = (uint32_t)L->launched;
     Prof frame_span(c, 5);       // (profile mode 2 only: count + offsets + fill between ONE pair of events)
     // one parameter block serves both passes: the count pass ignores the output capacity
-    MH_TRY(launch_pairs<false>(c, nullptr, nullptr, nullptr, 0, 0.f, 0.f, nullptr, cap0));
-    if (c->record_count_done) {
-        MH_HIP(hipEventRecord(c->count_done, c->stream));
-        c->count_done_set = true;
-    }
+    MH_TRY(launch_pairs<false>(c, call, PairOut{}));
     {
         Prof prof(c, 2);
         MH_TRY(scan_slot_counts(c, (unsigned long long *)sizes_dev));
     }
-    if (cap0) MH_TRY(launch_pairs<true>(c, outP.as<uint2>(), c->resident_no_dist ? nullptr : outD.as<float>(), nullptr, 0, 0.f, 0.f, nullptr, cap0,
+    if (cap0) MH_TRY(launch_pairs<true>(c, call, PairOut{outP.as<uint2>(), pairs_only ? nullptr : outD.as<float>()}, HistTarget{},
                                         /*params_resident=*/true));
     if (!sizes_dev) {
         MH_HIP(hipMemcpyAsync(sizes, c->slot_base.as<unsigned long long>() + c->nslots_bound, 8, hipMemcpyDeviceToHost, c->stream));
@@ -2413,7 +2439,7 @@ static bool resident_covered(molar_hip_ctx *c, const void *sizes, unsigned long 
 
 // With `sizes` delivered and the search still the context's cached one: grow what was too small and repeat the
 // affected passes (first frame of a trajectory; later frames are the same size +- noise).
-static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD, const void *sizes, const ResidentLaunch &L) {
+static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD, const void *sizes, const ResidentLaunch &L, bool pairs_only) {
     const bool fast_kind = c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE;
     unsigned long long res[2] = {0, 0};
     std::memcpy(res, sizes, 16);
@@ -2424,7 +2450,7 @@ static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD,
     if (c->mask_units > L.maskcap0) {        // hit bits did not fit: grow, record them, fill again
         if (c->mask_units > c->maskbuf.cap / 256u)
             MH_TRY(c->maskbuf.reserve((size_t)(c->mask_units + c->mask_units / 4u) * 256u + 256u));
-        MH_TRY(launch_pairs<false>(c, nullptr, nullptr, nullptr));
+        MH_TRY(launch_pairs<false>(c, SearchCall{}, PairOut{}));
         refill = true;
     }
     if (c->total > L.cap0) {
@@ -2433,23 +2459,23 @@ static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD,
         refill = true;
     }
     if (refill && c->total) {
-        MH_TRY(launch_pairs<true>(c, outP.as<uint2>(), c->resident_no_dist ? nullptr : outD.as<float>(), nullptr));
+        MH_TRY(launch_pairs<true>(c, SearchCall{}, PairOut{outP.as<uint2>(), pairs_only ? nullptr : outD.as<float>()}));
         MH_HIP(hipStreamSynchronize(c->stream));   // like the common case, the result is complete when the call returns
     }
     return 0;
 }
 
 // One whole resident search, complete when the call returns (the stream has been waited for).
-static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD) {
+static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD, bool pairs_only) {
     MH_TRY(ensure_pinned(c, 64));
     ResidentLaunch L;
     std::memset(c->h_pinned, 0, 32);
-    MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L));
+    MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
     if (L.degenerate) return 0;
     MH_HIP(hipStreamSynchronize(c->stream));
     if (!resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->kind)) {       // too few slots launched: once more, over the bound
         std::memset(c->h_pinned, 0, 32);
-        MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L));
+        MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
         MH_HIP(hipStreamSynchronize(c->stream));
         (void)resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->kind);
     }
@@ -2458,7 +2484,7 @@ static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::De
         std::memcpy(&occ, (const char *)c->h_pinned + 24, 8);
         occ_note(c, occ_key_of(c), occ);
     }
-    return resident_settle(c, outP, outD, c->h_pinned, L);
+    return resident_settle(c, outP, outD, c->h_pinned, L, pairs_only);
 }
 
 }  // extern "C"
@@ -2467,19 +2493,11 @@ static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::De
 int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, void *sizes_pinned, ResidentLaunch *L,
                                 const unsigned long long **total_dev, const uint32_t **pairs_dev, bool drop_nonfinite) {
     std::memset(sizes_pinned, 0, 24);
-    {   // the chained stages (the membrane's patches) read the (i, j) plane only; their passes launch the bound (searches of 1e4
-        // markers: nothing to trim, and nobody reads the plan's size back in between)
-        const bool keep = c->resident_no_dist;
-        const unsigned long long keep_trim = c->trim_real;
-        c->resident_no_dist = true;
-        c->trim_real = 0;
-        c->grid_drop_nonfinite = drop_nonfinite;
-        const int rc = resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, L);
-        c->grid_drop_nonfinite = false;
-        c->resident_no_dist = keep;
-        c->trim_real = keep_trim;
-        MH_TRY(rc);
-    }
+    // the chained stages (the membrane's patches) read the (i, j) plane only; their passes launch the bound (searches of 1e4
+    // markers: nothing to trim, and nobody reads the plan's size back in between)
+    SearchCall call;
+    call.drop_nonfinite = drop_nonfinite;
+    MH_TRY(resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, L, /*pairs_only=*/true, /*trim=*/false, call));
     c->have_search = false;              // the sizes are not known to the host: not a cached search for the fill calls
     *total_dev = L->degenerate ? nullptr : c->slot_base.as<unsigned long long>() + c->nslots_bound;
     *pairs_dev = c->out_pairs.as<uint32_t>();
@@ -2510,7 +2528,7 @@ int molar_hip_search_resident(molar_hip_ctx *c, const molar_hip_search_desc *q, 
     if (!c) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: null argument");
     // Count, scan and fill are enqueued back to back against the capacities left by earlier frames; one
     // read-back tells whether the hit-bit buffer or the result buffers were too small.
-    MH_TRY(resident_run(c, q, c->out_pairs, c->out_dist));
+    MH_TRY(resident_run(c, q, c->out_pairs, c->out_dist, c->resident_no_dist));
     if (out_count) *out_count = c->total;
     if (d_pairs) *d_pairs = c->out_pairs.as<uint32_t>();
     if (d_dist) *d_dist = c->resident_no_dist ? nullptr : c->out_dist.as<float>();
@@ -2543,25 +2561,19 @@ int molar_hip_search_resident_begin(molar_hip_ctx *c, const molar_hip_search_des
     T.desc = *q;
     ResidentLaunch L;
     c->set = c->set_store[slot];         // this ticket's grid generation (the other one may still be read by the frame in flight)
-    c->want_side = !c->env_no_side;
-    c->side_wait = c->gen_free[slot];    // an asynchronous histogram call may have been the last reader of this generation
+    SearchCall call;
+    call.side = !c->env_no_side;
+    call.side_wait = c->gen_free[slot];  // an asynchronous histogram call may have been the last reader of this generation
     // The grid of this frame is built on the side stream beside the kernels of the frame in flight, in one-wave workgroups
     // (place_order_kernel) so that it gets wave slots while they run.  Nothing about that is free: whatever shares the chip
     // with a pair kernel stretches it by about its own stand-alone duration (round 4: 115 us of grid kernels cost the fill
     // pass 40-60 us when they ran under it, the count pass 35-50 us when they run under that; frames/s the same in six
     // alternations).  The grid starts as soon as its generation is free - it then runs under the COUNT pass of the frame in
     // flight, whose workgroups leave one wave slot per SIMD open, and the fill pass has the chip and the write path to
-    // itself.  MOLAR_HIP_GRID_LATE holds it back until that count pass has ended (the round-3 order).
-    c->side_wait2 = (c->count_done_set && c->env_grid_late) ? c->count_done : nullptr;
-    if (c->env_grid_late && !c->count_done) MH_HIP(hipEventCreateWithFlags(&c->count_done, hipEventDisableTiming));
-    c->record_count_done = c->env_grid_late;
+    // itself.  (Holding it back until that count pass has ended - the round-3 order - gave the same frames/s.)
     std::memset((char *)c->h_sizes + 32 * slot + 24, 0, 8);      // (occupied cells: zero = not reported)
-    const int erc = resident_enqueue(c, q, c->out_pairs_set[slot], c->out_dist_set[slot], (char *)c->h_sizes + 32 * slot, &L);
-    c->record_count_done = false;
-    c->want_side = false;
-    c->side_wait = nullptr;
-    c->side_wait2 = nullptr;
-    MH_TRY(erc);
+    MH_TRY(resident_enqueue(c, q, c->out_pairs_set[slot], c->out_dist_set[slot], (char *)c->h_sizes + 32 * slot, &L, c->resident_no_dist,
+                            /*trim=*/true, call));
     MH_HIP(hipEventRecord(T.done, c->stream));
     T.cap0 = L.cap0;
     T.maskcap0 = L.maskcap0;
@@ -2614,12 +2626,12 @@ int molar_hip_search_resident_end(molar_hip_ctx *c, int32_t ticket, uint64_t *ou
                 }
                 MH_TRY(ensure_pinned(c, 64));
                 std::memset(c->h_pinned, 0, 32);
-                MH_TRY(resident_enqueue(c, &T.desc, outP, outD, c->h_pinned, &L));
+                MH_TRY(resident_enqueue(c, &T.desc, outP, outD, c->h_pinned, &L, c->resident_no_dist));
                 MH_HIP(hipStreamSynchronize(c->stream));
                 sizes = c->h_pinned;
                 (void)resident_covered(c, sizes, L.launched, L.ntasks, T.kind);      // (launched over the bound: covered)
             }
-            MH_TRY(resident_settle(c, outP, outD, sizes, L));
+            MH_TRY(resident_settle(c, outP, outD, sizes, L, c->resident_no_dist));
             MH_HIP(hipStreamSynchronize(c->stream));
             total = c->total;
         }
@@ -2740,23 +2752,19 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
     // histogram kernel of the frame before (each generation's last reader is marked by an event on the main stream).
     const bool async = is_device_ptr(bins) && !out_count && !c->tickets[0].pending && !c->tickets[1].pending;
     int gen = 0;
+    SearchCall call;
     if (async) {
         MH_HIP(hipSetDevice(c->device));
         gen = (c->hist_gen ^= 1);
         c->set = c->set_store[gen];
-        c->side_wait = c->gen_free[gen];
-        c->want_side = !c->env_no_side;
+        call.side_wait = c->gen_free[gen];
+        call.side = !c->env_no_side;
     }
     // the fixed-cutoff kinds plan inside launch_pairs (hist_plan_kernel): prepare_search builds the grid only
-    const bool hist_plan = q->kind == MOLAR_HIP_SEARCH_SINGLE || q->kind == MOLAR_HIP_SEARCH_DOUBLE;
-    c->skip_plan = hist_plan;
-    c->hist_plan_now = hist_plan;
-    const int prc = prepare_search(c, q, /*size_masks=*/false);     // the fused pass records no hit bits
-    c->skip_plan = false;
-    c->hist_plan_now = false;
-    c->want_side = false;
-    c->side_wait = nullptr;
-    MH_TRY(prc);
+    call.hist_plan = q->kind == MOLAR_HIP_SEARCH_SINGLE || q->kind == MOLAR_HIP_SEARCH_DOUBLE;
+    call.plan = !call.hist_plan;
+    call.size_masks = false;                 // the fused pass records no hit bits
+    MH_TRY(prepare_search(c, q, call));
     if (out_count) *out_count = 0;
     if (c->have_search) return MOLAR_HIP_OK;     // degenerate (empty vdw input)
     // single pass: no counts, no offsets - every emitted distance goes straight into the histogram
@@ -2764,7 +2772,7 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
     if (async) {
         // bins in device memory and no count wanted: the kernels add straight into the caller's bins (integer atomics:
         // the same sums) - no scratch histogram to zero before and to add after, two launches less per frame
-        MH_TRY(launch_pairs<true>(c, nullptr, nullptr, nullptr, (uint32_t)nbins, hmin, hmax, reinterpret_cast<unsigned long long *>(bins)));
+        MH_TRY(launch_pairs<true>(c, call, PairOut{}, HistTarget{(uint32_t)nbins, hmin, hmax, reinterpret_cast<unsigned long long *>(bins)}));
         if (!c->gen_free[gen]) MH_HIP(hipEventCreateWithFlags(&c->gen_free[gen], hipEventDisableTiming));
         MH_HIP(hipEventRecord(c->gen_free[gen], c->stream));
         return MOLAR_HIP_OK;
@@ -2772,8 +2780,8 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
     MH_TRY(c->hist.reserve((nbins + 1) * 8));
     hipLaunchKernelGGL(zero2_kernel, dim3(1), dim3(256), 0, c->stream, c->hist.as<uint32_t>(), (nbins + 1) * 2, (uint32_t *)nullptr,
                        (size_t)0);
-    MH_TRY(launch_pairs<true>(c, nullptr, nullptr, nullptr, (uint32_t)nbins, hmin, hmax, c->hist.as<unsigned long long>(), ~0ull, false,
-                              c->hist.as<unsigned long long>() + nbins));
+    MH_TRY(launch_pairs<true>(c, call, PairOut{},
+                              HistTarget{(uint32_t)nbins, hmin, hmax, c->hist.as<unsigned long long>(), c->hist.as<unsigned long long>() + nbins}));
     if (is_device_ptr(bins)) {
         hipLaunchKernelGGL(add_u64_kernel, dim3((unsigned)((nbins + 255) / 256)), dim3(256), 0, c->stream,
                            reinterpret_cast<unsigned long long *>(bins), c->hist.as<unsigned long long>(), nbins);
@@ -2804,12 +2812,13 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
 //   main stream : one hist_kernel over the joint list.
 // Two generations of everything the side stream writes; the side stream starts on a generation when the launch two before has
 // ended (gen_free, the event the asynchronous single-frame calls use as well: the two forms may be mixed on a context).
-// Returns 1 when the group does not qualify (the caller then walks it frame by frame), 0 when enqueued.
+// *batched: false when the group does not qualify (nothing was enqueued: the caller then walks it frame by frame).
 constexpr int HIST_BATCH = MH_HIST_BATCH;
 static_assert(HIST_BATCH <= (int)(sizeof(((molar_hip_ctx *)nullptr)->hb_sets[0]) / sizeof(((molar_hip_ctx *)nullptr)->hb_sets[0][0])), "hb_sets holds a group");
 
 static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, size_t first, int W, size_t stride1, size_t stride2,
-                             const float *boxes9, float hmin, float hmax, size_t nbins, unsigned long long *bins) {
+                             const float *boxes9, float hmin, float hmax, size_t nbins, unsigned long long *bins, bool *batched) {
+    *batched = false;
     // ---- what every frame of the group comes to on the host: box, grid dims.  One shape for all of them, or no batch.
     const float cutoff = q->cutoff;
     if (!(cutoff > 0.0f)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: cutoff must be positive (got %g)", (double)cutoff);
@@ -2817,7 +2826,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     const int nsets = two ? 2 : 1;
     const size_t nsel[2] = {q->idx1 ? q->n1 : q->natoms1, two ? (q->idx2 ? q->n2 : q->natoms2) : 0};
     for (int s = 0; s < nsets; ++s)
-        if (nsel[s] == 0 || nsel[s] >= 0x7FFFFFFFull || (s ? q->natoms2 : q->natoms1) >= 0xFFFFFFFFull) return 1;
+        if (nsel[s] == 0 || nsel[s] >= 0x7FFFFFFFull || (s ? q->natoms2 : q->natoms1) >= 0xFFFFFFFFull) return 0;
     molar_hip_box boxes[HIST_BATCH];
     uint32_t dims[3] = {0, 0, 0};
     for (int f = 0; f < W; ++f) {
@@ -2828,12 +2837,12 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
         c->box = boxes[f];
         MH_TRY(dims_from_extents(c, cutoff, ext));
         if (f == 0) for (int d = 0; d < 3; ++d) dims[d] = c->dims[d];
-        else if (dims[0] != c->dims[0] || dims[1] != c->dims[1] || dims[2] != c->dims[2]) return 1;
+        else if (dims[0] != c->dims[0] || dims[1] != c->dims[1] || dims[2] != c->dims[2]) return 0;
     }
     const uint64_t ncells64 = (uint64_t)dims[0] * dims[1] * dims[2];
-    if (ncells64 + 1 > 32768ull) return 1;                                   // one-wave scan per frame
+    if (ncells64 + 1 > 32768ull) return 0;                                   // one-wave scan per frame
     for (int s = 0; s < nsets; ++s)
-        if ((uint64_t)nsel[s] > 384ull * ncells64) return 1;               // big cells are ordered by a device sort
+        if ((uint64_t)nsel[s] > 384ull * ncells64) return 0;               // big cells are ordered by a device sort
     const uint32_t ncells = (uint32_t)ncells64;
     const uint32_t n[2] = {(uint32_t)nsel[0], (uint32_t)nsel[1]};
     c->kind = q->kind;
@@ -2846,7 +2855,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     // slots of one frame (prepare_search) incl. the 32-row slots of the same-cell entries
     const uint64_t bound1 = (two ? 28ull : 14ull) * (((uint64_t)n[0] + 63ull) / 64ull) + c->ntasks + 28ull * 512ull + ((uint64_t)n[0] + 31ull) / 32ull + ncells64;
     const uint64_t bound = bound1 * (uint64_t)W;
-    if (bound >= 0xFFFFFFF0ull) return 1;
+    if (bound >= 0xFFFFFFF0ull) return 0;
     const int gen = (c->hist_gen ^= 1);
     MH_TRY(c->hb_lean[gen].reserve((bound1 * HIST_BATCH + 1) * sizeof(SlotDesc)));
     MH_TRY(c->hb_rest[gen].reserve((bound1 * HIST_BATCH + 1) * sizeof(SlotDesc)));
@@ -2856,12 +2865,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
         MH_HIP(hipHostMalloc(&c->hb_pin, 4 * blk_bytes, hipHostMallocDefault));
         for (auto &e : c->hb_pin_ev) MH_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    if (!c->side_stream) {
-        int lo = 0, hi = 0;
-        MH_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        MH_HIP(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, hi));
-        MH_HIP(hipEventCreateWithFlags(&c->grid_done, hipEventDisableTiming));
-    }
+    MH_TRY(ensure_side_stream(c));
     MH_TRY(ensure_hist_edges(c, hmin, hmax, nbins));
     if (!c->hist_queue.p) {
         MH_TRY(c->hist_queue.reserve(hist_queue_words() * 4));
@@ -2878,11 +2882,11 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     GridFrame *hG = reinterpret_cast<GridFrame *>(pin + HIST_BATCH * sizeof(SearchParams));
     SearchParams *dP = c->hb_blocks[gen].as<SearchParams>();
     GridFrame *dG = reinterpret_cast<GridFrame *>((char *)c->hb_blocks[gen].p + HIST_BATCH * sizeof(SearchParams));
-    mh::GridSet *keep_set = c->set;
     const uint32_t pad_shift[2] = {grid_pad_shift(n[0], ncells), two ? grid_pad_shift(n[1], ncells) : 0u};
     size_t dyn_lds = (size_t)nbins * 4;
     bool big = false;
     for (int f = 0; f < W; ++f) {
+        Restore<mh::GridSet *> cached_set(c->set);         // make_params reads the frame's sets through c->set
         mh::GridSet *SS = c->hb_sets[gen][f];
         for (int s = 0; s < nsets; ++s) {
             mh::GridSet &S = SS[s];
@@ -2890,8 +2894,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
             S.d_xyz = s ? q->xyz2 + (first + f) * stride2 : q->xyz1 + (first + f) * stride1;
             S.d_idx = s ? q->idx2 : q->idx1;
             S.d_vdw = nullptr;
-            const int rrc = grid_reserve(S, ncells);
-            if (rrc) { c->set = keep_set; return rrc; }
+            MH_TRY(grid_reserve(S, ncells));
         }
         c->box = boxes[f];
         c->set = SS;                              // (SINGLE: set[1] is never read)
@@ -2917,7 +2920,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
         for (int s = 0; s < nsets; ++s) {
             mh::GridSet &S = SS[s];
             GridFrame g{};
-            g.P = grid_bin_params(c, S);
+            g.P = grid_bin_params(c, S, /*drop_nonfinite=*/false);
             g.key = S.key.as<uint32_t>();
             g.cursor = S.cursor.as<uint32_t>();
             g.cell_count = S.cell_count.as<uint32_t>();
@@ -2933,7 +2936,6 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
             hG[s * HIST_BATCH + f] = g;
         }
     }
-    c->set = keep_set;
     // ---- side stream: records, grids, plans
     hipStream_t ss = c->side_stream;
     if (c->gen_free[gen]) MH_HIP(hipStreamWaitEvent(ss, c->gen_free[gen], 0));
@@ -2993,6 +2995,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     }
     if (!c->gen_free[gen]) MH_HIP(hipEventCreateWithFlags(&c->gen_free[gen], hipEventDisableTiming));
     MH_HIP(hipEventRecord(c->gen_free[gen], c->stream));
+    *batched = true;
     return 0;
 }
 
@@ -3014,12 +3017,10 @@ int molar_hip_search_histogram_frames(molar_hip_ctx *c, const molar_hip_search_d
     size_t f = 0;
     while (f < nframes) {
         const int W = (int)std::min<size_t>(HIST_BATCH, nframes - f);
-        int rc = 1;
-        if (batch && W >= 2) {
-            rc = hist_frames_group(c, q, f, W, xyz1_stride, xyz2_stride, boxes9, hmin, hmax, nbins, reinterpret_cast<unsigned long long *>(bins));
-            if (rc < 0 || rc > 1) return rc;
-        }
-        if (rc == 1) {               // frame by frame (the form molar_hip_search_histogram documents), same sums
+        bool batched = false;
+        if (batch && W >= 2)
+            MH_TRY(hist_frames_group(c, q, f, W, xyz1_stride, xyz2_stride, boxes9, hmin, hmax, nbins, reinterpret_cast<unsigned long long *>(bins), &batched));
+        if (!batched) {              // frame by frame (the form molar_hip_search_histogram documents), same sums
             for (int k = 0; k < W; ++k) {
                 molar_hip_search_desc qf = *q;
                 qf.xyz1 = q->xyz1 + (f + k) * xyz1_stride;
@@ -3179,7 +3180,9 @@ int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
     molar_hip_ctx *s = K.s;
     molar_hip_search_desc qq = *q;
     qq.ids_local = 1;                       // ids are positions in the selection, whatever the caller's list would carry
-    MH_TRY(prepare_search(s, &qq, /*size_masks=*/false));      // (the plan kernel leaves the parameter block in s->params)
+    SearchCall call;
+    call.size_masks = false;
+    MH_TRY(prepare_search(s, &qq, call));      // (the plan kernel leaves the parameter block in s->params)
     s->params_fresh = false;
     if (s->nslots_bound == 0) return 0;
     ContactArgs A{};
@@ -3261,10 +3264,11 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within: null argument");
     if (q->kind != MOLAR_HIP_SEARCH_WITHIN) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within: the request must be of kind MOLAR_HIP_SEARCH_WITHIN");
     c->have_within = false;
-    c->skip_plan = true;                          // no slots, no offsets: this path walks cells
-    const int prc = prepare_search(c, q, /*size_masks=*/false);
-    c->skip_plan = false;
-    MH_TRY(prc);
+    SearchCall call;
+    call.plan = false;                            // no slots, no offsets: this path walks cells
+    call.size_masks = false;
+    call.within_set = true;
+    MH_TRY(prepare_search(c, q, call));
     c->have_search = false;                       // not a cached search for the fill calls of the stream form
     const uint64_t nflags = q->ids_local ? c->set[0].n : (q->idx1 ? q->natoms1 : c->set[0].n);
     c->within_nflags = nflags;
@@ -3393,15 +3397,10 @@ int molar_hip_search_connectivity(molar_hip_ctx *c, const molar_hip_search_desc 
     if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity: ids of one selection index the lists - the request must be of kind MOLAR_HIP_SEARCH_SINGLE");
     c->have_conn = false;
-    uint64_t npairs = 0;
-    const uint32_t *d_pairs = nullptr;
-    {   // the lists hold ids only: the (i, j) plane alone (DistanceSearchOutput of (usize, usize), distance_search.rs:14-20)
-        const bool keep = c->resident_no_dist;
-        c->resident_no_dist = true;
-        const int rc = molar_hip_search_resident(c, q, &npairs, &d_pairs, nullptr);
-        c->resident_no_dist = keep;
-        MH_TRY(rc);
-    }
+    // the lists hold ids only: the (i, j) plane alone (DistanceSearchOutput of (usize, usize), distance_search.rs:14-20)
+    MH_TRY(resident_run(c, q, c->out_pairs, c->out_dist, /*pairs_only=*/true));
+    const uint64_t npairs = c->total;
+    const uint32_t *d_pairs = c->out_pairs.as<uint32_t>();
     const size_t nsel = q->idx1 ? q->n1 : q->natoms1;
     const uint64_t nrows = q->ids_local ? nsel : (q->idx1 ? q->natoms1 : nsel);
     if (nrows >= 0xFFFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity: too many rows");

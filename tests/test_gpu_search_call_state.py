@@ -1,0 +1,178 @@
+"""A request that fails, or a request of another form, leaves nothing behind for the next one on the same context.
+
+What one request asks of the shared search helpers (plan or not, side stream, output capacity, pairs plane only, dropping
+non-finite atoms ...) travels as an argument of the call; the context keeps only what outlasts a request.  Every comparison
+here is bit for bit against the same request on a freshly created Engine; the single and double lists of the sequence are
+compared once against the f32 oracle as well.  The error cases are argument errors that prepare_search returns: nothing
+reaches the device."""
+import numpy as np
+import pytest
+
+from molar_amd import synth
+
+pytestmark = pytest.mark.gpu
+
+N, N2 = 4096, 512
+CUTOFF = 0.8          # a cube of 4096 atoms at 100 atoms / nm^3 is 3.45 nm across: 4 x 4 x 4 cells (side stream, plan, both passes)
+HIST = (0.0, 0.8, 64)
+
+
+@pytest.fixture(scope="module")
+def a():
+    from molar_amd import build
+    import molar_amd.api as api
+    build.build_library()
+    return api
+
+
+@pytest.fixture(scope="module")
+def sys_(a):
+    import torch
+    box = synth.box_ortho(N)
+    pos = synth.frame(N, box, 0)
+    pos2 = synth.frame(N2, box, 7, seed=4321)
+    pos2b = synth.frame(N2, box, 8, seed=999)
+    box_mid = (box * np.float32(1.3)).astype(np.float32)          # 5 x 5 x 5 cells at the same cutoff
+    frames = np.stack([pos, synth.frame(N, box_mid, 1), synth.frame(N, box, 2)])
+    nan = pos.copy()
+    nan[1234, 1] = np.nan
+    s = dict(box=box, pos=pos, pos2=pos2, nan=nan, frames=frames, boxes=np.stack([box, box_mid, box]),
+             d_pos=torch.from_numpy(pos).cuda(), d_pos2=torch.from_numpy(pos2).cuda(), d_pos2b=torch.from_numpy(pos2b).cuda(),
+             d_frames=torch.from_numpy(frames).cuda())
+    e = a.Engine(0)
+    e.search_count(a.SEARCH_SINGLE, CUTOFF, pos, box=box, pbc=7)
+    dims = tuple(e.grid_dims())
+    assert min(dims) >= 3
+    e.search_count(a.SEARCH_SINGLE, CUTOFF, frames[1], box=box_mid, pbc=7)
+    assert tuple(e.grid_dims()) != dims          # the middle frame of the block takes the frames form off its batched path
+    return s
+
+
+def count_fill(a, e, s, pos=None):
+    cnt = e.search_count(a.SEARCH_SINGLE, CUTOFF, s["pos"] if pos is None else pos, box=s["box"], pbc=7)
+    return (cnt,) + e.search_fill(cnt)
+
+
+def same_list(got, want, what):
+    assert got[0] == want[0] > 0, what
+    assert got[1].tobytes() == want[1].tobytes() and got[2].tobytes() == want[2].tobytes(), what
+
+
+def resident_arrays(a, res, want_dist=True):
+    import torch
+    cnt, pp, dp = res
+    pairs = a.device_view(pp, (cnt, 2), torch.int32).cpu().numpy().view(np.uint32)
+    if not want_dist:
+        return cnt, pairs, None
+    assert dp, "the resident search must deliver distances"
+    return cnt, pairs, a.device_view(dp, (cnt,), torch.float32).cpu().numpy()
+
+
+def bins_tensor():
+    import torch
+    return torch.zeros(HIST[2], dtype=torch.int64, device="cuda")
+
+
+@pytest.fixture(scope="module")
+def fresh_single(a, sys_):
+    return count_fill(a, a.Engine(0), sys_)
+
+
+def test_failed_asynchronous_histogram_leaves_no_side_stream_or_skipped_plan(a, sys_, fresh_single):
+    """(a) device bins, no count, cutoff 0: fails in prepare_search after the call asked for the side stream and for no plan."""
+    e = a.Engine(0)
+    with pytest.raises(a.MolarHipError):
+        e.search_histogram(a.SEARCH_SINGLE, 0.0, *HIST, sys_["d_pos"], box=sys_["box"], pbc=7, bins=bins_tensor(), want_count=False)
+    same_list(count_fill(a, e, sys_), fresh_single, "count + fill after the failed histogram")
+
+
+def test_failed_within_set_leaves_planning_on(a, sys_, fresh_single):
+    """(b) no box, no lower / upper: fails in prepare_search with planning switched off."""
+    e = a.Engine(0)
+    with pytest.raises(a.MolarHipError):
+        e.within_set(CUTOFF, sys_["d_pos"], xyz2=sys_["d_pos2"])
+    same_list(count_fill(a, e, sys_), fresh_single, "count + fill after the failed within_set")
+
+
+def test_failed_resident_begin_leaves_both_tickets_and_the_distances(a, sys_):
+    """(c) begin with cutoff 0 fails; both tickets stay free, their results are the plain call's, distances still come."""
+    e, f = a.Engine(0), a.Engine(0)
+    bad, _k0 = e.make_search_desc(a.SEARCH_SINGLE, 0.0, sys_["d_pos"], box=sys_["box"], pbc=7)
+    with pytest.raises(a.MolarHipError):
+        e.search_resident_begin(bad)
+    want = resident_arrays(a, f.search_resident(a.SEARCH_SINGLE, CUTOFF, sys_["d_pos"], box=sys_["box"], pbc=7))
+    good, _k1 = e.make_search_desc(a.SEARCH_SINGLE, CUTOFF, sys_["d_pos"], box=sys_["box"], pbc=7)
+    t0 = e.search_resident_begin(good)
+    t1 = e.search_resident_begin(good)
+    assert {t0, t1} == {0, 1}
+    for t in (t0, t1):
+        same_list(resident_arrays(a, e.search_resident_end(t)), want, f"ticket {t}")
+    same_list(resident_arrays(a, e.search_resident(a.SEARCH_SINGLE, CUTOFF, sys_["d_pos"], box=sys_["box"], pbc=7)), want, "plain call")
+
+
+def sequence(a, e, s):
+    """(d) one request of every form; returns what each step produced."""
+    import torch
+    out = {}
+    b = bins_tensor()
+    e.search_histogram(a.SEARCH_SINGLE, CUTOFF, *HIST, s["d_pos"], box=s["box"], pbc=7, bins=b, want_count=False)
+    e.synchronize()
+    out["hist"] = b.cpu().numpy()
+    e.within_hold(True)
+    dev_ids = lambda n: torch.empty(n, dtype=torch.int64, device="cuda")
+    out["within1"] = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2"], box=s["box"], pbc=7, device_out=dev_ids).cpu().numpy()
+    out["within2"] = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2b"], box=s["box"], pbc=7, device_out=dev_ids).cpu().numpy()
+    e.within_hold(False)
+    c = e.search_contacts(a.SEARCH_SINGLE, CUTOFF, s["d_pos"], box=s["box"], pbc=7)
+    out["contacts"] = (c.count, c.deg1.cpu().numpy())
+    out["conn"] = e.search_connectivity(CUTOFF, s["d_pos"], box=s["box"], pbc=7)
+    out["double"] = resident_arrays(a, e.search_resident(a.SEARCH_DOUBLE, CUTOFF, s["d_pos"], xyz2=s["d_pos2"], box=s["box"], pbc=7))
+    b = bins_tensor()
+    e.search_histogram_frames(a.SEARCH_SINGLE, CUTOFF, *HIST, s["d_frames"], box=s["boxes"], pbc=7, bins=b)
+    e.synchronize()
+    out["hist_frames"] = b.cpu().numpy()
+    out["single"] = count_fill(a, e, s)
+    return out
+
+
+def same_sequence(got, want, what):
+    for k in ("hist", "within1", "within2", "hist_frames"):
+        assert got[k].dtype == want[k].dtype and got[k].tobytes() == want[k].tobytes() and got[k].any(), f"{what}: {k}"
+    assert got["contacts"][0] == want["contacts"][0] > 0 and got["contacts"][1].tobytes() == want["contacts"][1].tobytes(), f"{what}: contacts"
+    for g, w in zip(got["conn"], want["conn"]):
+        assert g.tobytes() == w.tobytes() and len(g) > 1, f"{what}: connectivity"
+    same_list(got["double"], want["double"], f"{what}: resident double search")
+    same_list(got["single"], want["single"], f"{what}: count + fill")
+
+
+def test_requests_of_every_form_in_turn_equal_a_fresh_engine(a, sys_, orc32):
+    s = sys_
+    want = sequence(a, a.Engine(0), s)
+    ob = orc32.box_from_matrix(s["box"])
+    ref = orc32.search_single_pbc(CUTOFF, s["pos"], ob, 7, nthreads=4)
+    cnt, pairs, dist = want["single"]
+    assert cnt == len(ref["i"]) and np.array_equal(pairs[:, 0], ref["i"]) and np.array_equal(pairs[:, 1], ref["j"]) and np.array_equal(dist, ref["d"])
+    ref = orc32.search_double_pbc(CUTOFF, s["pos"], s["pos2"], ob, 7, nthreads=4)
+    cnt, pairs, dist = want["double"]
+    assert cnt == len(ref["i"]) and np.array_equal(pairs[:, 0], ref["i"]) and np.array_equal(pairs[:, 1], ref["j"]) and np.array_equal(dist, ref["d"])
+    e = a.Engine(0)
+    for rnd in range(2):             # the second round starts from whatever the first left
+        same_sequence(sequence(a, e, s), want, f"round {rnd}")
+
+
+def test_membrane_frame_then_a_search_with_a_nan_coordinate(a, sys_):
+    """(e) the membrane's marker search drops non-finite atoms from its grid and fills the pairs plane only; a plain search
+    behind it on the same context bins a NaN atom the way the reference does and delivers distances."""
+    from molar_amd import membrane as mb
+    xyz, box, first, tpl, masses = mb.build_bilayer(20, 3000)
+    e, f = a.Engine(0), a.Engine(0)
+    res = []
+    for eng in (e, f):
+        m = mb.Membrane(eng, len(xyz), first, tpl, masses, mb.MembraneOptions(cutoff=1.5, order_type=1))
+        assert m.fusable()
+        res.append(m.compute_end(m.compute_begin(xyz.copy(), box)))
+    for k in ("patch_off", "patch_ids", "normals", "valid"):
+        assert np.ascontiguousarray(res[0][k]).tobytes() == np.ascontiguousarray(res[1][k]).tobytes(), k
+    assert len(res[0]["patch_ids"]) > 0
+    want = count_fill(a, a.Engine(0), sys_, pos=sys_["nan"])
+    same_list(count_fill(a, e, sys_, pos=sys_["nan"]), want, "count + fill of a frame with a NaN after the membrane frame")
