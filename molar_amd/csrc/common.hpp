@@ -117,6 +117,25 @@ struct GridSet {
     DevBuf cell_org;           // float4 per cell: origin (centre of the bounding box), .w = bound on |position - origin|
 };
 
+// ---------------------------------------------------------------- the shape of one search
+// What the host helpers of search.hip need to know about the search in hand; what follows from it alone (grid dimensions,
+// kernel family, slot bound, the policy for wrapped pairs) is in search_shape.hpp.  The context keeps one, the cached search;
+// a caller that describes frames which are not the cached search (hist_frames_group) builds its own and hands them down.
+struct SearchShape {
+    int kind = 0;
+    bool use_box = false;
+    uint8_t pbc = 0;
+    float cutoff = 0.f;
+    molar_hip_box box{};
+    float lower[3]{}, upper[3]{};
+    uint32_t dims[3]{1, 1, 1};
+    uint64_t ntasks = 0;
+    uint64_t nslots_bound = 0;   // host-side upper bound of the slot count (sizes the launches)
+    GridSet *set = nullptr;      // set[0], set[1]: the grids of the first / second set
+    uint32_t occ_use[2] = {0, 0};   // occupied cells of the two grids, latched per search from the context's hint
+                                    // (0: not known for this search, the grid's cell count stands in)
+};
+
 }  // namespace mh
 
 struct molar_hip_search64_state;        // the cached f64 search (search_f64.hip)
@@ -147,22 +166,21 @@ struct molar_hip_ctx {
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
     // ---- cached search (count -> fill)
+    // Three things describe a search, and only the first two are kept here:
+    //  * its SHAPE - kind, box, cutoff, grid dimensions, plan and slot bounds, the grid generation it refers to - is `cur`, one
+    //    value; the helpers of search.hip are functions of a shape, so frames that are not the cached search are described by
+    //    shapes of the caller's own and leave `cur` alone;
+    //  * what OUTLASTS a request: have_search / total / mask_units, the buffers, the hints (occ_key, occ_cells, occ_valid), the
+    //    tickets, the record of a held `within` grid;
+    //  * what ONE request asks of the shared helpers (plan or not, side stream, output capacity ...) travels down the call
+    //    chain as a SearchCall argument (search.hip).
     bool have_search = false;
-    int kind = 0;
-    bool use_box = false;
-    uint8_t pbc = 0;
-    float cutoff = 0.f;
-    molar_hip_box box{};
-    float lower[3]{}, upper[3]{};
-    uint32_t dims[3]{1, 1, 1};
-    uint64_t ntasks = 0;
+    mh::SearchShape cur;                 // the cached search; cur.set = the grid generation it refers to
     uint64_t total = 0;
     // Two generations of the grids: the pipelined resident search (molar_hip_search_resident_begin) builds the grid of
     // the next frame on `side_stream` while the pair kernels of the frame before it still read theirs.
     mh::GridSet set_store[2][2];
-    mh::GridSet *set = set_store[0];     // the generation the cached search refers to (set[0], set[1]: first / second set)
-    // What ONE request asks of the shared helpers (plan or not, side stream, output capacity ...) is not kept here: it travels
-    // down the call chain as a SearchCall argument (search.hip).
+    molar_hip_ctx() { cur.set = set_store[0]; }
     hipStream_t side_stream = nullptr;   // grid build of a pipelined search (created on first use, highest priority)
     hipEvent_t grid_done = nullptr;
     bool env_no_side = false;            // MOLAR_HIP_NO_SIDE_STREAM, read once in molar_hip_create
@@ -180,7 +198,6 @@ struct molar_hip_ctx {
     bool on_side = false;                // `stream` is side_stream for the grid build in hand (scans then use scan_tmp_side); set
                                          // and restored together with `stream` by one scope guard in prepare_search
     mh::DevBuf scan_tmp_side;
-    uint64_t nslots_bound = 0; // host-side upper bound of the slot count (sizes the launches)
     mh::DevBuf params;         // SearchParams block read by the pair kernels
     mh::DevBuf task_desc;      // TaskDesc per task (plan entry)
     mh::DevBuf task_nb;        // u32 per task (+1): 64-row blocks of the task, scanned in place -> first slot
@@ -220,11 +237,10 @@ struct molar_hip_ctx {
     void *h_sizes = nullptr;                // pinned: 32 bytes of result sizes per ticket (total, history units, slots, occupied cells)
     // Occupied cells of the two sets' grids as the last finished search of this shape found them (the grid build counts them, the
     // offsets kernel hands them to the host with the sizes): small_cell_lanes() judges a frame by its atoms per OCCUPIED cell when it
-    // knows - a slab or a solute in a mostly empty periodic box has a small mean and crowded cells.  occ_use: latched per search.
+    // knows - a slab or a solute in a mostly empty periodic box has a small mean and crowded cells.  Latched per search into cur.occ_use.
     unsigned long long occ_key = 0;
     uint32_t occ_cells[2] = {0, 0};
     bool occ_valid = false;
-    uint32_t occ_use[2] = {0, 0};           // 0: not known for the search in hand (the grid's cell count stands in)
     mh::DevBuf out_ids;
     mh::DevBuf wide_i, wide_j; // usize widening
     mh::DevBuf hist;           // u64 bins

@@ -27,6 +27,7 @@
 
 #include "pair_kernels.hpp"
 #include "contact_kernels.hpp"
+#include "search_shape.hpp"
 #include "stages.hpp"
 #include "unwrap_walk.hpp"
 
@@ -1031,13 +1032,14 @@ __global__ void __launch_bounds__(256) slot_offsets_kernel(const uint32_t *__res
 
 // slot counts -> output offsets (n = slots + 1 terminator), the grand total also to `sizes_host` (pinned, may be null)
 int scan_slot_counts(molar_hip_ctx *c, unsigned long long *sizes_host) {
-    const uint64_t n = c->nslots_bound + 1;
+    const SearchShape &cur = c->cur;
+    const uint64_t n = cur.nslots_bound + 1;
     const uint64_t ntiles = (n + 255) / 256;
     const uint32_t *occ[2] = {nullptr, nullptr};
     if (sizes_host) {
-        const size_t ncells = (size_t)c->dims[0] * c->dims[1] * c->dims[2];
-        for (int s = 0; s < (c->kind == MOLAR_HIP_SEARCH_SINGLE ? 1 : 2); ++s)
-            if (c->set[s].cell_count.cap >= (ncells + 1 + OCC_WORDS) * 4) occ[s] = c->set[s].cell_count.as<uint32_t>() + ncells + 1;
+        const size_t ncells = (size_t)grid_cells(cur);
+        for (int s = 0; s < (cur.kind == MOLAR_HIP_SEARCH_SINGLE ? 1 : 2); ++s)
+            if (cur.set[s].cell_count.cap >= (ncells + 1 + OCC_WORDS) * 4) occ[s] = cur.set[s].cell_count.as<uint32_t>() + ncells + 1;
     }
     if (ntiles <= SLOT_SCAN_MAX_TILES && !c->env_no_tile_sum) {
         MH_TRY(c->tile_sum.reserve(ntiles * 8));
@@ -1050,7 +1052,7 @@ int scan_slot_counts(molar_hip_ctx *c, unsigned long long *sizes_host) {
     }
     MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->slot_cnt.as<uint32_t>(), c->slot_base.as<unsigned long long>(), n)));
     if (sizes_host)
-        MH_HIP(hipMemcpyAsync(sizes_host, c->slot_base.as<unsigned long long>() + c->nslots_bound, 8, hipMemcpyDefault, c->stream));
+        MH_HIP(hipMemcpyAsync(sizes_host, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDefault, c->stream));
     return 0;
 }
 
@@ -1159,56 +1161,11 @@ __global__ void upload_params_kernel(SearchParams P, SearchParams *dst) {
 
 // ================================================================= host orchestration
 
-// Grid::from_cutoff_and_extents (distance_search.rs:103-110)
-int dims_from_extents(molar_hip_ctx *c, float cutoff, const float ext[3]) {
-    double cells = 1.0;
-    for (int d = 0; d < 3; ++d) {
-        const float q = std::floor(ext[d] / cutoff);
-        uint64_t s = (q > 0.0f) ? (q >= 4.0e9f ? 4000000000ull : (uint64_t)q) : 0ull;   // `as usize` saturates
-        if (s < 1) s = 1;
-        c->dims[d] = (uint32_t)s;
-        cells *= (double)s;
-    }
-    if (cells > 1.0e8)
-        return fail(MOLAR_HIP_ERR_TOO_LARGE, "search grid %u x %u x %u has too many cells (cutoff %g)", c->dims[0],
-                    c->dims[1], c->dims[2], (double)cutoff);
-    return 0;
-}
-
-// Frames of small cells (contact / hydrogen-bond cutoffs) of the fixed-cutoff kinds go to pair_small.hip: 16 lanes per slot up to 13
-// atoms per cell on average, 32 up to 19, 0 = the regular kernels (1M atoms: 0.30 / 0.35 / 0.40 / 0.45 / 0.50 nm take 1.30 / 1.00 /
-// 0.89 / 1.01 / 0.99 ms per frame against 2.91 / 2.14 / 1.66 / 1.30 / 1.07; at 0.55 nm - 23 atoms per cell - the regular kernels win).
-// Decided from the sets' sizes and the grid alone: the grid build (no spatial order for these) and both passes agree on it.
-int small_cell_lanes(const molar_hip_ctx *c) {
-#ifdef MH_NO_SMALL_CELLS
-    return 0;           // (A/B builds: every frame through the regular kernels)
-#endif
-    if (c->kind != MOLAR_HIP_SEARCH_SINGLE && c->kind != MOLAR_HIP_SEARCH_DOUBLE) return 0;
-    const uint64_t ncells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
-    // atoms per OCCUPIED cell where the last search of this shape has told (prepare_search latches occ_use), per cell otherwise
-    int lanes = 16;
-    const int nsets = c->kind == MOLAR_HIP_SEARCH_SINGLE ? 1 : 2;
-    for (int s = 0; s < nsets; ++s) {
-        const uint64_t cells = c->occ_use[s] ? std::min<uint64_t>(c->occ_use[s], ncells) : ncells;
-        const uint64_t n = c->set[s].n;
-        const int l = n <= 13ull * cells ? 16 : (n <= 19ull * cells ? 32 : 0);
-        lanes = (l == 0 || lanes == 0) ? 0 : std::max(lanes, l);
-    }
-    return lanes;
-}
-
-// the shape a grid's occupancy is remembered for
-static unsigned long long occ_key_of(const molar_hip_ctx *c) {
-    unsigned long long h = 1469598103934665603ull;
-    auto mix = [&](unsigned long long v) { h = (h ^ v) * 1099511628211ull; };
-    mix((unsigned long long)c->kind + 1u); mix(c->set[0].n); mix(c->kind == MOLAR_HIP_SEARCH_SINGLE ? 0u : c->set[1].n);
-    mix(c->dims[0]); mix(c->dims[1]); mix(c->dims[2]); mix(c->use_box ? 1u : 2u);
-    return h ? h : 1ull;
-}
+// the context's occupancy hint, if it is for the cached search's shape: what small_cell_lanes() and pair_family() answer from here on
 static void occ_latch(molar_hip_ctx *c) {
-    const bool known = c->occ_valid && c->occ_key == occ_key_of(c);
-    c->occ_use[0] = known ? c->occ_cells[0] : 0u;
-    c->occ_use[1] = known ? c->occ_cells[1] : 0u;
+    const bool known = c->occ_valid && c->occ_key == occ_key_of(c->cur);
+    c->cur.occ_use[0] = known ? c->occ_cells[0] : 0u;
+    c->cur.occ_use[1] = known ? c->occ_cells[1] : 0u;
 }
 static void occ_note(molar_hip_ctx *c, unsigned long long key, unsigned long long packed) {
     if (!key || !(uint32_t)packed) return;          // (a search that did not report: the hint stays as it is)
@@ -1216,13 +1173,6 @@ static void occ_note(molar_hip_ctx *c, unsigned long long key, unsigned long lon
     c->occ_cells[0] = (uint32_t)packed;
     c->occ_cells[1] = (uint32_t)(packed >> 32);
     c->occ_valid = true;
-}
-
-// Does the count pass of this search record hit history for the fill pass to replay?  The fixed-cutoff kinds do - except on
-// frames of small cells: pair_small.hip evaluates in both passes and never touches the buffer, so its plan accounts for none
-// (a plan that did made the first resident frame of such a trajectory grow the buffer and run count and fill again for nothing).
-static bool records_hit_history(const molar_hip_ctx *c) {
-    return (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE) && small_cell_lanes(c) == 0;
 }
 
 // What ONE request asks of the helpers below (prepare_search, build_grid, the plan, launch_pairs), beyond its descriptor.  It
@@ -1240,17 +1190,17 @@ struct SearchCall {
     uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
 };
 
-// restores a field of the context on every exit from the scope
-template <class T>
-struct Restore {
-    T &ref;
-    const T old;
-    explicit Restore(T &r) : ref(r), old(r) {}
-    ~Restore() { ref = old; }
-    Restore(const Restore &) = delete;
-};
 // launches go to the side stream while one of these lives (c->stream and c->on_side move together)
 struct OnSideStream {
+    // restores a field of the context on every exit from the scope
+    template <class T>
+    struct Restore {
+        T &ref;
+        const T old;
+        explicit Restore(T &r) : ref(r), old(r) {}
+        ~Restore() { ref = old; }
+        Restore(const Restore &) = delete;
+    };
     Restore<hipStream_t> stream;
     Restore<bool> on_side;
     explicit OnSideStream(molar_hip_ctx *c) : stream(c->stream), on_side(c->on_side) {
@@ -1269,23 +1219,23 @@ static int ensure_side_stream(molar_hip_ctx *c) {
     return 0;
 }
 
-// what the grid kernels take of the request (the context's cached search) and of a set
-static BinParams grid_bin_params(const molar_hip_ctx *c, const GridSet &S, bool drop_nonfinite) {
+// what the grid kernels take of a search's shape and of a set
+static BinParams grid_bin_params(const SearchShape &shape, const GridSet &S, bool drop_nonfinite) {
     BinParams P{};
     P.xyz = S.d_xyz;
     P.idx = S.d_idx;
     P.n = S.n;
-    P.dx = c->dims[0];
-    P.dy = c->dims[1];
-    P.dz = c->dims[2];
-    P.pbc = c->pbc;
-    P.use_box = c->use_box ? 1u : 0u;
+    P.dx = shape.dims[0];
+    P.dy = shape.dims[1];
+    P.dz = shape.dims[2];
+    P.pbc = shape.pbc;
+    P.use_box = shape.use_box ? 1u : 0u;
     P.drop_nonfinite = drop_nonfinite ? 1u : 0u;
     for (int d = 0; d < 3; ++d) {
-        P.lower[d] = c->lower[d];
-        P.upper[d] = c->upper[d];
+        P.lower[d] = shape.lower[d];
+        P.upper[d] = shape.upper[d];
     }
-    P.box = c->box;
+    P.box = shape.box;
     return P;
 }
 
@@ -1311,8 +1261,9 @@ static int grid_reserve(GridSet &S, uint32_t ncells) {
 
 int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_local) {
     Prof prof(c, 0);
-    const uint32_t ncells = c->dims[0] * c->dims[1] * c->dims[2];
-    const BinParams P = grid_bin_params(c, S, call.drop_nonfinite);
+    const SearchShape &cur = c->cur;
+    const uint32_t ncells = (uint32_t)grid_cells(cur);
+    const BinParams P = grid_bin_params(cur, S, call.drop_nonfinite);
     MH_TRY(grid_reserve(S, ncells));
     const uint32_t pad_shift = grid_pad_shift(S.n, ncells);
     const size_t npad = pad_shift ? ((size_t)ncells << pad_shift) : 0;
@@ -1349,7 +1300,7 @@ int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_loc
         MH_TRY((exclusive_scan<uint32_t, uint32_t>(c, S.cell_count.as<uint32_t>(), S.cell_count.as<uint32_t>(),
                                                    (uint64_t)ncells + 1)));
         // cells of more than 384 atoms on average: the order comes from a stable sort (sort_prep_kernel)
-        const bool by_sort = (uint64_t)S.n > 384ull * ncells;
+        const bool by_sort = sorted_by_device_sort(S.n, ncells);
         if (by_sort) {
             MH_TRY(S.sort_buf.reserve((size_t)S.n * 16));
             uint32_t *k_in = S.sort_buf.as<uint32_t>(), *v_in = k_in + S.n, *k_out = v_in + S.n, *v_out = k_out + S.n;
@@ -1362,8 +1313,7 @@ int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_loc
         hipLaunchKernelGGL(scatter_kernel, dim3(nb), dim3(bs), 0, c->stream, S.n, S.key.as<uint32_t>(),
                            S.cell_count.as<uint32_t>(), S.cursor.as<uint32_t>(), S.tmp_key.as<uint32_t>());
         // (the spatial order serves the regular count pass and the fused histogram; pair_small.hip reads the placed records only)
-        const int want_order = ((c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE) &&
-                                (call.hist_plan || small_cell_lanes(c) == 0)) ? 1 : 0;
+        const int want_order = (fixed_cutoff_kind(cur.kind) && (call.hist_plan || small_cell_lanes(cur) == 0)) ? 1 : 0;
         if (!want_order && !by_sort && (uint64_t)S.n < 16ull * ncells)
             hipLaunchKernelGGL(place_small_kernel, dim3((unsigned)(((uint64_t)ncells * 16u + bs - 1u) / bs)), dim3(bs), 0, c->stream, P, ncells,
                                ids_local, S.cell_count.as<uint32_t>(), S.tmp_key.as<uint32_t>(), S.d_vdw, S.sorted.as<float4>(),
@@ -1397,119 +1347,50 @@ int stage_set(molar_hip_ctx *c, GridSet &S, const float *xyz, size_t natoms, con
     return 0;
 }
 
-SearchParams make_params(molar_hip_ctx *c) {
+// The parameter block of the pair kernels: the context's buffers and env knobs, the geometry of `shape` and its grids, and the
+// policy for wrapped pairs (search_shape.hpp).  Output capacity and histogram fields are the caller's.
+SearchParams make_params(const molar_hip_ctx *c, const SearchShape &shape) {
     SearchParams P{};
-    const bool two = c->kind != MOLAR_HIP_SEARCH_SINGLE;
-    P.sa = c->set[0].sorted.as<float4>();
-    P.csa = c->set[0].cell_count.as<uint32_t>();
-    P.sb = two ? c->set[1].sorted.as<float4>() : P.sa;
-    P.csb = two ? c->set[1].cell_count.as<uint32_t>() : P.csa;
-    P.vdwa = c->set[0].sorted_vdw.as<float>();
-    P.vdwb = c->set[1].sorted_vdw.as<float>();
-    P.aabb_b = two ? c->set[1].aabb.as<float4>() : c->set[0].aabb.as<float4>();
-    P.perm_b = two ? c->set[1].perm.as<float4>() : c->set[0].perm.as<float4>();
-    P.chunk_aabb_b = two ? c->set[1].chunk_aabb.as<float4>() : c->set[0].chunk_aabb.as<float4>();
-    P.h16_b = two ? c->set[1].h16.as<uint4>() : c->set[0].h16.as<uint4>();
-    P.cell_org_b = two ? c->set[1].cell_org.as<float4>() : c->set[0].cell_org.as<float4>();
+    const GridSet &A = shape.set[0], &B = shape.kind != MOLAR_HIP_SEARCH_SINGLE ? shape.set[1] : shape.set[0];
+    P.sa = A.sorted.as<float4>();
+    P.csa = A.cell_count.as<uint32_t>();
+    P.sb = B.sorted.as<float4>();
+    P.csb = B.cell_count.as<uint32_t>();
+    P.vdwa = A.sorted_vdw.as<float>();
+    P.vdwb = shape.set[1].sorted_vdw.as<float>();
+    P.aabb_b = B.aabb.as<float4>();
+    P.perm_b = B.perm.as<float4>();
+    P.chunk_aabb_b = B.chunk_aabb.as<float4>();
+    P.h16_b = B.h16.as<uint4>();
+    P.cell_org_b = B.cell_org.as<float4>();
     P.mfma_count = c->env_no_mfma ? 0u : (c->env_no_mfma_wrapped ? 1u : 3u);
     P.task_desc = c->task_desc.as<TaskDesc>();
     P.maskbuf = c->maskbuf.as<uint32_t>();
     P.task_moff = c->task_moff.as<unsigned long long>();
     P.mask_cap_units = c->maskbuf.cap / 256u;
     P.out_cap = ~0ull;
-    P.dx = c->dims[0];
-    P.dy = c->dims[1];
-    P.dz = c->dims[2];
-    P.pbc = c->use_box ? c->pbc : 0u;
-    P.use_box = c->use_box ? 1u : 0u;
-    P.cutoff2 = c->cutoff * c->cutoff;
-    P.ntasks = c->ntasks;
-    P.nblocks = (uint32_t)c->nslots_bound;      // count / fill: one wave per workgroup (launch_pairs adjusts the histogram mode)
-    P.box = c->box;
-    for (int k = 0; k < 96; ++k) P.shifts4[k] = (c->use_box && k < 3 * c->box.nshift) ? c->box.shifts[k] : 0.0f;
+    P.dx = shape.dims[0];
+    P.dy = shape.dims[1];
+    P.dz = shape.dims[2];
+    P.pbc = shape.use_box ? shape.pbc : 0u;
+    P.use_box = shape.use_box ? 1u : 0u;
+    P.cutoff2 = shape.cutoff * shape.cutoff;
+    P.ntasks = shape.ntasks;
+    P.nblocks = (uint32_t)shape.nslots_bound;      // count / fill: one wave per workgroup (launch_pairs adjusts the histogram mode)
+    P.box = shape.box;
+    for (int k = 0; k < 96; ++k) P.shifts4[k] = (shape.use_box && k < 3 * shape.box.nshift) ? shape.box.shifts[k] : 0.0f;
     P.hist_nbins = 0u;
     P.hist_min = P.hist_max = 0.f;
     P.hist_bins = nullptr;
     P.hist_total = nullptr;
     P.hist_nslots = nullptr;
-    // zero pattern shared by the matrix and its inverse -> which products a wrapped pair may skip
-    P.wrap_kind = 3u;   // WK_GENERAL
-    if (c->use_box) {
-        const float *m = c->box.m, *iv = c->box.inv;
-        auto z = [&](int k) { return m[k] == 0.0f && iv[k] == 0.0f; };
-        const bool lower_zero = z(1) && z(2) && z(5);            // (1,0) (2,0) (2,1)
-        const bool upper_zero = z(3) && z(6) && z(7);            // (0,1) (0,2) (1,2)
-        if (lower_zero && upper_zero) P.wrap_kind = 1u;          // WK_DIAG
-        else if (lower_zero) P.wrap_kind = 2u;                   // WK_UPPER (GROMACS-style boxes)
-    }
-    // image-box pruning of wrapped entries argues with n_d = round(f_d) in {-1,0,1}; keep the exhaustive
-    // path on degenerate grids (a periodic dimension with fewer than 3 cells): they are tiny anyway
-    P.prune_wrapped = 0u;
-    if (c->use_box) {
-        bool ok = true;
-        for (int d = 0; d < 3; ++d)
-            if (((c->pbc >> d) & 1u) && c->dims[d] < 3u) ok = false;
-        P.prune_wrapped = ok ? 1u : 0u;
-    }
-    // Wrapped entries: classify with the plain distance to the image cell (b + S - a), decide exactly inside a band
-    // around cutoff^2, and prune rows against the image box with a margin.  How far can the two evaluations of a
-    // wrapped difference vector disagree?  u = 2^-24, L = largest |coordinate| the box allows (lab extents, box
-    // vectors), kappa = || |M| |M^-1| ||_inf (1 for a rectangular box, grows with shear):
-    //   reference (periodic_box.rs:291-297): v = p2 - p1 (error <= u L per component), f = inv v (3 products, 2 sums:
-    //     <= 4u sum|inv||v| per component), s = M f (the error of f amplified by |M|: <= 4u kappa L, plus 4u L of
-    //     its own roundings)                                            => <= (4 kappa + 5) u L per component
-    //   approximate: S summed from box columns (<= 2u L), b + S (u L), - a (u L)   => <= 4u L per component
-    // so a component of the difference vector differs by at most e = (4 kappa + 9) u L, a distance by sqrt(3) e, and
-    // d2 near cutoff^2 by 2 sqrt(3) rc e, i.e. by 2 sqrt(3) (4 kappa + 9) u L/rc relative to cutoff^2.  The band is
-    // 2e-4 plus FOUR times that; the pruning margin is 1e-3 nm plus four times sqrt(3) e.  Both therefore scale with
-    // the box size AND its shear; boxes for which the band would exceed 5 % of cutoff^2 or the margin 5 % of the
-    // cutoff take the exact path for every wrapped candidate.
-    P.approx_wrapped = 0u;
-    P.band_lo = P.band_hi = P.cutoff2;
-    float margin = 1.0e-3f;
-    if (c->use_box) {
-        bool ok = (uint64_t)c->set[0].n + (uint64_t)c->set[1].n < (1ull << 26);   // (row<<26 | position) packing
-        float ext[3], lmax = 0.f;
-        molar_hip_box_lab_extents(&c->box, ext);
-        for (int d = 0; d < 3; ++d) {
-            if (((c->pbc >> d) & 1u) && c->dims[d] < 4u) ok = false;   // round(f_d) must be +-1 for wrapped pairs
-            lmax = std::fmax(lmax, std::fabs(ext[d]));
-            for (int k = 0; k < 3; ++k) lmax = std::fmax(lmax, std::fabs(c->box.m[3 * k + d]));
-        }
-        // atoms sit inside the cell along periodic dims, so a coordinate is bounded by the sum of the |box vectors|
-        float lsum = 0.f;
-        for (int d = 0; d < 3; ++d) {
-            float row = 0.f;
-            for (int k = 0; k < 3; ++k) row += std::fabs(c->box.m[3 * k + d]);
-            lsum = std::fmax(lsum, row);
-        }
-        lmax = std::fmax(lmax, lsum);
-        double kappa = 0.0;
-        for (int i = 0; i < 3; ++i) {
-            double row = 0.0;
-            for (int j = 0; j < 3; ++j) {
-                double e = 0.0;
-                for (int k = 0; k < 3; ++k) e += std::fabs((double)c->box.m[3 * k + i]) * std::fabs((double)c->box.inv[3 * j + k]);
-                row += e;
-            }
-            kappa = std::fmax(kappa, row);
-        }
-        const double u = 5.9604645e-8;
-        const double e = (4.0 * kappa + 9.0) * u * (double)lmax;                   // per-component disagreement bound
-        const double rel = 2.0e-4 + 4.0 * 2.0 * 1.7320508 * e / (double)c->cutoff;
-        margin = (float)(1.0e-3 + 4.0 * 1.7320508 * e);
-        if (!(margin < 0.05f * c->cutoff) || !std::isfinite(kappa)) {
-            P.prune_wrapped = 0u;
-            ok = false;
-        }
-        if (ok && rel < 0.05) {
-            P.approx_wrapped = 1u;
-            P.band_lo = P.cutoff2 * (float)(1.0 - rel);
-            P.band_hi = P.cutoff2 * (float)(1.0 + rel);
-        }
-    }
-    const float lim = c->cutoff + margin;
-    P.prune_limit2 = lim * lim;
+    const WrapPolicy W = wrapped_pair_policy(shape);
+    P.wrap_kind = W.wrap_kind;
+    P.prune_wrapped = W.prune_wrapped;
+    P.approx_wrapped = W.approx_wrapped;
+    P.band_lo = W.band_lo;
+    P.band_hi = W.band_hi;
+    P.prune_limit2 = W.prune_limit2;
 #ifdef MOLAR_HIP_DEBUG_KNOBS
     P.debug_skip = c->env_debug_skip;
     P.dbg = nullptr;
@@ -1539,7 +1420,8 @@ int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, c
     if (FILL && (((uintptr_t)out.pairs & 15u) || ((uintptr_t)out.dist & 7u)))
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search fill: device outputs must be aligned to 16 bytes (pairs) and 8 bytes (distances)");
     Prof prof(c, FILL ? 3 : 1);
-    SearchParams P = make_params(c);
+    const SearchShape &cur = c->cur;
+    SearchParams P = make_params(c, cur);
     if (P.nblocks == 0) return 0;
     P.out_cap = call.out_cap;
     P.hist_nbins = hist.nbins;
@@ -1561,12 +1443,10 @@ int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, c
         if (P.nblocks > cap) P.nblocks = cap;
         // plain, same-cell and band-classified wrapped slots go to the lean kernel (8 waves per SIMD), the rest to
         // pair_kernel<MODE_HIST>; both add into the same bins
-        P.hist_lean = (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE) ? 1u : 0u;
-        {   // cells of more than KREG * 64 atoms are the rule (the grids' own criterion for ordering them by a sort, build_grid)
-            const uint64_t ncells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
-            const uint64_t nb_set = c->kind == MOLAR_HIP_SEARCH_SINGLE ? c->set[0].n : c->set[1].n;
-            P.hist_big = (P.hist_lean && nb_set > 384ull * ncells) ? 1u : 0u;
-        }
+        P.hist_lean = fixed_cutoff_kind(cur.kind) ? 1u : 0u;
+        // cells of more than KREG * 64 atoms are the rule (the grids' own criterion for ordering them by a sort, build_grid)
+        const uint64_t nb_set = cur.kind == MOLAR_HIP_SEARCH_SINGLE ? cur.set[0].n : cur.set[1].n;
+        P.hist_big = (P.hist_lean && sorted_by_device_sort(nb_set, grid_cells(cur))) ? 1u : 0u;
         if (P.hist_lean && c->edges_nbins == hist.nbins && c->edges_min == hist.min && c->edges_max == hist.max) {
             P.hist_edges = c->hist_edges.as<float>();
             P.hist_scale = (float)hist.nbins / (hist.max - hist.min);
@@ -1591,7 +1471,7 @@ int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, c
         hipLaunchKernelGGL(upload_params_kernel, dim3(1), dim3(256), 0, c->stream, P, c->params.as<SearchParams>());
     const SearchParams *dP = c->params.as<SearchParams>();
     const SlotDesc *tf = c->slot_desc.as<SlotDesc>();
-    uint32_t st = (uint32_t)c->nslots_bound;
+    uint32_t st = (uint32_t)cur.nslots_bound;
     if (call.slot_launch && !hist.nbins && call.slot_launch < st) P.nblocks = st = call.slot_launch;      // resident searches, see common.hpp
     uint32_t *sc = c->slot_cnt.as<uint32_t>();
     auto *sb = c->slot_base.as<unsigned long long>();
@@ -1606,39 +1486,19 @@ int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, c
         uint32_t *queue = c->hist_queue.as<uint32_t>();
         const int lslot = (int)(c->hist_frames++ & 3u);
         P.hist_nslots = hist_list_count(queue, lslot, 1);
-        launch_hist_plan(c->kind, c->stream, P, c->params.as<SearchParams>(), c->slot_desc.as<SlotDesc>(), c->slot_desc_rest.as<SlotDesc>(), queue, lslot);
-        launch_hist_lean(c->kind, (unsigned)c->num_cus, dyn_lds, c->stream, dP, tf, st, queue, lslot, P.hist_big != 0u);
+        launch_hist_plan(cur.kind, c->stream, P, c->params.as<SearchParams>(), c->slot_desc.as<SlotDesc>(), c->slot_desc_rest.as<SlotDesc>(), queue, lslot);
+        launch_hist_lean(cur.kind, (unsigned)c->num_cus, dyn_lds, c->stream, dP, tf, st, queue, lslot, P.hist_big != 0u);
         tf = c->slot_desc_rest.as<SlotDesc>();
     }
-    // frames of large cells (more than 448 atoms per cell of the second set on average, i.e. cells above 512 are common): the
-    // instances with 128 registers per lane and up to 16 chunks of the second cell resident
-    if (!hist.nbins && !out.ids && (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE)) {
-        // (per occupied cell where the last search of this shape has counted them, like small_cell_lanes: a slab in a mostly empty box)
-        const int sb_set = c->kind == MOLAR_HIP_SEARCH_SINGLE ? 0 : 1;
-        const uint64_t all_cells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
-        const uint64_t ncells = c->occ_use[sb_set] ? std::min<uint64_t>(c->occ_use[sb_set], all_cells) : all_cells;
-        const uint64_t nb_set = c->set[sb_set].n;
-        if (nb_set > 1000ull * ncells) {       // cells above 1024 atoms are the rule: 256 registers per lane, up to 2048 atoms resident (pair_k7.hip)
-            launch_pair_huge(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
-            MH_HIP(hipGetLastError());
-            return 0;
-        }
-        if (nb_set > 448ull * ncells) {
-            launch_pair_wide(c->kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
-            MH_HIP(hipGetLastError());
-            return 0;
-        }
+    // frames of large cells (the wide and huge instances) and of small cells (several slots per wave, pair_small.hip)
+    if (const int family = (!hist.nbins && !out.ids) ? pair_family(cur) : 0) {
+        if (family == -2) launch_pair_huge(cur.kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
+        else if (family == -1) launch_pair_wide(cur.kind, mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
+        else launch_pair_small(mode, family, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
+        MH_HIP(hipGetLastError());
+        return 0;
     }
-    // frames of small cells (contact / hydrogen-bond cutoffs): several slots per wave, pair_small.hip
-    if (!hist.nbins && !out.ids) {
-        const int lanes = small_cell_lanes(c);
-        if (lanes) {
-            launch_pair_small(mode, lanes, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
-            MH_HIP(hipGetLastError());
-            return 0;
-        }
-    }
-    switch (c->kind) {
+    switch (cur.kind) {
         case MOLAR_HIP_SEARCH_SINGLE: launch_pair_single(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
         case MOLAR_HIP_SEARCH_DOUBLE: launch_pair_double(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
         case MOLAR_HIP_SEARCH_WITHIN: launch_pair_within(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
@@ -1748,22 +1608,23 @@ int device_fmax2(molar_hip_ctx *c, const float *d_v1, uint32_t n1, const float *
 // Second half of the plan, for the kernels that walk slots (count / fill / histogram): slot index of every plan entry and
 // (fast kinds) its first hit-history unit by one single-pass scan over both, then one record per slot.
 int enqueue_plan_slots(molar_hip_ctx *c, unsigned long long *sizes_dev) {
-    const uint32_t fast_kind = records_hit_history(c) ? 1u : 0u;
+    const SearchShape &cur = c->cur;
+    const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
     const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
-    if (c->ntasks + 1 > (1ull << 18)) {
+    if (cur.ntasks + 1 > (1ull << 18)) {
         // sparse giant plans (a vdW search of 1M atoms: 4e6 entries): the single-pass scan's chain of tiles - each waits for the
         // one before it - took 0.3 ms there; three launches of the tile scan do not chain (in place: a thread reads its items first)
-        MH_TRY((exclusive_scan<uint32_t, uint32_t>(c, c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), c->ntasks + 1)));
-        if (fast_kind) MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->task_mu.as<uint32_t>(), c->task_moff.as<unsigned long long>(), c->ntasks + 1)));
+        MH_TRY((exclusive_scan<uint32_t, uint32_t>(c, c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), cur.ntasks + 1)));
+        if (fast_kind) MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->task_mu.as<uint32_t>(), c->task_moff.as<unsigned long long>(), cur.ntasks + 1)));
     } else
     MH_TRY((scan_lookback<uint32_t, uint32_t, uint32_t, unsigned long long>(
         c, c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), fast_kind ? c->task_mu.as<uint32_t>() : nullptr,
-        c->task_moff.as<unsigned long long>(), c->ntasks + 1, c->scan_state.as<unsigned long long>())));
+        c->task_moff.as<unsigned long long>(), cur.ntasks + 1, c->scan_state.as<unsigned long long>())));
     // one record per slot (threads past the tasks blank the slots between the real count and the bound)
-    const unsigned nbs = (unsigned)((c->ntasks + c->nslots_bound + 1 + pbs - 1) / pbs);
-    hipLaunchKernelGGL(slotmap_kernel, dim3(nbs), dim3(pbs), 0, c->stream, c->ntasks, c->task_nb.as<uint32_t>(),
+    const unsigned nbs = (unsigned)((cur.ntasks + cur.nslots_bound + 1 + pbs - 1) / pbs);
+    hipLaunchKernelGGL(slotmap_kernel, dim3(nbs), dim3(pbs), 0, c->stream, cur.ntasks, c->task_nb.as<uint32_t>(),
                        c->task_desc.as<TaskDesc>(), fast_kind ? c->task_moff.as<unsigned long long>() : nullptr,
-                       c->slot_desc.as<SlotDesc>(), c->nslots_bound, sizes_dev);
+                       c->slot_desc.as<SlotDesc>(), cur.nslots_bound, sizes_dev);
     MH_HIP(hipGetLastError());
     return 0;
 }
@@ -1776,20 +1637,21 @@ int enqueue_plan_slots(molar_hip_ctx *c, unsigned long long *sizes_dev) {
 //    mostly empty - 3.2e6 workgroups launched for 1.6e5 slots cost 0.8 ms per pass in bare launches - so the launches of this
 //    search shrink to the slots that exist.  (Slot counters and records were prepared for the bound: a superset.)
 int size_plan(molar_hip_ctx *c) {
-    const bool fast_kind = records_hit_history(c);
-    if (!fast_kind && c->nslots_bound <= 65536ull) return 0;       // nothing to size, too few launches to save: no round trip
+    SearchShape &cur = c->cur;
+    const bool fast_kind = records_hit_history(cur);
+    if (!fast_kind && cur.nslots_bound <= 65536ull) return 0;       // nothing to size, too few launches to save: no round trip
     MH_TRY(ensure_pinned(c, 64));
     unsigned long long *h = reinterpret_cast<unsigned long long *>(c->h_pinned);
     h[0] = h[1] = 0ull;
-    if (fast_kind) MH_HIP(hipMemcpyAsync(&h[0], c->task_moff.as<unsigned long long>() + c->ntasks, 8, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipMemcpyAsync(&h[1], c->task_nb.as<uint32_t>() + c->ntasks, 4, hipMemcpyDeviceToHost, c->stream));      // task_nb is scanned in place: the total
+    if (fast_kind) MH_HIP(hipMemcpyAsync(&h[0], c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(&h[1], c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));      // task_nb is scanned in place: the total
     MH_HIP(hipStreamSynchronize(c->stream));
     if (fast_kind) {
         c->mask_units = h[0];
         MH_TRY(c->maskbuf.reserve((size_t)h[0] * 256u + 256u));
     }
     const uint64_t real = (uint32_t)h[1];
-    if (real < c->nslots_bound) c->nslots_bound = real;
+    if (real < cur.nslots_bound) cur.nslots_bound = real;
     return 0;
 }
 
@@ -1798,12 +1660,13 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
     MH_HIP(hipSetDevice(c->device));
     c->have_search = false;
-    c->kind = q->kind;
+    SearchShape &cur = c->cur;
+    cur.kind = q->kind;
     const bool two = q->kind != MOLAR_HIP_SEARCH_SINGLE;
     const bool vdw = q->kind == MOLAR_HIP_SEARCH_DOUBLE_VDW;
-    c->use_box = q->box9 != nullptr;
-    c->pbc = q->pbc & 7u;
-    if (c->use_box) MH_TRY(molar_hip_box_from_matrix(q->box9, &c->box));
+    cur.use_box = q->box9 != nullptr;
+    cur.pbc = q->pbc & 7u;
+    if (cur.use_box) MH_TRY(molar_hip_box_from_matrix(q->box9, &cur.box));
     // molar_hip_within_hold: consecutive `within` requests against the SAME first set (same pointers and sizes, same box, same
     // grid) reuse its staged coordinates and its grid; anything else that stages or bins set 0 ends the hold's validity
     const bool may_hold = c->within_hold && q->kind == MOLAR_HIP_SEARCH_WITHIN && call.within_set;
@@ -1824,43 +1687,43 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
         for (size_t a = n > 64 ? n - 64 : 0; a < n; ++a) mix(a);
         fp |= 1ull;
     }
-    bool reuse0 = may_hold && c->hold_valid && c->hold_fp == fp && c->hold_set == c->set && c->hold_xyz == q->xyz1 && c->hold_natoms == q->natoms1 &&
-                  c->hold_idx == q->idx1 && c->hold_n == q->n1 && c->hold_ids_local == q->ids_local && c->hold_use_box == c->use_box &&
-                  c->hold_pbc == c->pbc && (!c->use_box || std::memcmp(&c->hold_box, &c->box, sizeof c->box) == 0);
+    bool reuse0 = may_hold && c->hold_valid && c->hold_fp == fp && c->hold_set == cur.set && c->hold_xyz == q->xyz1 && c->hold_natoms == q->natoms1 &&
+                  c->hold_idx == q->idx1 && c->hold_n == q->n1 && c->hold_ids_local == q->ids_local && c->hold_use_box == cur.use_box &&
+                  c->hold_pbc == cur.pbc && (!cur.use_box || std::memcmp(&c->hold_box, &cur.box, sizeof cur.box) == 0);
     if (!reuse0) {
         c->hold_valid = false;
-        MH_TRY(stage_set(c, c->set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
+        MH_TRY(stage_set(c, cur.set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
     }
-    if (two) MH_TRY(stage_set(c, c->set[1], q->xyz2, q->natoms2, q->idx2, q->n2, q->vdw2, vdw));
-    else c->set[1].n = 0;
+    if (two) MH_TRY(stage_set(c, cur.set[1], q->xyz2, q->natoms2, q->idx2, q->n2, q->vdw2, vdw));
+    else cur.set[1].n = 0;
 
     float cutoff = q->cutoff;
     if (vdw) {
         // cutoff = max(vdw1) + max(vdw2) + EPSILON (:781-783); the reference panics on empty input
-        if (c->set[0].n == 0 || c->set[1].n == 0) {
-            c->dims[0] = c->dims[1] = c->dims[2] = 1;
-            c->ntasks = 0;
+        if (cur.set[0].n == 0 || cur.set[1].n == 0) {
+            cur.dims[0] = cur.dims[1] = cur.dims[2] = 1;
+            cur.ntasks = 0;
             c->total = 0;
             c->have_search = true;
             return 0;
         }
         float m1, m2;
-        MH_TRY(device_fmax2(c, c->set[0].d_vdw, c->set[0].n, c->set[1].d_vdw, c->set[1].n, &m1, &m2));
+        MH_TRY(device_fmax2(c, cur.set[0].d_vdw, cur.set[0].n, cur.set[1].d_vdw, cur.set[1].n, &m1, &m2));
         cutoff = (m1 + m2) + F32_EPS;
     }
     if (!(cutoff > 0.0f)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: cutoff must be positive (got %g)", (double)cutoff);
-    c->cutoff = cutoff;
+    cur.cutoff = cutoff;
 
     float ext[3];
-    if (c->use_box) {
-        molar_hip_box_lab_extents(&c->box, ext);                       // Grid::from_cutoff_and_box :116-118
+    if (cur.use_box) {
+        molar_hip_box_lab_extents(&cur.box, ext);                       // Grid::from_cutoff_and_box :116-118
     } else {
         if (q->kind == MOLAR_HIP_SEARCH_WITHIN) {
             if (!q->lower3 || !q->upper3)
                 return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "non-periodic within search needs lower3/upper3");
             for (int d = 0; d < 3; ++d) {
-                c->lower[d] = q->lower3[d];
-                c->upper[d] = q->upper3[d];
+                cur.lower[d] = q->lower3[d];
+                cur.upper[d] = q->upper3[d];
             }
         } else {
             // compute_bounding_box_single/double (:618-646), min/max seeded with zeros (:602-616)
@@ -1869,54 +1732,47 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
             uint32_t seed[6];
             for (int d = 0; d < 6; ++d) seed[d] = f2ord_host(0.0f);
             MH_HIP(hipMemcpyAsync(d_mm, seed, sizeof seed, hipMemcpyHostToDevice, c->stream));
-            MH_TRY(bbox_accumulate(c, d_mm, c->set[0]));
-            if (two) MH_TRY(bbox_accumulate(c, d_mm, c->set[1]));
+            MH_TRY(bbox_accumulate(c, d_mm, cur.set[0]));
+            if (two) MH_TRY(bbox_accumulate(c, d_mm, cur.set[1]));
             uint32_t mm[6];
             MH_TRY(read_back(c, mm, d_mm, sizeof mm));
             for (int d = 0; d < 3; ++d) {
-                c->lower[d] = ord2f(mm[d]) + (-cutoff - F32_EPS);
-                c->upper[d] = ord2f(mm[3 + d]) + (cutoff + F32_EPS);
+                cur.lower[d] = ord2f(mm[d]) + (-cutoff - F32_EPS);
+                cur.upper[d] = ord2f(mm[3 + d]) + (cutoff + F32_EPS);
             }
         }
-        for (int d = 0; d < 3; ++d) ext[d] = c->upper[d] - c->lower[d];   // from_cutoff_and_min_max :112-114
+        for (int d = 0; d < 3; ++d) ext[d] = cur.upper[d] - cur.lower[d];   // from_cutoff_and_min_max :112-114
     }
-    MH_TRY(dims_from_extents(c, cutoff, ext));
+    MH_TRY(dims_from_extents(cur, ext));
     if (reuse0) {          // the same cells? (the cutoff and, without a box, the caller's bounds decide the grid)
-        bool same = c->hold_dims[0] == c->dims[0] && c->hold_dims[1] == c->dims[1] && c->hold_dims[2] == c->dims[2];
-        for (int d = 0; d < 3 && !c->use_box; ++d) same = same && c->hold_lower[d] == c->lower[d] && c->hold_upper[d] == c->upper[d];
+        bool same = c->hold_dims[0] == cur.dims[0] && c->hold_dims[1] == cur.dims[1] && c->hold_dims[2] == cur.dims[2];
+        for (int d = 0; d < 3 && !cur.use_box; ++d) same = same && c->hold_lower[d] == cur.lower[d] && c->hold_upper[d] == cur.upper[d];
         if (!same) {
             reuse0 = false;
             c->hold_valid = false;
-            MH_TRY(stage_set(c, c->set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
+            MH_TRY(stage_set(c, cur.set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
         }
     }
     occ_latch(c);        // kind, set sizes and grid dimensions stand: what small_cell_lanes() answers for this search from here on
-    const uint64_t ncells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
-    c->ntasks = ncells * 14ull * (two ? 2ull : 1ull);
-    // every set-1 cell is the first cell of at most 14 (two grids: 28) tasks, so
-    // sum_t ceil(n1(t)/64) <= mult*N1/64 + ntasks
-    c->nslots_bound = (two ? 28ull : 14ull) * (((uint64_t)c->set[0].n + 63ull) / 64ull) + c->ntasks;
-    // entries wrapping in all three dims of a triclinic box use 2-row (<= 1024 rows) or 8-row slots: <= 28 tasks of <= 512 slots
-    c->nslots_bound += 28ull * 512ull;
-    // (the one-kernel plan of the fused histogram cuts same-cell entries into 32-row slots: one such entry per cell)
-    if (call.hist_plan) c->nslots_bound += ((uint64_t)c->set[0].n + 31ull) / 32ull + ncells;
-    if (c->ntasks >= 0xFFFFFFF0ull || c->nslots_bound >= 0xFFFFFFF0ull || c->ntasks + c->nslots_bound >= 0xFFFFFF00ull)
-        return fail(MOLAR_HIP_ERR_TOO_LARGE, "search plan too large (%llu entries)", (unsigned long long)c->ntasks);
-    MH_TRY(c->task_nb.reserve((c->ntasks + 1) * 4));
-    MH_TRY(c->task_desc.reserve((c->ntasks + 1) * sizeof(TaskDesc)));
-    MH_TRY(c->slot_desc.reserve((c->nslots_bound + 1) * sizeof(SlotDesc)));
-    if (call.hist_plan) MH_TRY(c->slot_desc_rest.reserve((c->nslots_bound + 1) * sizeof(SlotDesc)));
-    MH_TRY(c->slot_cnt.reserve((c->nslots_bound + 1) * 4));
-    MH_TRY(c->slot_base.reserve((c->nslots_bound + 1) * 8));
+    cur.ntasks = plan_entries(cur);
+    cur.nslots_bound = slots_bound(cur, call.hist_plan);
+    if (cur.ntasks >= 0xFFFFFFF0ull || cur.nslots_bound >= 0xFFFFFFF0ull || cur.ntasks + cur.nslots_bound >= 0xFFFFFF00ull)
+        return fail(MOLAR_HIP_ERR_TOO_LARGE, "search plan too large (%llu entries)", (unsigned long long)cur.ntasks);
+    MH_TRY(c->task_nb.reserve((cur.ntasks + 1) * 4));
+    MH_TRY(c->task_desc.reserve((cur.ntasks + 1) * sizeof(TaskDesc)));
+    MH_TRY(c->slot_desc.reserve((cur.nslots_bound + 1) * sizeof(SlotDesc)));
+    if (call.hist_plan) MH_TRY(c->slot_desc_rest.reserve((cur.nslots_bound + 1) * sizeof(SlotDesc)));
+    MH_TRY(c->slot_cnt.reserve((cur.nslots_bound + 1) * 4));
+    MH_TRY(c->slot_base.reserve((cur.nslots_bound + 1) * 8));
     MH_TRY(c->params.reserve(sizeof(SearchParams)));
-    const size_t st_tasks = lookback_state_words(c->ntasks + 1), st_slots = lookback_state_words(c->nslots_bound + 1);
+    const size_t st_tasks = lookback_state_words(cur.ntasks + 1), st_slots = lookback_state_words(cur.nslots_bound + 1);
     MH_TRY(c->scan_state.reserve((st_tasks + st_slots) * 8));
-    MH_TRY(c->task_mu.reserve((c->ntasks + 1) * 4));
-    MH_TRY(c->task_moff.reserve((c->ntasks + 1) * 8));
-    const uint32_t fast_kind = records_hit_history(c) ? 1u : 0u;
+    MH_TRY(c->task_mu.reserve((cur.ntasks + 1) * 4));
+    MH_TRY(c->task_moff.reserve((cur.ntasks + 1) * 8));
+    const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
     auto enqueue_plan = [&]() -> int {
         Prof prof(c, 0);
-        SearchParams P = make_params(c);
+        SearchParams P = make_params(c, cur);
         // Resident searches (no host round trip between plan and count: the hit-history buffer keeps its size): the plan
         // kernel also writes the parameter block the count and fill passes read, output capacity included.
         SearchParams *params_dst = nullptr;
@@ -1927,43 +1783,43 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
             c->params_fresh = true;
             c->params_fresh_cap = P.out_cap;
         }
-        if (!c->on_side && c->ntasks + 1 <= FPLAN_MAX_TASKS) {
+        if (!c->on_side && cur.ntasks + 1 <= FPLAN_MAX_TASKS) {
             // main stream, a plan of at most 2^22 entries: plan and tile scan, then offsets and slot records - two launches (three
             // above 2^18 entries, plan_groups_kernel), no chain
-            const uint32_t ntiles = (uint32_t)((c->ntasks + 1 + 255) / 256);
+            const uint32_t ntiles = (uint32_t)((cur.ntasks + 1 + 255) / 256);
             const uint32_t ngroups = ntiles > 1024u ? (ntiles + PLAN_GROUP - 1u) / PLAN_GROUP : 0u;
-            MH_TRY(c->fplan_tiles.reserve((size_t)ntiles * 16 + (c->ntasks + 1) * 8 + (size_t)ngroups * 16));
+            MH_TRY(c->fplan_tiles.reserve((size_t)ntiles * 16 + (cur.ntasks + 1) * 8 + (size_t)ngroups * 16));
             unsigned long long *moff = fast_kind ? c->task_moff.as<unsigned long long>() : nullptr;
             unsigned long long *tt = c->fplan_tiles.as<unsigned long long>();
             unsigned long long *lmoff = tt + 2 * (size_t)ntiles;           // offsets inside the tiles: hit-history units ...
             uint32_t *lfirst = c->task_mu.as<uint32_t>();                  // ... and slots
-            if (c->kind == MOLAR_HIP_SEARCH_SINGLE)
+            if (cur.kind == MOLAR_HIP_SEARCH_SINGLE)
                 hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), c->nslots_bound + 1, tt, params_dst);
+                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst);
             else          // the three two-grid kinds decode tasks identically
                 hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), c->nslots_bound + 1, tt, params_dst);
-            unsigned long long *gt = ngroups ? lmoff + (c->ntasks + 1) : nullptr;
+                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst);
+            unsigned long long *gt = ngroups ? lmoff + (cur.ntasks + 1) : nullptr;
             if (ngroups) hipLaunchKernelGGL(plan_groups_kernel, dim3(ngroups), dim3(64), 0, c->stream, ntiles, tt, gt);
-            hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, c->ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
-                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), c->nslots_bound, call.sizes_dev, gt);
+            hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, cur.ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
+                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), cur.nslots_bound, call.sizes_dev, gt);
             MH_HIP(hipGetLastError());
             return 0;
         }
         // ntasks + 1 threads (the last one writes the scan terminators); the same grid zeroes the slot counters and the
         // descriptors of the two look-back scans of this search
-        const uint64_t nplan = std::max<uint64_t>(std::max<uint64_t>(c->ntasks + 1, c->nslots_bound + 1), st_tasks + st_slots);
+        const uint64_t nplan = std::max<uint64_t>(std::max<uint64_t>(cur.ntasks + 1, cur.nslots_bound + 1), st_tasks + st_slots);
         const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
         const unsigned nb = (unsigned)((nplan + pbs - 1) / pbs);
-        switch (c->kind) {
+        switch (cur.kind) {
             case MOLAR_HIP_SEARCH_SINGLE:
                 hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
-                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), c->nslots_bound + 1,
+                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
                                    c->scan_state.as<unsigned long long>(), (uint64_t)(st_tasks + st_slots), params_dst);
                 break;
             default:   // the three two-grid kinds decode tasks identically
                 hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
-                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), c->nslots_bound + 1,
+                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
                                    c->scan_state.as<unsigned long long>(), (uint64_t)(st_tasks + st_slots), params_dst);
                 break;
         }
@@ -1974,15 +1830,15 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     // side stream.  It touches only this generation's GridSet (last read by the search two frames back, which has been
     // ended) and its own scan scratch, so it needs to wait for nothing and overlaps the pair kernels of the frame in
     // front of it; the plan and the pair kernels of THIS search wait for it on the main stream.
-    const bool side = call.side && c->own_stream && c->use_box && !vdw && c->set[0].d_xyz == q->xyz1 &&
-                      c->set[0].d_idx == q->idx1 && (!two || (c->set[1].d_xyz == q->xyz2 && c->set[1].d_idx == q->idx2));
+    const bool side = call.side && c->own_stream && cur.use_box && !vdw && cur.set[0].d_xyz == q->xyz1 &&
+                      cur.set[0].d_idx == q->idx1 && (!two || (cur.set[1].d_xyz == q->xyz2 && cur.set[1].d_idx == q->idx2));
     if (side) {
         MH_TRY(ensure_side_stream(c));
         if (call.side_wait) MH_HIP(hipStreamWaitEvent(c->side_stream, call.side_wait, 0));
         {
             OnSideStream on_side(c);
-            if (!reuse0) MH_TRY(build_grid(c, call, c->set[0], q->ids_local || vdw));
-            if (two) MH_TRY(build_grid(c, call, c->set[1], q->ids_local || vdw));
+            if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
+            if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
             MH_HIP(hipEventRecord(c->grid_done, c->side_stream));
         }
         // The plan and the pair kernels of this search need the grid.  A wait command on the main stream costs that stream
@@ -1992,16 +1848,16 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
         if (c->env_host_grid_wait) MH_HIP(hipEventSynchronize(c->grid_done));
         else MH_HIP(hipStreamWaitEvent(c->stream, c->grid_done, 0));
     } else {
-        if (!reuse0) MH_TRY(build_grid(c, call, c->set[0], q->ids_local || vdw));
-        if (two) MH_TRY(build_grid(c, call, c->set[1], q->ids_local || vdw));
+        if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
+        if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
     }
     if (may_hold && !reuse0) {        // this grid of set 0 is the one later `within` requests may reuse
         c->hold_valid = true;
         c->hold_fp = fp;
-        c->hold_set = c->set;
+        c->hold_set = cur.set;
         c->hold_xyz = q->xyz1; c->hold_natoms = q->natoms1; c->hold_idx = q->idx1; c->hold_n = q->n1;
-        c->hold_ids_local = q->ids_local; c->hold_use_box = c->use_box; c->hold_pbc = c->pbc; c->hold_box = c->box;
-        for (int d = 0; d < 3; ++d) { c->hold_dims[d] = c->dims[d]; c->hold_lower[d] = c->lower[d]; c->hold_upper[d] = c->upper[d]; }
+        c->hold_ids_local = q->ids_local; c->hold_use_box = cur.use_box; c->hold_pbc = cur.pbc; c->hold_box = cur.box;
+        for (int d = 0; d < 3; ++d) { c->hold_dims[d] = cur.dims[d]; c->hold_lower[d] = cur.lower[d]; c->hold_upper[d] = cur.upper[d]; }
     }
 
     // (Round 4: the plan kernels - 32 us of small launches - on the side stream behind the grid, with a second generation
@@ -2037,9 +1893,9 @@ int finish_count(molar_hip_ctx *c) {
         unsigned long long occ = 0;
         std::memcpy(&tot, c->h_pinned, 8);
         std::memcpy(&occ, (const char *)c->h_pinned + 24, 8);
-        occ_note(c, occ_key_of(c), occ);
+        occ_note(c, occ_key_of(c->cur), occ);
     } else {
-        MH_TRY(read_back(c, &tot, c->slot_base.as<unsigned long long>() + c->nslots_bound, 8));
+        MH_TRY(read_back(c, &tot, c->slot_base.as<unsigned long long>() + c->cur.nslots_bound, 8));
     }
     c->total = tot;
     c->have_search = true;
@@ -2272,23 +2128,16 @@ int molar_hip_search_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
 
 int molar_hip_search_grid_dims(molar_hip_ctx *c, uint64_t dims[3]) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
-    for (int d = 0; d < 3; ++d) dims[d] = c->dims[d];
+    for (int d = 0; d < 3; ++d) dims[d] = c->cur.dims[d];
     return MOLAR_HIP_OK;
 }
 
 int molar_hip_search_cell_kernels(molar_hip_ctx *c, int32_t *lanes, uint64_t occupied_cells[2]) {
     if (!c || !lanes) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_cell_kernels: null argument");
-    *lanes = small_cell_lanes(c);
-    if (*lanes == 0 && (c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE)) {      // (launch_pairs' rule for large cells)
-        const int sb_set = c->kind == MOLAR_HIP_SEARCH_SINGLE ? 0 : 1;
-        const uint64_t all_cells = (uint64_t)c->dims[0] * c->dims[1] * c->dims[2];
-        const uint64_t ncells = c->occ_use[sb_set] ? std::min<uint64_t>(c->occ_use[sb_set], all_cells) : all_cells;
-        if (c->set[sb_set].n > 1000ull * ncells) *lanes = -2;
-        else if (c->set[sb_set].n > 448ull * ncells) *lanes = -1;
-    }
+    *lanes = pair_family(c->cur);
     if (occupied_cells) {
-        occupied_cells[0] = c->occ_use[0];
-        occupied_cells[1] = c->occ_use[1];
+        occupied_cells[0] = c->cur.occ_use[0];
+        occupied_cells[1] = c->cur.occ_use[1];
     }
     return MOLAR_HIP_OK;
 }
@@ -2296,7 +2145,7 @@ int molar_hip_search_cell_kernels(molar_hip_ctx *c, int32_t *lanes, uint64_t occ
 static int fill_common(molar_hip_ctx *c, uint2 *d_pairs, float *d_dist, uint32_t *d_ids) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
     MH_HIP(hipSetDevice(c->device));
-    if (c->total == 0 || c->ntasks == 0) return 0;
+    if (c->total == 0 || c->cur.ntasks == 0) return 0;
     // The fill pass stores two results per lane (16-byte / 8-byte stores relative to the output bases).  A caller's device view
     // that is not aligned like that (an offset slice of a larger tensor) is filled through the context's own buffers and copied
     // device to device - correct at the cost of one more pass over the result, instead of an error.
@@ -2319,7 +2168,7 @@ static int fill_common(molar_hip_ctx *c, uint2 *d_pairs, float *d_dist, uint32_t
 
 int molar_hip_search_fill(molar_hip_ctx *c, uint32_t *pairs, float *dist) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
-    if (c->kind == MOLAR_HIP_SEARCH_WITHIN)
+    if (c->cur.kind == MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within search yields ids: use molar_hip_search_fill_ids");
     const bool pd = is_device_ptr(pairs), dd = is_device_ptr(dist);
     uint2 *dp = nullptr;
@@ -2355,7 +2204,7 @@ int molar_hip_search_fill(molar_hip_ctx *c, uint32_t *pairs, float *dist) {
 
 int molar_hip_search_fill_device(molar_hip_ctx *c, const uint32_t **d_pairs, const float **d_dist) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
-    if (c->kind == MOLAR_HIP_SEARCH_WITHIN)
+    if (c->cur.kind == MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within search yields ids: use molar_hip_search_fill_ids");
     MH_TRY(c->out_pairs.reserve((size_t)(c->total ? c->total : 1) * 8));
     MH_TRY(c->out_dist.reserve((size_t)(c->total ? c->total : 1) * 4));
@@ -2391,13 +2240,14 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
     *L = ResidentLaunch{};
     L->degenerate = c->have_search;
     if (L->degenerate) return 0;
-    const bool fast_kind = records_hit_history(c);
+    const SearchShape &cur = c->cur;
+    const bool fast_kind = records_hit_history(cur);
     L->maskcap0 = c->maskbuf.cap / 256u;
-    L->mask_units_dev = fast_kind ? c->task_moff.as<unsigned long long>() + c->ntasks : nullptr;
+    L->mask_units_dev = fast_kind ? c->task_moff.as<unsigned long long>() + cur.ntasks : nullptr;
     // slots the two passes are launched over: what the plan of the search before came to, with a margin (common.hpp, trim_real)
-    L->launched = c->nslots_bound;
-    L->ntasks = c->ntasks;
-    if (trim && c->trim_real && c->trim_ntasks == c->ntasks && c->trim_kind == c->kind) {
+    L->launched = cur.nslots_bound;
+    L->ntasks = cur.ntasks;
+    if (trim && c->trim_real && c->trim_ntasks == cur.ntasks && c->trim_kind == cur.kind) {
         const unsigned long long want = c->trim_real + c->trim_real / 32u + 512ull;
         if (want < L->launched) L->launched = want;
     }
@@ -2412,10 +2262,10 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
     if (cap0) MH_TRY(launch_pairs<true>(c, call, PairOut{outP.as<uint2>(), pairs_only ? nullptr : outD.as<float>()}, HistTarget{},
                                         /*params_resident=*/true));
     if (!sizes_dev) {
-        MH_HIP(hipMemcpyAsync(sizes, c->slot_base.as<unsigned long long>() + c->nslots_bound, 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipMemcpyAsync(sizes, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDeviceToHost, c->stream));
         if (fast_kind)
-            MH_HIP(hipMemcpyAsync((char *)sizes + 8, c->task_moff.as<unsigned long long>() + c->ntasks, 8, hipMemcpyDeviceToHost, c->stream));
-        MH_HIP(hipMemcpyAsync((char *)sizes + 16, c->task_nb.as<uint32_t>() + c->ntasks, 4, hipMemcpyDeviceToHost, c->stream));   // (little-endian: the upper half was zeroed)
+            MH_HIP(hipMemcpyAsync((char *)sizes + 8, c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipMemcpyAsync((char *)sizes + 16, c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));   // (little-endian: the upper half was zeroed)
     }
     L->cap0 = cap0;
     return 0;
@@ -2440,7 +2290,7 @@ static bool resident_covered(molar_hip_ctx *c, const void *sizes, unsigned long 
 // With `sizes` delivered and the search still the context's cached one: grow what was too small and repeat the
 // affected passes (first frame of a trajectory; later frames are the same size +- noise).
 static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD, const void *sizes, const ResidentLaunch &L, bool pairs_only) {
-    const bool fast_kind = c->kind == MOLAR_HIP_SEARCH_SINGLE || c->kind == MOLAR_HIP_SEARCH_DOUBLE;
+    const bool fast_kind = fixed_cutoff_kind(c->cur.kind);
     unsigned long long res[2] = {0, 0};
     std::memcpy(res, sizes, 16);
     c->total = res[0];
@@ -2473,16 +2323,16 @@ static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::De
     MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
     if (L.degenerate) return 0;
     MH_HIP(hipStreamSynchronize(c->stream));
-    if (!resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->kind)) {       // too few slots launched: once more, over the bound
+    if (!resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->cur.kind)) {       // too few slots launched: once more, over the bound
         std::memset(c->h_pinned, 0, 32);
         MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
         MH_HIP(hipStreamSynchronize(c->stream));
-        (void)resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->kind);
+        (void)resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->cur.kind);
     }
     {
         unsigned long long occ = 0;
         std::memcpy(&occ, (const char *)c->h_pinned + 24, 8);
-        occ_note(c, occ_key_of(c), occ);
+        occ_note(c, occ_key_of(c->cur), occ);
     }
     return resident_settle(c, outP, outD, c->h_pinned, L, pairs_only);
 }
@@ -2499,7 +2349,7 @@ int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q
     call.drop_nonfinite = drop_nonfinite;
     MH_TRY(resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, L, /*pairs_only=*/true, /*trim=*/false, call));
     c->have_search = false;              // the sizes are not known to the host: not a cached search for the fill calls
-    *total_dev = L->degenerate ? nullptr : c->slot_base.as<unsigned long long>() + c->nslots_bound;
+    *total_dev = L->degenerate ? nullptr : c->slot_base.as<unsigned long long>() + c->cur.nslots_bound;
     *pairs_dev = c->out_pairs.as<uint32_t>();
     return 0;
 }
@@ -2560,7 +2410,7 @@ int molar_hip_search_resident_begin(molar_hip_ctx *c, const molar_hip_search_des
     if (!T.done) MH_HIP(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
     T.desc = *q;
     ResidentLaunch L;
-    c->set = c->set_store[slot];         // this ticket's grid generation (the other one may still be read by the frame in flight)
+    c->cur.set = c->set_store[slot];         // this ticket's grid generation (the other one may still be read by the frame in flight)
     SearchCall call;
     call.side = !c->env_no_side;
     call.side_wait = c->gen_free[slot];  // an asynchronous histogram call may have been the last reader of this generation
@@ -2580,7 +2430,7 @@ int molar_hip_search_resident_begin(molar_hip_ctx *c, const molar_hip_search_des
     T.launched = L.launched;
     T.ntasks = L.ntasks;
     T.kind = q->kind;
-    T.occ_key = occ_key_of(c);
+    T.occ_key = occ_key_of(c->cur);
     T.degenerate = L.degenerate;
     T.serial = c->search_serial;
     T.pending = true;
@@ -2644,7 +2494,7 @@ int molar_hip_search_resident_end(molar_hip_ctx *c, int32_t ticket, uint64_t *ou
 
 int molar_hip_search_fill_usize(molar_hip_ctx *c, uint64_t *oi, uint64_t *oj, float *dist) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
-    if (c->kind == MOLAR_HIP_SEARCH_WITHIN)
+    if (c->cur.kind == MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within search yields ids: use molar_hip_search_fill_ids");
     const size_t n = (size_t)c->total;
     MH_TRY(c->out_pairs.reserve((n ? n : 1) * 8));
@@ -2696,7 +2546,7 @@ int molar_hip_search_fill_usize(molar_hip_ctx *c, uint64_t *oi, uint64_t *oj, fl
 
 int molar_hip_search_fill_ids(molar_hip_ctx *c, uint64_t *ids) {
     if (!c || !c->have_search) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached search: call molar_hip_search_count first");
-    if (c->kind != MOLAR_HIP_SEARCH_WITHIN)
+    if (c->cur.kind != MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "fill_ids is for within searches");
     const size_t n = (size_t)c->total;
     if (n == 0 || !ids) return MOLAR_HIP_OK;
@@ -2756,7 +2606,7 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
     if (async) {
         MH_HIP(hipSetDevice(c->device));
         gen = (c->hist_gen ^= 1);
-        c->set = c->set_store[gen];
+        c->cur.set = c->set_store[gen];
         call.side_wait = c->gen_free[gen];
         call.side = !c->env_no_side;
     }
@@ -2827,33 +2677,38 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     const size_t nsel[2] = {q->idx1 ? q->n1 : q->natoms1, two ? (q->idx2 ? q->n2 : q->natoms2) : 0};
     for (int s = 0; s < nsets; ++s)
         if (nsel[s] == 0 || nsel[s] >= 0x7FFFFFFFull || (s ? q->natoms2 : q->natoms1) >= 0xFFFFFFFFull) return 0;
+    // (the frames are not the context's cached search: they are described by shapes of this call's own - `group` for what they
+    // share, sets that carry only their sizes; one per frame, below, with the frame's box and grids)
+    mh::GridSet sizes[2];
+    sizes[0].n = (uint32_t)nsel[0];
+    sizes[1].n = (uint32_t)nsel[1];
+    SearchShape group;
+    group.kind = q->kind;
+    group.use_box = true;
+    group.pbc = q->pbc & 7u;
+    group.cutoff = cutoff;
+    group.set = sizes;
     molar_hip_box boxes[HIST_BATCH];
-    uint32_t dims[3] = {0, 0, 0};
     for (int f = 0; f < W; ++f) {
         const float *b9 = boxes9 ? boxes9 + 9 * (first + f) : q->box9;
         MH_TRY(molar_hip_box_from_matrix(b9, &boxes[f]));
         float ext[3];
         molar_hip_box_lab_extents(&boxes[f], ext);
-        c->box = boxes[f];
-        MH_TRY(dims_from_extents(c, cutoff, ext));
-        if (f == 0) for (int d = 0; d < 3; ++d) dims[d] = c->dims[d];
-        else if (dims[0] != c->dims[0] || dims[1] != c->dims[1] || dims[2] != c->dims[2]) return 0;
+        SearchShape frame = group;
+        MH_TRY(dims_from_extents(frame, ext));
+        if (f == 0) group = frame;
+        else if (std::memcmp(group.dims, frame.dims, sizeof frame.dims) != 0) return 0;
     }
-    const uint64_t ncells64 = (uint64_t)dims[0] * dims[1] * dims[2];
+    const uint64_t ncells64 = grid_cells(group);
     if (ncells64 + 1 > 32768ull) return 0;                                   // one-wave scan per frame
     for (int s = 0; s < nsets; ++s)
-        if ((uint64_t)nsel[s] > 384ull * ncells64) return 0;               // big cells are ordered by a device sort
+        if (sorted_by_device_sort(nsel[s], ncells64)) return 0;              // big cells are ordered by a device sort
     const uint32_t ncells = (uint32_t)ncells64;
-    const uint32_t n[2] = {(uint32_t)nsel[0], (uint32_t)nsel[1]};
-    c->kind = q->kind;
-    c->use_box = true;
-    c->pbc = q->pbc & 7u;
-    c->cutoff = cutoff;
+    const uint32_t n[2] = {sizes[0].n, sizes[1].n};
     c->have_search = false;
     c->hold_valid = false;
-    c->ntasks = ncells64 * 14ull * (two ? 2ull : 1ull);
-    // slots of one frame (prepare_search) incl. the 32-row slots of the same-cell entries
-    const uint64_t bound1 = (two ? 28ull : 14ull) * (((uint64_t)n[0] + 63ull) / 64ull) + c->ntasks + 28ull * 512ull + ((uint64_t)n[0] + 31ull) / 32ull + ncells64;
+    group.ntasks = plan_entries(group);
+    const uint64_t bound1 = slots_bound(group, /*hist_plan=*/true);          // slots of one frame
     const uint64_t bound = bound1 * (uint64_t)W;
     if (bound >= 0xFFFFFFF0ull) return 0;
     const int gen = (c->hist_gen ^= 1);
@@ -2886,7 +2741,6 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     size_t dyn_lds = (size_t)nbins * 4;
     bool big = false;
     for (int f = 0; f < W; ++f) {
-        Restore<mh::GridSet *> cached_set(c->set);         // make_params reads the frame's sets through c->set
         mh::GridSet *SS = c->hb_sets[gen][f];
         for (int s = 0; s < nsets; ++s) {
             mh::GridSet &S = SS[s];
@@ -2896,10 +2750,10 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
             S.d_vdw = nullptr;
             MH_TRY(grid_reserve(S, ncells));
         }
-        c->box = boxes[f];
-        c->set = SS;                              // (SINGLE: set[1] is never read)
-        c->nslots_bound = bound;
-        SearchParams P = make_params(c);
+        SearchShape frame = group;
+        frame.box = boxes[f];
+        frame.set = SS;
+        SearchParams P = make_params(c, frame);
         P.nblocks = 0;
         P.out_cap = ~0ull;
         P.hist_nbins = (uint32_t)nbins;
@@ -2920,7 +2774,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
         for (int s = 0; s < nsets; ++s) {
             mh::GridSet &S = SS[s];
             GridFrame g{};
-            g.P = grid_bin_params(c, S, /*drop_nonfinite=*/false);
+            g.P = grid_bin_params(frame, S, /*drop_nonfinite=*/false);
             g.key = S.key.as<uint32_t>();
             g.cursor = S.cursor.as<uint32_t>();
             g.cell_count = S.cell_count.as<uint32_t>();
@@ -2969,7 +2823,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
             hipLaunchKernelGGL(scatter_frames_kernel, dim3((ns + 255u) / 256u, fw), dim3(256), 0, ss, G, ns);
             hipLaunchKernelGGL(place_order_frames_kernel, dim3(ncells, fw), dim3(64), 0, ss, G, ncells, q->ids_local);
         }
-        launch_hist_plan_frames(q->kind, ss, dP, fw, c->ntasks, c->hb_lean[gen].as<SlotDesc>(), c->hb_rest[gen].as<SlotDesc>(), queue, lslot);
+        launch_hist_plan_frames(q->kind, ss, dP, fw, group.ntasks, c->hb_lean[gen].as<SlotDesc>(), c->hb_rest[gen].as<SlotDesc>(), queue, lslot);
         // The generic kernel (the triclinic corner entries of every frame of the group: short latency-bound slots) runs HERE, behind
         // its plan on the side stream, not behind the persistent kernel on the main stream: there it met the next group's placement
         // kernel - 10^4 one-wave workgroups of 5 KB of LDS each, from the stream of higher priority - and waited for it to drain
@@ -3184,7 +3038,8 @@ int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
     call.size_masks = false;
     MH_TRY(prepare_search(s, &qq, call));      // (the plan kernel leaves the parameter block in s->params)
     s->params_fresh = false;
-    if (s->nslots_bound == 0) return 0;
+    const SearchShape &cur = s->cur;
+    if (cur.nslots_bound == 0) return 0;
     ContactArgs A{};
     A.g1 = K.g1;
     A.g2 = K.g2;
@@ -3197,7 +3052,7 @@ int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
     A.count = K.t_count;
     {
         Prof prof(s, 3);
-        launch_contacts(s->kind, (unsigned)s->num_cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)s->nslots_bound, A);
+        launch_contacts(cur.kind, (unsigned)s->num_cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)cur.nslots_bound, A);
         MH_HIP(hipGetLastError());
     }
     if (K.t_frame) {
@@ -3270,15 +3125,16 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     call.within_set = true;
     MH_TRY(prepare_search(c, q, call));
     c->have_search = false;                       // not a cached search for the fill calls of the stream form
-    const uint64_t nflags = q->ids_local ? c->set[0].n : (q->idx1 ? q->natoms1 : c->set[0].n);
+    const SearchShape &cur = c->cur;
+    const uint64_t nflags = q->ids_local ? cur.set[0].n : (q->idx1 ? q->natoms1 : cur.set[0].n);
     c->within_nflags = nflags;
     c->within_total = 0;
     if (out_count) *out_count = 0;
-    if (c->set[0].n == 0 || c->set[1].n == 0 || nflags == 0) {
+    if (cur.set[0].n == 0 || cur.set[1].n == 0 || nflags == 0) {
         c->have_within = true;
         return MOLAR_HIP_OK;
     }
-    const uint32_t ncells = c->dims[0] * c->dims[1] * c->dims[2];
+    const uint32_t ncells = (uint32_t)grid_cells(cur);
     const uint64_t ntiles = (nflags + 2047) / 2048;
     const size_t flag_bytes = (nflags + 3) & ~(size_t)3;
     const bool fresh_flags = c->w_flags.cap < flag_bytes;
@@ -3286,7 +3142,7 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     MH_TRY(c->w_tile_cnt.reserve((ntiles + 1) * 4));
     MH_TRY(c->w_tile_off.reserve((ntiles + 1) * 8));
     MH_TRY(c->params.reserve(sizeof(SearchParams)));
-    const SearchParams P = make_params(c);
+    const SearchParams P = make_params(c, cur);
     hipLaunchKernelGGL(upload_params_kernel, dim3(1), dim3(256), 0, c->stream, P, c->params.as<SearchParams>());
     // flags: all zero between calls.  A small-path call leaves only the flags of its list set: those are cleared through the list.
     if (fresh_flags || c->w_flags_all_dirty) MH_HIP(hipMemsetAsync(c->w_flags.p, 0, flag_bytes, c->stream));
@@ -3295,15 +3151,15 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
                            (uint32_t)c->w_list_dirty, c->w_flags.as<uint8_t>());
     c->w_flags_all_dirty = false;
     c->w_list_dirty = 0;
-    c->w_small = (uint64_t)c->set[1].n * 28ull <= (1ull << 17);           // <= 4681 second-set atoms: one wave per (atom, combination)
+    c->w_small = (uint64_t)cur.set[1].n * 28ull <= (1ull << 17);           // <= 4681 second-set atoms: one wave per (atom, combination)
     if (c->w_small) {
         MH_TRY(c->w_list.reserve((nflags + 1) * 4));
         MH_HIP(hipMemsetAsync(c->w_list.p, 0, 4, c->stream));               // word 0: the list's length, then the ids
         // cells of many 64-row blocks (large cutoffs) get several waves per (cell, combination)
-        uint32_t wsplit = (uint32_t)(((uint64_t)c->set[0].n / 64u) / ncells) + 1u;
+        uint32_t wsplit = (uint32_t)(((uint64_t)cur.set[0].n / 64u) / ncells) + 1u;
         if (wsplit > 64u) wsplit = 64u;
-        const uint32_t by_cell = ncells < c->set[1].n ? 1u : 0u;
-        hipLaunchKernelGGL(within_small_kernel, dim3((by_cell ? ncells : c->set[1].n) * 28u, wsplit), dim3(64), 0, c->stream, c->params.as<SearchParams>(), c->set[1].n, ncells, by_cell,
+        const uint32_t by_cell = ncells < cur.set[1].n ? 1u : 0u;
+        hipLaunchKernelGGL(within_small_kernel, dim3((by_cell ? ncells : cur.set[1].n) * 28u, wsplit), dim3(64), 0, c->stream, c->params.as<SearchParams>(), cur.set[1].n, ncells, by_cell,
                            c->w_flags.as<uint32_t>(), c->w_list.as<uint32_t>() + 1, c->w_list.as<uint32_t>());
         MH_HIP(hipGetLastError());
         uint32_t tot = 0;
@@ -3319,10 +3175,10 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     MH_TRY(c->w_part.reserve((size_t)ncells * WITHIN_MAX_PART * 4));
     MH_HIP(hipMemsetAsync(c->w_part_cnt.p, 0, (size_t)ncells * 4, c->stream));
     MH_HIP(hipMemsetAsync(c->w_tile_cnt.p, 0, (ntiles + 1) * 4, c->stream));
-    hipLaunchKernelGGL(within_partners_kernel, dim3((unsigned)((c->ntasks + 255) / 256)), dim3(256), 0, c->stream, c->params.as<SearchParams>(),
+    hipLaunchKernelGGL(within_partners_kernel, dim3((unsigned)((cur.ntasks + 255) / 256)), dim3(256), 0, c->stream, c->params.as<SearchParams>(),
                        c->w_part_cnt.as<uint32_t>(), c->w_part.as<uint32_t>());
     // big cells get several waves (a share of their 64-row blocks each)
-    uint32_t nsplit = (uint32_t)(((uint64_t)c->set[0].n / 64u) / ncells) + 1u;
+    uint32_t nsplit = (uint32_t)(((uint64_t)cur.set[0].n / 64u) / ncells) + 1u;
     if (nsplit > 64u) nsplit = 64u;
     hipLaunchKernelGGL(within_flags_kernel, dim3(ncells, nsplit), dim3(64), 0, c->stream, c->params.as<SearchParams>(),
                        c->w_part_cnt.as<uint32_t>(), c->w_part.as<uint32_t>(), c->w_flags.as<uint8_t>(), nsplit);

@@ -43,6 +43,22 @@ def test_rotation_solver_cpu():
     assert r.returncode == 0 and "all linalg tests passed" in r.stdout, r.stdout + r.stderr
 
 
+def test_search_shape_cpu():
+    """molar_amd/csrc/search_shape.hpp on the host (hipcc, no GPU needed to run): grid dims, the wrapped-pair policy, the kernel
+    family, the slot bound and the occupancy key against values recorded from the commit before the functions were split out."""
+    from molar_amd import build
+    build.build_library()
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, "test_search_shape")
+    libdir = os.path.join(ROOT, "molar_amd")
+    cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
+           os.path.join(ROOT, "tests", "cpp", "test_search_shape.cpp"), "-o", exe, "-L", libdir, "-lmolar_hip", f"-Wl,-rpath,{libdir}"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "all search-shape tests passed" in r.stdout, r.stdout + r.stderr
+
+
 @pytest.mark.gpu
 def test_host_api_gpu():
     from oracle import oracle as o

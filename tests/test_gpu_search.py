@@ -936,7 +936,7 @@ def test_matrix_core_count_band_at_other_length_scales(eng, orc32, scale, monkey
 @pytest.mark.parametrize("boxkind,L", [("dodecahedron", 60.0), ("sheared", 40.0), ("sheared_huge", 160.0)])
 def test_wrapped_band_adversarial_large_sheared_boxes(eng, orc32, boxkind, L):
     """The band / pruning margins of the wrapped fast path scale with ulp(L) and with the conditioning of the box
-    (search.hip make_params).  Adversarial cases at large L/rc: a 60-degree rhombic dodecahedron of 60 nm and a strongly
+    (search_shape.hpp wrapped_pair_policy).  Adversarial cases at large L/rc: a 60-degree rhombic dodecahedron of 60 nm and a strongly
     sheared 40 nm box at rc = 0.3 with >= 1e4 boundary-crossing pairs at rc*(1 +- 1e-6..1e-4), where the f32 evaluation
     of inv*v / M*f carries errors comparable to the distance from the cutoff; and a 160 nm sheared box at rc = 1.0 (the
     conditioning term dominates the margin).  Lists must be bit-identical to the oracle's."""

@@ -160,6 +160,74 @@ def test_requests_of_every_form_in_turn_equal_a_fresh_engine(a, sys_, orc32):
         same_sequence(sequence(a, e, s), want, f"round {rnd}")
 
 
+NO_SEARCH = 52          # MOLAR_HIP_ERR_NO_SEARCH
+
+
+def single_frame_histograms(a, e, s, which, box):
+    """The frames `which` of the block one by one through the single-frame histogram, summed into one set of device bins."""
+    b = bins_tensor()
+    for k in which:
+        e.search_histogram(a.SEARCH_SINGLE, CUTOFF, *HIST, s["d_frames"][k], box=box[k] if box.ndim == 3 else box, pbc=7, bins=b, want_count=False)
+    e.synchronize()
+    return b.cpu().numpy()
+
+
+def no_cached_search(a, e):
+    for call in (e.grid_dims, lambda: e.search_fill(1)):
+        with pytest.raises(a.MolarHipError) as err:
+            call()
+        assert err.value.code == NO_SEARCH
+
+
+def test_batched_frames_leave_the_cached_search_shape_alone(a, sys_, fresh_single):
+    """A batched frames call describes its frames by shapes of its own: search_cell_kernels() keeps answering for the context's
+    last search proper - also when the group's grid (5 x 5 x 5 under box_mid) is not that search's (4 x 4 x 4).  The group is
+    frames 0 and 2 of the block, which share `box`: two frames of one shape, everything in device memory."""
+    s = sys_
+    box_mid = s["boxes"][1]
+    e = a.Engine(0)
+    assert count_fill(a, e, s)[0] == fresh_single[0] and e.grid_dims() == (4, 4, 4)
+    before = e.search_cell_kernels()
+    pair = s["d_frames"][::2]                     # frames 0 and 2, a strided view
+    for box in (s["box"], box_mid):
+        want = single_frame_histograms(a, a.Engine(0), s, (0, 2), box)
+        b = bins_tensor()
+        e.search_histogram_frames(a.SEARCH_SINGLE, CUTOFF, *HIST, pair, box=box, pbc=7, bins=b)
+        e.synchronize()
+        got = b.cpu().numpy()
+        assert got.tobytes() == want.tobytes() and got.any()
+        assert e.search_cell_kernels() == before
+        no_cached_search(a, e)
+        same_list(count_fill(a, e, s), fresh_single, "count + fill after the batched frames call")
+        assert e.search_cell_kernels()[0] == before[0]
+        before = e.search_cell_kernels()          # (the second count knows the grid's occupied cells from the first)
+
+
+def test_frames_that_give_up_batching_leave_nothing_behind(a, sys_):
+    """The three-frame block whose middle frame has other grid dims leaves the batched path after its dims loop and is walked
+    frame by frame: those are searches proper, so the context then answers for the last of them, as an Engine does that was
+    handed the three frames singly - and a count + fill on another box equals a fresh Engine's."""
+    s = sys_
+    box_mid = s["boxes"][1]
+    e, g = a.Engine(0), a.Engine(0)
+    for eng in (e, g):
+        count_fill(a, eng, s)
+    want = single_frame_histograms(a, g, s, (0, 1, 2), s["boxes"])
+    b = bins_tensor()
+    e.search_histogram_frames(a.SEARCH_SINGLE, CUTOFF, *HIST, s["d_frames"], box=s["boxes"], pbc=7, bins=b)
+    e.synchronize()
+    got = b.cpu().numpy()
+    assert got.tobytes() == want.tobytes() and got.any()
+    assert e.search_cell_kernels() == g.search_cell_kernels()
+    no_cached_search(a, e)
+
+    def on_mid(eng):
+        cnt = eng.search_count(a.SEARCH_SINGLE, CUTOFF, s["frames"][1], box=box_mid, pbc=7)
+        return (cnt,) + eng.search_fill(cnt)
+    same_list(on_mid(e), on_mid(a.Engine(0)), "count + fill on another box after the frames call")
+    assert e.grid_dims() == (5, 5, 5)
+
+
 def test_membrane_frame_then_a_search_with_a_nan_coordinate(a, sys_):
     """(e) the membrane's marker search drops non-finite atoms from its grid and fills the pairs plane only; a plain search
     behind it on the same context bins a NaN atom the way the reference does and delivers distances."""
