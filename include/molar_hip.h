@@ -617,6 +617,70 @@ int molar_hip_fluct_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes
                         const uint64_t *idx, size_t n, const double *mass, const double *ref, int fit, int iterations,
                         double *mean, double *rmsf, double *cov, size_t ld, double *fit_out);
 
+/* ---- Mean-squared displacement of a block of trajectory frames: the no-jump unwrap of every selected atom along time, the
+ * displacement of each particle (an atom, or the centre of mass of a group of atoms), the optional removal of the drift of a
+ * reference set, and MSD(tau), its fourth moment and the per-particle curves over all time origins, in one call (gmx msd,
+ * MDAnalysis EinsteinMSD).  Frame f is at frames + f * frame_stride (elements, >= 3 natoms), as for molar_hip_rmsd_matrix.
+ * Operation by operation (Real = float, or double for _f64; everything below is formed and accumulated in double from the
+ * exact inputs, only the outputs are rounded to Real; F = nframes):
+ *   selection idx[0..n), shared by all frames; idx == NULL: atoms 0 .. n-1.  w_k = mass[idx[k]] (mass: one per ATOM, >= 0);
+ *   mass == NULL: w_k = 1.
+ *   boxes: one column-major box9 for all frames (box_stride == 0) or [F][9] (box_stride == 9), made a PeriodicBox in double
+ *     (from_matrix: inverse and triclinic corrections); boxes == NULL or pbc == 0: the trajectory is taken as already
+ *     unwrapped and no image is removed.  pbc is the PbcDims byte.
+ *   no-jump displacement, per selected atom k:  u_k(0) = 0;  for f >= 1  s = x_k(f) - x_k(f-1) (exact in double for float
+ *     inputs),  d = shortest_vector_dims(box_f, s, pbc) (periodic_box.rs:286-318: fractional rounding half away from zero on
+ *     the periodic dimensions, the triclinic image search for the full mask only),  u_k(f) = u_k(f-1) + d, added in frame
+ *     order.  The box of the LATER frame is used: the displacement ("toroidal-view") scheme, valid under a fluctuating box.
+ *   particles: group_offsets[nparticles + 1] is a CSR over the selection order, atoms [off[g], off[g+1]) of the selection
+ *     form particle g; group_offsets == NULL: every selected atom is a particle, P = n (nparticles is not read).
+ *     U_g(f) = sum_k w_k u_k(f) / W_g over the atoms of g in index order (a group of more than 256 atoms: in pieces of 256,
+ *     each by a fixed tree, the pieces in order), W_g = sum_k w_k: the displacement of the group's centre of mass, correct
+ *     even when the molecule is split across the box in frame 0, because only displacements enter.
+ *   drift removal: ref_idx[0..nref) is a second selection (ref_idx == NULL: atoms 0 .. nref-1), weighted with mass;
+ *     D(f) = its weighted mean no-jump displacement, U_g(f) -= D(f).  nref == 0: none.
+ *   lags: msd_dims (bits x, y, z; 1 .. 7) picks the components of r^2 = sum_d Delta_d^2, Delta = U_g(t+tau) - U_g(t); the
+ *     origins are t = 0, origin_stride, 2 origin_stride, ... while t + tau <= F - 1, count[tau] their number.  For
+ *     tau = 0 .. max_lag:  msd[tau] = sum_g sum_t r^2 / (P count[tau]);  m4[tau] the same with r^4 (the non-Gaussian
+ *     parameter is ndims / (ndims + 2) * m4 / msd^2 - 1);  msd_particle[g][tau] = sum_t r^2 / count[tau], laid out [P][ld],
+ *     ld >= max_lag + 1, the rest of a row is not touched.  msd[0] is exactly 0.  r^2 and the sum of r^4 are formed with
+ *     fused multiply-adds.
+ *   disp [F][P][3]: the U_g(f) themselves, the unwrapped particle trajectory relative to frame 0.
+ *   All sums have a fixed order that depends on the sizes alone (no floating-point atomics): the same call gives the same bits.
+ * Every output (msd [max_lag+1], m4 [max_lag+1], msd_particle, disp) may be NULL and is then not computed; with only disp
+ * asked for the lag kernel does not run.  frames, idx, mass, boxes, group_offsets, ref_idx and every output may each be host
+ * or device memory (group_offsets in device memory are copied to the host first: they decide the launch geometry).  Device
+ * outputs are written on the context's stream and not waited for (the call itself waits once, after the unwrap, for the 16
+ * bytes that decide its status).
+ * Errors: n == 0, msd_particle != NULL with ld below max_lag + 1, offsets that do not start at 0, are not increasing (an empty
+ * group) or do not end at n: ERR_SIZES; W_g == 0 for a particle or for the reference set: ERR_ZERO_MASS; max_lag >= nframes
+ * (with nframes >= 1), origin_stride == 0, msd_dims == 0 or > 7, pbc > 7, a box_stride other than 0 and 9, an index not below
+ * natoms, natoms == 0, n (or nref) > natoms without an index, a stride below 3 natoms (with more than one frame):
+ * ERR_INVALID_ARGUMENT; pbc != 0 with boxes == NULL: ERR_NO_PBC; a box with a vector of zero length:
+ * ERR_ZERO_LENGTH_VECTOR, one without an inverse: ERR_INVERSE_FAILED (as PeriodicBox::from_matrix); a workspace or a result that cannot be allocated: ERR_TOO_LARGE with the byte count in
+ * molar_hip_last_error().  The errors of the arguments alone are reported before the context is used.  nframes == 0 is a
+ * successful no-op.  A non-finite selected coordinate gives NaN in its
+ * particle's disp from that frame on, in that particle's row of msd_particle and in every msd / m4 entry the particle
+ * enters; rows of other particles are as without it; with drift removal and the atom in the reference set everything is
+ * NaN; the status stays MOLAR_HIP_OK and nothing is read back for it.
+ * molar_hip_msd_plan is a pure host function: the bytes of device workspace such a call allocates (kept by the context,
+ * grows only; staging of host-memory arguments not included; never smaller for a larger argument; per_frame_boxes: the
+ * call has box_stride == 9 and pbc != 0; want_lags == 0: only disp is asked for, and nothing is reserved for the lag
+ * stage) and the two launch-shape sizes of the lag kernel: particle_chunk, the particles a workgroup adds in order, and
+ * lag_block, the lags of a workgroup (one lane each). */
+int molar_hip_msd_plan(size_t nframes, size_t n, size_t nparticles, size_t nref, size_t max_lag, int per_frame_boxes,
+                       int want_lags, size_t *workspace_bytes, uint32_t *particle_chunk, uint32_t *lag_block);
+int molar_hip_msd(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                  const uint64_t *idx, size_t n, const float *mass, const float *boxes, size_t box_stride, uint8_t pbc,
+                  const uint64_t *group_offsets, size_t nparticles, const uint64_t *ref_idx, size_t nref, size_t max_lag,
+                  size_t origin_stride, uint32_t msd_dims, float *msd, float *m4, float *msd_particle, size_t ld,
+                  float *disp);
+int molar_hip_msd_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *idx, size_t n, const double *mass, const double *boxes, size_t box_stride,
+                      uint8_t pbc, const uint64_t *group_offsets, size_t nparticles, const uint64_t *ref_idx, size_t nref,
+                      size_t max_lag, size_t origin_stride, uint32_t msd_dims, double *msd, double *m4,
+                      double *msd_particle, size_t ld, double *disp);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

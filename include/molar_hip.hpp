@@ -536,6 +536,67 @@ inline FluctuationsOf<double> fluctuations_f64(Engine &eng, const double *frames
     return out;
 }
 
+// Mean-squared displacement of a block of frames over all time origins (molar_hip_msd; the definition: molar_hip.h): every
+// selected atom followed from frame to frame with the periodic jumps removed (`boxes`: one column-major box9, or one per
+// frame with per_frame_boxes; null: already unwrapped), particles = the selected atoms, or their groups (`group_offsets`: CSR
+// over the selection order, empty: every atom) by centre of mass, the drift of `ref_index` removed (empty: none).
+struct MsdOptions {
+    size_t max_lag = SIZE_MAX;        // SIZE_MAX: nframes - 1
+    size_t origin_stride = 1;
+    uint32_t dims = 7;                // bits x, y, z of the components that enter
+    uint8_t pbc = MOLAR_HIP_PBC_FULL;
+    bool per_frame_boxes = false;
+    bool mass_weighted = true;
+    bool want_particle = false, want_disp = false;
+};
+template <class Real>
+struct MsdOf {
+    std::vector<Real> msd, m4;        // [max_lag + 1]
+    std::vector<Real> msd_particle;   // [P][max_lag + 1], empty unless asked for
+    std::vector<Real> disp;           // [F][P][3], empty unless asked for
+    size_t nparticles = 0, max_lag = 0;
+};
+using Msd = MsdOf<Float>;
+inline Msd msd(const SelBound &sel, const std::vector<Pos> &frames, const Float *boxes = nullptr, const MsdOptions &opt = MsdOptions(),
+               const std::vector<usize> &group_offsets = {}, const std::vector<usize> &ref_index = {}) {
+    const size_t natoms = sel.natoms(), n = sel.len();
+    if (natoms == 0 || frames.size() % natoms) throw MolarError(MOLAR_HIP_ERR_SIZES, "msd: the block is not a whole number of frames");
+    const size_t F = frames.size() / natoms;
+    Msd out;
+    if (F == 0) return out;
+    out.nparticles = group_offsets.empty() ? n : group_offsets.size() - 1;
+    out.max_lag = opt.max_lag == SIZE_MAX ? F - 1 : opt.max_lag;
+    out.msd.resize(out.max_lag + 1);
+    out.m4.resize(out.max_lag + 1);
+    if (opt.want_particle) out.msd_particle.resize(out.nparticles * (out.max_lag + 1));
+    if (opt.want_disp) out.disp.resize(F * out.nparticles * 3);
+    check(molar_hip_msd(sel.ctx(), &frames[0].x, F, natoms * 3, natoms, sel.get_index_slice().data(), n, opt.mass_weighted ? sel.masses() : nullptr, boxes,
+                        opt.per_frame_boxes ? 9 : 0, boxes ? opt.pbc : uint8_t(0), group_offsets.empty() ? nullptr : group_offsets.data(), out.nparticles,
+                        ref_index.empty() ? nullptr : ref_index.data(), ref_index.size(), out.max_lag, opt.origin_stride, opt.dims, out.msd.data(),
+                        out.m4.data(), opt.want_particle ? out.msd_particle.data() : nullptr, out.max_lag + 1, opt.want_disp ? out.disp.data() : nullptr));
+    return out;
+}
+// the same on f64 frames, masses and boxes (MolAR's f64 feature): molar_hip_msd_f64; mass: one per atom, or null; an empty
+// index means every atom
+inline MsdOf<double> msd_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const std::vector<usize> &index, const double *mass,
+                             const double *boxes = nullptr, const MsdOptions &opt = MsdOptions(), const std::vector<usize> &group_offsets = {},
+                             const std::vector<usize> &ref_index = {}) {
+    const size_t n = index.empty() ? natoms : index.size();
+    MsdOf<double> out;
+    if (nframes == 0) return out;
+    out.nparticles = group_offsets.empty() ? n : group_offsets.size() - 1;
+    out.max_lag = opt.max_lag == SIZE_MAX ? nframes - 1 : opt.max_lag;
+    out.msd.resize(out.max_lag + 1);
+    out.m4.resize(out.max_lag + 1);
+    if (opt.want_particle) out.msd_particle.resize(out.nparticles * (out.max_lag + 1));
+    if (opt.want_disp) out.disp.resize(nframes * out.nparticles * 3);
+    check(molar_hip_msd_f64(eng.ctx(), frames, nframes, natoms * 3, natoms, index.empty() ? nullptr : index.data(), n, mass, boxes,
+                            opt.per_frame_boxes ? 9 : 0, boxes ? opt.pbc : uint8_t(0), group_offsets.empty() ? nullptr : group_offsets.data(), out.nparticles,
+                            ref_index.empty() ? nullptr : ref_index.data(), ref_index.size(), out.max_lag, opt.origin_stride, opt.dims, out.msd.data(),
+                            out.m4.data(), opt.want_particle ? out.msd_particle.data() : nullptr, out.max_lag + 1, opt.want_disp ? out.disp.data() : nullptr));
+    return out;
+}
+
 // The per-frame fit of an AnalysisTask whose States live in host memory (analysis_task.rs:245-252 hands them over frame by frame),
 // at the rate the SELECTION crosses the link: molar_hip_fit_stream_*.  Built on the selection and the reference once;
 //     auto t1 = fs.begin(state_k1.coords);  FitRecord r = fs.end(t0);      // up to three frames in flight

@@ -190,6 +190,9 @@ SYMBOLS = {
     "molar_hip_fluct_plan": (_I, [_SZ, _SZ, _I, _P, _P]),
     "molar_hip_fluct": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     "molar_hip_fluct_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
+    "molar_hip_msd_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _I, _I, _P, _P, _P]),
+    "molar_hip_msd": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),
+    "molar_hip_msd_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

@@ -1155,6 +1155,22 @@ class Engine:
         `out`: an optional Fluctuations (or 4-tuple) of destinations of the same kind; None entries are allocated."""
         return _fluct_call(self.lib, self.lib.molar_hip_fluct, self.ctx, frames, idx, mass, ref, fit, iterations, cov, fit_out, out, np.float32)
 
+    def msd(self, frames, idx=None, mass=None, boxes=None, pbc=7, groups=None, ref_idx=None, max_lag=None, origin_stride=1, dims=7,
+            m4=True, per_particle=False, disp=False, msd=True, out=None):
+        """Mean-squared displacement over all time origins of frames [F, natoms, 3] float32 (molar_hip_msd; the definition:
+        molar_hip.h).  Every selected atom (`idx`, None: every atom) is followed from frame to frame with the periodic jumps
+        removed (`boxes`: one column-major box [9] or [3, 3] transposed into it, or one per frame [F, 9]; None: the
+        trajectory is already unwrapped; `pbc`: the PbcDims byte, see pbc_mask).  `groups`: CSR offsets [P + 1] over the
+        selection order, each group a particle followed by its centre of mass (`mass`: one per atom, None: unit weights);
+        None: every selected atom is a particle.  `ref_idx`: a second selection whose weighted mean displacement (the drift)
+        is subtracted.  Lags 0 .. max_lag (None: F - 1), origins 0, origin_stride, ...; `dims`: the bits x, y, z of the
+        components that enter.  Returns Msd(msd [L + 1], m4 [L + 1], msd_particle [P, L + 1], disp [F, P, 3]); the entries
+        not asked for (msd=, m4=, per_particle=, disp=) are None.  numpy in, numpy out; torch CUDA in, torch CUDA out, written
+        on the ENGINE's stream and not waited for (`Engine.synchronize()` before torch reads them).  `out`: an optional Msd
+        (or 4-tuple) of destinations of the same kind; None entries are allocated."""
+        return _msd_call(self.lib, self.lib.molar_hip_msd, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride, dims,
+                         msd, m4, per_particle, disp, out, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -1352,6 +1368,98 @@ def _rmsd_matrix_call(lib, fn, ctx, frames, idx, mass, frames2, fit, out, real):
     return out
 
 
+def msd_plan(nframes, n, nparticles=None, nref=0, max_lag=None, per_frame_boxes=False, want_lags=True):
+    """(workspace_bytes, particle_chunk, lag_block) of an msd call of these sizes (molar_hip_msd_plan): the device workspace and
+    the particles and lags a workgroup of the lag kernel owns.  nparticles=None: every atom is a particle; max_lag=None:
+    nframes - 1; want_lags=False: only `disp` is asked for.  A host function: no GPU is needed."""
+    P = int(n) if nparticles is None else int(nparticles)
+    L = max(int(nframes) - 1, 0) if max_lag is None else int(max_lag)
+    ws, pc, lb = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_msd_plan(int(nframes), int(n), P, int(nref), L, 1 if per_frame_boxes else 0, 1 if want_lags else 0,
+                                         C.addressof(ws), C.addressof(pc), C.addressof(lb)))
+    return int(ws.value), int(pc.value), int(lb.value)
+
+
+def msd_alpha2(msd, m4, ndims):
+    """The non-Gaussian parameter alpha_2 = ndims / (ndims + 2) * m4 / msd^2 - 1 per lag, in float64 (0 for a Gaussian
+    displacement distribution in ndims dimensions; NaN where msd is 0, as at lag 0)."""
+    msd = np.asarray(msd, np.float64)
+    m4 = np.asarray(m4, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return ndims / (ndims + 2.0) * m4 / (msd * msd) - 1.0
+
+
+def msd_diffusion(msd, dt, lo, hi, ndims):
+    """(slope, intercept, D) of the least-squares line through (tau * dt, msd[tau]) for the lags lo .. hi inclusive;
+    D = slope / (2 ndims) (the Einstein relation).  float64 on the host."""
+    lo, hi = int(lo), int(hi)
+    y = np.asarray(msd, np.float64)[lo:hi + 1]
+    assert y.shape[0] >= 2, "a line needs two lags"
+    x = np.arange(lo, hi + 1, dtype=np.float64) * float(dt)
+    xm, ym = x.mean(), y.mean()
+    slope = float(((x - xm) * (y - ym)).sum() / ((x - xm) ** 2).sum())
+    return slope, float(ym - slope * xm), slope / (2.0 * ndims)
+
+
+Msd = collections.namedtuple("Msd", ["msd", "m4", "msd_particle", "disp"])
+
+
+def _msd_call(lib, fn, ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride, dims, want_msd, want_m4, per_particle,
+              want_disp, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (idx, mass, boxes, groups, ref_idx)
+    idx = _u64(idx); mass = conv(mass); groups = _u64(groups); ref_idx = _u64(ref_idx)
+    box_stride = 0
+    if boxes is None:
+        pbc = 0                                  # already unwrapped: no image is removed
+    else:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    n = natoms if idx is None else idx.shape[0]
+    P = n if groups is None else groups.shape[0] - 1
+    nref = 0 if ref_idx is None else ref_idx.shape[0]
+    if mass is not None:
+        assert mass.shape[0] == natoms, "one mass per atom"
+    L = max(F - 1, 0) if max_lag is None else int(max_lag)
+    want = (bool(want_msd), bool(want_m4), bool(per_particle), bool(want_disp))
+    shapes = ((L + 1,), (L + 1,), (P, L + 1), (F, P, 3))
+    given = tuple(out) if out is not None else (None,) * 4
+    res = []
+    for w, shape, g in zip(want, shapes, given):
+        if not w:
+            res.append(None)
+        elif g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape
+            assert (g.dtype == fr.dtype and g.is_contiguous()) if dev else (g.dtype == real and g.flags.c_contiguous)
+            res.append(g)
+        elif dev:
+            import torch
+            res.append(torch.zeros(shape, dtype=fr.dtype, device=fr.device))
+        else:
+            res.append(np.zeros(shape, real))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ia, k1 = _addr(idx); ma, k2 = _addr(mass); ba, k3 = _addr(boxes); ga, k4 = _addr(groups); ra, k5 = _addr(ref_idx)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ia, n, ma, ba, box_stride, int(pbc), ga, P, ra, nref, L, int(origin_stride), int(dims),
+             addr[0], addr[1], addr[2], L + 1, addr[3]))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((idx, mass, boxes, groups, ref_idx), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return Msd(*res)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -1543,6 +1651,12 @@ class MeasureF64:
     def fluctuations(self, frames, idx=None, mass=None, ref=None, fit=True, iterations=0, cov=False, fit_out=False, out=None):
         """Engine.fluctuations on float64 frames, masses and reference (molar_hip_fluct_f64): float64 results."""
         return _fluct_call(self.lib, self.lib.molar_hip_fluct_f64, self.ctx, frames, idx, mass, ref, fit, iterations, cov, fit_out, out, np.float64)
+
+    def msd(self, frames, idx=None, mass=None, boxes=None, pbc=7, groups=None, ref_idx=None, max_lag=None, origin_stride=1, dims=7,
+            m4=True, per_particle=False, disp=False, msd=True, out=None):
+        """Engine.msd on float64 frames, masses and boxes (molar_hip_msd_f64): float64 results."""
+        return _msd_call(self.lib, self.lib.molar_hip_msd_f64, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride,
+                         dims, msd, m4, per_particle, disp, out, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

@@ -8,6 +8,7 @@ namespace mh { void search64_release(molar_hip_ctx *c); }
 namespace mh { void sasa_release(molar_hip_ctx *c); }
 namespace mh { void rmsd_matrix_release(molar_hip_ctx *c); }
 namespace mh { void fluct_release(molar_hip_ctx *c); }
+namespace mh { void msd_release(molar_hip_ctx *c); }
 #include <cstdlib>
 
 using namespace mh;
@@ -217,6 +218,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::sasa_release(c);
     mh::rmsd_matrix_release(c);
     mh::fluct_release(c);
+    mh::msd_release(c);
     if (c->h_sizes) (void)hipHostFree(c->h_sizes);
     for (auto &t : c->tickets)
         if (t.done) (void)hipEventDestroy(t.done);

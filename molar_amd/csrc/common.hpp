@@ -142,6 +142,7 @@ struct molar_hip_search64_state;        // the cached f64 search (search_f64.hip
 struct molar_hip_sasa_state;            // point tables, grid and scratch of the surface-area calls (sasa.hip)
 struct molar_hip_rmsd_matrix_state;     // packed operands, partial covariances and staging of the all-pairs RMSD (rmsd_matrix.hip)
 struct molar_hip_fluct_state;           // fits, packed deviations, partial covariances and staging of the fluctuations (fluct.hip)
+struct molar_hip_msd_state;             // boxes, unwrapped particle trajectories, partial lag sums and staging of the displacements (msd.hip)
 
 // frames per launch of molar_hip_search_histogram_frames (search.hip, hist_frames_group)
 #ifndef MH_HIST_BATCH
@@ -161,6 +162,7 @@ struct molar_hip_ctx {
     molar_hip_sasa_state *sasa = nullptr;         // created by the first molar_hip_sasa*
     molar_hip_rmsd_matrix_state *rmsdm = nullptr; // created by the first molar_hip_rmsd_matrix*
     molar_hip_fluct_state *fluct = nullptr;       // created by the first molar_hip_fluct*
+    molar_hip_msd_state *msd = nullptr;           // created by the first molar_hip_msd*
     // ring of pinned chunks for large results that go to pageable host memory (hoststream.hpp), allocated on first use
     void *ring[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -861,6 +861,92 @@ impl Engine {
         self.plugin.check(unsafe { (self.plugin.fns.fluct_plan)(nframes, n, want_cov as i32, &mut ws, &mut ks) })?;
         Ok((ws, ks))
     }
+
+    /// Mean-squared displacement of a block of frames over all time origins through molar_hip_msd (the definition:
+    /// molar_hip.h): every selected atom is followed from frame to frame with the periodic jumps removed (`boxes`: one
+    /// column-major box of 9 numbers, or 9 per frame; None: the frames are already unwrapped; `pbc`: the PbcDims byte),
+    /// particles are the selected atoms or, with `group_offsets` (CSR over the selection order), the centres of mass of their
+    /// groups, and the weighted mean displacement of `ref_index` (the drift) is subtracted when given.  Lags 0 ..= `max_lag`
+    /// (None: nframes - 1), origins 0, `origin_stride`, ...; `dims`: the bits x, y, z of the components that enter.
+    #[allow(clippy::too_many_arguments)]
+    pub fn msd(
+        &self, frames: &[[f32; 3]], natoms: usize, index: Option<&[usize]>, masses: Option<&[f32]>, boxes: Option<&[f32]>, pbc: u8,
+        group_offsets: Option<&[usize]>, ref_index: Option<&[usize]>, max_lag: Option<usize>, origin_stride: usize, dims: u32, want_particle: bool,
+        want_disp: bool,
+    ) -> Result<Msd, EngineError> {
+        check_index(index, natoms, "msd")?;
+        check_index(ref_index, natoms, "msd: reference set")?;
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("msd: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        if let Some(m) = masses {
+            check_column(m.len(), natoms, "msd: masses")?;
+        }
+        let nframes = frames.len() / natoms;
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { natoms };
+        if nsel == 0 {
+            return Err(EngineError::Sizes("msd: empty selection".into()));
+        }
+        let box_stride = match boxes {
+            None => 0,
+            Some(b) if b.len() == 9 => 0,
+            Some(b) if b.len() == 9 * nframes => 9,
+            Some(b) => return Err(EngineError::Sizes(format!("msd: {} box numbers for {nframes} frames", b.len()))),
+        };
+        let nparticles = match group_offsets {
+            Some(g) if g.is_empty() => return Err(EngineError::Sizes("msd: empty group offsets".into())),
+            Some(g) => g.len() - 1,
+            None => nsel,
+        };
+        let lags = max_lag.unwrap_or(nframes.saturating_sub(1)) + 1;
+        let mut out = Msd {
+            msd: vec![0f32; lags],
+            m4: vec![0f32; lags],
+            msd_particle: if want_particle { vec![0f32; nparticles * lags] } else { Vec::new() },
+            disp: if want_disp { vec![[0f32; 3]; nframes * nparticles] } else { Vec::new() },
+            nparticles,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        let mp = masses.map_or(std::ptr::null(), |m| m.as_ptr());
+        let bp = boxes.map_or(std::ptr::null(), |b| b.as_ptr());
+        let gp = group_offsets.map_or(std::ptr::null(), |g| g.as_ptr() as *const u64);
+        let (rp, nref) = ref_index.map_or((std::ptr::null(), 0), |r| (r.as_ptr() as *const u64, r.len()));
+        let pp = if want_particle { out.msd_particle.as_mut_ptr() } else { std::ptr::null_mut() };
+        let dp = if want_disp { out.disp.as_mut_ptr() as *mut f32 } else { std::ptr::null_mut() };
+        self.plugin.check(unsafe {
+            (self.plugin.fns.msd)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, ip, nsel, mp, bp, box_stride,
+                                  if boxes.is_some() { pbc } else { 0 }, gp, nparticles, rp, nref, lags - 1, origin_stride, dims, out.msd.as_mut_ptr(),
+                                  out.m4.as_mut_ptr(), pp, lags, dp)
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes, particles per workgroup and lags per workgroup of the lag kernel for an `msd` call of these
+    /// sizes (molar_hip_msd_plan, a host function).  `want_lags` false: only the displacements are asked for.
+    #[allow(clippy::too_many_arguments)]
+    pub fn msd_plan(
+        &self, nframes: usize, n: usize, nparticles: usize, nref: usize, max_lag: usize, per_frame_boxes: bool, want_lags: bool,
+    ) -> Result<(usize, u32, u32), EngineError> {
+        let (mut ws, mut pc, mut lb) = (0usize, 0u32, 0u32);
+        self.plugin.check(unsafe {
+            (self.plugin.fns.msd_plan)(nframes, n, nparticles, nref, max_lag, per_frame_boxes as i32, want_lags as i32, &mut ws, &mut pc, &mut lb)
+        })?;
+        Ok((ws, pc, lb))
+    }
+}
+
+/// What `Engine::msd` returns: MSD and fourth moment per lag, the per-particle curves row by row and the unwrapped particle
+/// displacements [frame][particle] relative to frame 0 (the last two empty unless asked for).
+#[derive(Debug, Clone, Default)]
+pub struct Msd {
+    pub msd: Vec<f32>,
+    pub m4: Vec<f32>,
+    pub msd_particle: Vec<f32>,
+    pub disp: Vec<[f32; 3]>,
+    pub nparticles: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless
