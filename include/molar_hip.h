@@ -227,6 +227,15 @@ int molar_hip_search_grid_dims(molar_hip_ctx *ctx, uint64_t dims[3]);
  * second or third frame on.  occupied_cells (may be NULL): the counts that search went by, 0 = not known then.  Diagnostic; the
  * results do not depend on the choice. */
 int molar_hip_search_cell_kernels(molar_hip_ctx *ctx, int32_t *lanes, uint64_t occupied_cells[2]);
+/* How the plan of the search this context prepared LAST was cut into slots (one wave of the count and fill passes each): the number
+ * of slots it produced and the number that slots of 64 CONSECUTIVE rows per plan entry would have given.  Where the regular kernels
+ * of the fixed-cutoff kinds cut slots from the rows of an entry that can have a hit at all (dense frames)
+ * the first number is the smaller one; every other search that keeps the record - vdW and stream-form `within` searches included -
+ * reports two equal numbers.  The numbers sit in device memory and are read when asked for: the call waits for the context's
+ * stream, and with pipelined searches (molar_hip_search_resident_begin / _end) it answers for the search begun last, not for the
+ * one ended last.  MOLAR_HIP_ERR_NO_SEARCH when the search prepared last kept no such record: plans of more than 2^22 entries, the
+ * fused histograms of the fixed-cutoff kinds, `within` sets, contact counts.  Diagnostic; results do not depend on it. */
+int molar_hip_search_slot_counts(molar_hip_ctx *ctx, uint64_t *slots, uint64_t *consecutive_slots);
 /* Device-resident result of the cached search: fills ctx-owned buffers (reused across frames)
  * and returns their device addresses; valid until the next search on this ctx. */
 int molar_hip_search_fill_device(molar_hip_ctx *ctx, const uint32_t **d_pairs, const float **d_dist);

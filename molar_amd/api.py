@@ -306,6 +306,13 @@ class Engine:
         check(self.lib.molar_hip_search_cell_kernels(self.ctx, C.byref(lanes), occ))
         return int(lanes.value), (int(occ[0]), int(occ[1]))
 
+    def search_slot_counts(self):
+        """molar_hip_search_slot_counts: (slots the plan of the context's last search produced, slots that 64 consecutive rows per
+        plan entry would have given).  The first is smaller where slots are cut from live rows; equal everywhere else."""
+        slots, rows = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.molar_hip_search_slot_counts(self.ctx, C.byref(slots), C.byref(rows)))
+        return int(slots.value), int(rows.value)
+
     def search_resident_planes(self, want_dist=True):
         """molar_hip_search_resident_planes: want_dist=False makes the resident searches fill the (i, j) plane only
         (DistanceSearchOutput of (usize, usize)); the distance addresses they return are then None."""

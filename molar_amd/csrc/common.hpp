@@ -115,6 +115,9 @@ struct GridSet {
     DevBuf h16;                // 8 x f16 per sorted atom (the reference's cell order, like `sorted`): hi/lo split of the position relative to the
                                // cell's origin and of its squared norm - the B operand of the matrix-core count pass
     DevBuf cell_org;           // float4 per cell: origin (centre of the bounding box), .w = bound on |position - origin|
+    DevBuf live;               // first set of a search with live-row slots (search_shape.hpp, live_row_slots): per plan entry LIVE_ROW_GROUPS
+                               // 64-bit masks of the first cell's rows that can have a hit in the second cell, then a u32 live count per
+                               // entry (live_rows_kernel, behind the grid build: the masks are of the generation like the grid itself)
 };
 
 // ---------------------------------------------------------------- the shape of one search
@@ -213,6 +216,10 @@ struct molar_hip_ctx {
     mh::DevBuf sort_tmp, sort_tmp_side;   // scratch of the device sort (devsort.hip), per stream
     mh::DevBuf scan_state;     // ticket + tile descriptors of the single-pass scans (zeroed by the plan kernel)
     mh::DevBuf fplan_tiles;    // plan_tiles_kernel -> plan_slots_kernel: slot / hit-history totals per tile of 256 plan entries
+    mh::DevBuf slot_stat;      // u64[2] left by plan_slots_kernel: slots of the last plan, slots consecutive rows would have given
+    bool slot_stat_valid = false;          // ... the last search was planned that way (molar_hip_search_slot_counts)
+    bool plan_live = false;                // the slot records of the cached search are cut from live rows: launch_pairs takes the
+                                           // pair_kernel<.., LIVE = true> instances
     mh::DevBuf out_pairs_set[2];   // ctx-owned result buffers (device-resident results / host staging); the second
     mh::DevBuf out_dist_set[2];    // set exists for the pipelined begin/end searches only
     mh::DevBuf &out_pairs = out_pairs_set[0];

@@ -33,6 +33,8 @@ enum { MODE_COUNT = 0, MODE_FILL = 1, MODE_HIST = 2 };
 constexpr int waves_per_block(int mode) { return mode == MODE_HIST ? 4 : MH_WPB; }
 constexpr int KREG = 8;            // B-cell chunks (of 64 atoms) a lane keeps in registers
 constexpr int FIFO_CAP = 128;      // per-wave LDS FIFO entries (flush threshold 64, push <= 64)
+constexpr int LIVE_GROUPS = KREG;  // live-row masks per plan entry: 64-bit words, one per 64 rows of the first cell (live_rows_kernel)
+constexpr uint32_t SLOT_LIVE = 0x400u;   // TaskDesc / SlotDesc flags: the entry's slots are cut from its LIVE rows (i0 = rank of the first one)
 #ifndef MOLAR_HIP_NO_WIDE_FLUSH
 #define MOLAR_HIP_WIDE_FLUSH 1
 #endif
@@ -138,7 +140,7 @@ struct SlotDesc {
     uint32_t a0, n1, b0, n2;          // as TaskDesc
     uint32_t cb, flags, i0, frame;    // i0: first row of the slot inside the first cell; frame: which parameter block of the launch the slot
                                       // belongs to (fused histogram over several frames, molar_hip_search_histogram_frames; 0 everywhere else)
-    unsigned long long moff, pad1;    // first 64-word unit of the slot in maskbuf
+    unsigned long long moff, pad1;    // first 64-word unit of the slot in maskbuf; pad1: SLOT_LIVE slots - address of the entry's LIVE_GROUPS mask words
 };
 static_assert(sizeof(SlotDesc) == 48, "SlotDesc is read with three 16-byte loads");
 
@@ -153,6 +155,17 @@ struct Task {
     bool tri;
     bool valid;
 };
+
+// A task as one slot of pair_kernel sees it.  Live-ranked slot (SLOT_LIVE; regular count / fill instances only): the slot is rows
+// [i0, i0 + 64) of the entry's LIVE rows in row order - lane l loads row `lrow` of the first cell, n1 counts the entry's live rows,
+// and no row is pruned again.  (Its own type: Task stays what the plan kernels and the other families compile against.)
+struct SlotTask : Task {
+    bool live = false;
+    uint32_t lrow = 0;
+};
+
+// the row of the first cell that lane `lane` of a slot loads
+__device__ __forceinline__ uint32_t slot_row(const SlotTask &T, uint32_t i0, uint32_t lane) { return T.live ? T.lrow : i0 + lane; }
 
 // search_plan (distance_search.rs:217-269).  Task index == position in the reference's plan
 // enumeration (x outer, z inner, 14 masks; for two-grid searches each entry is two tasks:
@@ -727,12 +740,12 @@ __device__ __forceinline__ float aabb_d2(float ax, float ay, float az, float lx,
 // the 13 neighbour entries go away.  Row-outer loop (one LDS broadcast per row), a scalar test per chunk,
 // VALU-only counting as in run_fast.
 template <int KIND, int NCH, bool TRI>
-__device__ __forceinline__ uint32_t run_count_sorted(const SearchParams &P, const Task &T, uint32_t i0, float4 *la,
+__device__ __forceinline__ uint32_t run_count_sorted(const SearchParams &P, const SlotTask &T, uint32_t i0, float4 *la,
                                                      uint32_t lane) {
     const float cutoff2 = P.cutoff2;
     const uint32_t rows = __builtin_amdgcn_readfirstlane(T.n1 - i0 < T.rps ? T.n1 - i0 : T.rps);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < rows) a = gload4(P.sa, T.a0 + i0 + lane);
+    if (lane < rows) a = gload4(P.sa, T.a0 + slot_row(T, i0, lane));
     la[lane] = a;
     float bx[NCH], by[NCH], bz[NCH];
     uint32_t bpos[NCH];          // position of the atom in the reference's cell order (same-cell entries: j > i)
@@ -825,7 +838,7 @@ __device__ __forceinline__ bool mfma_bound_usable(float R, float E, float c) {
 }
 
 template <int KIND, bool TRI>
-__device__ __forceinline__ uint32_t run_count_mfma(const SearchParams &P, const Task &T, uint32_t i0, float4 *la, uint4 *lh,
+__device__ __forceinline__ uint32_t run_count_mfma(const SearchParams &P, const SlotTask &T, uint32_t i0, float4 *la, uint4 *lh,
                                                    uint32_t lane, bool &done) {
     typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) u4_t lds_u4;
@@ -839,7 +852,7 @@ __device__ __forceinline__ uint32_t run_count_mfma(const SearchParams &P, const 
     // records: a slot is a chain of memory latencies, not of arithmetic (one block column prefetched: 0.50 ms for the
     // count kernel, exactly what 8 waves x (2 + 9 exposed latencies) per slot predict).
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < rows) a = gload4(P.sa, T.a0 + i0 + lane);
+    if (lane < rows) a = gload4(P.sa, T.a0 + slot_row(T, i0, lane));
     const float4 org = gload4(P.cell_org_b, T.cb);
     // Rows that cannot have a hit (run_fast's exact pruning against the second cell's bounding box: the same f32
     // expression on the point-to-box distances bounds every d2 of the row from below) are left out, and the rows that
@@ -848,7 +861,7 @@ __device__ __forceinline__ uint32_t run_count_mfma(const SearchParams &P, const 
     // rows pruned) and a third of the edge entries'.  Same-cell entries keep their rows in place (the j > i mask below
     // argues with positions, and a row inside its own cell's box is never pruned).
     bool need = lane < rows;
-    if (!TRI) {
+    if (!TRI && !T.live) {           // (a live-ranked slot holds live rows only)
         const float4 blo = gload4(P.aabb_b, 2 * T.cb), bhi = gload4(P.aabb_b, 2 * T.cb + 1);
         need = need && !(aabb_d2(a.x, a.y, a.z, blo.x, blo.y, blo.z, bhi.x, bhi.y, bhi.z) > cutoff2);
     }
@@ -995,7 +1008,7 @@ __device__ __forceinline__ uint32_t run_count_mfma(const SearchParams &P, const 
 //    nibble interleave put them into row order.
 // Returns false (nothing written) when the slot has to take the vector path: bound too wide, not finite.
 template <int KIND>
-__device__ __forceinline__ bool run_count_mfma_wrapped(const SearchParams &P, const Task &T, uint32_t i0, float4 *la, uint4 *lh,
+__device__ __forceinline__ bool run_count_mfma_wrapped(const SearchParams &P, const SlotTask &T, uint32_t i0, float4 *la, uint4 *lh,
                                                        uint32_t lane, uint32_t *mwords, uint32_t &count_out) {
     typedef uint32_t u4_t __attribute__((ext_vector_type(4)));
     typedef __attribute__((address_space(3))) u4_t lds_u4;
@@ -1014,11 +1027,14 @@ __device__ __forceinline__ bool run_count_mfma_wrapped(const SearchParams &P, co
         Sz += sgn * P.box.m[3 * d + 2];
     }
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (lane < rows) a = gload4(P.sa, T.a0 + i0 + lane);
+    if (lane < rows) a = gload4(P.sa, T.a0 + slot_row(T, i0, lane));
     const float4 org = gload4(P.cell_org_b, T.cb);
-    const float4 blo = gload4(P.aabb_b, 2 * T.cb), bhi = gload4(P.aabb_b, 2 * T.cb + 1);
-    // the live rows, exactly as run_fast finds them in both passes
-    const bool need = lane < rows && !(aabb_d2(a.x - Sx, a.y - Sy, a.z - Sz, blo.x, blo.y, blo.z, bhi.x, bhi.y, bhi.z) > P.prune_limit2);
+    // the live rows, exactly as run_fast finds them in both passes (a live-ranked slot holds live rows only)
+    bool need = lane < rows;
+    if (!T.live) {
+        const float4 blo = gload4(P.aabb_b, 2 * T.cb), bhi = gload4(P.aabb_b, 2 * T.cb + 1);
+        need = need && !(aabb_d2(a.x - Sx, a.y - Sy, a.z - Sz, blo.x, blo.y, blo.z, bhi.x, bhi.y, bhi.z) > P.prune_limit2);
+    }
     const unsigned long long live = __builtin_amdgcn_ballot_w64(need);
     const uint32_t nlive = (uint32_t)__popcll(live);
     if (nlive == 0u) {
@@ -1162,7 +1178,7 @@ __device__ __forceinline__ bool run_count_mfma_wrapped(const SearchParams &P, co
 }
 
 template <int KIND, bool FILL, bool WRAPPED, int NCH, bool TRI, bool MASKED>
-__device__ __forceinline__ uint32_t run_fast(const SearchParams &P, const Task &T, uint32_t i0, Fifo &F, float4 *la,
+__device__ __forceinline__ uint32_t run_fast(const SearchParams &P, const SlotTask &T, uint32_t i0, Fifo &F, float4 *la,
                                              uint32_t lane, uint32_t *mwords) {
     static_assert(!(WRAPPED && TRI), "a triangular (same-cell) entry never wraps on the fast path");
     if constexpr (!FILL && !WRAPPED && MASKED_COUNT_SORTED) return run_count_sorted<KIND, NCH, TRI>(P, T, i0, la, lane);
@@ -1200,12 +1216,17 @@ __device__ __forceinline__ uint32_t run_fast(const SearchParams &P, const Task &
     unsigned long long live;   // rows of this slot that can have a hit at all (same value in both passes)
     {
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lane < rows) a = gload4(P.sa, T.a0 + i0 + lane);
+        if (lane < rows) a = gload4(P.sa, T.a0 + slot_row(T, i0, lane));
         la[lane] = a;
-        const float4 lo = gload4(P.aabb_b, 2 * T.cb), hi = gload4(P.aabb_b, 2 * T.cb + 1);
+        float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+        if (!T.live) {
+            lo = gload4(P.aabb_b, 2 * T.cb);
+            hi = gload4(P.aabb_b, 2 * T.cb + 1);
+        }
         bool need = true;
-        if (TRI) {
+        if (TRI || T.live) {
             // same cell (i < j triangle, :439-451): the atom lies inside its own cell's box, nothing to prune
+            // (live-ranked slot: its rows are the ones this test leaves, live_rows_kernel)
         } else if (!WRAPPED) {
             // Exact row pruning.  Every B position lies inside the cell's bounding box [lo,hi], and each
             // f32 operation of d2 = ((dx*dx)+(dy*dy))+(dz*dz) is monotone in |dx|,|dy|,|dz|, so the same
@@ -1441,7 +1462,7 @@ __device__ __forceinline__ uint32_t run_fast(const SearchParams &P, const Task &
 constexpr int KMAX_WIDE = 16;
 constexpr int KMAX_HUGE = 32;      // ... of the instances with 3 (or 2) waves per SIMD: 168 (256) registers per lane
 template <int KIND, bool FILL, int WK, bool MASKED, int KMAX = KREG>
-__device__ __forceinline__ uint32_t run_task_nch(const SearchParams &P, const Task &T, uint32_t i0, Fifo &F, float4 *la,
+__device__ __forceinline__ uint32_t run_task_nch(const SearchParams &P, const SlotTask &T, uint32_t i0, Fifo &F, float4 *la,
                                                  uint32_t lane, uint32_t *mwords) {
     const uint32_t nchunks = (T.n2 + 63u) >> 6;
     if constexpr (KMAX > KMAX_WIDE) {
@@ -1640,7 +1661,7 @@ __device__ __forceinline__ bool hist_lean_slot(const SearchParams &P, uint32_t f
 // average (launch_pair_wide, pair_k5.hip): with 128 registers per lane a slot keeps up to 16 chunks (1024 atoms) of the second
 // cell resident (run_task_nch, KMAX) - the regular instances stream cells above 512 atoms from memory for every row (1M atoms
 // in the sheared box at rc 1.6 nm, 636 atoms per cell: 65 M pairs per ms against 220-240 up to 1.4 nm).  0: the usual budget.
-template <int KIND, int MODE, int WPE = 0>
+template <int KIND, int MODE, int WPE = 0, bool LIVE = false>
 __global__ void __launch_bounds__(64 * waves_per_block(MODE))
 __attribute__((amdgpu_waves_per_eu(WPE ? WPE : (MODE == MODE_HIST ? 4 : (MODE == MODE_COUNT ? MH_COUNT_WPE : MH_FILL_WPE))))) pair_kernel(const SearchParams *__restrict__ Pp,
                                                      const SlotDesc *__restrict__ slot_desc,
@@ -1658,6 +1679,13 @@ __attribute__((amdgpu_waves_per_eu(WPE ? WPE : (MODE == MODE_HIST ? 4 : (MODE ==
     __shared__ float4 lds_a[WAVES_PER_BLOCK][64];
     __shared__ uint4 lds_h[MODE == MODE_COUNT ? WAVES_PER_BLOCK : 1][MODE == MODE_COUNT ? 128 : 1];       // matrix-core row records of the count pass
     constexpr bool FILL = MODE != MODE_COUNT;
+    // Live-ranked slots (SLOT_LIVE) are walked by instances of their own, pair_kernel<KIND, COUNT | FILL, 0, LIVE = true> of the
+    // fixed-cutoff kinds (pair_k10 / pair_k11.hip), which launch_pairs takes for plans cut from live rows (search_shape.hpp,
+    // live_row_slots) and for nothing else: every other instance is compiled without the path, and a search whose plan has
+    // consecutive slots throughout runs the kernels it ran before the path existed.
+    static_assert(!LIVE || (WPE == 0 && MODE != MODE_HIST && (KIND == MOLAR_HIP_SEARCH_SINGLE || KIND == MOLAR_HIP_SEARCH_DOUBLE)),
+                  "live-ranked slots: regular count / fill instances of the fixed-cutoff kinds");
+    constexpr bool LIVE_SLOTS = LIVE;
     extern __shared__ uint32_t lds_hist[];     // histogram mode only (hist_nbins counters)
     // The parameter block lives in device memory: a by-value struct this large, indexed dynamically
     // (box.shifts[k]), gets copied to scratch by the compiler and drags every field into VGPRs.
@@ -1699,7 +1727,7 @@ __attribute__((amdgpu_waves_per_eu(WPE ? WPE : (MODE == MODE_HIST ? 4 : (MODE ==
             if (w < full) wr = ((q / XCD_RUN) * 8u + x) * XCD_RUN + (q % XCD_RUN);
         }
         const uint32_t slot = nslots - 1u - wr;
-        Task T;   // record prepared by slotmap_kernel: one dependent load between the kernel arguments and the atoms
+        SlotTask T;   // record prepared by slotmap_kernel: one dependent load between the kernel arguments and the atoms
         uint32_t i0;
         unsigned long long moff;
         uint32_t frame = 0u;
@@ -1722,6 +1750,41 @@ __attribute__((amdgpu_waves_per_eu(WPE ? WPE : (MODE == MODE_HIST ? 4 : (MODE ==
             T.valid = true;
             T.wrap_b = (fl >> 12) & 7u;
             T.rps = fl >> 16;
+            if constexpr (LIVE_SLOTS) {
+                if (fl & SLOT_LIVE) {
+                    // Live-ranked slot: rows [i0, i0 + 64) of the entry's live rows.  The entry's mask words (one per 64 rows, bit =
+                    // the row can have a hit) turn "rank" into "row": per word the ranks of its set bits are its prefix count plus
+                    // mbcnt, and the rows whose rank falls into the slot drop their number into LDS at rank - i0.
+                    typedef __attribute__((address_space(1))) unsigned long long glb_u64;
+                    const uint2 mp = reinterpret_cast<const uint2 *>(slot_desc + slot)[5];
+                    // (the builtin returns int: without the casts the low half would be sign-extended over the high one)
+                    const glb_u64 *mk = (const glb_u64 *)(((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(mp.y) << 32) |
+                                                          (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane(mp.x));
+                    unsigned long long mw = 0ull;
+                    if (lane < (uint32_t)LIVE_GROUPS) mw = mk[lane];
+                    uint32_t *scr = lds[wave][0];           // (the output queue is not in use yet)
+                    uint32_t before = 0u;
+#pragma unroll
+                    for (int g = 0; g < LIVE_GROUPS; ++g) {
+                        const uint32_t wlo = __builtin_amdgcn_readlane((uint32_t)mw, g), whi = __builtin_amdgcn_readlane((uint32_t)(mw >> 32), g);
+                        const uint32_t n = (uint32_t)__popc(wlo) + (uint32_t)__popc(whi);
+                        if (n != 0u && before + n > i0 && before < i0 + 64u) {
+                            const uint32_t rank = before + __builtin_amdgcn_mbcnt_hi(whi, __builtin_amdgcn_mbcnt_lo(wlo, 0u)) - i0;
+                            const bool bit = (((lane < 32u ? wlo : whi) >> (lane & 31u)) & 1u) != 0u;
+                            if (bit && rank < 64u) scr[rank] = 64u * (uint32_t)g + lane;
+                        }
+                        before += n;
+                    }
+                    __builtin_amdgcn_wave_barrier();
+                    T.lrow = scr[lane];
+                    __builtin_amdgcn_wave_barrier();
+                    T.live = true;
+                    // From here on n1 is the number of the entry's LIVE rows, not the first cell's population (the record keeps
+                    // that): `rows = min(n1 - i0, rps)` in run_fast and the three count routines then cuts the slot from the live
+                    // rows, and nothing else on a live-ranked slot's path reads n1.
+                    T.n1 = before;
+                }
+            }
         }
         const SearchParams &P = MODE == MODE_HIST ? Pp[frame] : P0;
         Fifo F;
@@ -1822,7 +1885,7 @@ inline dim3 pair_grid(unsigned nblocks) {
 }
 
 // one launch of the pair kernel for a search kind / mode
-template <int KIND, int MODE, int WPE = 0>
+template <int KIND, int MODE, int WPE = 0, bool LIVE = false>
 inline void launch_pair_kernel(unsigned nblocks, size_t dyn_lds, hipStream_t stream, const SearchParams *dP,
                                const SlotDesc *slot_desc, uint32_t nslots, uint32_t *slot_cnt,
                                const unsigned long long *slot_base, uint2 *pairs, float *dist, uint32_t *ids) {
@@ -1831,7 +1894,7 @@ inline void launch_pair_kernel(unsigned nblocks, size_t dyn_lds, hipStream_t str
 #ifdef MH_SLOT_LOOP
     if (MODE != MODE_HIST) nblocks = (nblocks + (unsigned)MH_SLOT_LOOP - 1u) / (unsigned)MH_SLOT_LOOP;
 #endif
-    hipLaunchKernelGGL((pair_kernel<KIND, MODE, WPE>), pair_grid(nblocks), dim3(64 * waves_per_block(MODE)), dyn_lds, stream, dP, slot_desc, nslots,
+    hipLaunchKernelGGL((pair_kernel<KIND, MODE, WPE, LIVE>), pair_grid(nblocks), dim3(64 * waves_per_block(MODE)), dyn_lds, stream, dP, slot_desc, nslots,
                        slot_cnt, slot_base, pairs, dist, ids);
 }
 
@@ -1867,6 +1930,13 @@ void launch_pair_single(int mode, unsigned nblocks, size_t dyn_lds, hipStream_t 
 void launch_pair_double(int mode, unsigned nblocks, size_t dyn_lds, hipStream_t stream, const pairk::SearchParams *dP,
                         const pairk::SlotDesc *slot_desc, uint32_t nslots, uint32_t *slot_cnt,
                         const unsigned long long *slot_base, uint2 *pairs, float *dist, uint32_t *ids);
+// (pair_k10.hip, pair_k11.hip) count / fill of the fixed-cutoff kinds over plans with live-ranked slots (pair_kernel<.., LIVE = true>)
+void launch_pair_single_live(int mode, unsigned nblocks, hipStream_t stream, const pairk::SearchParams *dP,
+                             const pairk::SlotDesc *slot_desc, uint32_t nslots, uint32_t *slot_cnt,
+                             const unsigned long long *slot_base, uint2 *pairs, float *dist);
+void launch_pair_double_live(int mode, unsigned nblocks, hipStream_t stream, const pairk::SearchParams *dP,
+                             const pairk::SlotDesc *slot_desc, uint32_t nslots, uint32_t *slot_cnt,
+                             const unsigned long long *slot_base, uint2 *pairs, float *dist);
 void launch_pair_within(int mode, unsigned nblocks, size_t dyn_lds, hipStream_t stream, const pairk::SearchParams *dP,
                         const pairk::SlotDesc *slot_desc, uint32_t nslots, uint32_t *slot_cnt,
                         const unsigned long long *slot_base, uint2 *pairs, float *dist, uint32_t *ids);

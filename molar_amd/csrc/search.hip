@@ -600,7 +600,7 @@ __global__ void __launch_bounds__(256) scan_tile_kernel(const TIn *in, TOut *out
 // Scans TWO arrays of the same length at once when in2 != nullptr (task slot counts and task hit-history units).
 // `state` holds 1 ticket word + 2 descriptors per tile and must be zero on entry.
 constexpr unsigned long long LB_MASK = (1ull << 62) - 1ull;
-constexpr uint64_t FPLAN_MAX_TASKS = 1ull << 22;                          // plan_tiles_kernel / plan_slots_kernel: plans up to this many entries (+ terminator)
+// (FPLAN_MAX_TASKS, search_shape.hpp: plan_tiles_kernel / plan_slots_kernel take plans up to that many entries + terminator)
 constexpr uint32_t PLAN_GROUP = 128;                                       // plans of more than 1024 tiles: tile totals are summed in groups of this many first (plan_groups_kernel)
 __device__ __forceinline__ unsigned long long lb_resolve(unsigned long long *desc, uint32_t tile, unsigned long long tot) {
     if (tile == 0) {
@@ -684,11 +684,67 @@ int scan_lookback(molar_hip_ctx *c, const TIn1 *in1, TOut1 *out1, const TIn2 *in
 // side stream starts at that very moment.)  plan_tiles_kernel also zeroes the slot counters and writes the parameter block, as
 // plan_kernel does; plan_slots_kernel also blanks the records between the real slot count and the host's bound (spread over all
 // workgroups: one workgroup alone took 45 us for 5e4 of them).
+// Live rows of the plan entries (searches of live_row_slots(), search_shape.hpp), once per frame behind the grid build.  Both pair
+// passes leave out the rows of a first cell that provably have no hit in the second one - the f32 lower bound of the row against the
+// second cell's bounding box (run_fast) - but they did so inside the slot: after it had been dispatched, had read its record and
+// loaded its rows and the whole second cell; two thirds of a corner entry's rows and 40 % of an edge entry's are such rows on
+// the 1M-atom frame.  Here the same predicate is evaluated per entry, one wave each: one 64-bit mask per 64 consecutive rows (LIVE_GROUPS
+// words per entry, indexed by the entry: no scan) and the entry's live count, from which the plan cuts slots of 64 LIVE rows.
+// Entries the passes do not prune (same cell, wrapped entries evaluated exactly, the triclinic corner entries, cells beyond the
+// masks' or the registers' reach) get LIVE_NONE: consecutive slots as before.
+constexpr uint32_t LIVE_NONE = 0xFFFFFFFFu;
+static_assert(LIVE_ROW_GROUPS == (uint32_t)LIVE_GROUPS, "the host sizes the masks the kernels index");
+template <int KIND>
+__global__ void __launch_bounds__(64) live_rows_kernel(SearchParams P, unsigned long long *__restrict__ masks, uint32_t *__restrict__ live_cnt) {
+    const uint64_t t = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
+    if (t >= P.ntasks) return;
+    const uint32_t lane = threadIdx.x;
+    const Task T = decode_task<KIND, true>(P, t);
+    const bool wrapped = P.use_box && T.wrap != 0u;
+    const bool approx = wrapped && P.approx_wrapped != 0u && !(P.box.nshift != 0 && T.wrap == MOLAR_HIP_PBC_FULL);      // as run_fast
+    if (!T.valid || T.tri || T.rps != 64u || T.n1 > 64u * (uint32_t)LIVE_GROUPS || T.n2 > 64u * (uint32_t)KREG || (wrapped && !approx)) {
+        if (lane == 0) live_cnt[t] = LIVE_NONE;
+        return;
+    }
+    float Sx = 0.f, Sy = 0.f, Sz = 0.f;      // b + S is the image of the second cell next to the first one (run_fast)
+    float limit2 = P.cutoff2;
+    if (approx) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            if (!((T.wrap >> d) & 1u)) continue;
+            const float sgn = ((T.wrap_b >> d) & 1u) ? 1.0f : -1.0f;
+            Sx += sgn * P.box.m[3 * d];
+            Sy += sgn * P.box.m[3 * d + 1];
+            Sz += sgn * P.box.m[3 * d + 2];
+        }
+        limit2 = P.prune_limit2;
+    }
+    const float4 lo = gload4(P.aabb_b, 2 * T.cb), hi = gload4(P.aabb_b, 2 * T.cb + 1);
+    unsigned long long mine = 0ull;
+    uint32_t nlive = 0u;
+#pragma unroll
+    for (int g = 0; g < LIVE_GROUPS; ++g) {
+        const uint32_t row = 64u * (uint32_t)g + lane;
+        if (64u * (uint32_t)g >= T.n1) break;
+        bool need = false;
+        if (row < T.n1) {
+            const float4 a = gload4(P.sa, T.a0 + row);
+            need = !(aabb_d2(a.x - Sx, a.y - Sy, a.z - Sz, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) > limit2);
+        }
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(need);
+        if (lane == (uint32_t)g) mine = m;
+        nlive += (uint32_t)__popcll(m);
+    }
+    if (lane < (uint32_t)LIVE_GROUPS) masks[t * (uint64_t)LIVE_GROUPS + lane] = mine;
+    if (lane == 0) live_cnt[t] = nlive;
+}
+
 template <int KIND>
 __global__ void __launch_bounds__(256) plan_tiles_kernel(SearchParams P, uint32_t *__restrict__ local_first, TaskDesc *__restrict__ task_desc,
                                                          unsigned long long *__restrict__ local_moff, uint32_t fast_kind,
                                                          uint32_t *__restrict__ slot_cnt, uint64_t nslot_cnt,
-                                                         unsigned long long *__restrict__ tile_tot, SearchParams *__restrict__ params_dst) {
+                                                         unsigned long long *__restrict__ tile_tot, SearchParams *__restrict__ params_dst,
+                                                         const uint32_t *__restrict__ live_cnt) {      // NULL: consecutive slots throughout
     const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     for (uint64_t w = t; w < nslot_cnt; w += (uint64_t)gridDim.x * 256u) slot_cnt[w] = 0u;   // the count kernel writes the slots that exist
     if (params_dst && blockIdx.x == 0) {
@@ -696,22 +752,26 @@ __global__ void __launch_bounds__(256) plan_tiles_kernel(SearchParams P, uint32_
         uint32_t *d = (uint32_t *)params_dst;
         for (uint32_t w = threadIdx.x; w < (uint32_t)(sizeof(SearchParams) / 4u); w += 256u) d[w] = src[w];
     }
-    uint32_t nb = 0;
+    uint32_t nb = 0, nb_rows = 0;                // slots of the entry; what consecutive rows would give
     unsigned long long mu = 0;
     if (t < P.ntasks) {
         const Task T = decode_task<KIND, false>(P, t);
-        nb = T.valid ? (T.n1 + T.rps - 1u) / T.rps : 0u;
+        nb = nb_rows = T.valid ? (T.n1 + T.rps - 1u) / T.rps : 0u;
+        // slots of 64 LIVE rows where live_rows_kernel counted them (rps is 64 there); an entry without a live row gets no slot
+        const uint32_t lc = (live_cnt && T.valid) ? live_cnt[t] : LIVE_NONE;
+        if (lc != LIVE_NONE) nb = (lc + 63u) >> 6;
         const uint32_t nch = (T.n2 + 63u) >> 6;
         mu = (fast_kind && P.use_box && T.wrap != 0u && nch <= (uint32_t)KREG) ? (unsigned long long)nb * 2u * nch : 0ull;   // as plan_kernel
         TaskDesc d;
         d.a0 = T.a0; d.n1 = T.n1; d.b0 = T.b0; d.n2 = T.n2; d.cb = T.cb;
-        d.flags = T.wrap | (T.tri ? 0x100u : 0u) | (T.valid ? 0x200u : 0u) | (T.wrap_b << 12) | (T.rps << 16);
+        d.flags = T.wrap | (T.tri ? 0x100u : 0u) | (T.valid ? 0x200u : 0u) | (lc != LIVE_NONE ? SLOT_LIVE : 0u) | (T.wrap_b << 12) | (T.rps << 16);
         d.pad0 = nb;                              // slots of the entry (plan_slots_kernel)
         d.pad1 = 0u;
         task_desc[t] = d;
     }
-    uint32_t tot_nb;
+    uint32_t tot_nb, tot_rows;
     const uint32_t first = block_exclusive_scan<uint32_t>(nb, &tot_nb);
+    (void)block_exclusive_scan<uint32_t>(nb_rows, &tot_rows);
     unsigned long long tot_mu = 0ull, m0 = 0ull;
     if (fast_kind) m0 = block_exclusive_scan<unsigned long long>(mu, &tot_mu);
     if (t <= P.ntasks) {                         // offsets inside the tile (t == ntasks: the terminator)
@@ -719,7 +779,9 @@ __global__ void __launch_bounds__(256) plan_tiles_kernel(SearchParams P, uint32_
         if (fast_kind) local_moff[t] = m0;
     }
     if (threadIdx.x == 0) {
-        tile_tot[2 * blockIdx.x] = tot_nb;
+        // (slots in the low half, the slots consecutive rows would have given in the high half: both stay below 2^32 summed over
+        // the plan - prepare_search checks the bound - so the sums plan_slots_kernel forms carry both)
+        tile_tot[2 * blockIdx.x] = (unsigned long long)tot_nb | ((unsigned long long)tot_rows << 32);
         tile_tot[2 * blockIdx.x + 1] = tot_mu;
     }
 }
@@ -750,7 +812,9 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
                                                                 const unsigned long long *__restrict__ tile_tot,
                                                                 SlotDesc *__restrict__ slot_desc, uint64_t nslots_bound,
                                                                 unsigned long long *__restrict__ sizes_host,    // pinned, or NULL
-                                                                const unsigned long long *__restrict__ group_tot) {  // NULL: at most 1024 tiles
+                                                                const unsigned long long *__restrict__ group_tot,    // NULL: at most 1024 tiles
+                                                                const unsigned long long *__restrict__ live_masks,   // mask words of the SLOT_LIVE entries
+                                                                unsigned long long *__restrict__ slot_stat) {  // [2]: slots, slots of consecutive rows
     __shared__ unsigned long long part[3][4];
     const uint32_t tile = blockIdx.x / (256u / PLAN_SUB), sub = blockIdx.x % (256u / PLAN_SUB);
     unsigned long long pn = 0, pm = 0, all_n = 0;           // slots / hit-history units in front of this tile, slots of the whole plan
@@ -787,7 +851,8 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
     __syncthreads();
     const uint32_t base_n = (uint32_t)((part[0][0] + part[0][1]) + (part[0][2] + part[0][3]));
     const unsigned long long base_m = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
-    const unsigned long long total = (part[2][0] + part[2][1]) + (part[2][2] + part[2][3]);
+    const unsigned long long total2 = (part[2][0] + part[2][1]) + (part[2][2] + part[2][3]);      // (low half: slots, see plan_tiles_kernel)
+    const unsigned long long total = total2 & 0xFFFFFFFFull;
     // this workgroup's entries in LDS: offsets inside the tile, descriptors, first hit-history unit
     __shared__ uint32_t lfirst[PLAN_SUB + 1];
     __shared__ TaskDesc ldesc[PLAN_SUB];
@@ -823,6 +888,10 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
                 sizes_host[1] = task_moff ? lm0[threadIdx.x] : 0ull;      // hit-history units of this search
                 sizes_host[2] = base_n + lfirst[threadIdx.x];             // its slots
             }
+            if (t == ntasks && slot_stat) {
+                slot_stat[0] = total;
+                slot_stat[1] = total2 >> 32;
+            }
         }
     }
     // One record per slot (as slotmap_kernel), written as the workgroup's contiguous run of 16-byte words: word i belongs to
@@ -841,10 +910,12 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
         const uint32_t q = sl - lfirst[lo], rps = d.flags >> 16, nch = (d.n2 + 63u) >> 6;
         uint4 w;
         if (part3 == 0u) w = make_uint4(d.a0, d.n1, d.b0, d.n2);
-        else if (part3 == 1u) w = make_uint4(d.cb, d.flags, q * rps, 0u);
+        else if (part3 == 1u) w = make_uint4(d.cb, d.flags, q * rps, 0u);          // (SLOT_LIVE: q * 64 is the rank of the slot's first live row)
         else {
             const unsigned long long mo = task_moff ? lm0[lo] + (unsigned long long)q * 2u * nch : lm0[lo];
-            w = make_uint4((uint32_t)mo, (uint32_t)(mo >> 32), 0u, 0u);
+            // SLOT_LIVE: where the entry's mask words are
+            const unsigned long long mp = (d.flags & SLOT_LIVE) ? (unsigned long long)(live_masks + (((uint64_t)tile * 256u + sub * PLAN_SUB + lo) * (uint64_t)LIVE_GROUPS)) : 0ull;
+            w = make_uint4((uint32_t)mo, (uint32_t)(mo >> 32), (uint32_t)mp, (uint32_t)(mp >> 32));
         }
         out[i] = w;
     }
@@ -1188,6 +1259,8 @@ struct SearchCall {
     unsigned long long *sizes_dev = nullptr;   // resident searches: device-side address of the pinned sizes the kernels write
     bool drop_nonfinite = false;   // the grid leaves atoms with a non-finite coordinate out (stages.hpp, search_resident_enqueue)
     uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
+    bool live_rows = true;         // the slots go to the count / fill passes, which walk live-ranked slots where live_row_slots() says so
+                                   // (false: another kernel reads the records - the contact kernels - and wants consecutive rows)
 };
 
 // launches go to the side stream while one of these lives (c->stream and c->on_side move together)
@@ -1498,6 +1571,13 @@ int launch_pairs(molar_hip_ctx *c, const SearchCall &call, const PairOut &out, c
         MH_HIP(hipGetLastError());
         return 0;
     }
+    // a plan cut from live rows (enqueue_plan): the instances that walk live-ranked slots
+    if (c->plan_live && mode != MODE_HIST && !out.ids && fixed_cutoff_kind(cur.kind)) {
+        if (cur.kind == MOLAR_HIP_SEARCH_SINGLE) launch_pair_single_live(mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
+        else launch_pair_double_live(mode, P.nblocks, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist);
+        MH_HIP(hipGetLastError());
+        return 0;
+    }
     switch (cur.kind) {
         case MOLAR_HIP_SEARCH_SINGLE: launch_pair_single(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
         case MOLAR_HIP_SEARCH_DOUBLE: launch_pair_double(mode, P.nblocks, dyn_lds, c->stream, dP, tf, st, sc, sb, out.pairs, out.dist, out.ids); break;
@@ -1660,6 +1740,8 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
     MH_HIP(hipSetDevice(c->device));
     c->have_search = false;
+    c->slot_stat_valid = false;        // until a plan of this search leaves its slot counts (enqueue_plan)
+    c->plan_live = false;
     SearchShape &cur = c->cur;
     cur.kind = q->kind;
     const bool two = q->kind != MOLAR_HIP_SEARCH_SINGLE;
@@ -1770,6 +1852,22 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     MH_TRY(c->task_mu.reserve((cur.ntasks + 1) * 4));
     MH_TRY(c->task_moff.reserve((cur.ntasks + 1) * 8));
     const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
+    MH_TRY(c->slot_stat.reserve(16));
+    // Live rows of the plan entries (live_rows_kernel): for the searches of live_row_slots() whose slot records go to the count / fill
+    // passes.  The masks belong to the grid generation and are computed at the end of its grid chain, on whichever stream that runs.
+    const bool use_live = call.plan && call.live_rows && !call.hist_plan && live_row_slots(cur);
+    auto enqueue_live_rows = [&]() -> int {
+        if (!use_live) return 0;
+        MH_TRY(cur.set[0].live.reserve(live_rows_bytes(cur)));
+        unsigned long long *masks = cur.set[0].live.as<unsigned long long>();
+        uint32_t *cnt = reinterpret_cast<uint32_t *>(masks + live_rows_mask_words(cur));
+        const SearchParams P = make_params(c, cur);          // the values plan_tiles_kernel sees (geometry, grids, wrap policy)
+        const dim3 grid = pair_grid((unsigned)cur.ntasks);
+        if (cur.kind == MOLAR_HIP_SEARCH_SINGLE) hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_SINGLE>), grid, dim3(64), 0, c->stream, P, masks, cnt);
+        else hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_DOUBLE>), grid, dim3(64), 0, c->stream, P, masks, cnt);
+        MH_HIP(hipGetLastError());
+        return 0;
+    };
     auto enqueue_plan = [&]() -> int {
         Prof prof(c, 0);
         SearchParams P = make_params(c, cur);
@@ -1793,17 +1891,23 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
             unsigned long long *tt = c->fplan_tiles.as<unsigned long long>();
             unsigned long long *lmoff = tt + 2 * (size_t)ntiles;           // offsets inside the tiles: hit-history units ...
             uint32_t *lfirst = c->task_mu.as<uint32_t>();                  // ... and slots
+            // live-row slots: the masks and counts live_rows_kernel left in this grid generation (behind the grid build, below)
+            const unsigned long long *live_masks = use_live ? cur.set[0].live.as<unsigned long long>() : nullptr;
+            const uint32_t *live_cnt = use_live ? reinterpret_cast<const uint32_t *>(live_masks + live_rows_mask_words(cur)) : nullptr;
             if (cur.kind == MOLAR_HIP_SEARCH_SINGLE)
                 hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst);
+                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
             else          // the three two-grid kinds decode tasks identically
                 hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst);
+                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
             unsigned long long *gt = ngroups ? lmoff + (cur.ntasks + 1) : nullptr;
             if (ngroups) hipLaunchKernelGGL(plan_groups_kernel, dim3(ngroups), dim3(64), 0, c->stream, ntiles, tt, gt);
             hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, cur.ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
-                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), cur.nslots_bound, call.sizes_dev, gt);
+                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), cur.nslots_bound, call.sizes_dev, gt,
+                               live_masks, c->slot_stat.as<unsigned long long>());
             MH_HIP(hipGetLastError());
+            c->slot_stat_valid = true;
+            c->plan_live = use_live;           // which instances of the pair kernels walk these records (launch_pairs)
             return 0;
         }
         // ntasks + 1 threads (the last one writes the scan terminators); the same grid zeroes the slot counters and the
@@ -1839,6 +1943,7 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
             OnSideStream on_side(c);
             if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
             if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
+            MH_TRY(enqueue_live_rows());
             MH_HIP(hipEventRecord(c->grid_done, c->side_stream));
         }
         // The plan and the pair kernels of this search need the grid.  A wait command on the main stream costs that stream
@@ -1850,6 +1955,7 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     } else {
         if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
         if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
+        MH_TRY(enqueue_live_rows());
     }
     if (may_hold && !reuse0) {        // this grid of set 0 is the one later `within` requests may reuse
         c->hold_valid = true;
@@ -2139,6 +2245,17 @@ int molar_hip_search_cell_kernels(molar_hip_ctx *c, int32_t *lanes, uint64_t occ
         occupied_cells[0] = c->cur.occ_use[0];
         occupied_cells[1] = c->cur.occ_use[1];
     }
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_search_slot_counts(molar_hip_ctx *c, uint64_t *slots, uint64_t *consecutive_slots) {
+    if (!c || !slots || !consecutive_slots) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_slot_counts: null argument");
+    if (!c->slot_stat_valid) return fail(MOLAR_HIP_ERR_NO_SEARCH, "search_slot_counts: the context's last search was not planned by plan_slots_kernel");
+    MH_HIP(hipSetDevice(c->device));
+    unsigned long long st[2] = {0ull, 0ull};
+    MH_TRY(read_back(c, st, c->slot_stat.p, sizeof st));
+    *slots = st[0];
+    *consecutive_slots = st[1];
     return MOLAR_HIP_OK;
 }
 
@@ -3036,6 +3153,7 @@ int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
     qq.ids_local = 1;                       // ids are positions in the selection, whatever the caller's list would carry
     SearchCall call;
     call.size_masks = false;
+    call.live_rows = false;                 // contact_kernel walks consecutive rows
     MH_TRY(prepare_search(s, &qq, call));      // (the plan kernel leaves the parameter block in s->params)
     s->params_fresh = false;
     const SearchShape &cur = s->cur;

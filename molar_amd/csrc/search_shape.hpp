@@ -102,6 +102,29 @@ inline uint64_t slots_bound(const SearchShape &s, bool hist_plan) {
     return bound;
 }
 
+// Plans of at most this many entries (+ terminator) go through plan_tiles_kernel / plan_slots_kernel on the main stream
+constexpr uint64_t FPLAN_MAX_TASKS = 1ull << 22;
+
+// Are the slots of this search cut from the LIVE rows of its plan entries (live_rows_kernel, search.hip)?  The regular family of
+// the fixed-cutoff kinds only - the instances of pair_kernel compiled with the gather - and plans that take plan_tiles_kernel /
+// plan_slots_kernel; everything else (small-, wide- and huge-cell families, vdW and `within`, the fused histogram's own plans, the
+// contact kernels, the f64 search) walks consecutive slots.  And frames whose first cells hold 96 atoms on average over ALL cells
+// of the grid: the liveness kernel costs one wave per plan entry, empty entries included, while slots are only saved where an
+// entry has more than one (measured, profiles/live_rows_ab.txt sections 1, 4 and 7: 1M atoms at 1.2 / 1.0 nm - 261 / 108 atoms per cell - gain 4-6 %
+// / hold; at 0.8 / 0.6 nm - 57 / 32 per cell, one slot per entry as a rule - the kernel's 1.9e5 / 4.4e5 waves beside the count
+// pass cost 1.4 / 30 %, and a slab in a mostly empty box up to 2x).  Plans of at most 8192 entries - the liveness kernel is then
+// at most one resident round of one-wave workgroups (256 CUs x 32 waves) - qualify whatever their density: frames without a box,
+// whose grid is padded by a shell of empty cells, are such.  The masks (68 bytes per entry, at most 28 entries per cell) thus stay below
+// 20 bytes per atom.
+constexpr uint32_t LIVE_ROW_GROUPS = 8;        // 64-row groups per entry: first cells of up to 512 atoms (KREG chunks)
+inline bool live_row_slots(const SearchShape &s) {
+    return fixed_cutoff_kind(s.kind) && pair_family(s) == 0 && plan_entries(s) + 1 <= FPLAN_MAX_TASKS &&
+           (plan_entries(s) <= 8192ull || (uint64_t)s.set[0].n >= 96ull * grid_cells(s));
+}
+// bytes of a generation's live-row buffer: the mask words of every entry, then the entries' live counts
+inline size_t live_rows_mask_words(const SearchShape &s) { return (size_t)plan_entries(s) * LIVE_ROW_GROUPS; }
+inline size_t live_rows_bytes(const SearchShape &s) { return live_rows_mask_words(s) * 8u + (size_t)plan_entries(s) * 4u; }
+
 // How the pair kernels treat entries that wrap around the box (SearchParams carries these six under the same names).
 struct WrapPolicy {
     uint32_t wrap_kind;        // 1 diagonal, 2 upper triangular (GROMACS-style boxes), 3 general: which products a wrapped pair may skip
