@@ -170,7 +170,8 @@ molar_hip_ctx *molar_hip_create(int device) {
     if (const char *dbg = std::getenv("MOLAR_HIP_DEBUG_SKIP")) c->env_debug_skip = (uint32_t)std::atoi(dbg);
     if (const char *dbg = std::getenv("MOLAR_HIP_DEBUG_LAUNCH")) c->env_debug_launch = (uint32_t)std::atoi(dbg);
 #endif
-    if (ensure_pinned(c, 1 << 16)) {
+    if (ensure_pinned(c, 1 << 16) || alloc_search_sizes(c)) {
+        if (c->h_pinned) (void)hipHostFree(c->h_pinned);
         (void)hipStreamDestroy(c->stream);
         delete c;
         return nullptr;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -139,6 +140,18 @@ struct SearchShape {
                                     // (0: not known for this search, the grid's cell count stands in)
 };
 
+// ---------------------------------------------------------------- the sizes of one search
+struct SearchSizes {            // written by the plan and offsets kernels into pinned host memory, read by the host after the stream
+    unsigned long long total;       // results of the search                   (slot_offsets_kernel / scan_slot_counts)
+    unsigned long long mask_units;  // hit-history units, 0 for kinds without  (slotmap_kernel / plan_slots_kernel)
+    unsigned long long slots;       // slots the plan came to                  (the same two)
+    unsigned long long occupied;    // occupied cells, set 1 << 32 | set 0; 0 = not reported
+};
+// the kernels' stores and the copy fallback of resident_enqueue (search.hip) address the fields at these offsets
+static_assert(sizeof(SearchSizes) == 32 && offsetof(SearchSizes, total) == 0 && offsetof(SearchSizes, mask_units) == 8 &&
+                  offsetof(SearchSizes, slots) == 16 && offsetof(SearchSizes, occupied) == 24,
+              "SearchSizes: total, mask_units, slots, occupied, 64 bits each, in this order");
+
 }  // namespace mh
 
 struct molar_hip_search64_state;        // the cached f64 search (search_f64.hip)
@@ -158,7 +171,9 @@ struct molar_hip_ctx {
     bool own_stream = false;
     int num_cus = 256;
 
-    // pinned host scratch for small read-backs
+    // Pinned bounce buffer: read-backs (read_back below), staging of small tables, results a kernel or a bulk copy leaves for the
+    // host to read after the stream.  Its contents mean nothing across any call that may use it, ensure_pinned may move it, nothing
+    // may hold its address across a call - and no kernel of the search stores here: its sizes have their own home (h_sizes).
     void *h_pinned = nullptr;
     size_t h_pinned_cap = 0;
     molar_hip_search64_state *s64 = nullptr;      // created by the first molar_hip_search_count_f64
@@ -243,7 +258,11 @@ struct molar_hip_ctx {
     // search that needed more slots than were launched is repeated with the bound where its sizes are read.
     unsigned long long trim_real = 0, trim_ntasks = 0;   // slots of the last resident search whose sizes were read, and its plan
     int trim_kind = -1;
-    void *h_sizes = nullptr;                // pinned: 32 bytes of result sizes per ticket (total, history units, slots, occupied cells)
+    // The one home of the searches' SearchSizes records: a pinned array allocated with the context, one entry per ticket and one
+    // for the calls that wait for their search themselves.  d_sizes is the array's device-side address, resolved once (null: the
+    // device cannot store there and the sizes are copied behind the passes, resident_enqueue).
+    static constexpr int SIZES_SYNC = 2, SIZES_ENTRIES = 3;
+    mh::SearchSizes *h_sizes = nullptr, *d_sizes = nullptr;
     // Occupied cells of the two sets' grids as the last finished search of this shape found them (the grid build counts them, the
     // offsets kernel hands them to the host with the sizes): small_cell_lanes() judges a frame by its atoms per OCCUPIED cell when it
     // knows - a slab or a solute in a mostly empty periodic box has a small mean and crowded cells.  Latched per search into cur.occ_use.
@@ -361,6 +380,45 @@ inline int ensure_pinned(molar_hip_ctx *c, size_t bytes) {
     c->h_pinned_cap = 0;
     MH_HIP(hipHostMalloc(&c->h_pinned, bytes + 4096, hipHostMallocDefault));
     c->h_pinned_cap = bytes + 4096;
+    return 0;
+}
+
+// The one read-back: `bytes` of device memory into `dst_host` through the bounce buffer, complete when the call returns.
+inline int read_back(molar_hip_ctx *c, void *dst_host, const void *src_dev, size_t bytes) {
+    MH_TRY(ensure_pinned(c, bytes));
+    MH_HIP(hipMemcpyAsync(c->h_pinned, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    std::memcpy(dst_host, c->h_pinned, bytes);
+    return 0;
+}
+
+// The status check of the fitted trajectory analyses (rmsd_matrix.hip, fluct.hip): the index flag their centring kernel raised and
+// the sum of the selected weights, from two device buffers under one wait.
+inline int check_selection(molar_hip_ctx *c, const uint32_t *index_flag_dev, const double *weight_sum_dev, const char *who, size_t natoms) {
+    MH_TRY(ensure_pinned(c, 16));
+    double *sum = static_cast<double *>(c->h_pinned);
+    uint32_t *flag = reinterpret_cast<uint32_t *>(sum + 1);
+    MH_HIP(hipMemcpyAsync(sum, weight_sum_dev, 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(flag, index_flag_dev, 4, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipStreamSynchronize(c->stream));
+    if (*flag) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
+    if (*sum == 0.0) return fail(MOLAR_HIP_ERR_ZERO_MASS, "%s: the selected masses add up to zero", who);
+    return 0;
+}
+
+// device-side address of a pinned SearchSizes record or array (null: the device cannot store there)
+inline SearchSizes *sizes_device_address(SearchSizes *pinned) {
+    void *d = nullptr;
+    if (hipHostGetDevicePointer(&d, pinned, 0) == hipSuccess) return static_cast<SearchSizes *>(d);
+    (void)hipGetLastError();
+    return nullptr;
+}
+
+// the context's SearchSizes array (molar_hip_ctx::h_sizes), once per context
+inline int alloc_search_sizes(molar_hip_ctx *c) {
+    MH_HIP(hipHostMalloc(reinterpret_cast<void **>(&c->h_sizes), molar_hip_ctx::SIZES_ENTRIES * sizeof(SearchSizes), hipHostMallocDefault));
+    for (int i = 0; i < molar_hip_ctx::SIZES_ENTRIES; ++i) c->h_sizes[i] = SearchSizes{};
+    c->d_sizes = sizes_device_address(c->h_sizes);
     return 0;
 }
 

@@ -809,14 +809,6 @@ int stage_sel(molar_hip_ctx *c, const float *xyz, size_t natoms, const uint64_t 
     return 0;
 }
 
-int pull(molar_hip_ctx *c, void *dst, const void *src_dev, size_t bytes) {
-    MH_TRY(ensure_pinned(c, bytes));
-    MH_HIP(hipMemcpyAsync(c->h_pinned, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(dst, c->h_pinned, bytes);
-    return 0;
-}
-
 // run a reduction for one frame and fetch its NV totals
 template <class Launch>
 int reduce1(molar_hip_ctx *c, uint32_t n, int nv, double *host_out, Launch launch) {
@@ -869,9 +861,9 @@ int com_pbc_host(molar_hip_ctx *c, const Sel &s, const molar_hip_box &box, uint8
     {
         MH_TRY(c->m_out.reserve(64));
         uint64_t a0 = 0;
-        if (s.idx) MH_TRY(pull(c, &a0, s.idx, 8));
-        MH_TRY(pull(c, p0, s.xyz + 3 * a0, 12));
-        if (s.mass) MH_TRY(pull(c, &m0, s.mass + a0, 4));
+        if (s.idx) MH_TRY(read_back(c, &a0, s.idx, 8));
+        MH_TRY(read_back(c, p0, s.xyz + 3 * a0, 12));
+        if (s.mass) MH_TRY(read_back(c, &m0, s.mass + a0, 4));
     }
     if (weighted) {
         const double mass = (double)m0 + r[0];
@@ -967,7 +959,7 @@ int molar_hip_min_max(molar_hip_ctx *c, const float *xyz, size_t natoms, const u
         MH_HIP(hipGetLastError());
     }
     uint32_t mm[6];
-    MH_TRY(pull(c, mm, c->m_out.p, sizeof mm));
+    MH_TRY(read_back(c, mm, c->m_out.p, sizeof mm));
     for (int d = 0; d < 6; ++d) {
         const uint32_t o = mm[d];
         const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
@@ -1181,7 +1173,7 @@ int molar_hip_center_batch(molar_hip_ctx *c, const float *xyz, size_t natoms, co
     MH_HIP(hipMemsetAsync(status, 0, 4, c->stream));
     MH_TRY(enqueue_center_batch(c, d_xyz, d_idx, d_off, (uint32_t)nsel, d_mass, d_out, status));
     int st = 0;
-    MH_TRY(pull(c, &st, status, 4));
+    MH_TRY(read_back(c, &st, status, 4));
     if (st) return fail(st, "zero mass");
     if (!out_dev) {
         MH_HIP(hipMemcpyAsync(out, d_out, nsel * 12, hipMemcpyDeviceToHost, c->stream));
@@ -1269,7 +1261,7 @@ int molar_hip_lipid_tail_order(molar_hip_ctx *c, const float *xyz, size_t natoms
     MH_HIP(hipMemsetAsync(status, 0, 4, c->stream));
     MH_TRY(enqueue_lipid_order(c, d_xyz, d_idx, d_toff, (uint32_t)ntails, order_type, d_norm, d_noff, d_bo, d_out, status));
     int st = 0;
-    MH_TRY(pull(c, &st, status, 4));
+    MH_TRY(read_back(c, &st, status, 4));
     if (st) return fail(st, "lipid order error (status %d)", st);
     if (!out_dev && nout) {
         MH_HIP(hipMemcpyAsync(out, d_out, nout * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1400,7 +1392,7 @@ int molar_hip_fit_rmsd_batch(molar_hip_ctx *c, float *frames, size_t nframes, si
 static int finish_batch(molar_hip_ctx *c, int *status, float *out, const float *d_out, size_t count, const char *what) {
     MH_HIP(hipGetLastError());
     int st = 0;
-    MH_TRY(pull(c, &st, status, 4));
+    MH_TRY(read_back(c, &st, status, 4));
     if (st) return fail(st, "%s: %s", what, st == MOLAR_HIP_ERR_ZERO_MASS ? "zero mass" : "empty selection");
     if (out != d_out && count) {
         MH_HIP(hipMemcpyAsync(out, d_out, count * 4, hipMemcpyDeviceToHost, c->stream));
@@ -1494,7 +1486,7 @@ int molar_hip_fit_batch(molar_hip_ctx *c, float *xyz1, size_t natoms1, const uin
                        d_off, (uint32_t)nsel, m1, m2, apply ? 1 : 0, o);
     MH_HIP(hipGetLastError());
     std::vector<float> h(nsel * 18);
-    MH_TRY(pull(c, h.data(), o, h.size() * 4));
+    MH_TRY(read_back(c, h.data(), o, h.size() * 4));
     for (size_t k = 0; k < nsel; ++k) {
         int st;
         std::memcpy(&st, &h[18 * k + 17], 4);

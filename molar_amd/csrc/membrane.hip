@@ -1868,7 +1868,7 @@ struct molar_hip_membrane_plan {
         size_t Ecap = 0;
         size_t Scap = 0;          // (0: the layout has no shell arrays)
         uint32_t shp = 0, shs = 0;   // the shell options of the frame in this slot
-        void *h = nullptr;        // pinned: 16 bytes of search sizes | FrameInfo at the end of the frame
+        void *h = nullptr;        // pinned: the marker search's SearchSizes record (32 bytes) | FrameInfo at the end of the frame
         void *h_mid = nullptr;    // pinned: what the host pass reads (roff | n1 | valid_prev | pids32) and writes (n2)
         size_t h_mid_cap = 0;
         hipEvent_t mid = nullptr, done = nullptr;
@@ -1890,6 +1890,8 @@ struct molar_hip_membrane_plan {
 namespace {
 
 constexpr size_t H_SIZES = 0, H_INFO = 64, H_BYTES = 128;
+static_assert(sizeof(SearchSizes) <= H_INFO - H_SIZES, "the slot's pinned block: the search's record ends before the FrameInfo");
+SearchSizes *slot_sizes(const molar_hip_membrane_plan::Slot &S) { return reinterpret_cast<SearchSizes *>((char *)S.h + H_SIZES); }
 
 // the slot's pinned block mirrors the head of the device blob [info .. pids32 + Ecap] at the same offsets; the normals
 // the host pass produces follow
@@ -1993,7 +1995,7 @@ int enqueue_b(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
     const unsigned long long *total_dev = nullptr;
     const uint32_t *pairs_dev = nullptr;
     // (the invalid lipids' NaN markers stay out of the grid: with most lipids dropped they would crowd one cell)
-    MH_TRY(search_resident_enqueue(c, &q, (char *)S.h + H_SIZES, &S.L, &total_dev, &pairs_dev, /*drop_nonfinite=*/true));
+    MH_TRY(search_resident_enqueue(c, &q, slot_sizes(S), &S.L, &total_dev, &pairs_dev, /*drop_nonfinite=*/true));
     S.cap_pairs = S.L.cap0;
     const size_t Ecap = S.Ecap;
     uint32_t *deg = P->work.as<uint32_t>(), *cursor = deg + (K + 1), *t_ord = cursor + K, *t_oth = t_ord + Ecap, *t_grp = t_oth + Ecap;
@@ -2035,12 +2037,11 @@ int host_pass(molar_hip_membrane_plan *P, molar_hip_membrane_plan::Slot &S, bool
         MH_HIP(hipEventSynchronize(S.mid));
         std::memcpy(&S.info, (char *)S.h_mid + S.lay.info, sizeof(FrameInfo));
         bool fits = true;
-        MH_TRY(search_resident_fits(c, (char *)S.h + H_SIZES, S.L, &fits));
-        unsigned long long sizes[2];
-        std::memcpy(sizes, (char *)S.h + H_SIZES, 16);
-        if (2ull * sizes[0] >= (1ull << 32)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "membrane frame: %llu patch entries (32-bit entry indices)", 2ull * sizes[0]);
-        if (2ull * sizes[0] > P->Ecap) {
-            P->Ecap = (size_t)(2ull * sizes[0] + sizes[0] / 4u + 1024u);
+        MH_TRY(search_resident_fits(c, slot_sizes(S), S.L, &fits));
+        const unsigned long long total = slot_sizes(S)->total;
+        if (2ull * total >= (1ull << 32)) return fail(MOLAR_HIP_ERR_TOO_LARGE, "membrane frame: %llu patch entries (32-bit entry indices)", 2ull * total);
+        if (2ull * total > P->Ecap) {
+            P->Ecap = (size_t)(2ull * total + total / 4u + 1024u);
             fits = false;
         }
         if (fits && !S.info.overflow) break;

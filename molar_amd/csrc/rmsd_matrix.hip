@@ -410,14 +410,8 @@ int rmsd_matrix_run(molar_hip_ctx *c, const char *who, const Real *frames1, size
     MH_HIP(hipMemsetAsync(flags, 0, 16, c->stream));
     hipLaunchKernelGGL(rm_centre_kernel<Real>, dim3((uint32_t)L.Ftot), dim3(256), 0, c->stream, P, centre, flags);
     if (!fit) hipLaunchKernelGGL(rm_origin_kernel, dim3(1), dim3(1), 0, c->stream, centre, F1, origin);
-    // the weights' sum and the index check decide the status: 16 bytes read back before the products are enqueued
-    MH_TRY(ensure_pinned(c, 16));
-    MH_HIP(hipMemcpyAsync(c->h_pinned, centre + 3, 8, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipMemcpyAsync(static_cast<char *>(c->h_pinned) + 8, flags, 4, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    if (*reinterpret_cast<uint32_t *>(static_cast<char *>(c->h_pinned) + 8))
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
-    if (*static_cast<double *>(c->h_pinned) == 0.0) return fail(MOLAR_HIP_ERR_ZERO_MASS, "%s: the selected masses add up to zero", who);
+    // the weights' sum and the index check decide the status, read back before the products are enqueued
+    MH_TRY(check_selection(c, flags, centre + 3, who, natoms));
 
     const size_t Fpad = ((size_t)L.T1p + (sym ? 0 : L.T2p)) * RM_TILE;
     const double *org = fit ? nullptr : origin;

@@ -646,10 +646,9 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
         if (volumes && !volumes_dev) MH_TRY(copy_out(c, volumes, d_volumes, nframes * (size_t)ns * sizeof(Real)));
         MH_TRY(copy_out(c, vtotals, Z.vtotals.p, nframes * 8));
     }
-    MH_TRY(ensure_pinned(c, 8));
-    MH_HIP(hipMemcpyAsync(c->h_pinned, Z.err.p, 4, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    if (*static_cast<uint32_t *>(c->h_pinned)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
+    uint32_t bad_index = 0;
+    MH_TRY(read_back(c, &bad_index, Z.err.p, 4));
+    if (bad_index) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
     return MOLAR_HIP_OK;
 }
 

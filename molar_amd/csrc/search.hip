@@ -811,7 +811,7 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
                                                                 unsigned long long *__restrict__ task_moff,      // NULL: no hit history
                                                                 const unsigned long long *__restrict__ tile_tot,
                                                                 SlotDesc *__restrict__ slot_desc, uint64_t nslots_bound,
-                                                                unsigned long long *__restrict__ sizes_host,    // pinned, or NULL
+                                                                SearchSizes *__restrict__ sizes_host,           // pinned, or NULL
                                                                 const unsigned long long *__restrict__ group_tot,    // NULL: at most 1024 tiles
                                                                 const unsigned long long *__restrict__ live_masks,   // mask words of the SLOT_LIVE entries
                                                                 unsigned long long *__restrict__ slot_stat) {  // [2]: slots, slots of consecutive rows
@@ -885,8 +885,8 @@ static __global__ void __launch_bounds__(256) plan_slots_kernel(uint64_t ntasks,
             task_first[t] = base_n + lfirst[threadIdx.x];
             if (task_moff) task_moff[t] = lm0[threadIdx.x];
             if (t == ntasks && sizes_host) {
-                sizes_host[1] = task_moff ? lm0[threadIdx.x] : 0ull;      // hit-history units of this search
-                sizes_host[2] = base_n + lfirst[threadIdx.x];             // its slots
+                sizes_host->mask_units = task_moff ? lm0[threadIdx.x] : 0ull;
+                sizes_host->slots = base_n + lfirst[threadIdx.x];
             }
             if (t == ntasks && slot_stat) {
                 slot_stat[0] = total;
@@ -1075,7 +1075,7 @@ __global__ void __launch_bounds__(256) tile_sums_kernel(const uint32_t *__restri
 __global__ void __launch_bounds__(256) slot_offsets_kernel(const uint32_t *__restrict__ slot_cnt,
                                                            const unsigned long long *__restrict__ tile_sum,
                                                            unsigned long long *__restrict__ slot_base, uint64_t n,
-                                                           unsigned long long *__restrict__ sizes_host,
+                                                           SearchSizes *__restrict__ sizes_host,
                                                            const uint32_t *__restrict__ occ0, const uint32_t *__restrict__ occ1) {
     __shared__ unsigned long long part[4];
     unsigned long long pre = 0;
@@ -1090,19 +1090,19 @@ __global__ void __launch_bounds__(256) slot_offsets_kernel(const uint32_t *__res
     const unsigned long long ex = block_exclusive_scan<unsigned long long>(v, &tot);
     if (i < n) slot_base[i] = base + ex;
     if (i + 1 == n && sizes_host) {
-        sizes_host[0] = base + ex;      // slot_cnt[n - 1] is the terminator: its offset is the grand total
+        sizes_host->total = base + ex;      // slot_cnt[n - 1] is the terminator: its offset is the grand total
         // the occupied cells of the two grids (counted by their placement kernels), for the host's choice of kernels next time
         uint32_t o0 = 0u, o1 = 0u;
         for (uint32_t k = 0; k < OCC_WORDS; ++k) {
             o0 += occ0 ? occ0[k] : 0u;
             o1 += occ1 ? occ1[k] : 0u;
         }
-        sizes_host[3] = ((unsigned long long)o1 << 32) | o0;
+        sizes_host->occupied = ((unsigned long long)o1 << 32) | o0;
     }
 }
 
 // slot counts -> output offsets (n = slots + 1 terminator), the grand total also to `sizes_host` (pinned, may be null)
-int scan_slot_counts(molar_hip_ctx *c, unsigned long long *sizes_host) {
+int scan_slot_counts(molar_hip_ctx *c, SearchSizes *sizes_host) {
     const SearchShape &cur = c->cur;
     const uint64_t n = cur.nslots_bound + 1;
     const uint64_t ntiles = (n + 255) / 256;
@@ -1123,7 +1123,7 @@ int scan_slot_counts(molar_hip_ctx *c, unsigned long long *sizes_host) {
     }
     MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->slot_cnt.as<uint32_t>(), c->slot_base.as<unsigned long long>(), n)));
     if (sizes_host)
-        MH_HIP(hipMemcpyAsync(sizes_host, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDefault, c->stream));
+        MH_HIP(hipMemcpyAsync(&sizes_host->total, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDefault, c->stream));
     return 0;
 }
 
@@ -1238,11 +1238,13 @@ static void occ_latch(molar_hip_ctx *c) {
     c->cur.occ_use[0] = known ? c->occ_cells[0] : 0u;
     c->cur.occ_use[1] = known ? c->occ_cells[1] : 0u;
 }
-static void occ_note(molar_hip_ctx *c, unsigned long long key, unsigned long long packed) {
-    if (!key || !(uint32_t)packed) return;          // (a search that did not report: the hint stays as it is)
+// entry `i` of the context's SearchSizes records as the device addresses it (null: the device cannot store there)
+static SearchSizes *sizes_dev_of(molar_hip_ctx *c, int i) { return c->d_sizes ? c->d_sizes + i : nullptr; }
+static void occ_note(molar_hip_ctx *c, unsigned long long key, const SearchSizes &sizes) {
+    if (!key || !(uint32_t)sizes.occupied) return;          // (a search that did not report: the hint stays as it is)
     c->occ_key = key;
-    c->occ_cells[0] = (uint32_t)packed;
-    c->occ_cells[1] = (uint32_t)(packed >> 32);
+    c->occ_cells[0] = (uint32_t)sizes.occupied;
+    c->occ_cells[1] = (uint32_t)(sizes.occupied >> 32);
     c->occ_valid = true;
 }
 
@@ -1256,7 +1258,7 @@ struct SearchCall {
     bool side = false;             // the grid may be built on the side stream (pipelined searches, asynchronous histograms) ...
     hipEvent_t side_wait = nullptr;            // ... which first waits for this (the last reader of the grid generation)
     unsigned long long out_cap = ~0ull;        // resident searches: the output capacity in the parameter block (plan kernel, pair passes)
-    unsigned long long *sizes_dev = nullptr;   // resident searches: device-side address of the pinned sizes the kernels write
+    SearchSizes *sizes_dev = nullptr;          // resident searches: device-side address of the pinned record the kernels write
     bool drop_nonfinite = false;   // the grid leaves atoms with a non-finite coordinate out (stages.hpp, search_resident_enqueue)
     uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
     bool live_rows = true;         // the slots go to the count / fill passes, which walk live-ranked slots where live_row_slots() says so
@@ -1650,14 +1652,6 @@ int ensure_hist_edges(molar_hip_ctx *c, float hmin, float hmax, size_t nbins) {
     return 0;
 }
 
-int read_back(molar_hip_ctx *c, void *dst_host, const void *src_dev, size_t bytes) {
-    MH_TRY(ensure_pinned(c, bytes));
-    MH_HIP(hipMemcpyAsync(c->h_pinned, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    std::memcpy(dst_host, c->h_pinned, bytes);
-    return 0;
-}
-
 // zero-seeded bounding box of one set, accumulated into c->scan_tmp-independent 6-word buffer
 int bbox_accumulate(molar_hip_ctx *c, uint32_t *d_mm, const GridSet &S) {
     if (!S.n) return 0;
@@ -1687,7 +1681,7 @@ int device_fmax2(molar_hip_ctx *c, const float *d_v1, uint32_t n1, const float *
 
 // Second half of the plan, for the kernels that walk slots (count / fill / histogram): slot index of every plan entry and
 // (fast kinds) its first hit-history unit by one single-pass scan over both, then one record per slot.
-int enqueue_plan_slots(molar_hip_ctx *c, unsigned long long *sizes_dev) {
+int enqueue_plan_slots(molar_hip_ctx *c, SearchSizes *sizes_dev) {
     const SearchShape &cur = c->cur;
     const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
     const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
@@ -1720,18 +1714,16 @@ int size_plan(molar_hip_ctx *c) {
     SearchShape &cur = c->cur;
     const bool fast_kind = records_hit_history(cur);
     if (!fast_kind && cur.nslots_bound <= 65536ull) return 0;       // nothing to size, too few launches to save: no round trip
-    MH_TRY(ensure_pinned(c, 64));
-    unsigned long long *h = reinterpret_cast<unsigned long long *>(c->h_pinned);
-    h[0] = h[1] = 0ull;
-    if (fast_kind) MH_HIP(hipMemcpyAsync(&h[0], c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipMemcpyAsync(&h[1], c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));      // task_nb is scanned in place: the total
+    SearchSizes *s = &c->h_sizes[molar_hip_ctx::SIZES_SYNC];
+    *s = SearchSizes{};
+    if (fast_kind) MH_HIP(hipMemcpyAsync(&s->mask_units, c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
+    MH_HIP(hipMemcpyAsync(&s->slots, c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));      // task_nb is scanned in place: the total (u32: the low half)
     MH_HIP(hipStreamSynchronize(c->stream));
     if (fast_kind) {
-        c->mask_units = h[0];
-        MH_TRY(c->maskbuf.reserve((size_t)h[0] * 256u + 256u));
+        c->mask_units = s->mask_units;
+        MH_TRY(c->maskbuf.reserve((size_t)s->mask_units * 256u + 256u));
     }
-    const uint64_t real = (uint32_t)h[1];
-    if (real < cur.nslots_bound) cur.nslots_bound = real;
+    if (s->slots < cur.nslots_bound) cur.nslots_bound = s->slots;
     return 0;
 }
 
@@ -1981,25 +1973,18 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
 int finish_count(molar_hip_ctx *c) {
     Prof *prof = new Prof(c, 2);
     // (the look-back scan is slower here: ~140 chained tiles take 43 us against 14 us for the three-kernel scan)
-    // the grand total (and the grids' occupied cells, for the next search of this shape) straight into pinned memory where the
-    // block is visible to the device; else one read-back of the total
-    void *sizes_dev = nullptr;
-    if (ensure_pinned(c, 64) == 0 && hipHostGetDevicePointer(&sizes_dev, c->h_pinned, 0) == hipSuccess && sizes_dev) {
-        std::memset(c->h_pinned, 0, 32);
-    } else {
-        (void)hipGetLastError();
-        sizes_dev = nullptr;
-    }
-    int rc = scan_slot_counts(c, (unsigned long long *)sizes_dev);
+    // the grand total (and the grids' occupied cells, for the next search of this shape) straight into the context's record of
+    // the synchronous calls where the device can store there; else one read-back of the total
+    SearchSizes *sizes = &c->h_sizes[molar_hip_ctx::SIZES_SYNC], *sizes_dev = sizes_dev_of(c, molar_hip_ctx::SIZES_SYNC);
+    *sizes = SearchSizes{};
+    int rc = scan_slot_counts(c, sizes_dev);
     delete prof;
     MH_TRY(rc);
     unsigned long long tot = 0;
     if (sizes_dev) {
         MH_HIP(hipStreamSynchronize(c->stream));
-        unsigned long long occ = 0;
-        std::memcpy(&tot, c->h_pinned, 8);
-        std::memcpy(&occ, (const char *)c->h_pinned + 24, 8);
-        occ_note(c, occ_key_of(c->cur), occ);
+        tot = sizes->total;
+        occ_note(c, occ_key_of(c->cur), *sizes);
     } else {
         MH_TRY(read_back(c, &tot, c->slot_base.as<unsigned long long>() + c->cur.nslots_bound, 8));
     }
@@ -2332,26 +2317,21 @@ int molar_hip_search_fill_device(molar_hip_ctx *c, const uint32_t **d_pairs, con
 }
 
 // Enqueue one whole resident search (grid, plan, count, offset scan, fill into outP/outD against their present
-// capacity) and the async read-back of its two sizes into `sizes` (pinned, 16 bytes).  No host wait.
+// capacity) and the delivery of its sizes into the pinned record `sizes`.  No host wait.
 // (struct ResidentLaunch: stages.hpp)
+// sizes_dev, the device-side address of `sizes`: the kernels write the record themselves (the plan its hit-history units and slots,
+// slot_offsets_kernel the grand total and the occupied cells) - no copy commands behind the fill pass.  Null: the sizes are copied.
 // pairs_only: the fill pass writes the (i, j) plane alone; trim: launch the passes over what the plan of the search before came
 // to (common.hpp, trim_real) where that is known.  Of `call` the caller sets side, side_wait and drop_nonfinite; the rest is set here.
-static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD,
-                            void *sizes, ResidentLaunch *L, bool pairs_only, bool trim = true, SearchCall call = SearchCall{}) {
+static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD, SearchSizes *sizes,
+                            SearchSizes *sizes_dev, ResidentLaunch *L, bool pairs_only, bool trim = true, SearchCall call = SearchCall{}) {
     if (q && q->kind == MOLAR_HIP_SEARCH_WITHIN)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within search yields ids: use molar_hip_search_count + fill_ids");
     const unsigned long long a = outP.cap / 8u, b = outD.cap / 4u;
     const unsigned long long cap0 = a < b ? a : b;
-    // `sizes` is pinned host memory: the kernels write the two sizes there themselves (slotmap_kernel the hit-history
-    // units, slot_offsets_kernel the grand total) - no copy commands behind the fill pass
-    void *sizes_dev = nullptr;
-    if (hipHostGetDevicePointer(&sizes_dev, sizes, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        sizes_dev = nullptr;
-    }
     call.size_masks = false;
     call.out_cap = cap0;
-    call.sizes_dev = (unsigned long long *)sizes_dev;
+    call.sizes_dev = sizes_dev;
     MH_TRY(prepare_search(c, q, call));
     ++c->search_serial;
     *L = ResidentLaunch{};
@@ -2374,15 +2354,15 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
     MH_TRY(launch_pairs<false>(c, call, PairOut{}));
     {
         Prof prof(c, 2);
-        MH_TRY(scan_slot_counts(c, (unsigned long long *)sizes_dev));
+        MH_TRY(scan_slot_counts(c, sizes_dev));
     }
     if (cap0) MH_TRY(launch_pairs<true>(c, call, PairOut{outP.as<uint2>(), pairs_only ? nullptr : outD.as<float>()}, HistTarget{},
                                         /*params_resident=*/true));
     if (!sizes_dev) {
-        MH_HIP(hipMemcpyAsync(sizes, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipMemcpyAsync(&sizes->total, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDeviceToHost, c->stream));
         if (fast_kind)
-            MH_HIP(hipMemcpyAsync((char *)sizes + 8, c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
-        MH_HIP(hipMemcpyAsync((char *)sizes + 16, c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));   // (little-endian: the upper half was zeroed)
+            MH_HIP(hipMemcpyAsync(&sizes->mask_units, c->task_moff.as<unsigned long long>() + cur.ntasks, 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipMemcpyAsync(&sizes->slots, c->task_nb.as<uint32_t>() + cur.ntasks, 4, hipMemcpyDeviceToHost, c->stream));   // (little-endian: the upper half was zeroed)
     }
     L->cap0 = cap0;
     return 0;
@@ -2391,14 +2371,12 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
 // The sizes of a resident search have been read: what its plan came to is the next search's launch size - and was this search
 // itself launched over enough slots?  If not (the frame before had fewer slots than this one less the margin), the next
 // enqueue of this plan launches the bound again.
-static bool resident_covered(molar_hip_ctx *c, const void *sizes, unsigned long long launched, unsigned long long ntasks, int kind) {
-    unsigned long long res[3] = {0, 0, 0};
-    std::memcpy(res, sizes, 24);
-    if (res[2] > launched) {
+static bool resident_covered(molar_hip_ctx *c, const SearchSizes *sizes, unsigned long long launched, unsigned long long ntasks, int kind) {
+    if (sizes->slots > launched) {
         c->trim_real = 0;
         return false;
     }
-    c->trim_real = res[2];
+    c->trim_real = sizes->slots;
     c->trim_ntasks = ntasks;
     c->trim_kind = kind;
     return true;
@@ -2406,12 +2384,10 @@ static bool resident_covered(molar_hip_ctx *c, const void *sizes, unsigned long 
 
 // With `sizes` delivered and the search still the context's cached one: grow what was too small and repeat the
 // affected passes (first frame of a trajectory; later frames are the same size +- noise).
-static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD, const void *sizes, const ResidentLaunch &L, bool pairs_only) {
+static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD, const SearchSizes *sizes, const ResidentLaunch &L, bool pairs_only) {
     const bool fast_kind = fixed_cutoff_kind(c->cur.kind);
-    unsigned long long res[2] = {0, 0};
-    std::memcpy(res, sizes, 16);
-    c->total = res[0];
-    c->mask_units = fast_kind ? res[1] : 0;
+    c->total = sizes->total;
+    c->mask_units = fast_kind ? sizes->mask_units : 0;
     c->have_search = true;
     bool refill = L.cap0 == 0 && c->total != 0;
     if (c->mask_units > L.maskcap0) {        // hit bits did not fit: grow, record them, fill again
@@ -2434,55 +2410,51 @@ static int resident_settle(molar_hip_ctx *c, mh::DevBuf &outP, mh::DevBuf &outD,
 
 // One whole resident search, complete when the call returns (the stream has been waited for).
 static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::DevBuf &outP, mh::DevBuf &outD, bool pairs_only) {
-    MH_TRY(ensure_pinned(c, 64));
+    SearchSizes *sizes = &c->h_sizes[molar_hip_ctx::SIZES_SYNC], *sizes_dev = sizes_dev_of(c, molar_hip_ctx::SIZES_SYNC);
     ResidentLaunch L;
-    std::memset(c->h_pinned, 0, 32);
-    MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
+    *sizes = SearchSizes{};
+    MH_TRY(resident_enqueue(c, q, outP, outD, sizes, sizes_dev, &L, pairs_only));
     if (L.degenerate) return 0;
     MH_HIP(hipStreamSynchronize(c->stream));
-    if (!resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->cur.kind)) {       // too few slots launched: once more, over the bound
-        std::memset(c->h_pinned, 0, 32);
-        MH_TRY(resident_enqueue(c, q, outP, outD, c->h_pinned, &L, pairs_only));
+    if (!resident_covered(c, sizes, L.launched, L.ntasks, c->cur.kind)) {       // too few slots launched: once more, over the bound
+        *sizes = SearchSizes{};
+        MH_TRY(resident_enqueue(c, q, outP, outD, sizes, sizes_dev, &L, pairs_only));
         MH_HIP(hipStreamSynchronize(c->stream));
-        (void)resident_covered(c, c->h_pinned, L.launched, L.ntasks, c->cur.kind);
+        (void)resident_covered(c, sizes, L.launched, L.ntasks, c->cur.kind);
     }
-    {
-        unsigned long long occ = 0;
-        std::memcpy(&occ, (const char *)c->h_pinned + 24, 8);
-        occ_note(c, occ_key_of(c->cur), occ);
-    }
-    return resident_settle(c, outP, outD, c->h_pinned, L, pairs_only);
+    occ_note(c, occ_key_of(c->cur), *sizes);
+    return resident_settle(c, outP, outD, sizes, L, pairs_only);
 }
 
 }  // extern "C"
 
 // stages.hpp: the resident search for callers that chain device work behind it
-int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, void *sizes_pinned, ResidentLaunch *L,
+int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, SearchSizes *sizes_pinned, ResidentLaunch *L,
                                 const unsigned long long **total_dev, const uint32_t **pairs_dev, bool drop_nonfinite) {
-    std::memset(sizes_pinned, 0, 24);
+    *sizes_pinned = SearchSizes{};
     // the chained stages (the membrane's patches) read the (i, j) plane only; their passes launch the bound (searches of 1e4
     // markers: nothing to trim, and nobody reads the plan's size back in between)
     SearchCall call;
     call.drop_nonfinite = drop_nonfinite;
-    MH_TRY(resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, L, /*pairs_only=*/true, /*trim=*/false, call));
+    MH_TRY(resident_enqueue(c, q, c->out_pairs, c->out_dist, sizes_pinned, sizes_device_address(sizes_pinned), L, /*pairs_only=*/true,
+                            /*trim=*/false, call));
     c->have_search = false;              // the sizes are not known to the host: not a cached search for the fill calls
     *total_dev = L->degenerate ? nullptr : c->slot_base.as<unsigned long long>() + c->cur.nslots_bound;
     *pairs_dev = c->out_pairs.as<uint32_t>();
     return 0;
 }
 
-int mh::search_resident_fits(molar_hip_ctx *c, const void *sizes_pinned, const ResidentLaunch &L, bool *fits) {
-    unsigned long long res[2] = {0, 0};
-    std::memcpy(res, sizes_pinned, 16);
+int mh::search_resident_fits(molar_hip_ctx *c, const SearchSizes *sizes_pinned, const ResidentLaunch &L, bool *fits) {
+    const unsigned long long total = sizes_pinned->total, mask_units = sizes_pinned->mask_units;
     *fits = true;
     if (L.degenerate) return 0;
-    if (res[1] > L.maskcap0) {
-        MH_TRY(c->maskbuf.reserve((size_t)(res[1] + res[1] / 4u) * 256u + 256u));
+    if (mask_units > L.maskcap0) {
+        MH_TRY(c->maskbuf.reserve((size_t)(mask_units + mask_units / 4u) * 256u + 256u));
         *fits = false;
     }
-    if (res[0] > L.cap0) {
-        MH_TRY(c->out_pairs.reserve((size_t)(res[0] + res[0] / 16u) * 8));
-        MH_TRY(c->out_dist.reserve((size_t)(res[0] + res[0] / 16u) * 4));
+    if (total > L.cap0) {
+        MH_TRY(c->out_pairs.reserve((size_t)(total + total / 16u) * 8));
+        MH_TRY(c->out_dist.reserve((size_t)(total + total / 16u) * 4));
         *fits = false;
     }
     return 0;
@@ -2520,10 +2492,6 @@ int molar_hip_search_resident_begin(molar_hip_ctx *c, const molar_hip_search_des
     if (T.pending)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "both result sets are in flight: call molar_hip_search_resident_end first");
     MH_HIP(hipSetDevice(c->device));
-    if (!c->h_sizes) {
-        MH_HIP(hipHostMalloc(&c->h_sizes, 64, hipHostMallocDefault));      // 32 bytes per ticket
-        std::memset(c->h_sizes, 0, 64);
-    }
     if (!T.done) MH_HIP(hipEventCreateWithFlags(&T.done, hipEventDisableTiming));
     T.desc = *q;
     ResidentLaunch L;
@@ -2538,8 +2506,8 @@ int molar_hip_search_resident_begin(molar_hip_ctx *c, const molar_hip_search_des
     // alternations).  The grid starts as soon as its generation is free - it then runs under the COUNT pass of the frame in
     // flight, whose workgroups leave one wave slot per SIMD open, and the fill pass has the chip and the write path to
     // itself.  (Holding it back until that count pass has ended - the round-3 order - gave the same frames/s.)
-    std::memset((char *)c->h_sizes + 32 * slot + 24, 0, 8);      // (occupied cells: zero = not reported)
-    MH_TRY(resident_enqueue(c, q, c->out_pairs_set[slot], c->out_dist_set[slot], (char *)c->h_sizes + 32 * slot, &L, c->resident_no_dist,
+    c->h_sizes[slot].occupied = 0;      // (zero = not reported)
+    MH_TRY(resident_enqueue(c, q, c->out_pairs_set[slot], c->out_dist_set[slot], &c->h_sizes[slot], sizes_dev_of(c, slot), &L, c->resident_no_dist,
                             /*trim=*/true, call));
     MH_HIP(hipEventRecord(T.done, c->stream));
     T.cap0 = L.cap0;
@@ -2568,11 +2536,9 @@ int molar_hip_search_resident_end(molar_hip_ctx *c, int32_t ticket, uint64_t *ou
     uint64_t total = 0;
     if (!T.degenerate) {
         MH_HIP(hipEventSynchronize(T.done));
-        const void *sizes = (const char *)c->h_sizes + 32 * ticket;
-        unsigned long long res[2], occ = 0;
-        std::memcpy(res, sizes, 16);
-        std::memcpy(&occ, (const char *)sizes + 24, 8);
-        occ_note(c, T.occ_key, occ);
+        const SearchSizes *sizes = &c->h_sizes[ticket];
+        const unsigned long long res[2] = {sizes->total, sizes->mask_units};      // (as delivered: a repeat below has sizes of its own)
+        occ_note(c, T.occ_key, *sizes);
         const bool fast_kind = T.desc.kind == MOLAR_HIP_SEARCH_SINGLE || T.desc.kind == MOLAR_HIP_SEARCH_DOUBLE;
         total = res[0];
         const bool covered = resident_covered(c, sizes, T.launched, T.ntasks, T.kind);
@@ -2591,11 +2557,11 @@ int molar_hip_search_resident_end(molar_hip_ctx *c, int32_t ticket, uint64_t *ou
                     MH_TRY(outP.reserve((size_t)(res[0] + res[0] / 16u) * 8));
                     MH_TRY(outD.reserve((size_t)(res[0] + res[0] / 16u) * 4));
                 }
-                MH_TRY(ensure_pinned(c, 64));
-                std::memset(c->h_pinned, 0, 32);
-                MH_TRY(resident_enqueue(c, &T.desc, outP, outD, c->h_pinned, &L, c->resident_no_dist));
+                SearchSizes *again = &c->h_sizes[molar_hip_ctx::SIZES_SYNC];
+                *again = SearchSizes{};
+                MH_TRY(resident_enqueue(c, &T.desc, outP, outD, again, sizes_dev_of(c, molar_hip_ctx::SIZES_SYNC), &L, c->resident_no_dist));
                 MH_HIP(hipStreamSynchronize(c->stream));
-                sizes = c->h_pinned;
+                sizes = again;
                 (void)resident_covered(c, sizes, L.launched, L.ntasks, T.kind);      // (launched over the bound: covered)
             }
             MH_TRY(resident_settle(c, outP, outD, sizes, L, c->resident_no_dist));

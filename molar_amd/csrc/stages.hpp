@@ -19,8 +19,8 @@ int enqueue_lipid_order(molar_hip_ctx *c, const float *xyz, const uint64_t *idx,
 
 // search.hip: the resident search (molar_hip_search_resident) without its wait.  Count, offset scan and fill go to the
 // context's result buffers against their present capacity; the number of results stays in device memory
-// (*total_dev, u64) for kernels enqueued behind it, and the two sizes the host needs to judge the capacities are
-// copied to `sizes_pinned` (24 bytes: results, hit-history units, slots of the plan).
+// (*total_dev, u64) for kernels enqueued behind it, and what the host needs to judge the capacities is delivered to
+// `sizes_pinned`, one SearchSizes record (32 bytes, common.hpp) in pinned memory of the caller's.
 struct ResidentLaunch {
     unsigned long long cap0 = 0;      // result capacity the fill pass was launched with (0: the fill was skipped)
     unsigned long long maskcap0 = 0;  // hit-history units the count pass could record
@@ -34,11 +34,11 @@ struct ResidentLaunch {
 };
 // drop_nonfinite: atoms with a non-finite coordinate are binned into no cell (the reference puts a NaN atom into cell 0; it pairs
 // with nothing either way, so the pair list is the same)
-int search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, void *sizes_pinned, ResidentLaunch *L,
+int search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, SearchSizes *sizes_pinned, ResidentLaunch *L,
                             const unsigned long long **total_dev, const uint32_t **pairs_dev, bool drop_nonfinite = false);
 // true if the sizes delivered for launch L fitted; otherwise the buffers have been grown and the search must be
 // enqueued again
-int search_resident_fits(molar_hip_ctx *c, const void *sizes_pinned, const ResidentLaunch &L, bool *fits);
+int search_resident_fits(molar_hip_ctx *c, const SearchSizes *sizes_pinned, const ResidentLaunch &L, bool *fits);
 
 // devsort.hip: stable radix sort of (u32, u32) pairs by the keys' low `end_bit` bits, exclusive prefix sums (rocPRIM)
 int device_sort_pairs_u32(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in,

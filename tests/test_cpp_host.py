@@ -59,6 +59,22 @@ def test_search_shape_cpu():
     assert r.returncode == 0 and "all search-shape tests passed" in r.stdout, r.stdout + r.stderr
 
 
+def test_search_sizes_cpu():
+    """mh::SearchSizes (molar_amd/csrc/common.hpp) on the host (hipcc, no GPU needed to run): the size and the four offsets the
+    kernels and the copy fallback rely on, and a fallback-style fill of the slot count's low half, read through the fields."""
+    from molar_amd import build
+    build.build_library()
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, "test_search_sizes")
+    libdir = os.path.join(ROOT, "molar_amd")
+    cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
+           os.path.join(ROOT, "tests", "cpp", "test_search_sizes.cpp"), "-o", exe, "-L", libdir, "-lmolar_hip", f"-Wl,-rpath,{libdir}"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "all search-sizes tests passed" in r.stdout, r.stdout + r.stderr
+
+
 @pytest.mark.gpu
 def test_host_api_gpu():
     from oracle import oracle as o

@@ -110,6 +110,52 @@ def test_failed_resident_begin_leaves_both_tickets_and_the_distances(a, sys_):
     same_list(resident_arrays(a, e.search_resident(a.SEARCH_SINGLE, CUTOFF, sys_["d_pos"], box=sys_["box"], pbc=7)), want, "plain call")
 
 
+def test_synchronous_calls_between_two_tickets_in_flight(a, sys_):
+    """With both tickets of search_resident_begin in flight: a count + fill of another kind and cutoff, a histogram whose edge
+    table the engine has to stage, a min_max - every one of them goes through the context's bounce buffer - and then the two
+    ends.  The tickets' sizes are delivered while those calls run, so nothing of a ticket may live where they stage or read
+    back.  Every result is bit for bit that of the same call on a fresh Engine; the occupied cells the last search reports (the
+    second ticket's: on an Engine without result buffers an end runs its search once more, knowing what the ticket's record
+    said) are those a fresh Engine reports that ran only this search, until it knew them - twice."""
+    s = sys_
+    hist = (0.1, 0.7, 48)          # not HIST: no Engine of this test has this edge table yet
+    desc = lambda eng: eng.make_search_desc(a.SEARCH_SINGLE, CUTOFF, s["d_pos"], box=s["box"], pbc=7)
+
+    def other_count_fill(eng):
+        cnt = eng.search_count(a.SEARCH_DOUBLE, 0.6, s["pos"], xyz2=s["pos2"], box=s["box"], pbc=7)
+        return (cnt,) + eng.search_fill(cnt)
+
+    def histogram(eng):
+        bins, cnt = eng.search_histogram(a.SEARCH_SINGLE, CUTOFF, *hist, s["pos"], box=s["box"], pbc=7)
+        return np.asarray(bins).copy(), cnt
+
+    e = a.Engine(0)
+    d, _keep = desc(e)
+    t0 = e.search_resident_begin(d)
+    t1 = e.search_resident_begin(d)
+    assert {t0, t1} == {0, 1}
+    got_double = other_count_fill(e)
+    got_bins, got_cnt = histogram(e)
+    got_lo, got_up = e.min_max(s["pos"])
+    first = resident_arrays(a, e.search_resident_end(t0))
+    second = resident_arrays(a, e.search_resident_end(t1))
+    got_cells = e.search_cell_kernels()
+
+    same_list(got_double, other_count_fill(a.Engine(0)), "count + fill between begin and end")
+    want_bins, want_cnt = histogram(a.Engine(0))
+    assert got_cnt == want_cnt > 0 and got_bins.dtype == want_bins.dtype and got_bins.tobytes() == want_bins.tobytes() and got_bins.any()
+    want_lo, want_up = a.Engine(0).min_max(s["pos"])
+    assert got_lo.tobytes() == want_lo.tobytes() and got_up.tobytes() == want_up.tobytes() and (want_up > want_lo).all()
+    f = a.Engine(0)
+    want = resident_arrays(a, f.search_resident(a.SEARCH_SINGLE, CUTOFF, s["d_pos"], box=s["box"], pbc=7))
+    same_list(first, want, "first ticket")
+    same_list(second, want, "second ticket")
+    same_list(second, first, "the two tickets")
+    same_list(resident_arrays(a, f.search_resident(a.SEARCH_SINGLE, CUTOFF, s["d_pos"], box=s["box"], pbc=7)), want, "the same search again")
+    want_cells = f.search_cell_kernels()          # (of the second run, which knows what the first one counted)
+    assert got_cells == want_cells and want_cells[1][0] > 0
+
+
 def sequence(a, e, s):
     """(d) one request of every form; returns what each step produced."""
     import torch
