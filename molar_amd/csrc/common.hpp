@@ -140,6 +140,25 @@ struct SearchShape {
                                     // (0: not known for this search, the grid's cell count stands in)
 };
 
+// ---------------------------------------------------------------- the held grid of `within` requests
+// molar_hip_within_hold: the first set of a `within` request as it was staged and binned, for later requests against the SAME
+// first set to reuse.  What decides the reuse is in search_shape.hpp (held_names_request, held_same_cells, held_remember); a
+// search that stages or bins the first set of that grid generation again ends it (valid = false).
+struct HeldGrid {
+    bool valid = false;
+    const GridSet *set = nullptr;      // the grid generation the held grid lives in
+    uint64_t fp = 0;                   // fingerprint of a host-memory first set as it was staged (0: device memory, read in place)
+    const float *xyz = nullptr;        // the request's first set as the caller named it ...
+    const uint64_t *idx = nullptr;
+    size_t natoms = 0, n = 0;
+    int ids_local = 0;
+    bool use_box = false;              // ... and the frame it was binned in
+    uint8_t pbc = 0;
+    molar_hip_box box{};
+    uint32_t dims[3]{0, 0, 0};
+    float lower[3]{}, upper[3]{};      // (the caller's bounds: they decide the grid of a request without a box)
+};
+
 // ---------------------------------------------------------------- the sizes of one search
 struct SearchSizes {            // written by the plan and offsets kernels into pinned host memory, read by the host after the stream
     unsigned long long total;       // results of the search                   (slot_offsets_kernel / scan_slot_counts)
@@ -186,14 +205,19 @@ struct molar_hip_ctx {
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
     // ---- cached search (count -> fill)
-    // Three things describe a search, and only the first two are kept here:
+    // Four things describe a search, and only the first two are kept here:
     //  * its SHAPE - kind, box, cutoff, grid dimensions, plan and slot bounds, the grid generation it refers to - is `cur`, one
     //    value; the helpers of search.hip are functions of a shape, so frames that are not the cached search are described by
     //    shapes of the caller's own and leave `cur` alone;
     //  * what OUTLASTS a request: have_search / total / mask_units, the buffers, the hints (occ_key, occ_cells, occ_valid), the
-    //    tickets, the record of a held `within` grid;
+    //    tickets, the record of a held `within` grid (`held`);
     //  * what ONE request asks of the shared helpers (plan or not, side stream, output capacity ...) travels down the call
-    //    chain as a SearchCall argument (search.hip).
+    //    chain as a SearchCall argument (search.hip);
+    //  * WHERE a grid is built - the stream, that stream's scan and sort scratch, the launch shape that goes with it - is a
+    //    GridLane argument (search.hip: main_lane, side_lane).  `stream` is assigned when the context is created or handed a
+    //    stream and never swapped for the length of a call: whatever reads it gets the main stream.
+    // have_search says that a count has finished and the fill calls may run - nothing else: a request that came to nothing
+    // (empty vdW input) is reported by prepare_search through its `degenerate` argument.
     bool have_search = false;
     mh::SearchShape cur;                 // the cached search; cur.set = the grid generation it refers to
     uint64_t total = 0;
@@ -215,9 +239,7 @@ struct molar_hip_ctx {
                                                    // stream waits for before it rebuilds the generation
     bool env_no_bin_tile = false;        // MOLAR_HIP_NO_BIN_TILE: the grid's binning with one global atomic per atom (A/B runs)
     int hist_gen = 0;                    // generation of the last asynchronous histogram call
-    bool on_side = false;                // `stream` is side_stream for the grid build in hand (scans then use scan_tmp_side); set
-                                         // and restored together with `stream` by one scope guard in prepare_search
-    mh::DevBuf scan_tmp_side;
+    mh::DevBuf scan_tmp_side;            // block sums of the scans on the side stream (the two streams may scan at the same time)
     mh::DevBuf params;         // SearchParams block read by the pair kernels
     mh::DevBuf task_desc;      // TaskDesc per task (plan entry)
     mh::DevBuf task_nb;        // u32 per task (+1): 64-row blocks of the task, scanned in place -> first slot
@@ -294,18 +316,8 @@ struct molar_hip_ctx {
     uint64_t conn_rows = 0, conn_entries = 0;
     bool have_conn = false;
     // molar_hip_within_hold: reuse of the first set's staged coordinates and grid across `within` requests
-    bool within_hold = false, hold_valid = false;
-    mh::GridSet *hold_set = nullptr;
-    uint64_t hold_fp = 0;      // fingerprint of a host-memory first set as it was staged (0: device memory, read in place)
-    const float *hold_xyz = nullptr;
-    const uint64_t *hold_idx = nullptr;
-    size_t hold_natoms = 0, hold_n = 0;
-    int hold_ids_local = 0;
-    bool hold_use_box = false;
-    uint8_t hold_pbc = 0;
-    molar_hip_box hold_box{};
-    uint32_t hold_dims[3]{0, 0, 0};
-    float hold_lower[3]{}, hold_upper[3]{};
+    bool within_hold = false;          // the caller's switch
+    mh::HeldGrid held;
     // `within` as a set (molar_hip_within_count / _fill)
     mh::DevBuf w_list;         // small second sets: ids found, in the order they were found (within_small_kernel)
     bool w_small = false;      // the cached within set was made by the small path (the list holds it)
@@ -348,6 +360,7 @@ namespace mh {
 struct Prof {
     molar_hip_ctx *c;
     int cls;
+    hipStream_t stream;
     hipEvent_t a = nullptr, b = nullptr;
     static hipEvent_t get(molar_hip_ctx *c) {
         if (!c->event_pool.empty()) {
@@ -359,16 +372,18 @@ struct Prof {
         (void)hipEventCreate(&e);
         return e;
     }
-    Prof(molar_hip_ctx *ctx, int k) : c(ctx), cls(k) {
+    // (on the context's stream unless the launches of the span go to another one: a grid build on the side stream)
+    Prof(molar_hip_ctx *ctx, int k) : Prof(ctx, k, ctx->stream) {}
+    Prof(molar_hip_ctx *ctx, int k, hipStream_t on) : c(ctx), cls(k), stream(on) {
         if (!c->profiling) return;
         if (c->profile_frames ? (k >= 1 && k <= 3) : k == 5) return;      // frame mode: the three passes share the frame's span
         a = get(c);
         b = get(c);
-        (void)hipEventRecord(a, c->stream);
+        (void)hipEventRecord(a, stream);
     }
     ~Prof() {
         if (!c->profiling || !a) return;
-        (void)hipEventRecord(b, c->stream);
+        (void)hipEventRecord(b, stream);
         c->spans.push_back({cls, a, b});
     }
 };

@@ -9,14 +9,14 @@
 
 namespace mh {
 
-int device_sort_pairs_u32(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in,
+int device_sort_pairs_u32(hipStream_t stream, DevBuf &tmp, const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in,
                           uint32_t *vals_out, size_t n, int end_bit) {
     if (n == 0) return 0;
     if (n >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "device sort: %zu items", n);
     size_t bytes = 0;
-    MH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, c->stream));
+    MH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, stream));
     MH_TRY(tmp.reserve(bytes ? bytes : 8));
-    MH_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, c->stream));
+    MH_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, bytes, keys_in, keys_out, vals_in, vals_out, (int)n, 0, end_bit, stream));
     return 0;
 }
 

@@ -606,7 +606,7 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
         hipLaunchKernelGGL(sasa_grid_kernel, dim3(1), dim3(1), 0, c->stream, Z.bounds.as<uint32_t>(), cap, Z.gridp.as<GridP>());
         hipLaunchKernelGGL(sasa_assign_kernel<Real>, dim3(nb256), dim3(256), 0, c->stream, S, Z.gridp.as<GridP>(), cap, Z.key_in.as<uint32_t>(),
                            Z.val_in.as<uint32_t>(), Z.cell_count.as<uint32_t>(), Z.err.as<uint32_t>());
-        MH_TRY(device_sort_pairs_u32(c, Z.cub_tmp, Z.key_in.as<uint32_t>(), Z.key_out.as<uint32_t>(), Z.val_in.as<uint32_t>(), Z.val_out.as<uint32_t>(), ns,
+        MH_TRY(device_sort_pairs_u32(c->stream, Z.cub_tmp, Z.key_in.as<uint32_t>(), Z.key_out.as<uint32_t>(), Z.val_in.as<uint32_t>(), Z.val_out.as<uint32_t>(), ns,
                                      end_bit));
         MH_TRY(device_exclusive_sum_u32(c, Z.cub_tmp, Z.cell_count.as<uint32_t>(), Z.cell_start.as<uint32_t>(), (size_t)cap + 2));
         hipLaunchKernelGGL(sasa_gather_kernel<Real>, dim3(nb256), dim3(256), 0, c->stream, S, cap, Z.key_out.as<uint32_t>(), Z.val_out.as<uint32_t>(),

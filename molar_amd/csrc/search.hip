@@ -660,14 +660,14 @@ __global__ void __launch_bounds__(256) scan_lookback_kernel(const TIn1 *in1, TOu
     }
 }
 
-// state words needed by scan_lookback for n elements (sized for the one-wave tiles of the side stream)
+// state words needed by scan_lookback for n elements (sized for tiles of one wave, four times what its tiles of 256 threads use)
 inline size_t lookback_state_words(uint64_t n) { return 1 + 2 * (size_t)((n + 64 * SCAN_ITEMS - 1) / (64 * SCAN_ITEMS)); }
 
 template <class TIn1, class TOut1, class TIn2, class TOut2>
 int scan_lookback(molar_hip_ctx *c, const TIn1 *in1, TOut1 *out1, const TIn2 *in2, TOut2 *out2, uint64_t n,
                   unsigned long long *zeroed_state) {
     if (n == 0) return 0;
-    const uint32_t block = c->on_side ? 64u : 256u;           // one-wave workgroups on the side stream (place_order_kernel)
+    const uint32_t block = 256u;
     const uint32_t ntiles = (uint32_t)((n + block * SCAN_ITEMS - 1) / (block * SCAN_ITEMS));
     hipLaunchKernelGGL((scan_lookback_kernel<TIn1, TOut1, TIn2, TOut2>), dim3(ntiles), dim3(block), 0, c->stream, in1, out1, in2, out2, n,
                        zeroed_state, ntiles);
@@ -1029,24 +1029,36 @@ __global__ void __launch_bounds__(64) scan_frames_kernel(const GridFrame *__rest
     }
 }
 
+// WHERE a grid is built and a scan runs: the stream, the scratch that belongs to that stream (the two streams may scan and sort at
+// the same time; the buffers outlast requests and stay in the context) and the launch shape that goes with it.  Handed down by
+// value like SearchCall (below): a helper launches on the lane it is given, and `c->stream` always is the main stream.
+struct GridLane {
+    hipStream_t stream;
+    mh::DevBuf &scan_tmp;      // block sums of exclusive_scan
+    mh::DevBuf &sort_tmp;      // scratch of the device sort (devsort.hip)
+    bool side_shape;           // the side stream's launch shape: one-wave workgroups (they get wave slots beside the pair kernels of the
+                               // frame in flight, place_order_kernel), scan_small_wave_kernel, privatised binning where it pays (build_grid)
+};
+static GridLane main_lane(molar_hip_ctx *c) { return {c->stream, c->scan_tmp, c->sort_tmp, false}; }
+static GridLane side_lane(molar_hip_ctx *c) { return {c->side_stream, c->scan_tmp_side, c->sort_tmp_side, true}; }
+
 template <class TIn, class TOut>
-int exclusive_scan(molar_hip_ctx *c, const TIn *in, TOut *out, uint64_t n) {
+int exclusive_scan(const GridLane &lane, const TIn *in, TOut *out, uint64_t n) {
     if (n == 0) return 0;
     if (n <= 8192ull) {
-        if (c->on_side) hipLaunchKernelGGL((scan_small_wave_kernel<TIn, TOut>), dim3(1), dim3(64), 0, c->stream, in, out, (uint32_t)n);
+        if (lane.side_shape) hipLaunchKernelGGL((scan_small_wave_kernel<TIn, TOut>), dim3(1), dim3(64), 0, lane.stream, in, out, (uint32_t)n);
         else
-        hipLaunchKernelGGL((scan_small_kernel<TIn, TOut>), dim3(1), dim3(256), 0, c->stream, in, out, (uint32_t)n);
+        hipLaunchKernelGGL((scan_small_kernel<TIn, TOut>), dim3(1), dim3(256), 0, lane.stream, in, out, (uint32_t)n);
         MH_HIP(hipGetLastError());
         return 0;
     }
     const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    mh::DevBuf &tmp = c->on_side ? c->scan_tmp_side : c->scan_tmp;   // the two streams may scan at the same time
-    MH_TRY(tmp.reserve(nb * sizeof(TOut)));
-    TOut *sums = tmp.as<TOut>();
-    hipLaunchKernelGGL((scan_tile_kernel<TIn, TOut>), dim3((unsigned)nb), dim3(256), 0, c->stream, in, out, sums, n);
+    MH_TRY(lane.scan_tmp.reserve(nb * sizeof(TOut)));
+    TOut *sums = lane.scan_tmp.as<TOut>();
+    hipLaunchKernelGGL((scan_tile_kernel<TIn, TOut>), dim3((unsigned)nb), dim3(256), 0, lane.stream, in, out, sums, n);
     if (nb > 1) {
-        hipLaunchKernelGGL((scan_sums_kernel<TOut>), dim3(1), dim3(256), 0, c->stream, sums, nb);
-        hipLaunchKernelGGL((scan_add_kernel<TOut>), dim3((unsigned)nb), dim3(256), 0, c->stream, out, sums, n);
+        hipLaunchKernelGGL((scan_sums_kernel<TOut>), dim3(1), dim3(256), 0, lane.stream, sums, nb);
+        hipLaunchKernelGGL((scan_add_kernel<TOut>), dim3((unsigned)nb), dim3(256), 0, lane.stream, out, sums, n);
     }
     MH_HIP(hipGetLastError());
     return 0;
@@ -1121,7 +1133,7 @@ int scan_slot_counts(molar_hip_ctx *c, SearchSizes *sizes_host) {
         MH_HIP(hipGetLastError());
         return 0;
     }
-    MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->slot_cnt.as<uint32_t>(), c->slot_base.as<unsigned long long>(), n)));
+    MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->slot_cnt.as<uint32_t>(), c->slot_base.as<unsigned long long>(), n)));
     if (sizes_host)
         MH_HIP(hipMemcpyAsync(&sizes_host->total, c->slot_base.as<unsigned long long>() + cur.nslots_bound, 8, hipMemcpyDefault, c->stream));
     return 0;
@@ -1250,6 +1262,8 @@ static void occ_note(molar_hip_ctx *c, unsigned long long key, const SearchSizes
 
 // What ONE request asks of the helpers below (prepare_search, build_grid, the plan, launch_pairs), beyond its descriptor.  It
 // lives on the caller's stack and goes down the call chain by reference; the context holds only what outlasts a request.
+// `side` is a wish: prepare_search decides (takes_side_lane) and hands the grid build the lane it chose (GridLane, above) - the
+// stream is an argument of the helpers that launch a grid, not a field they find swapped.
 struct SearchCall {
     bool plan = true;              // prepare_search enqueues the plan (false: the caller walks cells, or plans inside launch_pairs)
     bool within_set = false;       // the request is molar_hip_within_count's: its first set's grid may be held (molar_hip_within_hold)
@@ -1263,25 +1277,6 @@ struct SearchCall {
     uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
     bool live_rows = true;         // the slots go to the count / fill passes, which walk live-ranked slots where live_row_slots() says so
                                    // (false: another kernel reads the records - the contact kernels - and wants consecutive rows)
-};
-
-// launches go to the side stream while one of these lives (c->stream and c->on_side move together)
-struct OnSideStream {
-    // restores a field of the context on every exit from the scope
-    template <class T>
-    struct Restore {
-        T &ref;
-        const T old;
-        explicit Restore(T &r) : ref(r), old(r) {}
-        ~Restore() { ref = old; }
-        Restore(const Restore &) = delete;
-    };
-    Restore<hipStream_t> stream;
-    Restore<bool> on_side;
-    explicit OnSideStream(molar_hip_ctx *c) : stream(c->stream), on_side(c->on_side) {
-        c->stream = c->side_stream;
-        c->on_side = true;
-    }
 };
 
 // the side stream (highest priority) and the event its grid builds end with, created on first use
@@ -1334,8 +1329,8 @@ static int grid_reserve(GridSet &S, uint32_t ncells) {
     return 0;
 }
 
-int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_local) {
-    Prof prof(c, 0);
+int build_grid(molar_hip_ctx *c, const SearchCall &call, const GridLane &lane, GridSet &S, int ids_local) {
+    Prof prof(c, 0, lane.stream);
     const SearchShape &cur = c->cur;
     const uint32_t ncells = (uint32_t)grid_cells(cur);
     const BinParams P = grid_bin_params(cur, S, call.drop_nonfinite);
@@ -1345,57 +1340,57 @@ int build_grid(molar_hip_ctx *c, const SearchCall &call, GridSet &S, int ids_loc
     {
         const size_t nz = (size_t)ncells + 1 + npad;
         // workgroup size: one wave on the side stream (see place_order_kernel), four otherwise
-        const unsigned bs = c->on_side ? 64u : 256u;
+        const unsigned bs = lane.side_shape ? 64u : 256u;
         const unsigned zb = (unsigned)std::min<size_t>((nz + bs - 1) / bs, 2048u * (256u / bs));
-        hipLaunchKernelGGL(zero2_kernel, dim3(zb), dim3(bs), 0, c->stream, S.cell_count.as<uint32_t>(), (size_t)ncells + 1 + OCC_WORDS,
+        hipLaunchKernelGGL(zero2_kernel, dim3(zb), dim3(bs), 0, lane.stream, S.cell_count.as<uint32_t>(), (size_t)ncells + 1 + OCC_WORDS,
                            S.cnt_pad.as<uint32_t>(), npad);
     }
     if (S.n) {
-        const unsigned bs = c->on_side ? 64u : 256u;
+        const unsigned bs = lane.side_shape ? 64u : 256u;
         const unsigned nb = (S.n + bs - 1u) / bs;
         uint32_t *counters = pad_shift ? S.cnt_pad.as<uint32_t>() : S.cell_count.as<uint32_t>();
         // (on the side stream, beside the pair kernels of the frame in flight: there the privatised form wins - 692-695 against
         // 699-706 frames/s in three alternations; alone it is 10 us SLOWER on the 1M-atom frame - 123 workgroups - so searches
         // that build their grid on the main stream keep one atomic per atom)
-        const bool tile_ok = !c->env_no_bin_tile && c->on_side && ncells <= BIN_TILE_MAX_CELLS && (uint64_t)S.n >= 16ull * ncells;
+        const bool tile_ok = !c->env_no_bin_tile && lane.side_shape && ncells <= BIN_TILE_MAX_CELLS && (uint64_t)S.n >= 16ull * ncells;
         // (tiles of 8192 atoms for the 1M-atom frame; at 250k atoms 31 of those are too few - the grid's span grew from 0.12 to
         // 0.35 ms - so smaller frames take tiles of 2048)
         if (tile_ok && S.n >= (1u << 19))
-            hipLaunchKernelGGL(bin_tile_kernel<32>, dim3((S.n + 256u * 32u - 1u) / (256u * 32u)), dim3(256), (size_t)ncells * 4, c->stream,
+            hipLaunchKernelGGL(bin_tile_kernel<32>, dim3((S.n + 256u * 32u - 1u) / (256u * 32u)), dim3(256), (size_t)ncells * 4, lane.stream,
                                P, S.key.as<uint32_t>(), S.cursor.as<uint32_t>(), counters, pad_shift, ncells);
         else if (tile_ok && S.n >= (1u << 17))
-            hipLaunchKernelGGL(bin_tile_kernel<8>, dim3((S.n + 256u * 8u - 1u) / (256u * 8u)), dim3(256), (size_t)ncells * 4, c->stream,
+            hipLaunchKernelGGL(bin_tile_kernel<8>, dim3((S.n + 256u * 8u - 1u) / (256u * 8u)), dim3(256), (size_t)ncells * 4, lane.stream,
                                P, S.key.as<uint32_t>(), S.cursor.as<uint32_t>(), counters, pad_shift, ncells);
         else
-        hipLaunchKernelGGL(bin_kernel, dim3(nb), dim3(bs), 0, c->stream, P, S.key.as<uint32_t>(),
+        hipLaunchKernelGGL(bin_kernel, dim3(nb), dim3(bs), 0, lane.stream, P, S.key.as<uint32_t>(),
                            S.cursor.as<uint32_t>(), counters, pad_shift);
         if (pad_shift)
-            hipLaunchKernelGGL(unpad_kernel, dim3((ncells + bs - 1u) / bs), dim3(bs), 0, c->stream, ncells, counters, pad_shift,
+            hipLaunchKernelGGL(unpad_kernel, dim3((ncells + bs - 1u) / bs), dim3(bs), 0, lane.stream, ncells, counters, pad_shift,
                                S.cell_count.as<uint32_t>());
-        MH_TRY((exclusive_scan<uint32_t, uint32_t>(c, S.cell_count.as<uint32_t>(), S.cell_count.as<uint32_t>(),
+        MH_TRY((exclusive_scan<uint32_t, uint32_t>(lane, S.cell_count.as<uint32_t>(), S.cell_count.as<uint32_t>(),
                                                    (uint64_t)ncells + 1)));
         // cells of more than 384 atoms on average: the order comes from a stable sort (sort_prep_kernel)
         const bool by_sort = sorted_by_device_sort(S.n, ncells);
         if (by_sort) {
             MH_TRY(S.sort_buf.reserve((size_t)S.n * 16));
             uint32_t *k_in = S.sort_buf.as<uint32_t>(), *v_in = k_in + S.n, *k_out = v_in + S.n, *v_out = k_out + S.n;
-            hipLaunchKernelGGL(sort_prep_kernel, dim3((S.n + 255u) / 256u), dim3(256), 0, c->stream, S.n, ncells, S.key.as<uint32_t>(), k_in, v_in);
+            hipLaunchKernelGGL(sort_prep_kernel, dim3((S.n + 255u) / 256u), dim3(256), 0, lane.stream, S.n, ncells, S.key.as<uint32_t>(), k_in, v_in);
             int end_bit = 1;
             while (end_bit < 32 && (2ull * ncells) >> end_bit) ++end_bit;
-            MH_TRY(device_sort_pairs_u32(c, c->on_side ? c->sort_tmp_side : c->sort_tmp, k_in, k_out, v_in, v_out, S.n, end_bit));
-            hipLaunchKernelGGL(sort_tmpkey_kernel, dim3((S.n + 255u) / 256u), dim3(256), 0, c->stream, S.n, ncells, k_out, v_out, S.tmp_key.as<uint32_t>());
+            MH_TRY(device_sort_pairs_u32(lane.stream, lane.sort_tmp, k_in, k_out, v_in, v_out, S.n, end_bit));
+            hipLaunchKernelGGL(sort_tmpkey_kernel, dim3((S.n + 255u) / 256u), dim3(256), 0, lane.stream, S.n, ncells, k_out, v_out, S.tmp_key.as<uint32_t>());
         } else
-        hipLaunchKernelGGL(scatter_kernel, dim3(nb), dim3(bs), 0, c->stream, S.n, S.key.as<uint32_t>(),
+        hipLaunchKernelGGL(scatter_kernel, dim3(nb), dim3(bs), 0, lane.stream, S.n, S.key.as<uint32_t>(),
                            S.cell_count.as<uint32_t>(), S.cursor.as<uint32_t>(), S.tmp_key.as<uint32_t>());
         // (the spatial order serves the regular count pass and the fused histogram; pair_small.hip reads the placed records only)
         const int want_order = (fixed_cutoff_kind(cur.kind) && (call.hist_plan || small_cell_lanes(cur) == 0)) ? 1 : 0;
         if (!want_order && !by_sort && (uint64_t)S.n < 16ull * ncells)
-            hipLaunchKernelGGL(place_small_kernel, dim3((unsigned)(((uint64_t)ncells * 16u + bs - 1u) / bs)), dim3(bs), 0, c->stream, P, ncells,
+            hipLaunchKernelGGL(place_small_kernel, dim3((unsigned)(((uint64_t)ncells * 16u + bs - 1u) / bs)), dim3(bs), 0, lane.stream, P, ncells,
                                ids_local, S.cell_count.as<uint32_t>(), S.tmp_key.as<uint32_t>(), S.d_vdw, S.sorted.as<float4>(),
                                S.d_vdw ? S.sorted_vdw.as<float>() : nullptr, S.aabb.as<float4>(), S.cell_org.as<float4>(),
                                S.cell_count.as<uint32_t>() + ncells + 1);
         else
-        hipLaunchKernelGGL(place_order_kernel, dim3(ncells), dim3(64), 0, c->stream, P, ncells, ids_local,
+        hipLaunchKernelGGL(place_order_kernel, dim3(ncells), dim3(64), 0, lane.stream, P, ncells, ids_local,
                            S.cell_count.as<uint32_t>(), S.tmp_key.as<uint32_t>(), S.d_vdw, S.sorted.as<float4>(),
                            S.d_vdw ? S.sorted_vdw.as<float>() : nullptr, S.aabb.as<float4>(), S.perm.as<float4>(),
                            S.chunk_aabb.as<float4>(), S.h16.as<uint4>(), S.cell_org.as<float4>(), want_order, by_sort ? 1 : 0,
@@ -1684,12 +1679,12 @@ int device_fmax2(molar_hip_ctx *c, const float *d_v1, uint32_t n1, const float *
 int enqueue_plan_slots(molar_hip_ctx *c, SearchSizes *sizes_dev) {
     const SearchShape &cur = c->cur;
     const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
-    const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
+    const unsigned pbs = 256u;
     if (cur.ntasks + 1 > (1ull << 18)) {
         // sparse giant plans (a vdW search of 1M atoms: 4e6 entries): the single-pass scan's chain of tiles - each waits for the
         // one before it - took 0.3 ms there; three launches of the tile scan do not chain (in place: a thread reads its items first)
-        MH_TRY((exclusive_scan<uint32_t, uint32_t>(c, c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), cur.ntasks + 1)));
-        if (fast_kind) MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->task_mu.as<uint32_t>(), c->task_moff.as<unsigned long long>(), cur.ntasks + 1)));
+        MH_TRY((exclusive_scan<uint32_t, uint32_t>(main_lane(c), c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), cur.ntasks + 1)));
+        if (fast_kind) MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->task_mu.as<uint32_t>(), c->task_moff.as<unsigned long long>(), cur.ntasks + 1)));
     } else
     MH_TRY((scan_lookback<uint32_t, uint32_t, uint32_t, unsigned long long>(
         c, c->task_nb.as<uint32_t>(), c->task_nb.as<uint32_t>(), fast_kind ? c->task_mu.as<uint32_t>() : nullptr,
@@ -1727,13 +1722,12 @@ int size_plan(molar_hip_ctx *c) {
     return 0;
 }
 
-int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: null argument");
-    if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
-    MH_HIP(hipSetDevice(c->device));
-    c->have_search = false;
-    c->slot_stat_valid = false;        // until a plan of this search leaves its slot counts (enqueue_plan)
-    c->plan_live = false;
+// ---- prepare_search, step by step
+// Describe the request in c->cur: box, the staged sets, cutoff (the vdW maximum included), bounds, grid dimensions, the occupancy
+// hint, plan and slot bounds.  *degenerate: an empty vdW input - nothing is to be enqueued, the result is empty.  *reuse0: the
+// first set's staged coordinates and grid are the held ones (molar_hip_within_hold).  *to_hold: the record of the grid this
+// request is about to build for its first set, where later `within` requests may reuse it (valid = false: they may not).
+int describe_request(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call, bool *degenerate, bool *reuse0, HeldGrid *to_hold) {
     SearchShape &cur = c->cur;
     cur.kind = q->kind;
     const bool two = q->kind != MOLAR_HIP_SEARCH_SINGLE;
@@ -1744,28 +1738,12 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     // molar_hip_within_hold: consecutive `within` requests against the SAME first set (same pointers and sizes, same box, same
     // grid) reuse its staged coordinates and its grid; anything else that stages or bins set 0 ends the hold's validity
     const bool may_hold = c->within_hold && q->kind == MOLAR_HIP_SEARCH_WITHIN && call.within_set;
-    // A first set in HOST memory is staged, so the hold would serve a copy: a fingerprint of the caller's array (its two ends and
-    // 512 atoms spread over it) tells an array updated in place, or a new one that the allocator put at the old address, from the
-    // one that was staged.  Device memory is read in place by the grid build; there the caller's promise is all there is.
-    uint64_t fp = 0;
-    if (may_hold && q->xyz1 && q->natoms1 && !is_device_ptr(q->xyz1)) {
-        fp = 0xcbf29ce484222325ull;
-        auto mix = [&](size_t atom) {
-            uint32_t w[3];
-            std::memcpy(w, q->xyz1 + 3 * atom, 12);
-            for (int k = 0; k < 3; ++k) fp = (fp ^ w[k]) * 0x100000001b3ull;
-        };
-        const size_t n = q->natoms1, step = n > 512 ? n / 512 : 1;
-        for (size_t a = 0; a < n && a < 64; ++a) mix(a);
-        for (size_t a = 0; a < n; a += step) mix(a);
-        for (size_t a = n > 64 ? n - 64 : 0; a < n; ++a) mix(a);
-        fp |= 1ull;
-    }
-    bool reuse0 = may_hold && c->hold_valid && c->hold_fp == fp && c->hold_set == cur.set && c->hold_xyz == q->xyz1 && c->hold_natoms == q->natoms1 &&
-                  c->hold_idx == q->idx1 && c->hold_n == q->n1 && c->hold_ids_local == q->ids_local && c->hold_use_box == cur.use_box &&
-                  c->hold_pbc == cur.pbc && (!cur.use_box || std::memcmp(&c->hold_box, &cur.box, sizeof cur.box) == 0);
-    if (!reuse0) {
-        c->hold_valid = false;
+    // (host memory is fingerprinted - search_shape.hpp; device memory is read in place by the grid build: there the caller's
+    // promise is all there is)
+    const uint64_t fp = (may_hold && q->xyz1 && q->natoms1 && !is_device_ptr(q->xyz1)) ? held_fingerprint(q->xyz1, q->natoms1) : 0;
+    *reuse0 = may_hold && held_names_request(c->held, *q, cur, fp);
+    if (!*reuse0) {
+        c->held.valid = false;
         MH_TRY(stage_set(c, cur.set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
     }
     if (two) MH_TRY(stage_set(c, cur.set[1], q->xyz2, q->natoms2, q->idx2, q->n2, q->vdw2, vdw));
@@ -1778,7 +1756,7 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
             cur.dims[0] = cur.dims[1] = cur.dims[2] = 1;
             cur.ntasks = 0;
             c->total = 0;
-            c->have_search = true;
+            *degenerate = true;
             return 0;
         }
         float m1, m2;
@@ -1818,20 +1796,23 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
         for (int d = 0; d < 3; ++d) ext[d] = cur.upper[d] - cur.lower[d];   // from_cutoff_and_min_max :112-114
     }
     MH_TRY(dims_from_extents(cur, ext));
-    if (reuse0) {          // the same cells? (the cutoff and, without a box, the caller's bounds decide the grid)
-        bool same = c->hold_dims[0] == cur.dims[0] && c->hold_dims[1] == cur.dims[1] && c->hold_dims[2] == cur.dims[2];
-        for (int d = 0; d < 3 && !cur.use_box; ++d) same = same && c->hold_lower[d] == cur.lower[d] && c->hold_upper[d] == cur.upper[d];
-        if (!same) {
-            reuse0 = false;
-            c->hold_valid = false;
-            MH_TRY(stage_set(c, cur.set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
-        }
+    if (*reuse0 && !held_same_cells(c->held, cur)) {       // other cells: the first set is staged and binned again after all
+        *reuse0 = false;
+        c->held.valid = false;
+        MH_TRY(stage_set(c, cur.set[0], q->xyz1, q->natoms1, q->idx1, q->n1, q->vdw1, vdw));
     }
+    *to_hold = (may_hold && !*reuse0) ? held_remember(*q, cur, fp) : HeldGrid{};
     occ_latch(c);        // kind, set sizes and grid dimensions stand: what small_cell_lanes() answers for this search from here on
     cur.ntasks = plan_entries(cur);
     cur.nslots_bound = slots_bound(cur, call.hist_plan);
     if (cur.ntasks >= 0xFFFFFFF0ull || cur.nslots_bound >= 0xFFFFFFF0ull || cur.ntasks + cur.nslots_bound >= 0xFFFFFF00ull)
         return fail(MOLAR_HIP_ERR_TOO_LARGE, "search plan too large (%llu entries)", (unsigned long long)cur.ntasks);
+    return 0;
+}
+
+// the buffers of the plan of c->cur, sized by its bounds
+int reserve_plan(molar_hip_ctx *c, const SearchCall &call) {
+    const SearchShape &cur = c->cur;
     MH_TRY(c->task_nb.reserve((cur.ntasks + 1) * 4));
     MH_TRY(c->task_desc.reserve((cur.ntasks + 1) * sizeof(TaskDesc)));
     MH_TRY(c->slot_desc.reserve((cur.nslots_bound + 1) * sizeof(SlotDesc)));
@@ -1839,105 +1820,140 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     MH_TRY(c->slot_cnt.reserve((cur.nslots_bound + 1) * 4));
     MH_TRY(c->slot_base.reserve((cur.nslots_bound + 1) * 8));
     MH_TRY(c->params.reserve(sizeof(SearchParams)));
-    const size_t st_tasks = lookback_state_words(cur.ntasks + 1), st_slots = lookback_state_words(cur.nslots_bound + 1);
-    MH_TRY(c->scan_state.reserve((st_tasks + st_slots) * 8));
+    MH_TRY(c->scan_state.reserve((lookback_state_words(cur.ntasks + 1) + lookback_state_words(cur.nslots_bound + 1)) * 8));
     MH_TRY(c->task_mu.reserve((cur.ntasks + 1) * 4));
     MH_TRY(c->task_moff.reserve((cur.ntasks + 1) * 8));
-    const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
     MH_TRY(c->slot_stat.reserve(16));
-    // Live rows of the plan entries (live_rows_kernel): for the searches of live_row_slots() whose slot records go to the count / fill
-    // passes.  The masks belong to the grid generation and are computed at the end of its grid chain, on whichever stream that runs.
-    const bool use_live = call.plan && call.live_rows && !call.hist_plan && live_row_slots(cur);
-    auto enqueue_live_rows = [&]() -> int {
-        if (!use_live) return 0;
-        MH_TRY(cur.set[0].live.reserve(live_rows_bytes(cur)));
-        unsigned long long *masks = cur.set[0].live.as<unsigned long long>();
-        uint32_t *cnt = reinterpret_cast<uint32_t *>(masks + live_rows_mask_words(cur));
-        const SearchParams P = make_params(c, cur);          // the values plan_tiles_kernel sees (geometry, grids, wrap policy)
-        const dim3 grid = pair_grid((unsigned)cur.ntasks);
-        if (cur.kind == MOLAR_HIP_SEARCH_SINGLE) hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_SINGLE>), grid, dim3(64), 0, c->stream, P, masks, cnt);
-        else hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_DOUBLE>), grid, dim3(64), 0, c->stream, P, masks, cnt);
+    return 0;
+}
+
+// Live rows of the plan entries (live_rows_kernel): for the searches of live_row_slots() whose slot records go to the count / fill
+// passes.  The masks belong to the grid generation and are computed at the end of its grid chain, on whichever lane that runs.
+bool plans_live_rows(const SearchCall &call, const SearchShape &cur) { return call.plan && call.live_rows && !call.hist_plan && live_row_slots(cur); }
+
+int enqueue_live_rows(molar_hip_ctx *c, const SearchCall &call, const GridLane &lane) {
+    const SearchShape &cur = c->cur;
+    if (!plans_live_rows(call, cur)) return 0;
+    MH_TRY(cur.set[0].live.reserve(live_rows_bytes(cur)));
+    unsigned long long *masks = cur.set[0].live.as<unsigned long long>();
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(masks + live_rows_mask_words(cur));
+    const SearchParams P = make_params(c, cur);          // the values plan_tiles_kernel sees (geometry, grids, wrap policy)
+    const dim3 grid = pair_grid((unsigned)cur.ntasks);
+    if (cur.kind == MOLAR_HIP_SEARCH_SINGLE) hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_SINGLE>), grid, dim3(64), 0, lane.stream, P, masks, cnt);
+    else hipLaunchKernelGGL((live_rows_kernel<MOLAR_HIP_SEARCH_DOUBLE>), grid, dim3(64), 0, lane.stream, P, masks, cnt);
+    MH_HIP(hipGetLastError());
+    return 0;
+}
+
+// the grids of c->cur's sets (the first one unless it is held) and the live rows behind them, on one lane
+int build_grids(molar_hip_ctx *c, const SearchCall &call, const GridLane &lane, bool build0, int ids_local) {
+    SearchShape &cur = c->cur;
+    if (build0) MH_TRY(build_grid(c, call, lane, cur.set[0], ids_local));
+    if (cur.kind != MOLAR_HIP_SEARCH_SINGLE) MH_TRY(build_grid(c, call, lane, cur.set[1], ids_local));
+    return enqueue_live_rows(c, call, lane);
+}
+
+// The plan of c->cur on the main stream: plan entries, their slots and (fast kinds) hit-history units, one record per slot.
+int enqueue_plan(molar_hip_ctx *c, const SearchCall &call) {
+    Prof prof(c, 0);
+    const SearchShape &cur = c->cur;
+    const uint32_t fast_kind = records_hit_history(cur) ? 1u : 0u;
+    const bool use_live = plans_live_rows(call, cur);
+    SearchParams P = make_params(c, cur);
+    // Resident searches (no host round trip between plan and count: the hit-history buffer keeps its size): the plan
+    // kernel also writes the parameter block the count and fill passes read, output capacity included.
+    SearchParams *params_dst = nullptr;
+    c->params_fresh = false;
+    if (!call.size_masks) {
+        P.out_cap = call.out_cap;
+        params_dst = c->params.as<SearchParams>();
+        c->params_fresh = true;
+        c->params_fresh_cap = P.out_cap;
+    }
+    if (cur.ntasks + 1 <= FPLAN_MAX_TASKS) {
+        // a plan of at most 2^22 entries: plan and tile scan, then offsets and slot records - two launches (three above 2^18
+        // entries, plan_groups_kernel), no chain
+        const uint32_t ntiles = (uint32_t)((cur.ntasks + 1 + 255) / 256);
+        const uint32_t ngroups = ntiles > 1024u ? (ntiles + PLAN_GROUP - 1u) / PLAN_GROUP : 0u;
+        MH_TRY(c->fplan_tiles.reserve((size_t)ntiles * 16 + (cur.ntasks + 1) * 8 + (size_t)ngroups * 16));
+        unsigned long long *moff = fast_kind ? c->task_moff.as<unsigned long long>() : nullptr;
+        unsigned long long *tt = c->fplan_tiles.as<unsigned long long>();
+        unsigned long long *lmoff = tt + 2 * (size_t)ntiles;           // offsets inside the tiles: hit-history units ...
+        uint32_t *lfirst = c->task_mu.as<uint32_t>();                  // ... and slots
+        // live-row slots: the masks and counts live_rows_kernel left in this grid generation (behind the grid build)
+        const unsigned long long *live_masks = use_live ? cur.set[0].live.as<unsigned long long>() : nullptr;
+        const uint32_t *live_cnt = use_live ? reinterpret_cast<const uint32_t *>(live_masks + live_rows_mask_words(cur)) : nullptr;
+        if (cur.kind == MOLAR_HIP_SEARCH_SINGLE)
+            hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
+                               c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
+        else          // the three two-grid kinds decode tasks identically
+            hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
+                               c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
+        unsigned long long *gt = ngroups ? lmoff + (cur.ntasks + 1) : nullptr;
+        if (ngroups) hipLaunchKernelGGL(plan_groups_kernel, dim3(ngroups), dim3(64), 0, c->stream, ntiles, tt, gt);
+        hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, cur.ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
+                           c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), cur.nslots_bound, call.sizes_dev, gt,
+                           live_masks, c->slot_stat.as<unsigned long long>());
         MH_HIP(hipGetLastError());
+        c->slot_stat_valid = true;
+        c->plan_live = use_live;           // which instances of the pair kernels walk these records (launch_pairs)
         return 0;
-    };
-    auto enqueue_plan = [&]() -> int {
-        Prof prof(c, 0);
-        SearchParams P = make_params(c, cur);
-        // Resident searches (no host round trip between plan and count: the hit-history buffer keeps its size): the plan
-        // kernel also writes the parameter block the count and fill passes read, output capacity included.
-        SearchParams *params_dst = nullptr;
-        c->params_fresh = false;
-        if (!call.size_masks) {
-            P.out_cap = call.out_cap;
-            params_dst = c->params.as<SearchParams>();
-            c->params_fresh = true;
-            c->params_fresh_cap = P.out_cap;
-        }
-        if (!c->on_side && cur.ntasks + 1 <= FPLAN_MAX_TASKS) {
-            // main stream, a plan of at most 2^22 entries: plan and tile scan, then offsets and slot records - two launches (three
-            // above 2^18 entries, plan_groups_kernel), no chain
-            const uint32_t ntiles = (uint32_t)((cur.ntasks + 1 + 255) / 256);
-            const uint32_t ngroups = ntiles > 1024u ? (ntiles + PLAN_GROUP - 1u) / PLAN_GROUP : 0u;
-            MH_TRY(c->fplan_tiles.reserve((size_t)ntiles * 16 + (cur.ntasks + 1) * 8 + (size_t)ngroups * 16));
-            unsigned long long *moff = fast_kind ? c->task_moff.as<unsigned long long>() : nullptr;
-            unsigned long long *tt = c->fplan_tiles.as<unsigned long long>();
-            unsigned long long *lmoff = tt + 2 * (size_t)ntiles;           // offsets inside the tiles: hit-history units ...
-            uint32_t *lfirst = c->task_mu.as<uint32_t>();                  // ... and slots
-            // live-row slots: the masks and counts live_rows_kernel left in this grid generation (behind the grid build, below)
-            const unsigned long long *live_masks = use_live ? cur.set[0].live.as<unsigned long long>() : nullptr;
-            const uint32_t *live_cnt = use_live ? reinterpret_cast<const uint32_t *>(live_masks + live_rows_mask_words(cur)) : nullptr;
-            if (cur.kind == MOLAR_HIP_SEARCH_SINGLE)
-                hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
-            else          // the three two-grid kinds decode tasks identically
-                hipLaunchKernelGGL((plan_tiles_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(ntiles), dim3(256), 0, c->stream, P, lfirst,
-                                   c->task_desc.as<TaskDesc>(), lmoff, fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1, tt, params_dst, live_cnt);
-            unsigned long long *gt = ngroups ? lmoff + (cur.ntasks + 1) : nullptr;
-            if (ngroups) hipLaunchKernelGGL(plan_groups_kernel, dim3(ngroups), dim3(64), 0, c->stream, ntiles, tt, gt);
-            hipLaunchKernelGGL(plan_slots_kernel, dim3(ntiles * (256u / PLAN_SUB)), dim3(256), 0, c->stream, cur.ntasks, ntiles, lfirst, lmoff, c->task_nb.as<uint32_t>(),
-                               c->task_desc.as<TaskDesc>(), moff, tt, c->slot_desc.as<SlotDesc>(), cur.nslots_bound, call.sizes_dev, gt,
-                               live_masks, c->slot_stat.as<unsigned long long>());
-            MH_HIP(hipGetLastError());
-            c->slot_stat_valid = true;
-            c->plan_live = use_live;           // which instances of the pair kernels walk these records (launch_pairs)
-            return 0;
-        }
-        // ntasks + 1 threads (the last one writes the scan terminators); the same grid zeroes the slot counters and the
-        // descriptors of the two look-back scans of this search
-        const uint64_t nplan = std::max<uint64_t>(std::max<uint64_t>(cur.ntasks + 1, cur.nslots_bound + 1), st_tasks + st_slots);
-        const unsigned pbs = c->on_side ? 64u : 256u;          // one-wave workgroups on the side stream (place_order_kernel)
-        const unsigned nb = (unsigned)((nplan + pbs - 1) / pbs);
-        switch (cur.kind) {
-            case MOLAR_HIP_SEARCH_SINGLE:
-                hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
-                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
-                                   c->scan_state.as<unsigned long long>(), (uint64_t)(st_tasks + st_slots), params_dst);
-                break;
-            default:   // the three two-grid kinds decode tasks identically
-                hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
-                                   c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
-                                   c->scan_state.as<unsigned long long>(), (uint64_t)(st_tasks + st_slots), params_dst);
-                break;
-        }
-        MH_HIP(hipGetLastError());
-        return enqueue_plan_slots(c, call.sizes_dev);
-    };
-    // Pipelined search on a context that owns its stream, inputs already in device memory: the grid build goes to the
-    // side stream.  It touches only this generation's GridSet (last read by the search two frames back, which has been
-    // ended) and its own scan scratch, so it needs to wait for nothing and overlaps the pair kernels of the frame in
-    // front of it; the plan and the pair kernels of THIS search wait for it on the main stream.
-    const bool side = call.side && c->own_stream && cur.use_box && !vdw && cur.set[0].d_xyz == q->xyz1 &&
-                      cur.set[0].d_idx == q->idx1 && (!two || (cur.set[1].d_xyz == q->xyz2 && cur.set[1].d_idx == q->idx2));
-    if (side) {
+    }
+    // ntasks + 1 threads (the last one writes the scan terminators); the same grid zeroes the slot counters and the
+    // descriptors of the two look-back scans of this search
+    const uint64_t nstate = lookback_state_words(cur.ntasks + 1) + lookback_state_words(cur.nslots_bound + 1);
+    const uint64_t nplan = std::max<uint64_t>(std::max<uint64_t>(cur.ntasks + 1, cur.nslots_bound + 1), nstate);
+    const unsigned pbs = 256u;
+    const unsigned nb = (unsigned)((nplan + pbs - 1) / pbs);
+    switch (cur.kind) {
+        case MOLAR_HIP_SEARCH_SINGLE:
+            hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_SINGLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
+                               c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
+                               c->scan_state.as<unsigned long long>(), nstate, params_dst);
+            break;
+        default:   // the three two-grid kinds decode tasks identically
+            hipLaunchKernelGGL((plan_kernel<MOLAR_HIP_SEARCH_DOUBLE>), dim3(nb), dim3(pbs), 0, c->stream, P, c->task_nb.as<uint32_t>(), c->task_desc.as<TaskDesc>(),
+                               c->task_mu.as<uint32_t>(), fast_kind, c->slot_cnt.as<uint32_t>(), cur.nslots_bound + 1,
+                               c->scan_state.as<unsigned long long>(), nstate, params_dst);
+            break;
+    }
+    MH_HIP(hipGetLastError());
+    return enqueue_plan_slots(c, call.sizes_dev);
+}
+
+// Pipelined search on a context that owns its stream, inputs already in device memory: the grid build goes to the
+// side stream.  It touches only this generation's GridSet (last read by the search two frames back, which has been
+// ended) and its own scan and sort scratch, so it needs to wait for nothing and overlaps the pair kernels of the frame in
+// front of it; the plan and the pair kernels of THIS search wait for it on the main stream.
+bool takes_side_lane(const molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call) {
+    const SearchShape &cur = c->cur;
+    const bool two = q->kind != MOLAR_HIP_SEARCH_SINGLE;
+    return call.side && c->own_stream && cur.use_box && q->kind != MOLAR_HIP_SEARCH_DOUBLE_VDW && cur.set[0].d_xyz == q->xyz1 &&
+           cur.set[0].d_idx == q->idx1 && (!two || (cur.set[1].d_xyz == q->xyz2 && cur.set[1].d_idx == q->idx2));
+}
+
+// Everything of a search up to its pair passes: the request described in c->cur, the grids built, the plan enqueued.
+// *degenerate: the request came to nothing (empty vdW input) - nothing was enqueued, c->cur says one cell and no plan entries,
+// c->total is 0; what that means for the context's cached search is the caller's to say.
+int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call, bool *degenerate) {
+    *degenerate = false;
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: null argument");
+    if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
+    MH_HIP(hipSetDevice(c->device));
+    c->have_search = false;
+    c->slot_stat_valid = false;        // until a plan of this search leaves its slot counts (enqueue_plan)
+    c->plan_live = false;
+    bool reuse0 = false;
+    HeldGrid to_hold;
+    MH_TRY(describe_request(c, q, call, degenerate, &reuse0, &to_hold));
+    if (*degenerate) return 0;
+    MH_TRY(reserve_plan(c, call));
+    const int ids_local = q->ids_local || q->kind == MOLAR_HIP_SEARCH_DOUBLE_VDW;
+    if (takes_side_lane(c, q, call)) {
         MH_TRY(ensure_side_stream(c));
         if (call.side_wait) MH_HIP(hipStreamWaitEvent(c->side_stream, call.side_wait, 0));
-        {
-            OnSideStream on_side(c);
-            if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
-            if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
-            MH_TRY(enqueue_live_rows());
-            MH_HIP(hipEventRecord(c->grid_done, c->side_stream));
-        }
+        MH_TRY(build_grids(c, call, side_lane(c), !reuse0, ids_local));
+        MH_HIP(hipEventRecord(c->grid_done, c->side_stream));
         // The plan and the pair kernels of this search need the grid.  A wait command on the main stream costs that stream
         // ~25 us in front of the plan kernel even when the grid has long been finished (cross-queue barrier packet); the
         // host waiting for the side stream instead costs nothing there: the frame in flight still has its fill pass
@@ -1945,24 +1961,14 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
         if (c->env_host_grid_wait) MH_HIP(hipEventSynchronize(c->grid_done));
         else MH_HIP(hipStreamWaitEvent(c->stream, c->grid_done, 0));
     } else {
-        if (!reuse0) MH_TRY(build_grid(c, call, cur.set[0], q->ids_local || vdw));
-        if (two) MH_TRY(build_grid(c, call, cur.set[1], q->ids_local || vdw));
-        MH_TRY(enqueue_live_rows());
+        MH_TRY(build_grids(c, call, main_lane(c), !reuse0, ids_local));
     }
-    if (may_hold && !reuse0) {        // this grid of set 0 is the one later `within` requests may reuse
-        c->hold_valid = true;
-        c->hold_fp = fp;
-        c->hold_set = cur.set;
-        c->hold_xyz = q->xyz1; c->hold_natoms = q->natoms1; c->hold_idx = q->idx1; c->hold_n = q->n1;
-        c->hold_ids_local = q->ids_local; c->hold_use_box = cur.use_box; c->hold_pbc = cur.pbc; c->hold_box = cur.box;
-        for (int d = 0; d < 3; ++d) { c->hold_dims[d] = cur.dims[d]; c->hold_lower[d] = cur.lower[d]; c->hold_upper[d] = cur.upper[d]; }
-    }
-
+    if (to_hold.valid) c->held = to_hold;        // this grid of set 0 is the one later `within` requests may reuse
     // (Round 4: the plan kernels - 32 us of small launches - on the side stream behind the grid, with a second generation
     // of their buffers, one-wave workgroups: bit-identical, not faster; the fill pass of the frame in flight is stretched by
     // more than the main stream gains, 1.03 -> 1.06-1.12 ms.  Whatever shares the chip with the fill pass costs it at least
-    // its own stand-alone duration.)
-    if (call.plan) MH_TRY(enqueue_plan());
+    // its own stand-alone duration.  The plan therefore always runs on the main stream, in workgroups of 256.)
+    if (call.plan) MH_TRY(enqueue_plan(c, call));
     // hit-history buffer of the count -> fill pair: sized exactly (one small read-back; the fused histogram
     // mode does not use it, but sizing it here keeps a later count/fill on the same cached search valid)
     c->mask_units = 0;
@@ -2206,8 +2212,10 @@ extern "C" {
 
 int molar_hip_search_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uint64_t *out_count) {
     SearchCall call;
-    MH_TRY(prepare_search(c, q, call));
-    if (c->have_search) {   // degenerate (empty vdw input)
+    bool degenerate;
+    MH_TRY(prepare_search(c, q, call, &degenerate));
+    if (degenerate) {       // empty vdw input: a finished count of 0 - the fill calls return nothing, the grid is one cell
+        c->have_search = true;
         if (out_count) *out_count = 0;
         return MOLAR_HIP_OK;
     }
@@ -2332,11 +2340,15 @@ static int resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, mh
     call.size_masks = false;
     call.out_cap = cap0;
     call.sizes_dev = sizes_dev;
-    MH_TRY(prepare_search(c, q, call));
+    bool degenerate;
+    MH_TRY(prepare_search(c, q, call, &degenerate));
     ++c->search_serial;
     *L = ResidentLaunch{};
-    L->degenerate = c->have_search;
-    if (L->degenerate) return 0;
+    L->degenerate = degenerate;
+    if (degenerate) {    // empty vdw input: nothing to enqueue, and the host knows the sizes already - a cached search of 0 results
+        c->have_search = true;
+        return 0;
+    }
     const SearchShape &cur = c->cur;
     const bool fast_kind = records_hit_history(cur);
     L->maskcap0 = c->maskbuf.cap / 256u;
@@ -2697,9 +2709,13 @@ int molar_hip_search_histogram(molar_hip_ctx *c, const molar_hip_search_desc *q,
     call.hist_plan = q->kind == MOLAR_HIP_SEARCH_SINGLE || q->kind == MOLAR_HIP_SEARCH_DOUBLE;
     call.plan = !call.hist_plan;
     call.size_masks = false;                 // the fused pass records no hit bits
-    MH_TRY(prepare_search(c, q, call));
+    bool degenerate;
+    MH_TRY(prepare_search(c, q, call, &degenerate));
     if (out_count) *out_count = 0;
-    if (c->have_search) return MOLAR_HIP_OK;     // degenerate (empty vdw input)
+    if (degenerate) {       // empty vdw input: no pair, no distance - and, as after a count of 0, a cached search of 0 results
+        c->have_search = true;
+        return MOLAR_HIP_OK;
+    }
     // single pass: no counts, no offsets - every emitted distance goes straight into the histogram
     MH_TRY(ensure_hist_edges(c, hmin, hmax, nbins));
     if (async) {
@@ -2789,7 +2805,7 @@ static int hist_frames_group(molar_hip_ctx *c, const molar_hip_search_desc *q, s
     const uint32_t ncells = (uint32_t)ncells64;
     const uint32_t n[2] = {sizes[0].n, sizes[1].n};
     c->have_search = false;
-    c->hold_valid = false;
+    c->held.valid = false;
     group.ntasks = plan_entries(group);
     const uint64_t bound1 = slots_bound(group, /*hist_plan=*/true);          // slots of one frame
     const uint64_t bound = bound1 * (uint64_t)W;
@@ -3120,10 +3136,11 @@ int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
     SearchCall call;
     call.size_masks = false;
     call.live_rows = false;                 // contact_kernel walks consecutive rows
-    MH_TRY(prepare_search(s, &qq, call));      // (the plan kernel leaves the parameter block in s->params)
+    bool degenerate;
+    MH_TRY(prepare_search(s, &qq, call, &degenerate));      // (the plan kernel leaves the parameter block in s->params)
     s->params_fresh = false;
     const SearchShape &cur = s->cur;
-    if (cur.nslots_bound == 0) return 0;
+    if (degenerate || cur.nslots_bound == 0) return 0;      // (degenerate: never - empty sets have returned above)
     ContactArgs A{};
     A.g1 = K.g1;
     A.g2 = K.g2;
@@ -3207,7 +3224,8 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     call.plan = false;                            // no slots, no offsets: this path walks cells
     call.size_masks = false;
     call.within_set = true;
-    MH_TRY(prepare_search(c, q, call));
+    bool degenerate;                              // (never: a WITHIN request is no vdW request)
+    MH_TRY(prepare_search(c, q, call, &degenerate));
     c->have_search = false;                       // not a cached search for the fill calls of the stream form
     const SearchShape &cur = c->cur;
     const uint64_t nflags = q->ids_local ? cur.set[0].n : (q->idx1 ? q->natoms1 : cur.set[0].n);
@@ -3269,7 +3287,7 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
     hipLaunchKernelGGL(flag_tile_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, c->w_flags.as<uint8_t>(), nflags,
                        c->w_tile_cnt.as<uint32_t>());
     MH_HIP(hipGetLastError());
-    MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
+    MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
     unsigned long long tot = 0;
     MH_TRY(read_back(c, &tot, c->w_tile_off.as<unsigned long long>() + ntiles, 8));
     c->within_total = tot;
@@ -3286,7 +3304,7 @@ int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uin
 int molar_hip_within_hold(molar_hip_ctx *c, int on) {
     if (!c) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context");
     c->within_hold = on != 0;
-    if (!on) c->hold_valid = false;
+    if (!on) c->held.valid = false;
     return MOLAR_HIP_OK;
 }
 
@@ -3311,7 +3329,7 @@ int molar_hip_within_fill(molar_hip_ctx *c, uint64_t *ids) {
         MH_HIP(hipMemsetAsync(c->w_tile_cnt.p, 0, (ntiles + 1) * 4, c->stream));
         hipLaunchKernelGGL(flag_tile_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, c->w_flags.as<uint8_t>(), c->within_nflags,
                            c->w_tile_cnt.as<uint32_t>());
-        MH_TRY((exclusive_scan<uint32_t, unsigned long long>(c, c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
+        MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
     }
     if (!dev) {
         MH_TRY(c->wide_i.reserve((size_t)c->within_total * 8));
@@ -3356,7 +3374,7 @@ int molar_hip_search_connectivity(molar_hip_ctx *c, const molar_hip_search_desc 
         hipLaunchKernelGGL(conn_entries_kernel, dim3(nbP), dim3(256), 0, c->stream, pairs, (unsigned long long)npairs, row_in, nb_in);
         int end_bit = 1;
         while (end_bit < 32 && (nrows >> end_bit)) ++end_bit;
-        MH_TRY(device_sort_pairs_u32(c, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
+        MH_TRY(device_sort_pairs_u32(c->stream, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
         hipLaunchKernelGGL(conn_widen_kernel, dim3(nbE), dim3(256), 0, c->stream, nb_out, (unsigned long long)nent, c->conn_neigh.as<unsigned long long>());
     }
     hipLaunchKernelGGL(conn_offsets_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, c->stream, row_out, (unsigned long long)nent,

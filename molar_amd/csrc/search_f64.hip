@@ -981,7 +981,7 @@ static int build_grid64(molar_hip_ctx *c, molar_hip_search64_state &Z, const Set
                        Z.pos3.as<double>(), err_dev);
     int end_bit = 1;
     while (end_bit < 32 && (2ull * G.ncells) >> end_bit) ++end_bit;            // keys 0 .. 2 * ncells
-    MH_TRY(device_sort_pairs_u32(c, Z.cub_tmp, Z.key_in.as<uint32_t>(), Z.key_out.as<uint32_t>(), Z.val_in.as<uint32_t>(), Z.val_out.as<uint32_t>(),
+    MH_TRY(device_sort_pairs_u32(c->stream, Z.cub_tmp, Z.key_in.as<uint32_t>(), Z.key_out.as<uint32_t>(), Z.val_in.as<uint32_t>(), Z.val_out.as<uint32_t>(),
                                  n, end_bit));
     hipLaunchKernelGGL(gather64_kernel, dim3(nb), dim3(256), 0, c->stream, S, n, G.ncells, Z.key_out.as<uint32_t>(), Z.val_out.as<uint32_t>(),
                        Z.pos3.as<double>(), pos.as<double>(), id.as<unsigned long long>(), S.vdw ? vdw.as<double>() : nullptr);
@@ -1603,7 +1603,7 @@ int molar_hip_search_connectivity_f64(molar_hip_ctx *c, const molar_hip_search_d
                            Z.out_j.as<unsigned long long>(), (unsigned long long)npairs, row_in, nb_in);
         int end_bit = 1;
         while (end_bit < 32 && (nrows >> end_bit)) ++end_bit;
-        MH_TRY(device_sort_pairs_u32(c, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
+        MH_TRY(device_sort_pairs_u32(c->stream, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
         hipLaunchKernelGGL(conn_widen_kernel, dim3(nbE), dim3(256), 0, c->stream, nb_out, (unsigned long long)nent, c->conn_neigh.as<unsigned long long>());
     }
     hipLaunchKernelGGL(conn_offsets_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, c->stream, row_out, (unsigned long long)nent,

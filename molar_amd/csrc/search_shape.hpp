@@ -1,10 +1,11 @@
 // search_shape.hpp — what follows from the shape of a search alone (mh::SearchShape, common.hpp): grid dimensions, kernel
-// family, slot bound, the policy for wrapped pairs.  Host only and pure: no context, no HIP call (tests/cpp/test_search_shape.cpp
-// runs them without a device).
+// family, slot bound, the policy for wrapped pairs; and when a request may reuse the held grid of the `within` requests before
+// it (mh::HeldGrid).  Host only and pure: no context, no HIP call (tests/cpp/test_search_shape.cpp runs them without a device).
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 #include "common.hpp"
 
@@ -124,6 +125,54 @@ inline bool live_row_slots(const SearchShape &s) {
 // bytes of a generation's live-row buffer: the mask words of every entry, then the entries' live counts
 inline size_t live_rows_mask_words(const SearchShape &s) { return (size_t)plan_entries(s) * LIVE_ROW_GROUPS; }
 inline size_t live_rows_bytes(const SearchShape &s) { return live_rows_mask_words(s) * 8u + (size_t)plan_entries(s) * 4u; }
+
+// ---- the held grid of `within` requests (mh::HeldGrid, common.hpp; molar_hip_within_hold)
+// A first set in HOST memory is staged, so the hold would serve a copy: a fingerprint of the caller's array (its two ends and
+// 512 atoms spread over it - not every atom: the caller's promise covers the rest) tells an array updated in place, or a new one
+// that the allocator put at the old address, from the one that was staged.  Never 0, which stands for "device memory, read in place".
+inline uint64_t held_fingerprint(const float *xyz, size_t natoms) {
+    uint64_t fp = 0xcbf29ce484222325ull;
+    auto mix = [&](size_t atom) {
+        uint32_t w[3];
+        std::memcpy(w, xyz + 3 * atom, 12);
+        for (int k = 0; k < 3; ++k) fp = (fp ^ w[k]) * 0x100000001b3ull;
+    };
+    const size_t n = natoms, step = n > 512 ? n / 512 : 1;
+    for (size_t a = 0; a < n && a < 64; ++a) mix(a);
+    for (size_t a = 0; a < n; a += step) mix(a);
+    for (size_t a = n > 64 ? n - 64 : 0; a < n; ++a) mix(a);
+    return fp | 1ull;
+}
+
+// Does the request name the held first set?  Same grid generation, same pointers and sizes, same ids, same box and periodicity,
+// the same fingerprint (`s`: kind-independent part of the request's shape - set, use_box, pbc, box - as prepare_search has it
+// BEFORE staging: a request that passes keeps the staged coordinates).
+inline bool held_names_request(const HeldGrid &h, const molar_hip_search_desc &q, const SearchShape &s, uint64_t fp) {
+    return h.valid && h.fp == fp && h.set == s.set && h.xyz == q.xyz1 && h.natoms == q.natoms1 && h.idx == q.idx1 && h.n == q.n1 &&
+           h.ids_local == q.ids_local && h.use_box == s.use_box && h.pbc == s.pbc &&
+           (!s.use_box || std::memcmp(&h.box, &s.box, sizeof s.box) == 0);
+}
+
+// Does the search come to the same cells?  (The cutoff and, without a box, the caller's bounds decide the grid: asked once
+// dims_from_extents has run.)
+inline bool held_same_cells(const HeldGrid &h, const SearchShape &s) {
+    bool same = h.dims[0] == s.dims[0] && h.dims[1] == s.dims[1] && h.dims[2] == s.dims[2];
+    for (int d = 0; d < 3 && !s.use_box; ++d) same = same && h.lower[d] == s.lower[d] && h.upper[d] == s.upper[d];
+    return same;
+}
+
+// the record of the grid this request builds for its first set
+inline HeldGrid held_remember(const molar_hip_search_desc &q, const SearchShape &s, uint64_t fp) {
+    HeldGrid h;
+    h.valid = true;
+    h.set = s.set;
+    h.fp = fp;
+    h.xyz = q.xyz1; h.idx = q.idx1; h.natoms = q.natoms1; h.n = q.n1;
+    h.ids_local = q.ids_local;
+    h.use_box = s.use_box; h.pbc = s.pbc; h.box = s.box;
+    for (int d = 0; d < 3; ++d) { h.dims[d] = s.dims[d]; h.lower[d] = s.lower[d]; h.upper[d] = s.upper[d]; }
+    return h;
+}
 
 // How the pair kernels treat entries that wrap around the box (SearchParams carries these six under the same names).
 struct WrapPolicy {

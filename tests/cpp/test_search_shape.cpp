@@ -1,5 +1,5 @@
 // The functions of a search's shape (molar_amd/csrc/search_shape.hpp) on the host: grid dimensions, the policy for wrapped
-// pairs, the kernel family, the slot bound, the occupancy key.  No device is needed: boxes come from the library's
+// pairs, the kernel family, the slot bound, the occupancy key, the held grid of `within` requests.  No device is needed: boxes come from the library's
 // molar_hip_box_from_matrix, everything else is arithmetic.
 //
 // A wrong band or margin would change no search result - only which path wrapped pairs take - so the oracle suites cannot see
@@ -10,6 +10,7 @@
 // floats with %.9g).  Floats are compared bit for bit with the float nearest the printed value.
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../molar_amd/csrc/search_shape.hpp"
 
@@ -211,11 +212,119 @@ static void test_occ_key() {
     CHECK(single != 0 && single != key && occ_key_of(s) == single);        // SINGLE: the second set is not looked at
 }
 
+// ---- the held grid of `within` requests: the fingerprint of a host array, and what ends the reuse
+// Coordinates by a fixed integer recurrence (exact in f32: 24 bits times a power of two).
+static std::vector<float> recurrence(size_t natoms, uint32_t seed) {
+    std::vector<float> v(3 * natoms);
+    uint32_t x = seed;
+    for (float &f : v) {
+        x = x * 1664525u + 1013904223u;
+        f = (float)(x >> 8) * (8.0f / 16777216.0f);
+    }
+    return v;
+}
+
+// The expected values are RECORDED FROM COMMIT f7b1d91, the last one in which the fingerprint was an inline lambda of
+// prepare_search: a throwaway program held that block verbatim (around a struct with xyz1 and natoms1) and printed it for
+// these three arrays.  A record of a running hold never outlives the process, so the value itself is free to change - pinning it
+// is what makes this a regression test of the move.
+static void test_held_fingerprint() {
+    struct { size_t natoms; uint64_t want; size_t middle; } cases[] = {
+        {10, 0x2738aa20d12dd355ull, 5}, {600, 0xfd7799a0bb088febull, 300}, {5000, 0xf8cfb23434bec7c3ull, 9 * 200}};   // middle = step * k
+    for (size_t k = 0; k < 3; ++k) {
+        const size_t n = cases[k].natoms;
+        std::vector<float> v = recurrence(n, 12345u + (uint32_t)k);
+        const uint64_t fp = held_fingerprint(v.data(), n);
+        CHECK(fp == cases[k].want);
+        CHECK(fp & 1ull);
+        auto changed = [&](size_t atom) {
+            std::vector<float> w = v;
+            w[3 * atom + 1] += 0.25f;
+            return held_fingerprint(w.data(), n) != fp;
+        };
+        CHECK(changed(0));
+        CHECK(changed(n - 1));
+        CHECK(changed(cases[k].middle));
+        // what the fingerprint is: the two ends and every (n / 512)th atom - atom 1801 of 5000 is none of them
+        if (n == 5000) CHECK(!changed(9 * 200 + 1));
+    }
+}
+
+static void test_held_conditions() {
+    GridSet gen_a[2], gen_b[2];
+    const std::vector<float> xyz = recurrence(600, 7u);
+    const uint64_t ids[4] = {1, 2, 3, 5};
+    const float box9[9] = {4, 0, 0, 0, 5, 0, 0, 0, 6};
+    for (const bool use_box : {true, false}) {
+        SearchShape s;
+        s.set = gen_a;
+        s.kind = MOLAR_HIP_SEARCH_WITHIN;
+        s.use_box = use_box;
+        s.pbc = use_box ? 7 : 0;
+        if (use_box) CHECK(molar_hip_box_from_matrix(box9, &s.box) == 0);
+        s.dims[0] = 5; s.dims[1] = 6; s.dims[2] = 7;
+        for (int d = 0; d < 3; ++d) { s.lower[d] = -1.f - (float)d; s.upper[d] = 4.f + (float)d; }
+        molar_hip_search_desc q{};
+        q.kind = MOLAR_HIP_SEARCH_WITHIN;
+        q.xyz1 = xyz.data();
+        q.natoms1 = 600;
+        q.idx1 = ids;
+        q.n1 = 4;
+        q.ids_local = 0;
+        const uint64_t fp = held_fingerprint(q.xyz1, q.natoms1);
+        const HeldGrid h = held_remember(q, s, fp);
+        // the unchanged request is accepted; nothing is, against a record that is not valid
+        CHECK(h.valid && held_names_request(h, q, s, fp) && held_same_cells(h, s));
+        CHECK(!held_names_request(HeldGrid{}, q, s, fp));
+        HeldGrid ended = h;
+        ended.valid = false;
+        CHECK(!held_names_request(ended, q, s, fp));
+        // one thing at a time: the request
+        auto other_request = [&](auto change) {
+            molar_hip_search_desc r = q;
+            SearchShape v = s;
+            uint64_t f = fp;
+            change(r, v, f);
+            return !held_names_request(h, r, v, f);
+        };
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.xyz1 = xyz.data() + 3; }));
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.natoms1 = 599; }));
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.idx1 = ids + 1; }));
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.idx1 = nullptr; }));
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.n1 = 3; }));
+        CHECK(other_request([&](molar_hip_search_desc &r, SearchShape &, uint64_t &) { r.ids_local = 1; }));
+        CHECK(other_request([&](molar_hip_search_desc &, SearchShape &v, uint64_t &) { v.use_box = !v.use_box; }));
+        CHECK(other_request([&](molar_hip_search_desc &, SearchShape &v, uint64_t &) { v.pbc ^= 2; }));
+        CHECK(other_request([&](molar_hip_search_desc &, SearchShape &, uint64_t &f) { f ^= 2ull; }));
+        CHECK(other_request([&](molar_hip_search_desc &, SearchShape &, uint64_t &f) { f = 0; }));          // the same address, now device memory
+        CHECK(other_request([&](molar_hip_search_desc &, SearchShape &v, uint64_t &) { v.set = gen_b; }));  // the other grid generation
+        // one entry of the box matrix: part of the request with a box, not looked at without one
+        const bool box_matters = other_request([&](molar_hip_search_desc &, SearchShape &v, uint64_t &) { v.box.m[4] += 0.5f; });
+        CHECK(box_matters == use_box);
+        // the cutoff and the second set are not part of it
+        CHECK(!other_request([&](molar_hip_search_desc &r, SearchShape &v, uint64_t &) { r.cutoff = 0.7f; v.cutoff = 0.7f; r.xyz2 = xyz.data(); r.natoms2 = 9; }));
+        // one thing at a time: the grid
+        auto other_cells = [&](auto change) {
+            SearchShape v = s;
+            change(v);
+            return !held_same_cells(h, v);
+        };
+        for (int d = 0; d < 3; ++d) CHECK(other_cells([&](SearchShape &v) { v.dims[d] += 1; }));
+        // the caller's bounds decide the grid of a request without a box; with a box they are ignored
+        for (int d = 0; d < 3; ++d) {
+            CHECK(other_cells([&](SearchShape &v) { v.lower[d] -= 0.5f; }) == !use_box);
+            CHECK(other_cells([&](SearchShape &v) { v.upper[d] += 0.5f; }) == !use_box);
+        }
+    }
+}
+
 int main() {
     test_policy();
     test_family();
     test_slots_bound();
     test_occ_key();
+    test_held_fingerprint();
+    test_held_conditions();
     if (failures) {
         std::printf("%d search-shape checks failed\n", failures);
         return 1;

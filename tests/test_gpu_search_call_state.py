@@ -290,3 +290,86 @@ def test_membrane_frame_then_a_search_with_a_nan_coordinate(a, sys_):
     assert len(res[0]["patch_ids"]) > 0
     want = count_fill(a, a.Engine(0), sys_, pos=sys_["nan"])
     same_list(count_fill(a, e, sys_, pos=sys_["nan"]), want, "count + fill of a frame with a NaN after the membrane frame")
+
+
+# ---- the lane of a grid build: stream, scan scratch and sort scratch travel together
+# A pipelined resident search on an Engine that owns its stream builds its grid on the side stream, with that stream's scratch;
+# count + fill on another Engine builds the same grid on the main stream.  Two shapes reach the per-stream scratch:
+#  * more than 8191 cells: the cell counts are scanned in tiles, whose block sums live in the stream's scan scratch;
+#  * more than 384 atoms per cell on average: the cell order comes from the device sort and its scratch.
+N_CELLS, RC_CELLS = 30000, 0.3        # box_ortho: 100 atoms / nm^3, 6.69 nm across: 22 x 22 x 22 cells
+N_SORT, RC_SORT = 1000, 1.2           # 2.15 nm across: one cell of 1000 atoms
+
+
+@pytest.fixture(scope="module")
+def lanes(a):
+    """The frames of the two shapes on host and device, and what count + fill of ONE fresh Engine (grids on the main stream)
+    gives for each, with the grid it came to."""
+    import torch
+    f = {}
+    box = synth.box_ortho(N_CELLS)
+    f["A"] = dict(box=box, rc=RC_CELLS, pos=synth.frame(N_CELLS, box, 0))
+    f["B"] = dict(box=box, rc=RC_CELLS, pos=synth.frame(N_CELLS, box, 1))
+    box = synth.box_ortho(N_SORT)
+    f["C"] = dict(box=box, rc=RC_SORT, pos=synth.frame(N_SORT, box, 2))
+    main = a.Engine(0)
+    for v in f.values():
+        v["d_pos"] = torch.from_numpy(v["pos"]).cuda()
+        cnt = main.search_count(a.SEARCH_SINGLE, v["rc"], v["pos"], box=v["box"], pbc=7)
+        v["want"] = (cnt,) + main.search_fill(cnt)
+        v["dims"] = main.grid_dims()
+    return f
+
+
+def pipelined(a, e, lanes, names):
+    """The frames `names` through search_resident_begin / _end on `e`, two in flight; each result against the main-stream one."""
+    descs = {k: e.make_search_desc(a.SEARCH_SINGLE, lanes[k]["rc"], lanes[k]["d_pos"], box=lanes[k]["box"], pbc=7) for k in set(names)}
+    for k in range(0, len(names), 2):
+        pair = names[k:k + 2]
+        tickets = [e.search_resident_begin(descs[name][0]) for name in pair]
+        assert sorted(tickets) == [0, 1]
+        for name, t in zip(pair, tickets):
+            same_list(resident_arrays(a, e.search_resident_end(t)), lanes[name]["want"], f"frame {name}, step {k}")
+
+
+def against_oracle(orc32, v):
+    ref = orc32.search_single_pbc(v["rc"], v["pos"], orc32.box_from_matrix(v["box"]), 7, nthreads=4)
+    cnt, pairs, dist = v["want"]
+    assert cnt == len(ref["i"]) and np.array_equal(pairs[:, 0], ref["i"]) and np.array_equal(pairs[:, 1], ref["j"]) and np.array_equal(dist, ref["d"])
+
+
+def test_tile_scan_of_a_grid_built_on_the_side_stream(a, lanes, orc32):
+    assert int(np.prod(lanes["A"]["dims"])) + 1 > 8192 and lanes["B"]["dims"] == lanes["A"]["dims"]
+    pipelined(a, a.Engine(0), lanes, "ABAB")
+    against_oracle(orc32, lanes["A"])
+
+
+def test_device_sort_of_a_grid_built_on_the_side_stream(a, lanes, orc32):
+    """Alternating with a frame of many cells: the scan and sort scratch of the side stream have been sized by the other shape
+    before they are used again."""
+    assert N_SORT > 384 * int(np.prod(lanes["C"]["dims"]))
+    pipelined(a, a.Engine(0), lanes, "CACA")
+    against_oracle(orc32, lanes["C"])
+
+
+def test_empty_vdw_request_between_ordinary_ones(a, sys_, fresh_single):
+    """A vdW request with an empty second set comes to nothing: count 0, a grid of one cell, an empty fill - through count,
+    through the resident call and through the fused histogram - and the Engine answers the ordinary request as a fresh one does."""
+    s = sys_
+    empty = dict(xyz2=s["pos2"], idx2=np.zeros(1, np.uint64)[:0], vdw1=np.full(N, 0.15, np.float32), vdw2=np.ones(1, np.float32),
+                 box=s["box"], pbc=7)
+    e = a.Engine(0)
+    same_list(count_fill(a, e, s), fresh_single, "count + fill before")
+    assert e.grid_dims() == (4, 4, 4)
+    assert e.search_count(a.SEARCH_DOUBLE_VDW, None, s["pos"], **empty) == 0
+    assert e.grid_dims() == (1, 1, 1)
+    pairs, dist = e.search_fill(0)
+    assert pairs.shape == (0, 2) and dist.shape == (0,)
+    same_list(count_fill(a, e, s), fresh_single, "count + fill after the empty vdW count")
+    assert e.search_resident(a.SEARCH_DOUBLE_VDW, None, s["pos"], **empty)[0] == 0
+    assert e.grid_dims() == (1, 1, 1)
+    same_list(count_fill(a, e, s), fresh_single, "count + fill after the empty resident vdW search")
+    bins, cnt = e.search_histogram(a.SEARCH_DOUBLE_VDW, None, *HIST, s["pos"], **empty)
+    assert cnt == 0 and not np.asarray(bins).any()
+    assert e.grid_dims() == (1, 1, 1)
+    same_list(count_fill(a, e, s), fresh_single, "count + fill after the empty vdW histogram")
