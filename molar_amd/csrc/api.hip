@@ -4,11 +4,6 @@
 
 #include "common.hpp"
 #include "hoststream.hpp"
-namespace mh { void search64_release(molar_hip_ctx *c); }
-namespace mh { void sasa_release(molar_hip_ctx *c); }
-namespace mh { void rmsd_matrix_release(molar_hip_ctx *c); }
-namespace mh { void fluct_release(molar_hip_ctx *c); }
-namespace mh { void msd_release(molar_hip_ctx *c); }
 #include <cstdlib>
 
 using namespace mh;

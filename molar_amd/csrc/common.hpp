@@ -356,6 +356,13 @@ struct molar_hip_ctx {
 
 namespace mh {
 
+// the units that own a state of the context free it (molar_hip_destroy, api.hip)
+void search64_release(molar_hip_ctx *c);
+void sasa_release(molar_hip_ctx *c);
+void rmsd_matrix_release(molar_hip_ctx *c);
+void fluct_release(molar_hip_ctx *c);
+void msd_release(molar_hip_ctx *c);
+
 // RAII span: records an event pair around a group of launches when profiling is on
 struct Prof {
     molar_hip_ctx *c;
@@ -404,20 +411,6 @@ inline int read_back(molar_hip_ctx *c, void *dst_host, const void *src_dev, size
     MH_HIP(hipMemcpyAsync(c->h_pinned, src_dev, bytes, hipMemcpyDeviceToHost, c->stream));
     MH_HIP(hipStreamSynchronize(c->stream));
     std::memcpy(dst_host, c->h_pinned, bytes);
-    return 0;
-}
-
-// The status check of the fitted trajectory analyses (rmsd_matrix.hip, fluct.hip): the index flag their centring kernel raised and
-// the sum of the selected weights, from two device buffers under one wait.
-inline int check_selection(molar_hip_ctx *c, const uint32_t *index_flag_dev, const double *weight_sum_dev, const char *who, size_t natoms) {
-    MH_TRY(ensure_pinned(c, 16));
-    double *sum = static_cast<double *>(c->h_pinned);
-    uint32_t *flag = reinterpret_cast<uint32_t *>(sum + 1);
-    MH_HIP(hipMemcpyAsync(sum, weight_sum_dev, 8, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipMemcpyAsync(flag, index_flag_dev, 4, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    if (*flag) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
-    if (*sum == 0.0) return fail(MOLAR_HIP_ERR_ZERO_MASS, "%s: the selected masses add up to zero", who);
     return 0;
 }
 

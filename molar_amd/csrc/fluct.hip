@@ -26,6 +26,7 @@
 
 #include "common.hpp"
 #include "linalg3.hpp"
+#include "traj_block.hpp"
 
 using namespace mh;
 
@@ -36,8 +37,6 @@ struct molar_hip_fluct_state {
 };
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t FL_TILE = 16;                     // coordinates per tile: the M and N of the MFMA
 constexpr uint32_t FL_KSTEP = 4;                     // frames per MFMA
@@ -88,26 +87,23 @@ Layout make_layout(size_t F, size_t n, bool want_cov) {
     const size_t ksK = std::min<size_t>(FL_MAX_SPLITS, std::max<size_t>(1, L.ksteps / FL_MIN_SPLIT_STEPS));
     size_t ks = 1;
     if (want_cov && L.nupper) ks = std::min({ksK, FL_PART_BLOCKS / L.nupper, (FL_TARGET_WAVES + L.nupper - 1) / L.nupper});
-    if (ks < 2) ks = 1;
-    L.kper = (uint32_t)((L.ksteps + ks - 1) / ks);
-    if (L.kper == 0) L.kper = 1;
-    L.ksplits = L.ksteps ? (L.ksteps + L.kper - 1) / L.kper : 1;      // no empty split
+    const Splits sp = even_splits(L.ksteps, ks);
+    L.kper = sp.kper;
+    L.ksplits = sp.ksplits;
     const size_t part_blocks = std::min(ksK * L.nupper, FL_PART_BLOCKS);
-    auto take = [&](size_t &off, size_t bytes) {
-        off = L.bytes;
-        L.bytes += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.off_centre, F * 4 * 8);
-    take(L.off_refd, L.M * 8);
-    take(L.off_refc, 8 * 8);
-    take(L.off_origin, 4 * 8);
-    take(L.off_flags, 16);
-    take(L.off_fitpart, F * L.nchunks * 10 * 8);
-    take(L.off_rot, F * 9 * 8);
-    take(L.off_mprime, L.M * 8);
-    take(L.off_spart, std::min(by_frames * n, FL_STAT_THREADS + n) * 3 * 8);
-    take(L.off_packed, want_cov ? (size_t)L.Tp * FL_TILE * L.Fpad * 8 : 0);
-    take(L.off_part, want_cov && ksK > 1 ? part_blocks * FL_PART_DOUBLES * 8 : 0);
+    Carve ws;
+    ws.take(L.off_centre, F * 4 * 8);
+    ws.take(L.off_refd, L.M * 8);
+    ws.take(L.off_refc, 8 * 8);
+    ws.take(L.off_origin, 4 * 8);
+    ws.take(L.off_flags, 16);
+    ws.take(L.off_fitpart, F * L.nchunks * 10 * 8);
+    ws.take(L.off_rot, F * 9 * 8);
+    ws.take(L.off_mprime, L.M * 8);
+    ws.take(L.off_spart, std::min(by_frames * n, FL_STAT_THREADS + n) * 3 * 8);
+    ws.take(L.off_packed, want_cov ? (size_t)L.Tp * FL_TILE * L.Fpad * 8 : 0);
+    ws.take(L.off_part, want_cov && ksK > 1 ? part_blocks * FL_PART_DOUBLES * 8 : 0);
+    L.bytes = ws.bytes;
     return L;
 }
 
@@ -118,6 +114,7 @@ struct In {
     const uint64_t *idx;
     const Real *mass;
     uint32_t n;
+    __device__ __forceinline__ const Real *frame(size_t f) const { return frames + f * stride; }
 };
 
 // How a frame is brought onto the reference: z' = R_f (x - c_f) with R_f = rot + 9 f (column-major) and c_f = c + cstride f;
@@ -141,62 +138,6 @@ __device__ __forceinline__ void zprime(const Real *__restrict__ p, uint64_t a, c
     }
 }
 
-// the fixed tree of a workgroup of 256 over NV values per thread; the result is in sh[v][0]
-template <int NV>
-__device__ __forceinline__ void tree256(double (*sh)[256], const double *s) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) sh[v][threadIdx.x] = s[v];
-    __syncthreads();
-    for (uint32_t w = 128u; w > 0u; w >>= 1) {
-        if (threadIdx.x < w)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) sh[v][threadIdx.x] += sh[v][threadIdx.x + w];
-        __syncthreads();
-    }
-}
-
-// One workgroup per frame: {sum w p / sum w, sum w}, the scheme of rm_centre_kernel (rmsd_matrix.hip): thread t adds atoms
-// t, t + 256, ... in that order, then a fixed tree.  flags[0]: an index is not below natoms.
-template <class Real>
-__global__ void __launch_bounds__(256) fl_centre_kernel(In<Real> P, double *__restrict__ centre, uint32_t *__restrict__ flags) {
-    __shared__ double sh[4][256];
-    const size_t f = blockIdx.x;
-    const Real *p = P.frames + f * P.stride;
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (uint32_t k = threadIdx.x; k < P.n; k += 256u) {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
-        if (a >= P.natoms) {
-            flags[0] = 1u;
-            continue;
-        }
-        const double w = P.mass ? (double)P.mass[a] : 1.0;
-        s[0] += w * (double)p[3 * a];
-        s[1] += w * (double)p[3 * a + 1];
-        s[2] += w * (double)p[3 * a + 2];
-        s[3] += w;
-    }
-    tree256<4>(sh, s);
-    if (threadIdx.x < 4u) centre[f * 4 + threadIdx.x] = threadIdx.x < 3u ? sh[threadIdx.x][0] / sh[3][0] : sh[3][0];
-}
-
-// The common origin of the mode without a fit: the centre of frame 0; should that frame hold a non-finite coordinate, the
-// first centre that is finite (zeros when there is none).
-__global__ void fl_origin_kernel(const double *__restrict__ centre, size_t F, double *__restrict__ origin) {
-    double o[3] = {0.0, 0.0, 0.0};
-    for (size_t f = 0; f < F; ++f) {
-        const double x = centre[f * 4], y = centre[f * 4 + 1], z = centre[f * 4 + 2];
-        if (isfinite(x) && isfinite(y) && isfinite(z)) {
-            o[0] = x;
-            o[1] = y;
-            o[2] = z;
-            break;
-        }
-    }
-    origin[0] = o[0];
-    origin[1] = o[1];
-    origin[2] = o[2];
-}
-
 // The first reference in f64: the caller's packed [n][3], or the selection of frame 0.
 template <class Real>
 __global__ void __launch_bounds__(256) fl_ref_init_kernel(In<Real> P, const Real *__restrict__ ref, double *__restrict__ refd) {
@@ -207,7 +148,7 @@ __global__ void __launch_bounds__(256) fl_ref_init_kernel(In<Real> P, const Real
 #pragma unroll
         for (int d = 0; d < 3; ++d) v[d] = (double)ref[3 * k + d];
     } else {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
+        const uint64_t a = sel_atom(P, k);
         if (a < P.natoms)
 #pragma unroll
             for (int d = 0; d < 3; ++d) v[d] = (double)P.frames[3 * a + d];
@@ -216,15 +157,15 @@ __global__ void __launch_bounds__(256) fl_ref_init_kernel(In<Real> P, const Real
     for (int d = 0; d < 3; ++d) refd[3 * k + d] = v[d];
 }
 
-// One workgroup: refc = {c_ref (3), W, sum w |y|^2} of the reference refd, y = refd - c_ref; the sums as in fl_centre_kernel.
+// One workgroup: refc = {c_ref (3), W, sum w |y|^2} of the reference refd, y = refd - c_ref; the sums as in tb_centre_kernel.
 template <class Real>
 __global__ void __launch_bounds__(256) fl_ref_centre_kernel(In<Real> P, const double *__restrict__ refd, double *__restrict__ refc) {
     __shared__ double sh[4][256];
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (uint32_t k = threadIdx.x; k < P.n; k += 256u) {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
+        const uint64_t a = sel_atom(P, k);
         if (a >= P.natoms) continue;
-        const double w = P.mass ? (double)P.mass[a] : 1.0;
+        const double w = sel_weight(P, a);
         s[0] += w * refd[3 * k];
         s[1] += w * refd[3 * k + 1];
         s[2] += w * refd[3 * k + 2];
@@ -236,9 +177,9 @@ __global__ void __launch_bounds__(256) fl_ref_centre_kernel(In<Real> P, const do
     __syncthreads();
     double g[1] = {0.0};
     for (uint32_t k = threadIdx.x; k < P.n; k += 256u) {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
+        const uint64_t a = sel_atom(P, k);
         if (a >= P.natoms) continue;
-        const double w = P.mass ? (double)P.mass[a] : 1.0;
+        const double w = sel_weight(P, a);
         const double y0 = refd[3 * k] - c[0], y1 = refd[3 * k + 1] - c[1], y2 = refd[3 * k + 2] - c[2];
         g[0] += w * ((y0 * y0 + y1 * y1) + y2 * y2);
     }
@@ -267,8 +208,8 @@ __global__ void __launch_bounds__(256) fl_fit_sums_kernel(In<Real> P, const doub
 #pragma unroll
     for (int q = 0; q < 10; ++q) s[q] = 0.0;
     for (uint32_t k = k0 + threadIdx.x; k < k1; k += 256u) {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
-        const double w = P.mass ? (double)P.mass[a] : 1.0;
+        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;      // (sel_atom written out: through it two scalar registers change places)
+        const double w = sel_weight(P, a);
         const double x[3] = {(double)p[3 * a] - c[0], (double)p[3 * a + 1] - c[1], (double)p[3 * a + 2] - c[2]};
         const double y[3] = {refd[3 * (size_t)k] - cr[0], refd[3 * (size_t)k + 1] - cr[1], refd[3 * (size_t)k + 2] - cr[2]};
 #pragma unroll
@@ -372,7 +313,7 @@ __global__ void __launch_bounds__(256) fl_sums_kernel(In<Real> P, Pose Z, uint32
     const uint32_t ab = blockIdx.x % nab, split = blockIdx.x / nab;
     const size_t k = (size_t)ab * 256u + threadIdx.x;
     if (k >= P.n) return;
-    const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
+    const uint64_t a = sel_atom(P, k);
     const size_t f0 = (size_t)split * fper, f1 = f0 + fper < P.F ? f0 + fper : P.F;
     double m[3] = {0.0, 0.0, 0.0}, s[3] = {0.0, 0.0, 0.0};
     if (Second) {
@@ -439,7 +380,7 @@ __global__ void __launch_bounds__(256) fl_pack_kernel(In<Real> P, Pose Z, size_t
     const bool live = i < M;
     const size_t k = live ? i / 3 : 0;
     const uint32_t d = (uint32_t)(i - 3 * (i / 3));
-    const uint64_t a = live ? (P.idx ? P.idx[k] : (uint64_t)k) : 0;
+    const uint64_t a = live ? sel_atom(P, k) : 0;
     const double m = live ? mprime[i] : 0.0;
     const size_t f0 = (size_t)blockIdx.x * FL_PACK_FRAMES, f1 = f0 + FL_PACK_FRAMES < Fpad ? f0 + FL_PACK_FRAMES : Fpad;
     double *dst = packed + (size_t)tile * Fpad * FL_TILE + cl;
@@ -543,8 +484,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) fl
             for (int j = 0; j < (int)FL_BLOCK; ++j)
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    fl_store<Real>(O, ((size_t)bi * FL_BLOCK + i) * FL_TILE + (lane >> 4) + 4u * r, ((size_t)bj * FL_BLOCK + j) * FL_TILE + (lane & 15u),
-                                   acc[i][j][r]);
+                    fl_store<Real>(O, mfma_c_row(((size_t)bi * FL_BLOCK + i) * FL_TILE, lane, r), mfma_c_col(((size_t)bj * FL_BLOCK + j) * FL_TILE, lane), acc[i][j][r]);
     } else {
         const size_t nupper = (size_t)Q.NB * (Q.NB + 1u) / 2u;
         double *dst = Q.part + ((size_t)blockIdx.y * nupper + blockIdx.x) * FL_PART_DOUBLES + lane;
@@ -568,6 +508,7 @@ __global__ void __launch_bounds__(256) fl_cov_finish_kernel(const double *__rest
     const double *src = part + (size_t)blockIdx.x * FL_PART_DOUBLES + lane;
     for (uint32_t ij = 0; ij < 16u; ++ij) {
         const uint32_t i = ij >> 2, j = ij & 3u;
+        // (mfma_c_row / mfma_c_col written out: through them the compiler swaps the operands of two scalar ANDs below)
         const size_t row = ((size_t)bi * FL_BLOCK + i) * FL_TILE + (lane >> 4) + 4u * r, col = ((size_t)bj * FL_BLOCK + j) * FL_TILE + (lane & 15u);
         if (row >= O.M || col >= O.M || col < row) continue;
         double sum = 0.0;
@@ -576,55 +517,24 @@ __global__ void __launch_bounds__(256) fl_cov_finish_kernel(const double *__rest
     }
 }
 
-// a device destination as it is, a host destination through a staging buffer; a null destination stays null
-template <class Real>
-int out_buffer(Real *dst, size_t count, DevBuf &stage, const char *who, Real **dev) {
-    *dev = dst;
-    if (!dst || is_device_ptr(dst)) return 0;
-    if (count * sizeof(Real) > stage.cap) {
-        stage.release();
-        void *p = nullptr;
-        if (hipMalloc(&p, count * sizeof(Real)) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: a result of %zu bytes cannot be allocated", who, count * sizeof(Real));
-        }
-        stage.p = p;
-        stage.cap = count * sizeof(Real);
-    }
-    *dev = stage.as<Real>();
-    return 0;
-}
-
 template <class Real>
 int fluct_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, size_t stride, size_t natoms, const uint64_t *idx, size_t n,
               const Real *mass, const Real *ref, int fit, int iterations, Real *mean, Real *rmsf, Real *cov, size_t ld, Real *fit_out) {
     MH_CTX(c);
     if (n == 0) return fail(MOLAR_HIP_ERR_SIZES, "%s: empty selection", who);
     if (cov && ld < 3 * n) return fail(MOLAR_HIP_ERR_SIZES, "%s: ld = %zu is below the %zu columns of the covariance", who, ld, 3 * n);
-    if (!idx && n > natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: n = %zu exceeds natoms = %zu and there is no index", who, n, natoms);
-    if (F > 1 && stride < natoms * 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: the frame stride is below 3 * natoms = %zu", who, natoms * 3);
+    MH_TRY(check_no_index(who, "n", idx, n, natoms));
+    MH_TRY(check_stride(who, "the frame stride", F, stride, natoms));
     if (iterations < 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: iterations = %d is negative", who, iterations);
     if (n >= 0x2AAAAAA0ull || F >= 0x7FFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: more than 2^31 coordinates or frames", who);
     if (F == 0) return MOLAR_HIP_OK;
     if (!frames) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: the frames pointer is null", who);
-    if (idx && !is_device_ptr(idx))
-        for (size_t k = 0; k < n; ++k)
-            if (idx[k] >= natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: idx[%zu] = %llu is not below natoms = %zu", who, k, (unsigned long long)idx[k], natoms);
+    MH_TRY(check_index(who, "idx", idx, n, natoms));
     const Layout L = make_layout(F, n, cov != nullptr);
     if (cov && L.Tp > 65535u) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: a covariance of more than %u coordinates", who, 65532u * FL_TILE);
     if (L.nchunks > 65535u) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: a selection of more than %u atoms", who, 65535u * FL_CHUNK);
-    if (!c->fluct) c->fluct = new molar_hip_fluct_state;
-    molar_hip_fluct_state &Z = *c->fluct;
-    if (L.bytes > Z.ws.cap) {
-        Z.ws.release();
-        void *p = nullptr;
-        if (hipMalloc(&p, L.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: the workspace of %zu bytes cannot be allocated", who, L.bytes);
-        }
-        Z.ws.p = p;
-        Z.ws.cap = L.bytes;
-    }
+    molar_hip_fluct_state &Z = state_of(c->fluct);
+    MH_TRY(grow_exact(Z.ws, L.bytes, who, "the workspace"));
     char *W = Z.ws.as<char>();
     auto at = [&](size_t off) { return reinterpret_cast<double *>(W + off); };
     double *centre = at(L.off_centre), *refd = at(L.off_refd), *refc = at(L.off_refc), *origin = at(L.off_origin);
@@ -650,8 +560,8 @@ int fluct_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, s
 
     const uint32_t nblk_n = (uint32_t)((n + 255) / 256), nblk_M = (uint32_t)((L.M + 255) / 256);
     MH_HIP(hipMemsetAsync(flags, 0, 16, c->stream));
-    hipLaunchKernelGGL(fl_centre_kernel<Real>, dim3((uint32_t)F), dim3(256), 0, c->stream, P, centre, flags);
-    if (!fit) hipLaunchKernelGGL(fl_origin_kernel, dim3(1), dim3(1), 0, c->stream, centre, F, origin);
+    hipLaunchKernelGGL(tb_centre_kernel<In<Real>>, dim3((uint32_t)F), dim3(256), 0, c->stream, P, centre, flags);
+    if (!fit) hipLaunchKernelGGL(tb_origin_kernel<>, dim3(1), dim3(1), 0, c->stream, centre, F, origin);
     hipLaunchKernelGGL(fl_ref_init_kernel<Real>, dim3(nblk_n), dim3(256), 0, c->stream, P, ref_dev, refd);
     // the weights' sum and the index check decide the status, read back before the rest is enqueued
     MH_TRY(check_selection(c, flags, centre + 3, who, natoms));
@@ -705,24 +615,11 @@ int fluct_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, s
     }
     MH_HIP(hipGetLastError());
     bool wait = false;
-    if (mean && mean_dev != mean) {
-        MH_HIP(hipMemcpyAsync(mean, mean_dev, L.M * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (rmsf && rmsf_dev != rmsf) {
-        MH_HIP(hipMemcpyAsync(rmsf, rmsf_dev, n * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (fit_out && fit_dev != fit_out) {
-        MH_HIP(hipMemcpyAsync(fit_out, fit_dev, F * 13 * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (cov_host) {
-        MH_HIP(hipMemcpy2DAsync(cov, ld * sizeof(Real), cov_dev, L.M * sizeof(Real), L.M * sizeof(Real), L.M, hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (wait) MH_HIP(hipStreamSynchronize(c->stream));
-    return MOLAR_HIP_OK;
+    MH_TRY(copy_out(c, mean, mean_dev, L.M, wait));
+    MH_TRY(copy_out(c, rmsf, rmsf_dev, n, wait));
+    MH_TRY(copy_out(c, fit_out, fit_dev, F * 13, wait));
+    MH_TRY(copy_out_2d(c, cov, ld, cov_dev, L.M, L.M, wait));
+    return finish_copies(c, wait);
 }
 
 }  // namespace
@@ -731,9 +628,7 @@ namespace mh {
 void fluct_release(molar_hip_ctx *c) {
     if (!c->fluct) return;
     molar_hip_fluct_state &Z = *c->fluct;
-    for (DevBuf *b : {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_ref, &Z.ws, &Z.out_mean, &Z.out_rmsf, &Z.out_cov, &Z.out_fit}) b->release();
-    delete c->fluct;
-    c->fluct = nullptr;
+    release_state(c->fluct, {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_ref, &Z.ws, &Z.out_mean, &Z.out_rmsf, &Z.out_cov, &Z.out_fit});
 }
 }  // namespace mh
 

@@ -25,6 +25,7 @@
 
 #include "boxmath.hpp"
 #include "common.hpp"
+#include "traj_block.hpp"
 
 using namespace mh;
 
@@ -77,19 +78,17 @@ Layout make_layout(size_t F, size_t n, size_t P, size_t nref, size_t L, bool per
     Y.nchunks = (uint32_t)((P + Y.chunk - 1) / Y.chunk);
     // the chunks never exceed this, which grows with P: the reservation never shrinks when an argument grows
     const size_t chunks_bound = std::min<size_t>(P, 2 * MSD_TARGET_WGS) + P / MSD_MAX_CHUNK + 1;
-    auto take = [&](size_t &off, size_t bytes) {
-        off = Y.bytes;
-        Y.bytes += (bytes + 255) & ~(size_t)255;
-    };
-    take(Y.off_flags, 16);
-    take(Y.off_boxes, (per_frame_boxes ? F : 1) * sizeof(BoxD));
-    take(Y.off_drift, nref ? F * 3 * 8 : 0);
+    Carve ws;
+    ws.take(Y.off_flags, 16);
+    ws.take(Y.off_boxes, (per_frame_boxes ? F : 1) * sizeof(BoxD));
+    ws.take(Y.off_drift, nref ? F * 3 * 8 : 0);
     // the pieces by their bound, not by the count the offsets give: the plan entry sees sizes only, and what it reports must
     // neither differ from what the call takes nor shrink when an argument grows
-    take(Y.off_piece, pieces_bound(std::max(n, nref)) * F * 3 * 8);
-    take(Y.off_piecew, pieces_bound(std::max(n, nref)) * 8);
-    take(Y.off_traj, want_lags ? P * F * 3 * 8 : 0);
-    take(Y.off_part, want_lags ? chunks_bound * (L + 1) * 2 * 8 : 0);
+    ws.take(Y.off_piece, pieces_bound(std::max(n, nref)) * F * 3 * 8);
+    ws.take(Y.off_piecew, pieces_bound(std::max(n, nref)) * 8);
+    ws.take(Y.off_traj, want_lags ? P * F * 3 * 8 : 0);
+    ws.take(Y.off_part, want_lags ? chunks_bound * (L + 1) * 2 * 8 : 0);
+    Y.bytes = ws.bytes;
     return Y;
 }
 
@@ -161,15 +160,7 @@ struct Set {
     double *piece, *piecew;       // [pieces][F][3] and [pieces]: sums of w u and of w of the pieces of large groups
 };
 
-// the fixed tree of a workgroup of 256 over three values per thread; the result is in sh[d][0]
-__device__ __forceinline__ void tree3(double (*sh)[MSD_ATOMS]) {
-    for (uint32_t w = MSD_ATOMS / 2; w > 0u; w >>= 1) {
-        if (threadIdx.x < w)
-#pragma unroll
-            for (int d = 0; d < 3; ++d) sh[d][threadIdx.x] += sh[d][threadIdx.x + w];
-        __syncthreads();
-    }
-}
+static_assert(MSD_ATOMS == 256, "the pieces of a large group are summed by tree256_sum");
 
 // One workgroup per entry of S.blocks, one thread per atom of it.  flags[0]: an index not below natoms; flags[2]: a particle
 // whose weights add up to zero.
@@ -180,12 +171,12 @@ __global__ void __launch_bounds__(MSD_ATOMS) msd_unwrap_kernel(Set<Real> S, uint
     const uint32_t t = threadIdx.x;
     const bool live = t < B.count;
     const size_t k = (size_t)B.a0 + (live ? t : 0u);
-    uint64_t a = S.idx ? S.idx[k] : (uint64_t)k;
+    uint64_t a = sel_atom(S, k);
     if (a >= S.natoms) {
         flags[0] = 1u;
         a = 0;
     }
-    const double w = live ? (S.mass ? (double)S.mass[a] : 1.0) : 0.0;
+    const double w = live ? sel_weight(S, a) : 0.0;
     // the particle of this atom and, for the first atom of a particle within the workgroup, how many atoms follow
     size_t g = B.g0;
     uint32_t cnt = 0;
@@ -213,7 +204,7 @@ __global__ void __launch_bounds__(MSD_ATOMS) msd_unwrap_kernel(Set<Real> S, uint
     sh[2][t] = 0.0;
     __syncthreads();
     if (B.piece >= 0) {
-        tree3(sh);
+        tree256_sum<3>(sh);
         if (t == 0u) S.piecew[B.piece] = sh[0][0];
     } else if (whole) {
         for (uint32_t j = 0; j < cnt; ++j) W += sh[0][t + j];
@@ -242,7 +233,7 @@ __global__ void __launch_bounds__(MSD_ATOMS) msd_unwrap_kernel(Set<Real> S, uint
         sh[2][t] = w * u[2];
         __syncthreads();
         if (B.piece >= 0) {
-            tree3(sh);
+            tree256_sum<3>(sh);
             if (t < 3u) S.piece[((size_t)B.piece * S.F + f) * 3 + t] = sh[t][0];
         } else if (whole) {
             double s[3] = {sh[0][t], sh[1][t], sh[2][t]};
@@ -387,29 +378,6 @@ __global__ void __launch_bounds__(256) msd_finish_kernel(LagP Q, Real *__restric
     if (m4) m4[tau] = (Real)(b / scale);
 }
 
-inline int grow(DevBuf &b, size_t bytes, const char *who, const char *what) {
-    if (bytes <= b.cap) return 0;
-    b.release();
-    void *p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: %s of %zu bytes cannot be allocated", who, what, bytes);
-    }
-    b.p = p;
-    b.cap = bytes;
-    return 0;
-}
-
-// a device destination as it is, a host destination through a staging buffer; a null destination stays null
-template <class Real>
-int out_buffer(Real *dst, size_t count, DevBuf &stage, const char *who, Real **dev) {
-    *dev = dst;
-    if (!dst || is_device_ptr(dst)) return 0;
-    MH_TRY(grow(stage, count * sizeof(Real), who, "a result"));
-    *dev = stage.as<Real>();
-    return 0;
-}
-
 // The workgroups of the unwrap kernel for n atoms in particles off[0..P] (null: every atom is one): whole particles packed into
 // workgroups of at most MSD_ATOMS atoms in order; a group of more than MSD_ATOMS atoms in pieces of MSD_ATOMS.
 void make_blocks(const uint64_t *off, size_t n, size_t P, std::vector<Block> &blocks, std::vector<Big> &big) {
@@ -476,27 +444,21 @@ int msd_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, siz
     if (pbc > 7) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: pbc = %u is not a PbcDims byte", who, (unsigned)pbc);
     if (box_stride != 0 && box_stride != 9) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: box_stride = %zu is neither 0 nor 9", who, box_stride);
     if (natoms == 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection of %zu atoms out of natoms = 0", who, n);
-    if (!idx && n > natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: n = %zu exceeds natoms = %zu and there is no index", who, n, natoms);
-    if (nref && !ref_idx && nref > natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: nref = %zu exceeds natoms = %zu and there is no index", who, nref, natoms);
-    if (F > 1 && stride < natoms * 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: the frame stride is below 3 * natoms = %zu", who, natoms * 3);
+    MH_TRY(check_no_index(who, "n", idx, n, natoms));
+    MH_TRY(check_no_index(who, "nref", ref_idx, nref, natoms));
+    MH_TRY(check_stride(who, "the frame stride", F, stride, natoms));
     if (pbc != 0 && !boxes) return fail(MOLAR_HIP_ERR_NO_PBC, "%s: pbc operation without periodic box", who);
     if (n >= 0x7FFFFF00ull || nref >= 0x7FFFFF00ull || F >= 0x7FFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: more than 2^31 atoms or frames", who);
     if (F == 0) return MOLAR_HIP_OK;
     if (!frames) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: the frames pointer is null", who);
-    for (int pass = 0; pass < 2; ++pass) {
-        const uint64_t *ix = pass ? ref_idx : idx;
-        const size_t cnt = pass ? nref : n;
-        if (ix && !is_device_ptr(ix))
-            for (size_t k = 0; k < cnt; ++k)
-                if (ix[k] >= natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: %s[%zu] = %llu is not below natoms = %zu", who, pass ? "ref_idx" : "idx", k, (unsigned long long)ix[k], natoms);
-    }
+    MH_TRY(check_index(who, "idx", idx, n, natoms));
+    MH_TRY(check_index(who, "ref_idx", ref_idx, nref, natoms));
     MH_HIP(hipSetDevice(c->device));
     const bool use_box = boxes != nullptr && pbc != 0;
     const bool want_lags = msd || m4 || msd_particle;
     const Layout Y = make_layout(F, n, P, nref, L, use_box && box_stride == 9, want_lags);
-    if (!c->msd) c->msd = new molar_hip_msd_state;
-    molar_hip_msd_state &Z = *c->msd;
-    MH_TRY(grow(Z.ws, Y.bytes, who, "the workspace"));
+    molar_hip_msd_state &Z = state_of(c->msd);
+    MH_TRY(grow_exact(Z.ws, Y.bytes, who, "the workspace"));
     char *W = Z.ws.as<char>();
     auto at = [&](size_t o) { return reinterpret_cast<double *>(W + o); };
     uint32_t *flags = reinterpret_cast<uint32_t *>(W + Y.off_flags);
@@ -577,11 +539,11 @@ int msd_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, siz
         if (!sbig.empty())
             hipLaunchKernelGGL(msd_pieces_kernel<Real>, dim3(fblocks, (uint32_t)sbig.size()), dim3(256), 0, c->stream, S, reinterpret_cast<const Big *>(T + o_sg), flags);
     }
-    // the index check, the boxes and the weights' sums decide the status: 16 bytes read back before the lags are enqueued
-    MH_TRY(ensure_pinned(c, 16));
-    MH_HIP(hipMemcpyAsync(c->h_pinned, flags, 16, hipMemcpyDeviceToHost, c->stream));
-    MH_HIP(hipStreamSynchronize(c->stream));
-    const uint32_t *hf = static_cast<const uint32_t *>(c->h_pinned);
+    // the index check, the boxes and the weights' sums decide the status: 16 bytes read back before the lags are enqueued.  The
+    // tables behind byte 16 of the pinned buffer may still be in flight as the source of their copy: the read-back touches bytes
+    // 0 - 15 alone, and a buffer that holds the tables is not moved for 16 bytes
+    uint32_t hf[4];
+    MH_TRY(read_back(c, hf, flags, sizeof hf));
     if (hf[0]) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
     if (hf[3]) return fail(MOLAR_HIP_ERR_ZERO_LENGTH_VECTOR, "%s: zero length box vector", who);
     if (hf[1]) return fail(MOLAR_HIP_ERR_INVERSE_FAILED, "%s: box matrix inverse failed", who);
@@ -611,24 +573,11 @@ int msd_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, siz
     }
     MH_HIP(hipGetLastError());
     bool wait = false;
-    if (msd && msd_dev != msd) {
-        MH_HIP(hipMemcpyAsync(msd, msd_dev, (L + 1) * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (m4 && m4_dev != m4) {
-        MH_HIP(hipMemcpyAsync(m4, m4_dev, (L + 1) * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (mp_host) {
-        MH_HIP(hipMemcpy2DAsync(msd_particle, ld * sizeof(Real), mp_dev, (L + 1) * sizeof(Real), (L + 1) * sizeof(Real), P, hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (disp && disp_dev != disp) {
-        MH_HIP(hipMemcpyAsync(disp, disp_dev, F * P * 3 * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
-        wait = true;
-    }
-    if (wait) MH_HIP(hipStreamSynchronize(c->stream));
-    return MOLAR_HIP_OK;
+    MH_TRY(copy_out(c, msd, msd_dev, L + 1, wait));
+    MH_TRY(copy_out(c, m4, m4_dev, L + 1, wait));
+    MH_TRY(copy_out_2d(c, msd_particle, ld, mp_dev, L + 1, P, wait));
+    MH_TRY(copy_out(c, disp, disp_dev, F * P * 3, wait));
+    return finish_copies(c, wait);
 }
 
 }  // namespace
@@ -637,9 +586,7 @@ namespace mh {
 void msd_release(molar_hip_ctx *c) {
     if (!c->msd) return;
     molar_hip_msd_state &Z = *c->msd;
-    for (DevBuf *b : {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_boxes, &Z.in_off, &Z.in_ref, &Z.tab, &Z.ws, &Z.out_msd, &Z.out_m4, &Z.out_mp, &Z.out_disp}) b->release();
-    delete c->msd;
-    c->msd = nullptr;
+    release_state(c->msd, {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_boxes, &Z.in_off, &Z.in_ref, &Z.tab, &Z.ws, &Z.out_msd, &Z.out_m4, &Z.out_mp, &Z.out_disp});
 }
 }  // namespace mh
 

@@ -19,6 +19,7 @@
 
 #include "common.hpp"
 #include "linalg3.hpp"
+#include "traj_block.hpp"
 
 using namespace mh;
 
@@ -29,8 +30,6 @@ struct molar_hip_rmsd_matrix_state {
 };
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr uint32_t RM_TILE = 16;                     // frames per tile: the M and N of the MFMA
 constexpr uint32_t RM_KSTEP = 4;                     // atoms per MFMA
@@ -70,25 +69,22 @@ Layout make_layout(size_t F1, size_t F2, size_t n) {
     // reservation below grow with the sizes, so the workspace never shrinks when an argument grows
     const size_t npairs = (size_t)L.T1 * L.T2p;
     const size_t ksK = std::min<size_t>(RM_MAX_SPLITS, std::max<size_t>(1, L.ksteps / RM_MIN_SPLIT_STEPS));
-    size_t ks = npairs ? std::min(ksK, RM_PART_TILES / std::max<size_t>(npairs, 1)) : 1;
-    if (ks < 2) ks = 1;
-    L.kper = (uint32_t)((L.ksteps + ks - 1) / std::max<size_t>(ks, 1));
-    if (L.kper == 0) L.kper = 1;
-    L.ksplits = L.ksteps ? (L.ksteps + L.kper - 1) / L.kper : 1;      // no empty split
+    const size_t ks = npairs ? std::min(ksK, RM_PART_TILES / std::max<size_t>(npairs, 1)) : 1;
+    const Splits sp = even_splits(L.ksteps, ks);
+    L.kper = sp.kper;
+    L.ksplits = sp.ksplits;
     const size_t part_tiles = std::min(ksK * npairs, RM_PART_TILES);
-    auto take = [&](size_t &off, size_t bytes) {
-        off = L.bytes;
-        L.bytes += (bytes + 255) & ~(size_t)255;
-    };
-    take(L.off_packed1, (size_t)3 * L.T1p * RM_TILE * L.Kpad * 8);
-    take(L.off_packed2, sym ? 0 : (size_t)3 * L.T2p * RM_TILE * L.Kpad * 8);
+    Carve ws;
+    ws.take(L.off_packed1, (size_t)3 * L.T1p * RM_TILE * L.Kpad * 8);
+    ws.take(L.off_packed2, sym ? 0 : (size_t)3 * L.T2p * RM_TILE * L.Kpad * 8);
     const size_t Fpad = ((size_t)L.T1p + (sym ? 0 : L.T2p)) * RM_TILE;
-    take(L.off_centre, L.Ftot * 4 * 8);
-    take(L.off_gpart, (size_t)L.nchunks * Fpad * 8);
-    take(L.off_g, Fpad * 8);
-    take(L.off_origin, 4 * 8);
-    take(L.off_flags, 16);
-    take(L.off_part, ksK > 1 ? part_tiles * RM_PART_BYTES : 0);
+    ws.take(L.off_centre, L.Ftot * 4 * 8);
+    ws.take(L.off_gpart, (size_t)L.nchunks * Fpad * 8);
+    ws.take(L.off_g, Fpad * 8);
+    ws.take(L.off_origin, 4 * 8);
+    ws.take(L.off_flags, 16);
+    ws.take(L.off_part, ksK > 1 ? part_tiles * RM_PART_BYTES : 0);
+    L.bytes = ws.bytes;
     return L;
 }
 
@@ -100,62 +96,9 @@ struct PackIn {
     const uint64_t *idx;
     const Real *mass;
     uint32_t n;
+    // frame f of both blocks, the second behind the first
+    __device__ __forceinline__ const Real *frame(size_t f) const { return f < F1 ? frames1 + f * stride1 : frames2 + (f - F1) * stride2; }
 };
-
-template <class Real>
-__device__ __forceinline__ const Real *frame_ptr(const PackIn<Real> &P, size_t f) {
-    return f < P.F1 ? P.frames1 + f * P.stride1 : P.frames2 + (f - P.F1) * P.stride2;
-}
-
-// One workgroup per frame (of both blocks): {sum w p / sum w, sum w}.  Thread t adds atoms t, t + 256, ... in that order,
-// then a fixed tree: every frame's sum of the weights has the same bits.  flags[0]: an index is not below natoms.
-template <class Real>
-__global__ void __launch_bounds__(256) rm_centre_kernel(PackIn<Real> P, double *__restrict__ centre, uint32_t *__restrict__ flags) {
-    __shared__ double sh[4][256];
-    const size_t f = blockIdx.x;
-    const Real *p = frame_ptr(P, f);
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (uint32_t k = threadIdx.x; k < P.n; k += 256u) {
-        const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
-        if (a >= P.natoms) {
-            flags[0] = 1u;
-            continue;
-        }
-        const double w = P.mass ? (double)P.mass[a] : 1.0;
-        s[0] += w * (double)p[3 * a];
-        s[1] += w * (double)p[3 * a + 1];
-        s[2] += w * (double)p[3 * a + 2];
-        s[3] += w;
-    }
-#pragma unroll
-    for (int d = 0; d < 4; ++d) sh[d][threadIdx.x] = s[d];
-    __syncthreads();
-    for (uint32_t w = 128u; w > 0u; w >>= 1) {
-        if (threadIdx.x < w)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) sh[d][threadIdx.x] += sh[d][threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x < 4u) centre[f * 4 + threadIdx.x] = threadIdx.x < 3u ? sh[threadIdx.x][0] / sh[3][0] : sh[3][0];
-}
-
-// The common origin of the mode without a fit: the centre of frame 0 of the first block; should that frame hold a
-// non-finite coordinate, the first centre that is finite (zeros when there is none), so that the other frames stay right.
-__global__ void rm_origin_kernel(const double *__restrict__ centre, size_t F1, double *__restrict__ origin) {
-    double o[3] = {0.0, 0.0, 0.0};
-    for (size_t f = 0; f < F1; ++f) {
-        const double x = centre[f * 4], y = centre[f * 4 + 1], z = centre[f * 4 + 2];
-        if (isfinite(x) && isfinite(y) && isfinite(z)) {
-            o[0] = x;
-            o[1] = y;
-            o[2] = z;
-            break;
-        }
-    }
-    origin[0] = o[0];
-    origin[1] = o[1];
-    origin[2] = o[2];
-}
 
 // Workgroup (chunk, tile) of one block: thread t holds frame t & 15 of the tile and atoms (t >> 4) + 16 i of the chunk, so
 // that 16 lanes store 128 contiguous bytes.  q = sqrt(w) (p - c) in f64 from the exact inputs; the squares of the chunk go
@@ -171,7 +114,7 @@ __global__ void __launch_bounds__(256) rm_pack_kernel(PackIn<Real> P, int block2
     const size_t fb = (size_t)tile * RM_TILE + fl;            // frame within its block
     const bool live = fb < F;
     const size_t f = block2 ? P.F1 + fb : fb;                 // frame among both blocks
-    const Real *p = live ? frame_ptr(P, f) : nullptr;
+    const Real *p = live ? P.frame(f) : nullptr;
     double c[3] = {0.0, 0.0, 0.0};
     if (live) {
         const double *src = origin ? origin : centre + f * 4;
@@ -186,9 +129,9 @@ __global__ void __launch_bounds__(256) rm_pack_kernel(PackIn<Real> P, int block2
     for (size_t k = k0 + kk; k < k1; k += 16u) {
         double q[3] = {0.0, 0.0, 0.0};
         if (live && k < P.n) {
-            const uint64_t a = P.idx ? P.idx[k] : (uint64_t)k;
+            const uint64_t a = sel_atom(P, k);
             if (a < P.natoms) {
-                const double sw = sqrt(P.mass ? (double)P.mass[a] : 1.0);
+                const double sw = sqrt(P.mass ? (double)P.mass[a] : 1.0);      // (sel_weight written out: through it the kernel's scalar loads are grouped otherwise)
 #pragma unroll
                 for (int d = 0; d < 3; ++d) q[d] = sw * ((double)p[3 * a + d] - c[d]);
             }
@@ -315,7 +258,7 @@ __global__ void __launch_bounds__(64 * RM_ROWS) rm_gram_kernel(GramP Q, FinishP<
                         for (int r = 0; r < 4; ++r) v = jr == (uint32_t)(j * 4 + r) ? acc[j][d][e][r] : v;
                     S[d * 3 + e] = v;
                 }
-            rm_finish_pair<Real>(P, (size_t)ta * RM_TILE + (lane >> 4) + 4u * (jr & 3u), (size_t)(tb0 + (jr >> 2)) * RM_TILE + (lane & 15u), S);
+            rm_finish_pair<Real>(P, mfma_c_row((size_t)ta * RM_TILE, lane, jr & 3u), mfma_c_col((size_t)(tb0 + (jr >> 2)) * RM_TILE, lane), S);
         }
     } else {
         const size_t npairs = (size_t)Q.T1 * Q.T2p;
@@ -340,7 +283,7 @@ __global__ void __launch_bounds__(256) rm_finish_kernel(const double *__restrict
     const size_t pair = blockIdx.x;
     const uint32_t ta = (uint32_t)(pair / T2p), tb = (uint32_t)(pair % T2p);
     const uint32_t lane = threadIdx.x & 63u, r = threadIdx.x >> 6;
-    const size_t a = (size_t)ta * RM_TILE + (lane >> 4) + 4u * r, b = (size_t)tb * RM_TILE + (lane & 15u);
+    const size_t a = mfma_c_row((size_t)ta * RM_TILE, lane, r), b = mfma_c_col((size_t)tb * RM_TILE, lane);
     if (a >= P.F1 || b >= P.F2 || (P.sym && b < a)) return;
     const size_t npairs = (size_t)T1 * T2p;
     double S[9];
@@ -362,29 +305,17 @@ int rmsd_matrix_run(molar_hip_ctx *c, const char *who, const Real *frames1, size
     const size_t F1 = nframes1, F2 = sym ? 0 : nframes2, cols = sym ? nframes1 : nframes2;
     if (n == 0) return fail(MOLAR_HIP_ERR_SIZES, "%s: empty selection", who);
     if (ld < cols) return fail(MOLAR_HIP_ERR_SIZES, "%s: ld = %zu is below the %zu columns of the result", who, ld, cols);
-    if (!idx && n > natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: n = %zu exceeds natoms = %zu and there is no index", who, n, natoms);
-    if ((F1 > 1 && stride1 < natoms * 3) || (F2 > 1 && stride2 < natoms * 3))
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a frame stride is below 3 * natoms = %zu", who, natoms * 3);
+    MH_TRY(check_no_index(who, "n", idx, n, natoms));
+    MH_TRY(check_stride(who, "a frame stride", F1, stride1, natoms));
+    MH_TRY(check_stride(who, "a frame stride", F2, stride2, natoms));
     if (n >= 0x7FFFFFFCull || F1 >= 0x7FFFFFF0ull || F2 >= 0x7FFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: more than 2^31 atoms or frames", who);
     if (F1 == 0 || cols == 0) return MOLAR_HIP_OK;
     if (!frames1 || !out) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: frames or output pointer is null", who);
-    if (idx && !is_device_ptr(idx))
-        for (size_t k = 0; k < n; ++k)
-            if (idx[k] >= natoms) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: idx[%zu] = %llu is not below natoms = %zu", who, k, (unsigned long long)idx[k], natoms);
+    MH_TRY(check_index(who, "idx", idx, n, natoms));
     const Layout L = make_layout(F1, F2, n);
     if (L.T1p > 65535u || L.T2p > 65535u) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: a block of more than %u frames", who, 65534u * RM_TILE);
-    if (!c->rmsdm) c->rmsdm = new molar_hip_rmsd_matrix_state;
-    molar_hip_rmsd_matrix_state &Z = *c->rmsdm;
-    if (L.bytes > Z.ws.cap) {
-        Z.ws.release();
-        void *p = nullptr;
-        if (hipMalloc(&p, L.bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: the workspace of %zu bytes cannot be allocated", who, L.bytes);
-        }
-        Z.ws.p = p;
-        Z.ws.cap = L.bytes;
-    }
+    molar_hip_rmsd_matrix_state &Z = state_of(c->rmsdm);
+    MH_TRY(grow_exact(Z.ws, L.bytes, who, "the workspace"));
     char *W = Z.ws.as<char>();
     double *packed1 = reinterpret_cast<double *>(W + L.off_packed1);
     double *packed2 = sym ? packed1 : reinterpret_cast<double *>(W + L.off_packed2);
@@ -408,8 +339,8 @@ int rmsd_matrix_run(molar_hip_ctx *c, const char *who, const Real *frames1, size
     P.n = (uint32_t)n;
 
     MH_HIP(hipMemsetAsync(flags, 0, 16, c->stream));
-    hipLaunchKernelGGL(rm_centre_kernel<Real>, dim3((uint32_t)L.Ftot), dim3(256), 0, c->stream, P, centre, flags);
-    if (!fit) hipLaunchKernelGGL(rm_origin_kernel, dim3(1), dim3(1), 0, c->stream, centre, F1, origin);
+    hipLaunchKernelGGL(tb_centre_kernel<PackIn<Real>>, dim3((uint32_t)L.Ftot), dim3(256), 0, c->stream, P, centre, flags);
+    if (!fit) hipLaunchKernelGGL(tb_origin_kernel<>, dim3(1), dim3(1), 0, c->stream, centre, F1, origin);
     // the weights' sum and the index check decide the status, read back before the products are enqueued
     MH_TRY(check_selection(c, flags, centre + 3, who, natoms));
 
@@ -435,6 +366,7 @@ int rmsd_matrix_run(molar_hip_ctx *c, const char *who, const Real *frames1, size
         Fp.out = out;
         Fp.ld = ld;
     } else {
+        // not out_buffer: reserve adds headroom and reports MOLAR_HIP_ERR_HIP, which callers of this entry may rely on
         MH_TRY(Z.out.reserve(F1 * cols * sizeof(Real)));
         Fp.out = Z.out.as<Real>();
         Fp.ld = cols;
@@ -473,9 +405,7 @@ namespace mh {
 void rmsd_matrix_release(molar_hip_ctx *c) {
     if (!c->rmsdm) return;
     molar_hip_rmsd_matrix_state &Z = *c->rmsdm;
-    for (DevBuf *b : {&Z.in_frames1, &Z.in_frames2, &Z.in_idx, &Z.in_mass, &Z.ws, &Z.out}) b->release();
-    delete c->rmsdm;
-    c->rmsdm = nullptr;
+    release_state(c->rmsdm, {&Z.in_frames1, &Z.in_frames2, &Z.in_idx, &Z.in_mass, &Z.ws, &Z.out});
 }
 }  // namespace mh
 

@@ -75,6 +75,19 @@ def test_search_sizes_cpu():
     assert r.returncode == 0 and "all search-sizes tests passed" in r.stdout, r.stdout + r.stderr
 
 
+def test_traj_block_cpu():
+    """molar_amd/csrc/traj_block.hpp on the host (hipcc, no GPU needed to run): the carving of a workspace and the K splits against
+    the text the three trajectory-block units had of their own, the host checks of a selection with their message texts."""
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, "test_traj_block")
+    cmd = ["/opt/rocm/bin/hipcc", "-x", "hip", "--offload-arch=gfx950", "-O2", "-ffp-contract=off", "-std=c++17",
+           os.path.join(ROOT, "tests", "cpp", "test_traj_block.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "all traj-block tests passed" in r.stdout, r.stdout + r.stderr
+
+
 @pytest.mark.gpu
 def test_host_api_gpu():
     from oracle import oracle as o

@@ -3,7 +3,7 @@
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/prof_fluct.py b 10
 
-The per-kernel times of the stats file (fl_centre / fl_fit_sums / fl_rotation / fl_sums / fl_mean / fl_rmsf / fl_pack / fl_cov /
+The per-kernel times of the stats file (tb_centre / fl_fit_sums / fl_rotation / fl_sums / fl_mean / fl_rmsf / fl_pack / fl_cov /
 fl_cov_finish) say what part of the call's time each stage takes; bench_fluct.py itself only times the whole call.
 Usage: prof_fluct.py SHAPE [reps]"""
 import os

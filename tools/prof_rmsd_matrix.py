@@ -3,7 +3,7 @@
 
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- python tools/prof_rmsd_matrix.py a 10
 
-The per-kernel times of the stats file (rm_centre / rm_pack / rm_g / rm_gram / rm_finish) say what part of the call's time
+The per-kernel times of the stats file (tb_centre / rm_pack / rm_g / rm_gram / rm_finish) say what part of the call's time
 each stage takes; bench_rmsd_matrix.py itself only times the whole call.  Usage: prof_rmsd_matrix.py SHAPE [reps]"""
 import os
 import sys
