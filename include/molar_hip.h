@@ -328,6 +328,65 @@ int molar_hip_search_contacts_frames(molar_hip_ctx *ctx, const molar_hip_search_
                                      size_t nframes, size_t xyz1_stride, size_t xyz2_stride, const float *boxes9,
                                      uint64_t *deg1, uint64_t *deg2, uint64_t *map, uint32_t *occupancy);
 
+/* ------------------------------------------------------------------ hydrogen bonds
+ * The third consumer of the two-set search, with the geometric definition GROMACS (gmx hbond), MDAnalysis
+ * (HydrogenBondAnalysis) and VMD (hbonds) share; the reference has no such routine.  One frame and three selections: the
+ * donors are set 1 of a request of kind MOLAR_HIP_SEARCH_DOUBLE, the acceptors its set 2 - of the SAME frame array (xyz2 == xyz1,
+ * natoms2 == natoms1) - and the donors' hydrogens a CSR over the donors: the hydrogens of the donor at position p of set 1 are
+ * the atoms h_idx[h_offsets[p] .. h_offsets[p + 1]) of the frame (none, one or several; nh = h_offsets[n1] entries in all).
+ * (D, H, A) is a hydrogen bond when
+ *   1. (D, A) is in the list L the search described by `desc` emits (its f32 predicate d2 <= cutoff^2, its grid, plan and wrap
+ *      rules; L taken as a SET: its duplicates do not count twice),
+ *   2. D and A are not the same atom of the frame,
+ *   3. in f64 from the f32 coordinates, with minimum-image vectors over desc->pbc when there is a box (boxmath.hpp in double):
+ *      MOLAR_HIP_HBOND_DHA_MIN: angle(D-H-A) >= angle_deg (MDAnalysis / VMD, usually 150);
+ *      MOLAR_HIP_HBOND_HDA_MAX: angle(H-D-A) <= angle_deg (GROMACS, usually 30);
+ *      a triple with a zero-length arm (H on D, or H on A) is never a bond,
+ *   4. with max_ha > 0: |H -> A| <= max_ha.
+ * The result is the sorted set of triples, ordered by (position of D in set 1, position of H in the CSR, position of A in set 2),
+ * as frame atom indices uint32 [count][3], with the optional f64 columns dist_da = |D -> A|, dist_ha = |H -> A| and the angle of the
+ * chosen kind in degrees (atan2(|u x v|, u . v)).  Integer atomics only and a sort: the same call gives the same bits.
+ *
+ * molar_hip_hbonds_count runs the search and the stages and keeps the result in the context; molar_hip_hbonds_fill copies it out
+ * (each destination host or device memory, or NULL).  molar_hip_hbonds_counts does the same and adds, for every bond, 1 to
+ * don_count[position of D] (length n1), acc_count[position of A] (length n2) and map[group1[D's position]][group2[A's position]]
+ * (ngroups1 x ngroups2, row-major) - uint64, accumulated INTO, host or device memory, any of them NULL; label rules and the 2^24
+ * cap of the map as for molar_hip_search_contacts.  Its result can be filled as well.
+ *
+ * molar_hip_hbonds_frames walks a block of frames one after the other (layout of molar_hip_search_histogram_frames: frame k at
+ * desc->xyz1 + k * xyz_stride floats, box of frame k at boxes9 + 9 k, NULL: desc->box9 for every frame).  per_frame[k] is set to
+ * the bonds of frame k (uint64, host or device); the counts accumulate over the frames; *out_total is the number of entries and
+ * *out_unique the number of rows of the bond table.  Kept on the device for molar_hip_hbonds_frames_fill: the frames' lists one
+ * after the other (frame_offsets[nframes + 1], uint64) with their columns, the TABLE of the block - the sorted distinct triples,
+ * in the order above - with occupancy[row] = the number of frames the bond is present in (uint32), and bond_of_entry[entry] =
+ * the table row of every entry (uint32): the sparse presence matrix frames x bonds.
+ *
+ * The calls replace the context's cached search like any other search (they run the resident two-set search for the (i, j) plane
+ * and leave the setting of molar_hip_search_resident_planes as it was), and each form replaces the hydrogen-bond result of the
+ * other.  Every call waits for its result.  f32 only.
+ *   INVALID_ARGUMENT  a kind other than DOUBLE; xyz2 != xyz1 or natoms2 != natoms1; an h_idx entry >= natoms; h_offsets that do not
+ *                     start at 0, decrease, or do not end at nh; angle_deg outside [0, 180]; max_ha < 0; an unknown angle kind; a
+ *                     map without labels, a label >= ngroups; pipelined searches in flight (molar_hip_search_resident_begin)
+ *   TOO_LARGE         nh or the acceptors >= 2^32; 2^31 - 1 entries or more in a frame or a block; ngroups1 * ngroups2 > 2^24
+ *   NO_SEARCH         a fill without the count of its form
+ * A request that is refused adds nothing to any output. */
+enum {
+    MOLAR_HIP_HBOND_DHA_MIN = 0,
+    MOLAR_HIP_HBOND_HDA_MAX = 1
+};
+int molar_hip_hbonds_count(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const uint64_t *h_offsets, const uint64_t *h_idx,
+                           size_t nh, int32_t angle_kind, double angle_deg, double max_ha, uint64_t *out_count);
+int molar_hip_hbonds_fill(molar_hip_ctx *ctx, uint32_t *triples, double *dist_da, double *dist_ha, double *angle_deg);
+int molar_hip_hbonds_counts(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const uint64_t *h_offsets, const uint64_t *h_idx,
+                            size_t nh, int32_t angle_kind, double angle_deg, double max_ha, const molar_hip_contact_groups *groups,
+                            uint64_t *don_count, uint64_t *acc_count, uint64_t *map, uint64_t *out_count);
+int molar_hip_hbonds_frames(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const uint64_t *h_offsets, const uint64_t *h_idx,
+                            size_t nh, int32_t angle_kind, double angle_deg, double max_ha, size_t nframes, size_t xyz_stride,
+                            const float *boxes9, const molar_hip_contact_groups *groups, uint64_t *per_frame, uint64_t *don_count,
+                            uint64_t *acc_count, uint64_t *map, uint64_t *out_total, uint64_t *out_unique);
+int molar_hip_hbonds_frames_fill(molar_hip_ctx *ctx, uint64_t *frame_offsets, uint32_t *triples, double *dist_da, double *dist_ha,
+                                 double *angle_deg, uint32_t *bond_of_entry, uint32_t *table, uint32_t *occupancy);
+
 /* ---- the drivers for MolAR built with its `f64` feature (Float = f64, aliases.rs:10-13): every operation in double -
  * cell assignment, the predicate d2 <= cutoff^2 and the distances - results as (usize, usize, f64) columns or usize ids.
  * Same request / count-then-fill convention as above.  Coordinates, index lists, radii and the result columns may be host or

@@ -597,6 +597,103 @@ inline MsdOf<double> msd_f64(Engine &eng, const double *frames, size_t nframes, 
     return out;
 }
 
+// Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
+// donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
+// images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's
+// position in the CSR, acceptor's position).
+struct HBondOptions {
+    Float cutoff = 0.35f;
+    int32_t angle_kind = MOLAR_HIP_HBOND_DHA_MIN;
+    double angle_deg = 150.0;         // DHA_MIN: angle(D-H-A) >= angle_deg; HDA_MAX: angle(H-D-A) <= angle_deg
+    double max_ha = 0.0;              // > 0: |H -> A| <= max_ha as well
+    bool use_box = true;
+    uint8_t pbc = MOLAR_HIP_PBC_FULL;
+    bool want_columns = true;
+};
+struct HBonds {
+    std::vector<std::array<uint32_t, 3>> triples;    // (donor, hydrogen, acceptor) as atom indices
+    std::vector<double> dist_da, dist_ha, angle;     // per triple; empty unless asked for
+    std::vector<uint64_t> don_count, acc_count;      // per selected donor / acceptor (summed over the frames of a block)
+    // a block of frames only:
+    std::vector<uint64_t> per_frame, frame_offsets;  // [nframes], [nframes + 1]: the frames' lists one after the other in `triples`
+    std::vector<std::array<uint32_t, 3>> table;      // the block's distinct bonds, in the order of the triples
+    std::vector<uint32_t> occupancy, bond_of_entry;  // frames a table row is present in; the table row of every entry
+};
+namespace detail {
+inline molar_hip_search_desc hbonds_desc(const SelBound &donors, const SelBound &acceptors, const HBondOptions &opt, const std::vector<usize> &h_offsets,
+                                         const float *xyz) {
+    if (&donors.system() != &acceptors.system() || donors.ctx() != acceptors.ctx())
+        throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "hbonds: donors and acceptors are selections of one system and one engine");
+    if (h_offsets.size() != donors.len() + 1) throw MolarError(MOLAR_HIP_ERR_SIZES, "hbonds: h_offsets has not donors.len() + 1 entries");
+    molar_hip_search_desc d{};
+    d.kind = MOLAR_HIP_SEARCH_DOUBLE;
+    d.cutoff = opt.cutoff;
+    d.xyz1 = d.xyz2 = xyz;
+    d.natoms1 = d.natoms2 = donors.natoms();
+    d.idx1 = donors.get_index_slice().data();
+    d.n1 = donors.len();
+    d.idx2 = acceptors.get_index_slice().data();
+    d.n2 = acceptors.len();
+    d.pbc = opt.pbc;
+    return d;
+}
+}  // namespace detail
+inline HBonds hbonds(const SelBound &donors, const SelBound &acceptors, const std::vector<usize> &h_offsets, const std::vector<usize> &h_idx,
+                     const HBondOptions &opt = HBondOptions()) {
+    molar_hip_search_desc d = detail::hbonds_desc(donors, acceptors, opt, h_offsets, donors.coords_ptr());
+    if (opt.use_box) d.box9 = donors.require_box().colmajor9();
+    HBonds out;
+    out.don_count.assign(donors.len(), 0);
+    out.acc_count.assign(acceptors.len(), 0);
+    uint64_t n = 0;
+    check(molar_hip_hbonds_counts(donors.ctx(), &d, h_offsets.data(), h_idx.data(), h_idx.size(), opt.angle_kind, opt.angle_deg, opt.max_ha, nullptr,
+                                  out.don_count.data(), out.acc_count.data(), nullptr, &n));
+    out.triples.resize(n);
+    if (opt.want_columns) {
+        out.dist_da.resize(n);
+        out.dist_ha.resize(n);
+        out.angle.resize(n);
+    }
+    if (n)
+        check(molar_hip_hbonds_fill(donors.ctx(), &out.triples[0][0], opt.want_columns ? out.dist_da.data() : nullptr,
+                                    opt.want_columns ? out.dist_ha.data() : nullptr, opt.want_columns ? out.angle.data() : nullptr));
+    return out;
+}
+// the same for a block of frames (whole frames one after the other, donors.natoms() positions each; `boxes`: one column-major
+// box9 per frame, null: the state's box for every frame when opt.use_box)
+inline HBonds hbonds_frames(const SelBound &donors, const SelBound &acceptors, const std::vector<Pos> &frames, const std::vector<usize> &h_offsets,
+                            const std::vector<usize> &h_idx, const Float *boxes = nullptr, const HBondOptions &opt = HBondOptions()) {
+    const size_t natoms = donors.natoms();
+    if (natoms == 0 || frames.size() % natoms) throw MolarError(MOLAR_HIP_ERR_SIZES, "hbonds_frames: the block is not a whole number of frames");
+    const size_t F = frames.size() / natoms;
+    HBonds out;
+    out.don_count.assign(donors.len(), 0);
+    out.acc_count.assign(acceptors.len(), 0);
+    out.per_frame.assign(F, 0);
+    out.frame_offsets.assign(F + 1, 0);
+    if (F == 0) return out;
+    molar_hip_search_desc d = detail::hbonds_desc(donors, acceptors, opt, h_offsets, &frames[0].x);
+    if (boxes) d.box9 = boxes;
+    else if (opt.use_box) d.box9 = donors.require_box().colmajor9();
+    uint64_t n = 0, rows = 0;
+    check(molar_hip_hbonds_frames(donors.ctx(), &d, h_offsets.data(), h_idx.data(), h_idx.size(), opt.angle_kind, opt.angle_deg, opt.max_ha, F,
+                                  natoms * 3, boxes, nullptr, out.per_frame.data(), out.don_count.data(), out.acc_count.data(), nullptr, &n, &rows));
+    out.triples.resize(n);
+    out.bond_of_entry.resize(n);
+    out.table.resize(rows);
+    out.occupancy.resize(rows);
+    if (opt.want_columns) {
+        out.dist_da.resize(n);
+        out.dist_ha.resize(n);
+        out.angle.resize(n);
+    }
+    check(molar_hip_hbonds_frames_fill(donors.ctx(), out.frame_offsets.data(), n ? &out.triples[0][0] : nullptr,
+                                       n && opt.want_columns ? out.dist_da.data() : nullptr, n && opt.want_columns ? out.dist_ha.data() : nullptr,
+                                       n && opt.want_columns ? out.angle.data() : nullptr, n ? out.bond_of_entry.data() : nullptr,
+                                       rows ? &out.table[0][0] : nullptr, rows ? out.occupancy.data() : nullptr));
+    return out;
+}
+
 // The per-frame fit of an AnalysisTask whose States live in host memory (analysis_task.rs:245-252 hands them over frame by frame),
 // at the rate the SELECTION crosses the link: molar_hip_fit_stream_*.  Built on the selection and the reference once;
 //     auto t1 = fs.begin(state_k1.coords);  FitRecord r = fs.end(t0);      // up to three frames in flight

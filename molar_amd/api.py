@@ -782,6 +782,115 @@ class Engine:
         self._keep = keep
         return Contacts(None, deg1, deg2, cmap, occupancy)
 
+    # ------------------------------------------------------------ hydrogen bonds
+    def _hbonds_request(self, donors, hydrogens, acceptors, cutoff, pbc, angle, angle_kind, natoms):
+        donors = _sel(donors); acceptors = _sel(acceptors)
+        d, keep = self._contacts_desc(SEARCH_DOUBLE, cutoff, None, donors, None, acceptors, pbc)
+        d.natoms1 = d.natoms2 = int(natoms)
+        n1 = d.n1 if donors is not None else d.natoms1
+        n2 = d.n2 if acceptors is not None else d.natoms2
+        off, hidx = hydrogens_csr(hydrogens, n1)
+        kind = {"dha": HBOND_DHA_MIN, "hda": HBOND_HDA_MAX}.get(angle_kind, angle_kind)
+        (oa, ko), (ha, kh) = _addr(off), _addr(hidx)
+        keep += [ko, kh]
+        req = (oa, ha if hidx.shape[0] else None, int(hidx.shape[0]), int(kind), float(angle))
+        return d, keep, n1, n2, req
+
+    @staticmethod
+    def _hbonds_groups(group1, ngroups1, group2, ngroups2, keep):
+        group1 = _u32(group1); group2 = _u32(group2)
+        if group1 is None:
+            return None
+        g = ContactGroups()
+        (g.group1, k1), (g.group2, k2) = _addr(group1), _addr(group2)
+        g.ngroups1, g.ngroups2 = int(ngroups1), int(ngroups2)
+        keep += [k1, k2, g]
+        return C.byref(g)
+
+    def hbonds(self, xyz, donors, hydrogens, acceptors, box=None, pbc=7, cutoff=0.35, angle=150.0, angle_kind="dha", max_ha=0.0,
+               group1=None, ngroups1=0, group2=None, ngroups2=0, don_count=None, acc_count=None, cmap=None, want_counts=True,
+               want_map=None, want_columns=True):
+        """Hydrogen bonds of one frame (molar_hip_hbonds_counts + _fill; the definition is in include/molar_hip.h).  `donors` /
+        `acceptors`: atom indices into `xyz` (None: every atom); `hydrogens`: one atom index per donor, a list of lists, or
+        the CSR (offsets, idx) over the donors.  angle_kind "dha": angle(D-H-A) >= angle; "hda": angle(H-D-A) <= angle;
+        max_ha > 0 adds |H-A| <= max_ha.  `pbc` counts only with a box.  don_count / acc_count / cmap (uint64 numpy or int64
+        CUDA tensors) are accumulated into; missing ones are made as zeros when wanted (CUDA tensors when xyz is one).
+        Returns an `HBonds`; with xyz a CUDA tensor its arrays are CUDA tensors (triples int32, columns float64)."""
+        xyz = _f32(xyz)
+        d, keep, n1, n2, req = self._hbonds_request(donors, hydrogens, acceptors, cutoff, pbc, angle, angle_kind, xyz.shape[-2])
+        d.xyz1 = d.xyz2 = _addr(xyz)[0]
+        keep.append(xyz)
+        if box is not None:
+            ba, kb = self._box9(box)
+            keep.append(kb)
+            d.box9 = ba
+        if want_map is None:
+            want_map = group1 is not None
+        don_count = self._contacts_out(don_count, want_counts, (n1,), xyz)
+        acc_count = self._contacts_out(acc_count, want_counts, (n2,), xyz)
+        cmap = self._contacts_out(cmap, want_map, (int(ngroups1), int(ngroups2)), xyz)
+        g = self._hbonds_groups(group1, ngroups1, group2, ngroups2, keep)
+        cnt = C.c_uint64(0)
+        check(self.lib.molar_hip_hbonds_counts(self.ctx, C.byref(d), req[0], req[1], req[2], req[3], req[4], float(max_ha), g,
+                                               _addr(don_count)[0], _addr(acc_count)[0], _addr(cmap)[0], C.byref(cnt)))
+        self._keep = keep
+        n = int(cnt.value)
+        triples, cols = _hbonds_arrays(n, xyz, 3 if want_columns else 0)
+        check(self.lib.molar_hip_hbonds_fill(self.ctx, _addr(triples)[0] if n else None, *[_addr(a)[0] if n else None for a in cols]))
+        cols += [None] * (3 - len(cols))
+        return HBonds(n, triples, cols[0], cols[1], cols[2], don_count, acc_count, cmap)
+
+    def hbonds_frames(self, frames, donors, hydrogens, acceptors, box=None, pbc=7, cutoff=0.35, angle=150.0, angle_kind="dha", max_ha=0.0,
+                      group1=None, ngroups1=0, group2=None, ngroups2=0, don_count=None, acc_count=None, cmap=None, want_counts=True,
+                      want_map=None):
+        """Hydrogen bonds of a block of frames (molar_hip_hbonds_frames + _frames_fill): `frames` = [nframes, natoms, 3] float32
+        (numpy or a CUDA tensor, frames may have a gap between them), `box` one 3x3 matrix or [nframes, 3, 3].  The counts are
+        summed over the frames.  Returns an `HBondsBlock`: the frames' lists one after the other (`frame_offsets`), the table
+        of the block's distinct bonds with `occupancy` (frames present) and `bond_of_entry` (table row of every entry)."""
+        if _is_torch(frames) and frames.ndim == 3 and frames.stride(2) == 1 and frames.stride(1) == 3:
+            import torch
+            assert frames.dtype == torch.float32
+            stride = int(frames.stride(0))
+        else:
+            frames = _f32(frames)
+            assert frames.ndim == 3 and frames.shape[2] == 3
+            stride = int(frames.shape[1]) * 3
+        nframes = int(frames.shape[0])
+        d, keep, n1, n2, req = self._hbonds_request(donors, hydrogens, acceptors, cutoff, pbc, angle, angle_kind, frames.shape[1])
+        d.xyz1 = d.xyz2 = frames.data_ptr() if _is_torch(frames) else frames.ctypes.data
+        keep.append(frames)
+        boxes_ptr = None
+        if box is not None:
+            b = np.asarray(box.get_matrix() if isinstance(box, PeriodicBox) else box, np.float32)
+            if b.ndim == 3:
+                b9 = np.ascontiguousarray(np.transpose(b, (0, 2, 1))).reshape(nframes, 9)      # column-major per frame
+                boxes_ptr = b9.ctypes.data
+            else:
+                b9 = np.ascontiguousarray(b.reshape(3, 3).T).reshape(9)
+            d.box9 = b9.ctypes.data
+            keep.append(b9)
+        if want_map is None:
+            want_map = group1 is not None
+        don_count = self._contacts_out(don_count, want_counts, (n1,), frames)
+        acc_count = self._contacts_out(acc_count, want_counts, (n2,), frames)
+        cmap = self._contacts_out(cmap, want_map, (int(ngroups1), int(ngroups2)), frames)
+        g = self._hbonds_groups(group1, ngroups1, group2, ngroups2, keep)
+        per_frame = np.zeros(nframes, np.uint64)
+        total, unique = C.c_uint64(0), C.c_uint64(0)
+        check(self.lib.molar_hip_hbonds_frames(self.ctx, C.byref(d), req[0], req[1], req[2], req[3], req[4], float(max_ha), nframes, stride,
+                                               boxes_ptr, g, per_frame.ctypes.data if nframes else None, _addr(don_count)[0],
+                                               _addr(acc_count)[0], _addr(cmap)[0], C.byref(total), C.byref(unique)))
+        self._keep = keep
+        n, rows = int(total.value), int(unique.value)
+        frame_offsets = np.zeros(nframes + 1, np.uint64)
+        triples, cols = _hbonds_arrays(n, frames, 3)
+        table, _ = _hbonds_arrays(rows, frames, 0)
+        boe, occ = _hbonds_u32(n, frames), _hbonds_u32(rows, frames)
+        a = lambda x, m: _addr(x)[0] if m else None
+        check(self.lib.molar_hip_hbonds_frames_fill(self.ctx, frame_offsets.ctypes.data, a(triples, n), a(cols[0], n), a(cols[1], n), a(cols[2], n),
+                                                    a(boe, n), a(table, rows), a(occ, rows)))
+        return HBondsBlock(per_frame, frame_offsets, triples, cols[0], cols[1], cols[2], table, occ, boe, don_count, acc_count, cmap)
+
     # ------------------------------------------------------------ surface area
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Per-atom solvent-accessible surface area by Shrake-Rupley (molar_hip_sasa; the definition is in
@@ -1234,6 +1343,76 @@ class Contacts:
 
     def __init__(self, count, deg1, deg2, cmap, occupancy=None):
         self.count, self.deg1, self.deg2, self.map, self.occupancy = count, deg1, deg2, cmap, occupancy
+
+
+HBOND_DHA_MIN, HBOND_HDA_MAX = 0, 1
+
+
+class HBonds:
+    """Hydrogen bonds of a frame: `count`; `triples` [count, 3] (donor, hydrogen, acceptor as atom indices of the frame, sorted by
+    the donor's position in its selection, the hydrogen's position in the donors' CSR, the acceptor's position); the float64
+    columns `dist_da`, `dist_ha`, `angle` (degrees; of the kind that was asked for); `don_count` / `acc_count` per selected donor /
+    acceptor and `map` (donor group x acceptor group)."""
+
+    def __init__(self, count, triples, dist_da, dist_ha, angle, don_count, acc_count, cmap):
+        self.count, self.triples, self.dist_da, self.dist_ha, self.angle = count, triples, dist_da, dist_ha, angle
+        self.don_count, self.acc_count, self.map = don_count, acc_count, cmap
+
+
+class HBondsBlock:
+    """Hydrogen bonds of a block of frames: `per_frame` counts; the lists of the frames one after the other (`triples` and the
+    columns, frame f at frame_offsets[f] : frame_offsets[f + 1]); `table` [unique, 3] - the block's distinct bonds in the order
+    of HBonds.triples - with `occupancy` (frames in which the bond is present) and `bond_of_entry` (table row of every entry:
+    the sparse presence matrix frames x bonds); the counts summed over the frames."""
+
+    def __init__(self, per_frame, frame_offsets, triples, dist_da, dist_ha, angle, table, occupancy, bond_of_entry, don_count, acc_count, cmap):
+        self.per_frame, self.frame_offsets = per_frame, frame_offsets
+        self.triples, self.dist_da, self.dist_ha, self.angle = triples, dist_da, dist_ha, angle
+        self.table, self.occupancy, self.bond_of_entry = table, occupancy, bond_of_entry
+        self.don_count, self.acc_count, self.map = don_count, acc_count, cmap
+
+
+def hydrogens_csr(hydrogens, ndonors):
+    """The donors' hydrogens as the CSR (offsets [ndonors + 1], idx) the C ABI takes (uint64 numpy, or int64 tensors when that is
+    what was given), from one atom index per donor (a 1-D array of ndonors entries), a list of lists (none, one or several per
+    donor), or the tuple (offsets, idx) itself."""
+    if isinstance(hydrogens, tuple):
+        if len(hydrogens) != 2:
+            raise ValueError("hydrogens: a tuple is (offsets, idx)")
+        off, idx = _u64(hydrogens[0]), _u64(hydrogens[1])
+        if off.ndim != 1 or idx.ndim != 1 or off.shape[0] != ndonors + 1:
+            raise ValueError(f"hydrogens: {ndonors} donors need {ndonors + 1} offsets")
+        return off, idx
+    if _is_torch(hydrogens) or (isinstance(hydrogens, np.ndarray) and hydrogens.dtype != object):
+        idx = _u64(hydrogens)
+        if idx.ndim != 1 or idx.shape[0] != ndonors:
+            raise ValueError(f"hydrogens: one index per donor means {ndonors} entries")
+        return np.arange(ndonors + 1, dtype=np.uint64), idx
+    rows = list(hydrogens)
+    if len(rows) != ndonors:
+        raise ValueError(f"hydrogens: {len(rows)} entries for {ndonors} donors")
+    if all(np.ndim(r) == 0 for r in rows):
+        return np.arange(ndonors + 1, dtype=np.uint64), np.asarray(rows, dtype=np.uint64).reshape(ndonors)
+    rows = [np.atleast_1d(np.asarray(r, dtype=np.uint64)) for r in rows]
+    off = np.zeros(ndonors + 1, np.uint64)
+    np.cumsum([r.shape[0] for r in rows], out=off[1:])
+    return off, (np.concatenate(rows) if rows else np.zeros(0, np.uint64)).astype(np.uint64)
+
+
+def _hbonds_arrays(n, like, ncols):
+    """([n, 3] triples, ncols float64 columns) for a fill call: CUDA tensors when the coordinates are one."""
+    if _is_torch(like):
+        import torch
+        return (torch.empty((n, 3), dtype=torch.int32, device=like.device),
+                [torch.empty(n, dtype=torch.float64, device=like.device) for _ in range(ncols)])
+    return np.empty((n, 3), np.uint32), [np.empty(n, np.float64) for _ in range(ncols)]
+
+
+def _hbonds_u32(n, like):
+    if _is_torch(like):
+        import torch
+        return torch.empty(n, dtype=torch.int32, device=like.device)
+    return np.empty(n, np.uint32)
 
 
 class Sasa:
@@ -2307,6 +2486,53 @@ def contacts(cutoff, sel1: Sel, sel2: Sel | None = None, dims=None, groups1=None
         return eng.search_contacts(SEARCH_DOUBLE, cutoff, sel1.state.coords, sel1.index, sel2.state.coords, sel2.index, box=box, pbc=pbc,
                                    group1=g1, ngroups1=ng1, group2=g2, ngroups2=ng2)
     return eng.search_contacts(SEARCH_SINGLE, cutoff, sel1.state.coords, sel1.index, box=box, pbc=pbc, group1=g1, ngroups1=ng1)
+
+
+def hbond_donors(sel_heavy: Sel, sel_h: Sel, bond_cutoff=0.12, dims=None, search=None):
+    """The hydrogens of every atom of `sel_heavy` as the CSR (offsets, idx) that hbonds() takes: each atom of `sel_h` goes to its
+    nearest atom of `sel_heavy` within `bond_cutoff` (ties: the one listed first), found with the two-set search; a hydrogen
+    with no heavy atom in reach belongs to nobody.  `dims`: periodic dimensions (None: all three when the state has a box).
+    `search(cutoff, sel1, sel2, dims)` -> (pairs of atom indices, distances) replaces distance_search (tests)."""
+    if dims is None:
+        dims = (True, True, True) if sel_heavy.state.pbox is not None else (False, False, False)
+    pairs, dist = (search or distance_search)(bond_cutoff, sel_heavy, sel_h, dims)
+    return _donors_csr(np.asarray(sel_heavy.index, np.uint64), np.asarray(pairs, np.uint64).reshape(-1, 2), np.asarray(dist))
+
+
+def _donors_csr(heavy_index, pairs, dist):
+    pos = {int(a): p for p, a in enumerate(heavy_index)}
+    best = {}
+    for (i, j), d in zip(pairs.tolist(), dist.tolist()):
+        cand = (d, pos[i])
+        if j not in best or cand < best[j]:
+            best[j] = cand
+    rows = [[] for _ in range(len(heavy_index))]
+    for j in sorted(best):
+        rows[best[j][1]].append(j)
+    off = np.zeros(len(rows) + 1, np.uint64)
+    np.cumsum([len(r) for r in rows], out=off[1:])
+    return off, np.asarray([j for r in rows for j in r], np.uint64)
+
+
+def hbonds(donors: Sel, acceptors: Sel, hydrogens=None, dims=None, cutoff=0.35, angle=150.0, angle_kind="dha", max_ha=0.0,
+           groups1=None, groups2=None, sel_h: Sel | None = None):
+    """Hydrogen bonds between two selections of one state (Engine.hbonds).  `hydrogens`: as for Engine.hbonds; None: they are
+    found by hbond_donors(donors, sel_h) - `sel_h` is then the selection of the hydrogens.  `dims` as for contacts();
+    `groups1` / `groups2`: one label per donor / acceptor for the map.  Returns an `HBonds`."""
+    eng = donors.engine
+    pbc = pbc_mask(dims)
+    box = donors.require_box() if pbc else None
+    if hydrogens is None:
+        if sel_h is None:
+            raise ValueError("hbonds: without `hydrogens` the selection of the hydrogens (sel_h) is needed")
+        hydrogens = hbond_donors(donors, sel_h, dims=dims)
+    if (groups1 is None) != (groups2 is None):
+        raise ValueError("hbonds: labels are needed for both selections or for none")
+    g1 = None if groups1 is None else np.ascontiguousarray(groups1, np.uint32)
+    g2 = None if groups2 is None else np.ascontiguousarray(groups2, np.uint32)
+    return eng.hbonds(donors.state.coords, donors.index, hydrogens, acceptors.index, box=box, pbc=pbc, cutoff=cutoff, angle=angle,
+                      angle_kind=angle_kind, max_ha=max_ha, group1=g1, ngroups1=0 if g1 is None else int(g1.max()) + 1, group2=g2,
+                      ngroups2=0 if g2 is None else int(g2.max()) + 1)
 
 
 def fit_transform(sel1: Sel, sel2: Sel):

@@ -178,6 +178,7 @@ struct molar_hip_sasa_state;            // point tables, grid and scratch of the
 struct molar_hip_rmsd_matrix_state;     // packed operands, partial covariances and staging of the all-pairs RMSD (rmsd_matrix.hip)
 struct molar_hip_fluct_state;           // fits, packed deviations, partial covariances and staging of the fluctuations (fluct.hip)
 struct molar_hip_msd_state;             // boxes, unwrapped particle trajectories, partial lag sums and staging of the displacements (msd.hip)
+struct molar_hip_hbonds_state;          // keys, the cached bonds of a frame or a block and the block's table (hbonds.hip)
 
 // frames per launch of molar_hip_search_histogram_frames (search.hip, hist_frames_group)
 #ifndef MH_HIST_BATCH
@@ -200,6 +201,7 @@ struct molar_hip_ctx {
     molar_hip_rmsd_matrix_state *rmsdm = nullptr; // created by the first molar_hip_rmsd_matrix*
     molar_hip_fluct_state *fluct = nullptr;       // created by the first molar_hip_fluct*
     molar_hip_msd_state *msd = nullptr;           // created by the first molar_hip_msd*
+    molar_hip_hbonds_state *hbonds = nullptr;     // created by the first molar_hip_hbonds*
     // ring of pinned chunks for large results that go to pageable host memory (hoststream.hpp), allocated on first use
     void *ring[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -362,6 +364,7 @@ void sasa_release(molar_hip_ctx *c);
 void rmsd_matrix_release(molar_hip_ctx *c);
 void fluct_release(molar_hip_ctx *c);
 void msd_release(molar_hip_ctx *c);
+void hbonds_release(molar_hip_ctx *c);
 
 // RAII span: records an event pair around a group of launches when profiling is on
 struct Prof {

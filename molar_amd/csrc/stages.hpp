@@ -45,5 +45,11 @@ int device_sort_pairs_u32(hipStream_t stream, DevBuf &tmp, const uint32_t *keys_
                           uint32_t *vals_out, size_t n, int end_bit);
 int device_exclusive_sum_u32(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *in, uint32_t *out, size_t n);
 int device_exclusive_sum_u32_u64(molar_hip_ctx *c, DevBuf &tmp, const uint32_t *in, unsigned long long *out, size_t n);
+// ... and for lists of u64 keys (hbonds.hip): the sort on bits [0, end_bit), alone or carrying a u32 each; the first of every
+// run of equal neighbours (*count_dev: how many)
+int device_sort_keys_u64(hipStream_t stream, DevBuf &tmp, const uint64_t *keys_in, uint64_t *keys_out, size_t n, int end_bit);
+int device_sort_pairs_u64_u32(hipStream_t stream, DevBuf &tmp, const uint64_t *keys_in, uint64_t *keys_out, const uint32_t *vals_in,
+                              uint32_t *vals_out, size_t n, int end_bit);
+int device_unique_u64(hipStream_t stream, DevBuf &tmp, const uint64_t *in, uint64_t *out, unsigned long long *count_dev, size_t n);
 
 }  // namespace mh

@@ -592,6 +592,55 @@ impl Engine {
         Ok(count)
     }
 
+    /// Hydrogen bonds of one frame (`molar_hip_hbonds_counts` + `molar_hip_hbonds_fill`; the definition is in the header):
+    /// donors `index1` and acceptors `index2` of ONE frame `coords`, the donors' hydrogens as a CSR over the donors
+    /// (`h_offsets[ndonors + 1]`, `h_idx`: atom indices).  `angle_kind` 0: angle(D-H-A) >= `angle_deg`; 1: angle(H-D-A) <=
+    /// `angle_deg`; `max_ha` > 0 adds |H-A| <= `max_ha`.  `don_count[p]` / `acc_count[q]` += the bonds of the donor / acceptor at
+    /// that position, `map[g1 * ngroups2 + g2]` += 1.  Returns the sorted triples (donor, hydrogen, acceptor) and, per triple,
+    /// (|D-A|, |H-A|, the angle in degrees).
+    pub fn hbonds(
+        &self, cutoff: f32, coords: &[[f32; 3]], index1: Option<&[usize]>, h_offsets: &[usize], h_idx: &[usize], index2: Option<&[usize]>,
+        box9: Option<&[f32; 9]>, pbc: u8, angle_kind: i32, angle_deg: f64, max_ha: f64, don_count: Option<&mut [u64]>,
+        acc_count: Option<&mut [u64]>, labels1: Option<(&[u32], usize)>, labels2: Option<(&[u32], usize)>, map: Option<&mut [u64]>,
+    ) -> Result<(Vec<[u32; 3]>, Vec<[f64; 3]>), EngineError> {
+        check_index(index1, coords.len(), "hbonds (donors)")?;
+        check_index(index2, coords.len(), "hbonds (acceptors)")?;
+        check_index(Some(h_idx), coords.len(), "hbonds (hydrogens)")?;
+        let (i1, n1) = idx_ptr(index1);
+        let (i2, n2) = idx_ptr(index2);
+        let nsel1 = if index1.is_some() { n1 } else { coords.len() };
+        let nsel2 = if index2.is_some() { n2 } else { coords.len() };
+        if h_offsets.len() != nsel1 + 1 || h_offsets[0] != 0 || h_offsets[nsel1] != h_idx.len() || h_offsets.windows(2).any(|w| w[1] < w[0]) {
+            return Err(EngineError::Sizes("hbonds: h_offsets must run from 0 to h_idx.len() over ndonors + 1 entries without decreasing".into()));
+        }
+        if labels1.is_some() != labels2.is_some() {
+            return Err(EngineError::Sizes("hbonds: labels are needed for both sets or for none".into()));
+        }
+        let g = check_contact_outputs("hbonds", nsel1, don_count.as_deref(), labels1, labels2, nsel2, acc_count.as_deref(), map.as_deref())?;
+        let d = MolarHipSearchDesc {
+            kind: SEARCH_DOUBLE, cutoff, xyz1: coords.as_ptr() as *const f32, natoms1: coords.len(), idx1: i1, n1,
+            xyz2: coords.as_ptr() as *const f32, natoms2: coords.len(), idx2: i2, n2,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let mut count = 0u64;
+        self.plugin.check(unsafe {
+            (self.plugin.fns.hbonds_counts)(self.ctx, &d, h_offsets.as_ptr() as *const u64, h_idx.as_ptr() as *const u64, h_idx.len(), angle_kind,
+                                            angle_deg, max_ha, g.as_ref().map_or(std::ptr::null(), |g| g as *const MolarHipContactGroups),
+                                            don_count.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()),
+                                            acc_count.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()),
+                                            map.map_or(std::ptr::null_mut(), |s| s.as_mut_ptr()), &mut count)
+        })?;
+        let n = count as usize;
+        let mut triples = vec![[0u32; 3]; n];
+        let (mut da, mut ha, mut ang) = (vec![0f64; n], vec![0f64; n], vec![0f64; n]);
+        if n > 0 {
+            self.plugin.check(unsafe {
+                (self.plugin.fns.hbonds_fill)(self.ctx, triples.as_mut_ptr() as *mut u32, da.as_mut_ptr(), ha.as_mut_ptr(), ang.as_mut_ptr())
+            })?;
+        }
+        Ok((triples, (0..n).map(|k| [da[k], ha[k], ang[k]]).collect()))
+    }
+
     /// The fused radial distance histogram in f64: the pairs of `distance_search_single(_pbc)` with Float = f64, each
     /// distance through the f64 `Histogram1D::add_one` (molar_membrane/src/stats.rs:29-35) over `bins.len()` bins of
     /// [hmin, hmax), added into `bins`; no pair list.  Returns the number of pairs within the cutoff (binned or not).
