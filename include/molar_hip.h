@@ -387,6 +387,57 @@ int molar_hip_hbonds_frames(molar_hip_ctx *ctx, const molar_hip_search_desc *des
 int molar_hip_hbonds_frames_fill(molar_hip_ctx *ctx, uint64_t *frame_offsets, uint32_t *triples, double *dist_da, double *dist_ha,
                                  double *angle_deg, uint32_t *bond_of_entry, uint32_t *table, uint32_t *occupancy);
 
+/* ---- Lifetime correlations of presence data: the intermittent (Luzar-Chandler) and the continuous (survival) correlation
+ * numerators, the distribution of run lengths and per-row statistics of a sparse presence matrix frames x rows (gmx hbond
+ * -ac / -life, MDAnalysis HydrogenBondAnalysis.lifetime and SurvivalProbability).  Hydrogen bonds are one case (the rows of the
+ * bond table of molar_hip_hbonds_frames); contacts and the members of a shell (`within` sets per frame) are others.
+ *   input: F = nframes, R = nrows; frame_offsets[F + 1] (uint64) and row_of_entry[E] (uint32), E = frame_offsets[F]: the
+ *     entries of frame t are row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]).  h_r(t) = 1 iff row r occurs among the
+ *     entries of frame t (a row named twice in one frame counts once).  group_of_row[R] (uint32 labels below ngroups) puts
+ *     every row into a group; NULL: one group (ngroups is not read).
+ *   gap filling: gap = g >= 0 (MDAnalysis' intermittency) comes first: h'_r(u) = 1 iff h_r(u) = 1, or there are p < u < q with
+ *     h_r(p) = h_r(q) = 1 and q - p - 1 <= g.  Everything below is defined on h'.
+ *   curves per group G, uint64, for tau = 0 .. max_lag; the origins are t = 0, s, 2 s, ... (s = origin_stride >= 1) with
+ *     t + tau <= F - 1, and count[tau] = (F - 1 - tau) / s + 1 is their number, a function of F, s and tau alone:
+ *       inter[G][tau] = sum_{r in G} sum_t h'_r(t) h'_r(t + tau)                  (intermittent correlation, numerator)
+ *       cont[G][tau]  = sum_{r in G} sum_t prod_{u = t .. t + tau} h'_r(u)        (continuous correlation / survival, numerator)
+ *     laid out [ngroups][max_lag + 1].  C(tau) = (x[tau] / count[tau]) / (x[0] / count[0]) is the usual normalisation.
+ *     MDAnalysis' other normalisation, the mean over the origins of per-origin ratios, is NOT computed.
+ *   run_hist[G][l], l = 0 .. F, uint64, laid out [ngroups][F + 1]: the number of maximal runs of exactly l consecutive present
+ *     frames in the rows of G (the lifetime distribution); entry 0 is always 0.
+ *   per row, uint32 [R]: events[r] the number of runs, longest[r] the longest run, present[r] the number of present frames
+ *     (after gap filling).
+ * Every output may be NULL and is then not computed; each is host or device memory and is written, not accumulated into.
+ * frame_offsets, row_of_entry and group_of_row may each be host or device memory (offsets in device memory are copied to the
+ * host first: they are judged there).  Rows and labels in device memory are judged on the device before a kernel uses one as
+ * an address.  Integer atomics only: the same call gives the same bits.  The call waits for its result.
+ * molar_hip_hbonds_frames_lifetimes does the same on the block result the context keeps after molar_hip_hbonds_frames: the rows
+ * are the rows of the bond table, and nothing is copied out and back (bond_of_entry is read where it lies; the nframes + 1
+ * offsets, which the context keeps in host memory, are sent to the device).  Its outputs are sized by THAT block: R rows and F frames as
+ * molar_hip_hbonds_frames_shape reports them (each pointer may be NULL), with *serial the number of blocks the context has
+ * finished - a caller that kept the serial of the block it sized its outputs for knows from a different one that another block
+ * has taken its place.
+ *   ERR_SIZES         nrows == 0 or nframes == 0 (a block without a bond)
+ *   INVALID_ARGUMENT  max_lag >= nframes; origin_stride == 0; offsets that do not start at 0, decrease, or end at E > 0 with
+ *                     row_of_entry == NULL; a row >= nrows; a label >= ngroups
+ *   TOO_LARGE         the bit matrix cannot be allocated; 2^32 entries or more; 2^31 frames or more; more than 2^32 rows
+ *   NO_SEARCH         the chained call, or molar_hip_hbonds_frames_shape, without a block result
+ * A call that is refused writes nothing.  One GPU; cross-correlations between rows are out of scope.
+ * molar_hip_lifetimes_plan is a pure host function: the bytes of device workspace such a call allocates (kept by the context,
+ * grows only: the bit matrix of nrows x (ceil(nframes / 64) + 1) 64-bit words, the origin masks and, with want_cont, one
+ * histogram of ngroups x (nframes + 1) words; staging of host-memory arguments not included) and words_per_row =
+ * ceil(nframes / 64).  ngroups == 0 stands for one group. */
+int molar_hip_lifetimes_plan(size_t nframes, size_t nrows, size_t ngroups, int want_cont, size_t *workspace_bytes,
+                             uint32_t *words_per_row);
+int molar_hip_lifetimes(molar_hip_ctx *ctx, const uint64_t *frame_offsets, const uint32_t *row_of_entry, size_t nframes,
+                        size_t nrows, const uint32_t *group_of_row, size_t ngroups, size_t max_lag, size_t origin_stride,
+                        size_t gap, uint64_t *inter, uint64_t *cont, uint64_t *run_hist, uint32_t *events, uint32_t *longest,
+                        uint32_t *present);
+int molar_hip_hbonds_frames_shape(molar_hip_ctx *ctx, size_t *nframes, size_t *nrows, size_t *nentries, uint64_t *serial);
+int molar_hip_hbonds_frames_lifetimes(molar_hip_ctx *ctx, const uint32_t *group_of_row, size_t ngroups, size_t max_lag,
+                                      size_t origin_stride, size_t gap, uint64_t *inter, uint64_t *cont, uint64_t *run_hist,
+                                      uint32_t *events, uint32_t *longest, uint32_t *present);
+
 /* ---- the drivers for MolAR built with its `f64` feature (Float = f64, aliases.rs:10-13): every operation in double -
  * cell assignment, the predicate d2 <= cutoff^2 and the distances - results as (usize, usize, f64) columns or usize ids.
  * Same request / count-then-fill convention as above.  Coordinates, index lists, radii and the result columns may be host or

@@ -618,6 +618,7 @@ struct HBonds {
     std::vector<uint64_t> per_frame, frame_offsets;  // [nframes], [nframes + 1]: the frames' lists one after the other in `triples`
     std::vector<std::array<uint32_t, 3>> table;      // the block's distinct bonds, in the order of the triples
     std::vector<uint32_t> occupancy, bond_of_entry;  // frames a table row is present in; the table row of every entry
+    uint64_t serial = 0;                             // the engine's number of this block (hbonds_frames_lifetimes); 0: not a block
 };
 namespace detail {
 inline molar_hip_search_desc hbonds_desc(const SelBound &donors, const SelBound &acceptors, const HBondOptions &opt, const std::vector<usize> &h_offsets,
@@ -691,6 +692,68 @@ inline HBonds hbonds_frames(const SelBound &donors, const SelBound &acceptors, c
                                        n && opt.want_columns ? out.dist_da.data() : nullptr, n && opt.want_columns ? out.dist_ha.data() : nullptr,
                                        n && opt.want_columns ? out.angle.data() : nullptr, n ? out.bond_of_entry.data() : nullptr,
                                        rows ? &out.table[0][0] : nullptr, rows ? out.occupancy.data() : nullptr));
+    check(molar_hip_hbonds_frames_shape(donors.ctx(), nullptr, nullptr, nullptr, &out.serial));
+    return out;
+}
+
+// Lifetime correlations of a sparse presence matrix frames x rows (molar_hip_lifetimes; the definition: molar_hip.h): the rows
+// present in frame t are row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]).  group_of_row: one label per row, empty: one
+// group.  The numerators come as [ngroups][max_lag + 1], run_hist as [ngroups][nframes + 1]; count[tau] are the time origins of
+// lag tau, so that C(tau) = (x[tau] / count[tau]) / (x[0] / count[0]).
+struct LifetimeOptions {
+    size_t max_lag = (size_t)-1;      // (size_t)-1: nframes - 1
+    size_t origin_stride = 1;
+    size_t gap = 0;                   // zero runs of at most this many frames between two present frames are filled first
+    size_t ngroups = 1;               // read with labels only
+};
+struct Lifetimes {
+    size_t nframes = 0, nrows = 0, ngroups = 1, max_lag = 0;
+    std::vector<uint64_t> inter, cont, run_hist, count;
+    std::vector<uint32_t> events, longest, present;      // per row
+};
+namespace detail {
+inline Lifetimes lifetimes_sized(size_t F, size_t R, bool labels, const LifetimeOptions &opt) {
+    Lifetimes out;
+    out.nframes = F;
+    out.nrows = R;
+    out.ngroups = labels ? opt.ngroups : 1;
+    out.max_lag = opt.max_lag == (size_t)-1 ? (F ? F - 1 : 0) : opt.max_lag;
+    out.inter.assign(out.ngroups * (out.max_lag + 1), 0);
+    out.cont.assign(out.ngroups * (out.max_lag + 1), 0);
+    out.run_hist.assign(out.ngroups * (F + 1), 0);
+    out.events.assign(R, 0);
+    out.longest.assign(R, 0);
+    out.present.assign(R, 0);
+    if (opt.origin_stride && out.max_lag < F)
+        for (size_t tau = 0; tau <= out.max_lag; ++tau) out.count.push_back((F - 1 - tau) / opt.origin_stride + 1);
+    return out;
+}
+}  // namespace detail
+inline Lifetimes lifetimes(Engine &eng, const std::vector<uint64_t> &frame_offsets, const std::vector<uint32_t> &row_of_entry, size_t nrows,
+                           const std::vector<uint32_t> &group_of_row = {}, const LifetimeOptions &opt = LifetimeOptions()) {
+    if (frame_offsets.empty()) throw MolarError(MOLAR_HIP_ERR_SIZES, "lifetimes: frame_offsets is empty");
+    if (!group_of_row.empty() && group_of_row.size() != nrows) throw MolarError(MOLAR_HIP_ERR_SIZES, "lifetimes: one label per row");
+    Lifetimes out = detail::lifetimes_sized(frame_offsets.size() - 1, nrows, !group_of_row.empty(), opt);
+    check(molar_hip_lifetimes(eng.ctx(), frame_offsets.data(), row_of_entry.empty() ? nullptr : row_of_entry.data(), out.nframes, nrows,
+                              group_of_row.empty() ? nullptr : group_of_row.data(), out.ngroups, out.max_lag, opt.origin_stride, opt.gap,
+                              out.inter.data(), out.cont.data(), out.run_hist.data(), out.events.data(), out.longest.data(), out.present.data()));
+    return out;
+}
+// the same on the block the engine keeps after hbonds_frames (`block`: its result): rows are the rows of block.table, and the
+// presence matrix is read where it lies on the device.  The outputs are sized by what the engine holds (molar_hip_hbonds_frames_shape),
+// and MOLAR_HIP_ERR_NO_SEARCH is thrown when that is no longer `block`: the engine numbers its blocks and `block.serial` is its number.
+inline Lifetimes hbonds_frames_lifetimes(Engine &eng, const HBonds &block, const std::vector<uint32_t> &group_of_row = {},
+                                         const LifetimeOptions &opt = LifetimeOptions()) {
+    size_t R = 0, F = 0;
+    uint64_t held = 0;
+    check(molar_hip_hbonds_frames_shape(eng.ctx(), &F, &R, nullptr, &held));
+    if (held != block.serial || R != block.table.size() || F != block.per_frame.size())
+        throw MolarError(MOLAR_HIP_ERR_NO_SEARCH, "hbonds_frames_lifetimes: the engine has computed another block since this one");
+    if (!group_of_row.empty() && group_of_row.size() != R) throw MolarError(MOLAR_HIP_ERR_SIZES, "hbonds_frames_lifetimes: one label per table row");
+    Lifetimes out = detail::lifetimes_sized(F, R, !group_of_row.empty(), opt);
+    check(molar_hip_hbonds_frames_lifetimes(eng.ctx(), group_of_row.empty() ? nullptr : group_of_row.data(), out.ngroups, out.max_lag, opt.origin_stride,
+                                            opt.gap, out.inter.data(), out.cont.data(), out.run_hist.data(), out.events.data(), out.longest.data(),
+                                            out.present.data()));
     return out;
 }
 

@@ -196,6 +196,10 @@ SYMBOLS = {
     "molar_hip_hbonds_counts": (_I, [_P, _P, _P, _P, _SZ, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
     "molar_hip_hbonds_frames": (_I, [_P, _P, _P, _P, _SZ, C.c_int32, C.c_double, C.c_double, _SZ, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_hbonds_frames_fill": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_lifetimes_plan": (_I, [_SZ, _SZ, _SZ, _I, _P, _P]),
+    "molar_hip_lifetimes": (_I, [_P, _P, _P, _SZ, _SZ, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_hbonds_frames_shape": (_I, [_P, _P, _P, _P, _P]),
+    "molar_hip_hbonds_frames_lifetimes": (_I, [_P, _P, _SZ, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P]),
     "molar_hip_msd_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _I, _I, _P, _P, _P]),
     "molar_hip_msd": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),
     "molar_hip_msd_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),

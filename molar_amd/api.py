@@ -25,6 +25,9 @@ PBC_NONE = 0
 
 SEARCH_SINGLE, SEARCH_DOUBLE, SEARCH_WITHIN, SEARCH_DOUBLE_VDW = 0, 1, 2, 3
 
+ERR_NO_SEARCH = 52                                 # MOLAR_HIP_ERR_NO_SEARCH
+LIFETIME_OUTPUTS = ("inter", "cont", "run_hist", "events", "longest", "present")      # in the order of the C ABI
+
 
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
@@ -889,7 +892,48 @@ class Engine:
         a = lambda x, m: _addr(x)[0] if m else None
         check(self.lib.molar_hip_hbonds_frames_fill(self.ctx, frame_offsets.ctypes.data, a(triples, n), a(cols[0], n), a(cols[1], n), a(cols[2], n),
                                                     a(boe, n), a(table, rows), a(occ, rows)))
-        return HBondsBlock(per_frame, frame_offsets, triples, cols[0], cols[1], cols[2], table, occ, boe, don_count, acc_count, cmap)
+        blk = HBondsBlock(per_frame, frame_offsets, triples, cols[0], cols[1], cols[2], table, occ, boe, don_count, acc_count, cmap)
+        blk._engine = self
+        blk._serial = self._hbonds_block_shape()[3]
+        return blk
+
+    # ------------------------------------------------------------ lifetime correlations
+    def lifetimes(self, frame_offsets, row_of_entry, nrows, groups=None, ngroups=None, max_lag=None, origin_stride=1, gap=0,
+                  want=LIFETIME_OUTPUTS):
+        """Lifetime correlations of a sparse presence matrix frames x rows (molar_hip_lifetimes; the definition: molar_hip.h).
+        `frame_offsets` [F + 1] (uint64 numpy or int64 CUDA tensor) and `row_of_entry` [E] (uint32 numpy or int32 CUDA tensor):
+        the rows present in frame t are row_of_entry[frame_offsets[t] : frame_offsets[t + 1]].  `groups`: one label per row
+        (None: one group; `ngroups` None: the largest label + 1 of a numpy array).  Lags 0 .. max_lag (None: F - 1), origins
+        0, origin_stride, ...; `gap`: zero runs of at most this many frames between two present frames are filled first
+        (MDAnalysis' intermittency).  `want`: the outputs to compute, of "inter", "cont", "run_hist", "events", "longest",
+        "present".  Returns a `Lifetimes`; its arrays are CUDA tensors when row_of_entry is one (int64 / int32), numpy (uint64 /
+        uint32) otherwise.  The call waits for its result."""
+        off = _u64(frame_offsets)
+        rows = _u32(row_of_entry)
+        F = int(off.shape[0]) - 1
+        (oa, k1), (ra, k2) = _addr(off), _addr(rows)
+        if rows.shape[0] == 0:
+            ra = None
+        if _is_torch(off) or _is_torch(rows):
+            import torch
+            torch.cuda.current_stream().synchronize()      # torch made any contiguous copy on ITS stream
+        call = lambda g, G, L, a: self.lib.molar_hip_lifetimes(self.ctx, oa, ra, F, int(nrows), g, G, L, int(origin_stride), int(gap), *a)
+        return _lifetimes_call(call, F, int(nrows), groups, ngroups, max_lag, origin_stride, want, rows)
+
+    def _hbonds_block_shape(self):
+        """(nframes, rows, entries, serial) of the block the context holds (molar_hip_hbonds_frames_shape; NO_SEARCH without one)."""
+        F, R, E, serial = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_uint64(0)
+        check(self.lib.molar_hip_hbonds_frames_shape(self.ctx, C.byref(F), C.byref(R), C.byref(E), C.byref(serial)))
+        return int(F.value), int(R.value), int(E.value), int(serial.value)
+
+    def _hbonds_block_lifetimes(self, serial, like, groups, ngroups, max_lag, origin_stride, gap, want):
+        # the outputs are sized by what the CONTEXT holds, and only when that is still the caller's block
+        F, R, _, held = self._hbonds_block_shape()
+        if held != serial:
+            raise MolarHipError(ERR_NO_SEARCH, "HBondsBlock.lifetimes: the engine has computed another block since; its presence matrix "
+                                                    "is gone (Engine.lifetimes on this block's frame_offsets / bond_of_entry still works)")
+        call = lambda g, G, L, a: self.lib.molar_hip_hbonds_frames_lifetimes(self.ctx, g, G, L, int(origin_stride), int(gap), *a)
+        return _lifetimes_call(call, F, R, groups, ngroups, max_lag, origin_stride, want, like)
 
     # ------------------------------------------------------------ surface area
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
@@ -1370,6 +1414,102 @@ class HBondsBlock:
         self.triples, self.dist_da, self.dist_ha, self.angle = triples, dist_da, dist_ha, angle
         self.table, self.occupancy, self.bond_of_entry = table, occupancy, bond_of_entry
         self.don_count, self.acc_count, self.map = don_count, acc_count, cmap
+        self._engine, self._serial = None, None
+
+    def lifetimes(self, groups=None, ngroups=None, max_lag=None, origin_stride=1, gap=0, want=LIFETIME_OUTPUTS):
+        """Lifetime correlations of the block's bonds (molar_hip_hbonds_frames_lifetimes): Engine.lifetimes on the presence
+        matrix the engine still holds on the device - rows are the rows of `table`, nothing is copied out and back.  Valid
+        until the engine's next hydrogen-bond call, of a frame or of another block: MolarHipError NO_SEARCH after that (the
+        engine numbers its blocks, and this one remembers its number)."""
+        if self._engine is None:
+            raise ValueError("HBondsBlock.lifetimes: the block was not made by Engine.hbonds_frames")
+        return self._engine._hbonds_block_lifetimes(self._serial, self.bond_of_entry, groups, ngroups, max_lag, origin_stride, gap, want)
+
+
+class Lifetimes:
+    """Result of a lifetimes call: `inter` / `cont` [ngroups, max_lag + 1] - the numerators of the intermittent and the continuous
+    correlation -, `run_hist` [ngroups, F + 1], `events` / `longest` / `present` [nrows] (None for what was not asked for), and
+    `count` [max_lag + 1] (numpy uint64): the time origins of every lag.  `lifetime_curves` normalises."""
+
+    def __init__(self, inter, cont, run_hist, events, longest, present, count, nframes, origin_stride):
+        self.inter, self.cont, self.run_hist = inter, cont, run_hist
+        self.events, self.longest, self.present = events, longest, present
+        self.count, self.nframes, self.origin_stride = count, nframes, origin_stride
+
+
+def lifetime_count(nframes, max_lag, origin_stride=1):
+    """count[tau], tau = 0 .. max_lag: the origins t = 0, origin_stride, ... with t + tau <= nframes - 1 (numpy uint64)."""
+    tau = np.arange(int(max_lag) + 1, dtype=np.int64)
+    return ((int(nframes) - 1 - tau) // int(origin_stride) + 1).astype(np.uint64)
+
+
+def lifetimes_plan(nframes, nrows, ngroups=1, want_cont=True):
+    """(workspace_bytes, words_per_row) of a lifetimes call of these sizes (molar_hip_lifetimes_plan): the device workspace - the
+    bit matrix, the origin masks and, with want_cont, one histogram per group - and the 64-bit words of a row.  A host
+    function: no GPU is needed."""
+    ws, wpr = C.c_size_t(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_lifetimes_plan(int(nframes), int(nrows), int(ngroups), 1 if want_cont else 0, C.addressof(ws), C.addressof(wpr)))
+    return int(ws.value), int(wpr.value)
+
+
+LifetimeCurves = collections.namedtuple("LifetimeCurves", ["tau", "c_inter", "c_cont", "tau_inter", "tau_cont"])
+
+
+def lifetime_curves(res, dt=1.0):
+    """The normalised correlations of a `Lifetimes` in float64 on the host: C_x(tau) = (x[tau] / count[tau]) / (x[0] / count[0])
+    for x = inter, cont ([ngroups, max_lag + 1]; NaN where a denominator is 0; None for a curve that was not computed), and
+    their trapezoid integrals over tau * dt, the lifetimes [ngroups].  Returns LifetimeCurves(tau, c_inter, c_cont, tau_inter,
+    tau_cont) with tau = lag * dt."""
+    count = np.asarray(res.count, np.float64)
+    tau = np.arange(count.shape[0], dtype=np.float64) * float(dt)
+
+    def curve(x):
+        if x is None:
+            return None, None
+        x = np.asarray(x.cpu() if _is_torch(x) else x).astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            c = (x / count[None, :]) / (x[:, :1] / count[0])
+        integral = ((c[:, 1:] + c[:, :-1]) * 0.5 * np.diff(tau)[None, :]).sum(axis=1)
+        return c, integral
+
+    (ci, ti), (cc, tc) = curve(res.inter), curve(res.cont)
+    return LifetimeCurves(tau, ci, cc, ti, tc)
+
+
+def _lifetimes_call(call, F, R, groups, ngroups, max_lag, origin_stride, want, like):
+    """The shared end of Engine.lifetimes and HBondsBlock.lifetimes: labels, outputs of the kind of `like`, the call."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = set(want) - set(LIFETIME_OUTPUTS)
+    if unknown:
+        raise ValueError(f"lifetimes: unknown outputs {sorted(unknown)}")
+    groups = _u32(groups)
+    if groups is None:
+        G, ga = 1, None
+    else:
+        if ngroups is None:
+            if _is_torch(groups):
+                raise ValueError("lifetimes: ngroups is needed with labels in a tensor")
+            ngroups = int(groups.max()) + 1 if groups.shape[0] else 0
+        G, ga = int(ngroups), _addr(groups)[0]
+    L = max(F - 1, 0) if max_lag is None else int(max_lag)
+    dev = _is_torch(like)
+    shapes = {"inter": (G, L + 1), "cont": (G, L + 1), "run_hist": (G, F + 1), "events": (R,), "longest": (R,), "present": (R,)}
+    out = {}
+    for name in LIFETIME_OUTPUTS:
+        wide = name in ("inter", "cont", "run_hist")
+        if name not in want:
+            out[name] = None
+        elif dev:
+            import torch
+            out[name] = torch.zeros(shapes[name], dtype=torch.int64 if wide else torch.int32, device=like.device)
+        else:
+            out[name] = np.zeros(shapes[name], np.uint64 if wide else np.uint32)
+    if dev:
+        import torch
+        torch.cuda.current_stream().synchronize()          # torch made the outputs on ITS stream; the engine writes on its own
+    check(call(ga, G, L, [_addr(out[name])[0] for name in LIFETIME_OUTPUTS]))
+    count = lifetime_count(F, L, origin_stride)
+    return Lifetimes(out["inter"], out["cont"], out["run_hist"], out["events"], out["longest"], out["present"], count, F, int(origin_stride))
 
 
 def hydrogens_csr(hydrogens, ndonors):

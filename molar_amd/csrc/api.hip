@@ -216,6 +216,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::fluct_release(c);
     mh::msd_release(c);
     mh::hbonds_release(c);
+    mh::lifetimes_release(c);
     if (c->h_sizes) (void)hipHostFree(c->h_sizes);
     for (auto &t : c->tickets)
         if (t.done) (void)hipEventDestroy(t.done);

@@ -179,6 +179,7 @@ struct molar_hip_rmsd_matrix_state;     // packed operands, partial covariances 
 struct molar_hip_fluct_state;           // fits, packed deviations, partial covariances and staging of the fluctuations (fluct.hip)
 struct molar_hip_msd_state;             // boxes, unwrapped particle trajectories, partial lag sums and staging of the displacements (msd.hip)
 struct molar_hip_hbonds_state;          // keys, the cached bonds of a frame or a block and the block's table (hbonds.hip)
+struct molar_hip_lifetimes_state;       // the bit matrix, histograms and staging of the lifetime correlations (lifetimes.hip)
 
 // frames per launch of molar_hip_search_histogram_frames (search.hip, hist_frames_group)
 #ifndef MH_HIST_BATCH
@@ -202,6 +203,7 @@ struct molar_hip_ctx {
     molar_hip_fluct_state *fluct = nullptr;       // created by the first molar_hip_fluct*
     molar_hip_msd_state *msd = nullptr;           // created by the first molar_hip_msd*
     molar_hip_hbonds_state *hbonds = nullptr;     // created by the first molar_hip_hbonds*
+    molar_hip_lifetimes_state *lifetimes = nullptr;   // created by the first molar_hip_lifetimes*
     // ring of pinned chunks for large results that go to pageable host memory (hoststream.hpp), allocated on first use
     void *ring[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -365,6 +367,19 @@ void rmsd_matrix_release(molar_hip_ctx *c);
 void fluct_release(molar_hip_ctx *c);
 void msd_release(molar_hip_ctx *c);
 void hbonds_release(molar_hip_ctx *c);
+void lifetimes_release(molar_hip_ctx *c);
+
+// The block result the context keeps after molar_hip_hbonds_frames, for the units that consume it in place (lifetimes.hip):
+// the frames' offsets (HOST memory, nframes + 1), the table row of every entry (DEVICE memory), the rows of the table.
+struct HbondsBlockView {
+    const uint64_t *frame_offsets;
+    size_t nframes;
+    const uint32_t *bond_of_entry;
+    size_t rows, entries;
+    uint64_t serial;              // counts the blocks of this context: a caller's record of a block is stale when it differs
+};
+// false: the context holds no block result
+bool hbonds_block_view(const molar_hip_ctx *c, HbondsBlockView *out);
 
 // RAII span: records an event pair around a group of launches when profiling is on
 struct Prof {

@@ -34,6 +34,7 @@ struct molar_hip_hbonds_state {
     DevBuf ent, bsorted, perm, tkeys, occ, boe, table;   // the block's table
     std::vector<uint64_t> frame_off;                   // the block's frames in the result
     uint64_t count = 0, unique = 0;
+    uint64_t serial = 0;                               // blocks this context has finished (hbonds_block_view)
     int have = 0;                                      // 0: nothing, 1: a frame (molar_hip_hbonds_fill), 2: a block (_frames_fill)
 };
 
@@ -508,6 +509,13 @@ void hbonds_release(molar_hip_ctx *c) {
     release_state(c->hbonds, {&Z.in_off, &Z.in_hidx, &Z.in_g1, &Z.in_g2, &Z.ctr, &Z.keys, &Z.sorted, &Z.ukeys, &Z.triples, &Z.dda, &Z.dha, &Z.ang, &Z.acc,
                               &Z.ent, &Z.bsorted, &Z.perm, &Z.tkeys, &Z.occ, &Z.boe, &Z.table});
 }
+
+bool hbonds_block_view(const molar_hip_ctx *c, HbondsBlockView *out) {
+    if (!c->hbonds || c->hbonds->have != 2) return false;
+    const molar_hip_hbonds_state &Z = *c->hbonds;
+    *out = HbondsBlockView{Z.frame_off.data(), Z.frame_off.size() - 1, Z.boe.as<uint32_t>(), (size_t)Z.unique, (size_t)Z.count, Z.serial};
+    return true;
+}
 }  // namespace mh
 
 extern "C" {
@@ -570,6 +578,7 @@ int molar_hip_hbonds_frames(molar_hip_ctx *c, const molar_hip_search_desc *q, co
     Z.count = E;
     Z.unique = rows;
     Z.have = 2;
+    ++Z.serial;
     if (out_total) *out_total = E;
     if (out_unique) *out_unique = rows;
     return MOLAR_HIP_OK;

@@ -985,6 +985,104 @@ impl Engine {
         })?;
         Ok((ws, pc, lb))
     }
+
+    /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
+    /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
+    /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
+    /// frames between two present frames are filled first.
+    #[allow(clippy::too_many_arguments)]
+    pub fn lifetimes(
+        &self, frame_offsets: &[u64], row_of_entry: &[u32], nrows: usize, labels: Option<(&[u32], usize)>, max_lag: usize,
+        origin_stride: usize, gap: usize,
+    ) -> Result<Lifetimes, EngineError> {
+        if frame_offsets.is_empty() {
+            return Err(EngineError::Sizes("lifetimes: frame_offsets is empty".into()));
+        }
+        let nframes = frame_offsets.len() - 1;
+        if frame_offsets[nframes] as usize != row_of_entry.len() {
+            return Err(EngineError::Sizes("lifetimes: frame_offsets must end at row_of_entry.len()".into()));
+        }
+        let (gp, ngroups) = lifetime_labels("lifetimes", labels, nrows)?;
+        let mut out = Lifetimes::sized(nframes, nrows, ngroups, max_lag, origin_stride);
+        let rp = if row_of_entry.is_empty() { std::ptr::null() } else { row_of_entry.as_ptr() };
+        self.plugin.check(unsafe {
+            (self.plugin.fns.lifetimes)(self.ctx, frame_offsets.as_ptr(), rp, nframes, nrows, gp, ngroups, max_lag, origin_stride, gap,
+                                        out.inter.as_mut_ptr(), out.cont.as_mut_ptr(), out.run_hist.as_mut_ptr(), out.events.as_mut_ptr(),
+                                        out.longest.as_mut_ptr(), out.present.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// (frames, rows of the bond table, entries, serial number) of the block this engine keeps after `molar_hip_hbonds_frames`
+    /// (`molar_hip_hbonds_frames_shape`); an error without one.
+    pub fn hbonds_frames_shape(&self) -> Result<(usize, usize, usize, u64), EngineError> {
+        let (mut nframes, mut nrows, mut nentries, mut serial) = (0usize, 0usize, 0usize, 0u64);
+        self.plugin.check(unsafe { (self.plugin.fns.hbonds_frames_shape)(self.ctx, &mut nframes, &mut nrows, &mut nentries, &mut serial) })?;
+        Ok((nframes, nrows, nentries, serial))
+    }
+
+    /// The same on the block this engine keeps after `molar_hip_hbonds_frames` (`molar_hip_hbonds_frames_lifetimes`), read where it
+    /// lies on the device.  The outputs are sized by the frames and rows the LIBRARY reports for that block (`hbonds_frames_shape`,
+    /// in the same borrow of the engine), never by numbers of the caller's; `labels` must have one entry per row of that block.
+    pub fn hbonds_frames_lifetimes(
+        &self, labels: Option<(&[u32], usize)>, max_lag: usize, origin_stride: usize, gap: usize,
+    ) -> Result<Lifetimes, EngineError> {
+        let (nframes, nrows, _, _) = self.hbonds_frames_shape()?;
+        let (gp, ngroups) = lifetime_labels("hbonds_frames_lifetimes", labels, nrows)?;
+        let mut out = Lifetimes::sized(nframes, nrows, ngroups, max_lag, origin_stride);
+        self.plugin.check(unsafe {
+            (self.plugin.fns.hbonds_frames_lifetimes)(self.ctx, gp, ngroups, max_lag, origin_stride, gap, out.inter.as_mut_ptr(),
+                                                      out.cont.as_mut_ptr(), out.run_hist.as_mut_ptr(), out.events.as_mut_ptr(),
+                                                      out.longest.as_mut_ptr(), out.present.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and 64-bit words per row of a `lifetimes` call of these sizes (molar_hip_lifetimes_plan, a host
+    /// function).
+    pub fn lifetimes_plan(&self, nframes: usize, nrows: usize, ngroups: usize, want_cont: bool) -> Result<(usize, u32), EngineError> {
+        let (mut ws, mut wpr) = (0usize, 0u32);
+        self.plugin.check(unsafe { (self.plugin.fns.lifetimes_plan)(nframes, nrows, ngroups, want_cont as i32, &mut ws, &mut wpr) })?;
+        Ok((ws, wpr))
+    }
+}
+
+fn lifetime_labels(who: &str, labels: Option<(&[u32], usize)>, nrows: usize) -> Result<(*const u32, usize), EngineError> {
+    match labels {
+        None => Ok((std::ptr::null(), 1)),
+        Some((g, _)) if g.len() != nrows => Err(EngineError::Sizes(format!("{who}: one label per row"))),
+        Some((g, ngroups)) => Ok((g.as_ptr(), ngroups)),
+    }
+}
+
+/// What `Engine::lifetimes` returns: the numerators of the intermittent and the continuous correlation [ngroups][max_lag + 1],
+/// the runs by length [ngroups][nframes + 1], per row the runs, the longest run and the present frames, and `count[tau]`, the
+/// time origins of every lag: C(tau) = (x[tau] / count[tau]) / (x[0] / count[0]).
+#[derive(Debug, Clone, Default)]
+pub struct Lifetimes {
+    pub inter: Vec<u64>,
+    pub cont: Vec<u64>,
+    pub run_hist: Vec<u64>,
+    pub events: Vec<u32>,
+    pub longest: Vec<u32>,
+    pub present: Vec<u32>,
+    pub count: Vec<u64>,
+    pub ngroups: usize,
+}
+
+impl Lifetimes {
+    fn sized(nframes: usize, nrows: usize, ngroups: usize, max_lag: usize, origin_stride: usize) -> Self {
+        let lags = max_lag + 1;
+        let count = if origin_stride > 0 && max_lag < nframes {
+            (0..lags).map(|tau| ((nframes - 1 - tau) / origin_stride + 1) as u64).collect()
+        } else {
+            Vec::new()
+        };
+        Lifetimes {
+            inter: vec![0; ngroups * lags], cont: vec![0; ngroups * lags], run_hist: vec![0; ngroups * (nframes + 1)],
+            events: vec![0; nrows], longest: vec![0; nrows], present: vec![0; nrows], count, ngroups,
+        }
+    }
 }
 
 /// What `Engine::msd` returns: MSD and fourth moment per lag, the per-particle curves row by row and the unwrapped particle
