@@ -328,6 +328,40 @@ int molar_hip_search_contacts_frames(molar_hip_ctx *ctx, const molar_hip_search_
                                      size_t nframes, size_t xyz1_stride, size_t xyz2_stride, const float *boxes9,
                                      uint64_t *deg1, uint64_t *deg2, uint64_t *map, uint32_t *occupancy);
 
+/* The third fused consumer: connected components of the contact graph (clusters, aggregates, leaflets, the pieces of a
+ * selection).  Never materialises pairs.  The PARTICLES are the selected atoms of set 1 (ids = positions in the selection), or,
+ * with labels groups->group1 / ngroups1 (one label per selected atom; group2 / ngroups2 are ignored), the groups: P = n1 or
+ * ngroups1.  Two particles are joined when some entry (i, j) of the list L the search described by `desc` emits has its ends in
+ * them (L's own f32 predicate, L taken as a set); the components are those of that graph over all P particles.  A label no atom
+ * carries, and an atom the reference drops (outside a non-periodic dimension of the grid), is a component of its own.
+ * Components are numbered 0 .. C-1 IN THE ORDER OF THEIR SMALLEST PARTICLE, so every output is unique: the same call gives the
+ * same bits.  Outputs, each optional (NULL), host or device memory, sized by the caller from P alone, OVERWRITTEN:
+ *   comp_of[P]     uint32: the component of each particle;
+ *   sizes[P]       uint32: particles per component, entries C .. P-1 are 0;
+ *   offsets[P + 1] uint64, members[P] uint32: the particles of component k are members[offsets[k] .. offsets[k + 1]), ascending;
+ *                  entries C+1 .. P of offsets are P;
+ *   *out_ncomponents = C (host memory).
+ * The call is host-synchronous: everything is complete when it returns.  INVALID_ARGUMENT: any kind but
+ * MOLAR_HIP_SEARCH_SINGLE, a label >= ngroups1 (labels are checked as for molar_hip_search_contacts; nothing is written then).
+ * TOO_LARGE: P >= 2^31 - 2.  f32 only.  A component that is connected to its own periodic image is not told apart from any
+ * other.  Like the contacts calls it works on a search state of its own: a cached search of the context stays valid. */
+int molar_hip_search_clusters(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const molar_hip_contact_groups *groups /* may be NULL */,
+                              uint32_t *comp_of, uint32_t *sizes, uint64_t *offsets, uint32_t *members, uint32_t *out_ncomponents);
+/* The same for a block of a trajectory (frames laid out as for molar_hip_search_contacts_frames; set 1 only), each output
+ * optional, host or device: ncomponents[f] and largest[f] (uint32, per frame: C and the size of the largest component,
+ * overwritten), size_hist[P + 1] (uint64, ADDED INTO: size_hist[s] += the components of s particles, summed over the frames) and
+ * comp_of_frames[nframes * P] (each frame's comp_of, overwritten).  Labels are checked once for the block.  The frames are
+ * walked one after the other on one stream; the call is host-synchronous. */
+int molar_hip_search_clusters_frames(molar_hip_ctx *ctx, const molar_hip_search_desc *desc, const molar_hip_contact_groups *groups,
+                                     size_t nframes, size_t xyz1_stride, const float *boxes9, uint32_t *ncomponents, uint32_t *largest,
+                                     uint64_t *size_hist, uint32_t *comp_of_frames);
+/* Counters of the union-find, for measurements: out4 (may be NULL) receives what the clusters calls of this context added up
+ * since the counters were switched on - [hits of the pair loop, hits that reached the forest (the ends are different particles
+ * whose members cached in the wave differ), compare-and-swaps issued, path-shortening atomic minima issued] - then enable != 0
+ * zeroes them and switches them on (the calls take an instrumented instance of the kernel), 0 switches them off.  Diagnostic;
+ * results do not depend on it. */
+int molar_hip_search_clusters_counters(molar_hip_ctx *ctx, int32_t enable, uint64_t *out4);
+
 /* ------------------------------------------------------------------ hydrogen bonds
  * The third consumer of the two-set search, with the geometric definition GROMACS (gmx hbond), MDAnalysis
  * (HydrogenBondAnalysis) and VMD (hbonds) share; the reference has no such routine.  One frame and three selections: the

@@ -1066,6 +1066,68 @@ inline void ContactMap::add_trajectory_double_pbc(Engine &eng, const float *fram
     trajectory(eng, MOLAR_HIP_SEARCH_DOUBLE, frames_xyz, nframes, natoms, boxes9, cutoff, index1, &index2, pbc_dims);
 }
 
+// Connected components of the contact graph (molar_hip_search_clusters / _frames; the definition is in molar_hip.h): which
+// atoms - or, with labels, which groups - of a selection hang together at a cutoff.  Aggregates and their sizes, the leaflets
+// of a bilayer from its head groups, the pieces of a selection taken by distance.  Ids are positions in the selection (or
+// labels); components are numbered in the order of their smallest particle, so the result is unique.
+struct Clusters {
+    uint32_t ncomponents = 0;
+    std::vector<uint32_t> comp_of;            // per particle
+    std::vector<uint32_t> sizes;              // per component
+    std::vector<uint64_t> offsets;            // [ncomponents + 1] into members
+    std::vector<uint32_t> members;            // the particles of each component, ascending
+    // the components as lists of particles
+    std::vector<std::vector<usize>> split() const {
+        std::vector<std::vector<usize>> out(ncomponents);
+        for (uint32_t k = 0; k < ncomponents; ++k) out[k].assign(members.begin() + offsets[k], members.begin() + offsets[k + 1]);
+        return out;
+    }
+};
+// one frame: the components of distance_search_single(_pbc) of `sel`; labels (one per selected atom, each below ngroups) make
+// the groups the particles
+inline Clusters clusters(Float cutoff, const SelBound &sel, const PeriodicBox *pbox = nullptr, PbcDims pbc_dims = PBC_NONE,
+                         const std::vector<uint32_t> &labels = {}, usize ngroups = 0) {
+    const molar_hip_search_desc d = detail::desc(MOLAR_HIP_SEARCH_SINGLE, cutoff, sel, nullptr, true, pbox, pbc_dims);
+    const bool grouped = !labels.empty();
+    if (grouped && labels.size() != sel.len()) throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "clusters: one label per selected atom is needed");
+    molar_hip_contact_groups g{};
+    g.group1 = labels.data(); g.ngroups1 = ngroups;
+    const size_t np = grouped ? ngroups : sel.len();
+    Clusters c;
+    c.comp_of.assign(np, 0); c.sizes.assign(np, 0); c.offsets.assign(np + 1, 0); c.members.assign(np, 0);
+    check(molar_hip_search_clusters(sel.ctx(), &d, grouped ? &g : nullptr, c.comp_of.data(), c.sizes.data(), c.offsets.data(),
+                                    c.members.data(), &c.ncomponents));
+    c.sizes.resize(c.ncomponents);
+    c.offsets.resize((size_t)c.ncomponents + 1);
+    return c;
+}
+// a block of a trajectory in memory (laid out as for ContactMap::add_trajectory_single_pbc): per frame the number of components
+// and the largest one, and the components of each size summed over the frames, ADDED INTO size_hist (P + 1 entries)
+struct ClusterSizes {
+    std::vector<uint32_t> ncomponents, largest;      // per frame
+    std::vector<uint64_t> size_hist;                 // [P + 1]
+};
+inline void clusters_frames(Engine &eng, const float *frames_xyz, size_t nframes, size_t natoms, const float *boxes9, Float cutoff,
+                            const std::vector<usize> &index, PbcDims pbc_dims, ClusterSizes &out, const std::vector<uint32_t> &labels = {},
+                            usize ngroups = 0) {
+    molar_hip_search_desc d{};
+    d.kind = MOLAR_HIP_SEARCH_SINGLE;
+    d.cutoff = cutoff;
+    d.xyz1 = frames_xyz; d.natoms1 = natoms; d.idx1 = index.empty() ? nullptr : index.data(); d.n1 = index.size();
+    d.box9 = boxes9;
+    d.pbc = pbc_dims.raw();
+    const size_t nsel = index.empty() ? natoms : index.size();
+    if (!labels.empty() && labels.size() != nsel) throw MolarError(MOLAR_HIP_ERR_INVALID_ARGUMENT, "clusters_frames: one label per selected atom is needed");
+    molar_hip_contact_groups g{};
+    g.group1 = labels.data(); g.ngroups1 = ngroups;
+    const size_t np = labels.empty() ? nsel : ngroups;
+    out.ncomponents.assign(nframes, 0);
+    out.largest.assign(nframes, 0);
+    if (out.size_hist.size() != np + 1) out.size_hist.assign(np + 1, 0);
+    check(molar_hip_search_clusters_frames(eng.ctx(), &d, labels.empty() ? nullptr : &g, nframes, natoms * 3, boxes9, out.ncomponents.data(),
+                                           out.largest.data(), out.size_hist.data(), nullptr));
+}
+
 // ids: the reference takes an iterator; the two uses are the selection's own indices
 // (sel.iter_index(), ids_local = false) and 0..n (modify.rs:78, ids_local = true).
 template <class T>

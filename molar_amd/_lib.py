@@ -142,6 +142,9 @@ SYMBOLS = {
     "molar_hip_histogram_edges": (_I, [_F, _F, _SZ, _P]),
     "molar_hip_search_contacts": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_search_contacts_frames": (_I, [_P, _P, _P, _SZ, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_search_clusters": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_search_clusters_frames": (_I, [_P, _P, _P, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_search_clusters_counters": (_I, [_P, C.c_int32, _P]),
     "molar_hip_min_max": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),
     "molar_hip_center_of_geometry": (_I, [_P, _P, _SZ, _P, _SZ, _P]),
     "molar_hip_center_of_mass": (_I, [_P, _P, _SZ, _P, _SZ, _P, _P]),

@@ -785,6 +785,105 @@ class Engine:
         self._keep = keep
         return Contacts(None, deg1, deg2, cmap, occupancy)
 
+    # ------------------------------------------------------------ connected components
+    @staticmethod
+    def _clusters_out(want, shape, like, dtype64=False):
+        """An output of the clusters calls (overwritten by the engine): a CUDA tensor when the coordinates are one."""
+        if not want:
+            return None
+        if _is_torch(like):
+            import torch
+            return torch.zeros(shape, dtype=torch.int64 if dtype64 else torch.int32, device=like.device)
+        return np.zeros(shape, np.uint64 if dtype64 else np.uint32)
+
+    def search_clusters(self, cutoff, xyz, idx=None, box=None, pbc=0, group=None, ngroups=0, want_members=True):
+        """molar_hip_search_clusters: the connected components of the contact graph of one selection, fused into the pair loop
+        (no pair is written).  The particles are the selected atoms (ids = positions in the selection) or, with `group` (one
+        label per SELECTED atom) and `ngroups`, the groups; two particles are joined when distance_search_single(_pbc) lists a
+        pair with its ends in them.  Components are numbered in the order of their smallest particle.  Returns a `Clusters`
+        (numpy uint32 / uint64 arrays, int32 / int64 CUDA tensors when `xyz` is one); the call is complete when it returns."""
+        xyz = _f32(xyz); idx = _u64(idx); group = _u32(group)
+        d, keep = self._contacts_desc(SEARCH_SINGLE, cutoff, xyz, idx, None, None, pbc)
+        if box is not None:
+            ba, kb = self._box9(box)
+            keep.append(kb)
+            d.box9 = ba
+        n = d.n1 if idx is not None else d.natoms1
+        npart = int(ngroups) if group is not None else int(n)
+        comp_of = self._clusters_out(True, (npart,), xyz)
+        sizes = self._clusters_out(True, (npart,), xyz)
+        offsets = self._clusters_out(want_members, (npart + 1,), xyz, dtype64=True)
+        members = self._clusters_out(want_members, (npart,), xyz)
+        g = ContactGroups()
+        g.group1, k1 = _addr(group)
+        g.ngroups1 = int(ngroups)
+        keep.append(k1)
+        cnt = C.c_uint32(0)
+        check(self.lib.molar_hip_search_clusters(self.ctx, C.byref(d), C.byref(g) if group is not None else None, _addr(comp_of)[0],
+                                                 _addr(sizes)[0], _addr(offsets)[0], _addr(members)[0], C.byref(cnt)))
+        self._keep = keep
+        c = int(cnt.value)
+        return Clusters(c, comp_of, sizes[:c], None if offsets is None else offsets[:c + 1], members)
+
+    def search_clusters_frames(self, cutoff, frames, idx=None, box=None, pbc=0, group=None, ngroups=0, size_hist=None, want_comp_of=False):
+        """molar_hip_search_clusters_frames: `frames` = [nframes, natoms, 3] float32 (numpy or a CUDA tensor) through
+        search_clusters, one frame after the other.  `box`: one 3x3 matrix or [nframes, 3, 3].  `size_hist` (uint64 numpy or
+        int64 CUDA tensor of P + 1 entries) is ADDED INTO - size_hist[s] += components of s particles, summed over the frames -
+        and made as zeros when None.  Returns a `ClustersBlock`: ncomponents[nframes], largest[nframes], size_hist and, with
+        want_comp_of, comp_of[nframes, P] in each frame's canonical numbering."""
+        stride = None
+        if _is_torch(frames) and frames.ndim == 3 and frames.stride(2) == 1 and frames.stride(1) == 3:
+            import torch
+            assert frames.dtype == torch.float32
+            stride = int(frames.stride(0))
+            fa, k1 = frames.data_ptr(), frames
+        else:
+            frames = _f32(frames)
+            fa, k1 = _addr(frames)
+        assert frames.ndim == 3 and frames.shape[2] == 3
+        if stride is None:
+            stride = int(frames.shape[1]) * 3
+        idx = _u64(idx); group = _u32(group)
+        nframes = int(frames.shape[0])
+        d, keep = self._contacts_desc(SEARCH_SINGLE, cutoff, None, idx, None, None, pbc)
+        d.xyz1 = fa
+        d.natoms1 = int(frames.shape[1])
+        keep.append(k1)
+        boxes_ptr = None
+        if box is not None:
+            b = np.asarray(box.get_matrix() if isinstance(box, PeriodicBox) else box, np.float32)
+            if b.ndim == 3:
+                b9 = np.ascontiguousarray(np.transpose(b, (0, 2, 1))).reshape(nframes, 9)      # column-major per frame
+                boxes_ptr = b9.ctypes.data
+                d.box9 = boxes_ptr
+            else:
+                b9 = np.ascontiguousarray(b.reshape(3, 3).T).reshape(9)
+                d.box9 = b9.ctypes.data
+            keep.append(b9)
+        n = d.n1 if idx is not None else d.natoms1
+        npart = int(ngroups) if group is not None else int(n)
+        ncomp = self._clusters_out(True, (nframes,), frames)
+        largest = self._clusters_out(True, (nframes,), frames)
+        if size_hist is None:
+            size_hist = self._clusters_out(True, (npart + 1,), frames, dtype64=True)
+        comp_of = self._clusters_out(want_comp_of, (nframes, npart), frames)
+        g = ContactGroups()
+        g.group1, kg = _addr(group)
+        g.ngroups1 = int(ngroups)
+        keep.append(kg)
+        check(self.lib.molar_hip_search_clusters_frames(self.ctx, C.byref(d), C.byref(g) if group is not None else None, nframes, stride,
+                                                        boxes_ptr, _addr(ncomp)[0], _addr(largest)[0], _addr(size_hist)[0],
+                                                        _addr(comp_of)[0]))
+        self._keep = keep
+        return ClustersBlock(ncomp, largest, size_hist, comp_of)
+
+    def clusters_counters(self, enable):
+        """molar_hip_search_clusters_counters: returns [hits, hits that reached the forest, CAS, atomicMin] of the clusters
+        calls since the counters were switched on, then switches them on (zeroed) or off.  For measurements."""
+        out = (C.c_uint64 * 4)()
+        check(self.lib.molar_hip_search_clusters_counters(self.ctx, 1 if enable else 0, out))
+        return [int(v) for v in out]
+
     # ------------------------------------------------------------ hydrogen bonds
     def _hbonds_request(self, donors, hydrogens, acceptors, cutoff, pbc, angle, angle_kind, natoms):
         donors = _sel(donors); acceptors = _sel(acceptors)
@@ -1387,6 +1486,32 @@ class Contacts:
 
     def __init__(self, count, deg1, deg2, cmap, occupancy=None):
         self.count, self.deg1, self.deg2, self.map, self.occupancy = count, deg1, deg2, cmap, occupancy
+
+
+class Clusters:
+    """Connected components of a contact graph: `ncomponents` (C); `comp_of` [P], the component of each particle; `sizes` [C];
+    `offsets` [C + 1] and `members` [P], the particles of component k at members[offsets[k] : offsets[k + 1]], ascending (None
+    when the members were not asked for).  Components are numbered in the order of their smallest particle."""
+
+    def __init__(self, ncomponents, comp_of, sizes, offsets, members):
+        self.ncomponents, self.comp_of, self.sizes, self.offsets, self.members = ncomponents, comp_of, sizes, offsets, members
+
+    def split(self):
+        """The components as a list of index arrays (particle numbers, ascending), in the components' order."""
+        if self.members is None:
+            raise ValueError("Clusters.split: the call was made with want_members=False")
+        off = self.offsets.cpu().numpy() if _is_torch(self.offsets) else np.asarray(self.offsets)
+        mem = self.members.cpu().numpy() if _is_torch(self.members) else np.asarray(self.members)
+        off = off.astype(np.int64)
+        return [mem[off[k]:off[k + 1]].astype(np.int64) for k in range(self.ncomponents)]
+
+
+class ClustersBlock:
+    """Connected components over a block of frames: `ncomponents` and `largest` per frame, `size_hist` [P + 1] (components of
+    each size, summed over the frames) and `comp_of` [nframes, P] (None when not asked for)."""
+
+    def __init__(self, ncomponents, largest, size_hist, comp_of):
+        self.ncomponents, self.largest, self.size_hist, self.comp_of = ncomponents, largest, size_hist, comp_of
 
 
 HBOND_DHA_MIN, HBOND_HDA_MAX = 0, 1
@@ -2573,6 +2698,11 @@ class Sel:
         returns the list of local-index groups the reference returns as selections."""
         return self.engine.unwrap_connectivity(self.state.coords, self.require_box(), cutoff, dims, self.index)
 
+    def split_clusters(self, cutoff, dims=None):
+        """The selection split into its connected pieces at `cutoff` (clusters()): a list of `Sel`, in the order of each
+        piece's first atom - the reference's split into molecules, taken by distance instead of by bonds."""
+        return [Sel(self.top, self.state, self.index[part], self._engine) for part in clusters(cutoff, self, dims).split()]
+
 
 def distance_search(cutoff, data1: Sel, data2: Sel | None = None, dims=None):
     """molar_python/src/lib.rs:259-376 — same dispatch table:
@@ -2626,6 +2756,19 @@ def contacts(cutoff, sel1: Sel, sel2: Sel | None = None, dims=None, groups1=None
         return eng.search_contacts(SEARCH_DOUBLE, cutoff, sel1.state.coords, sel1.index, sel2.state.coords, sel2.index, box=box, pbc=pbc,
                                    group1=g1, ngroups1=ng1, group2=g2, ngroups2=ng2)
     return eng.search_contacts(SEARCH_SINGLE, cutoff, sel1.state.coords, sel1.index, box=box, pbc=pbc, group1=g1, ngroups1=ng1)
+
+
+def clusters(cutoff, sel: Sel, dims=None, groups=None):
+    """Connected components of the graph whose edges are what distance_search(cutoff, sel, dims=dims) lists (any periodic dim ->
+    the _pbc driver), without the list: aggregates, leaflets, the pieces of a selection taken by distance.  `groups`: one label
+    per selected atom (e.g. the residue or molecule number) - the particles are then the max(label) + 1 groups.  Returns a
+    `Clusters` whose ids are positions in the selection (or labels)."""
+    eng = sel.engine
+    pbc = pbc_mask(dims)
+    box = sel.require_box() if pbc else None
+    g = None if groups is None else np.ascontiguousarray(groups, np.uint32)
+    ng = 0 if g is None or g.size == 0 else int(g.max()) + 1
+    return eng.search_clusters(cutoff, sel.state.coords, sel.index, box=box, pbc=pbc, group=g, ngroups=ng)
 
 
 def hbond_donors(sel_heavy: Sel, sel_h: Sel, bond_cutoff=0.12, dims=None, search=None):

@@ -345,6 +345,12 @@ struct molar_hip_ctx {
     // of the frames form and the occupancy of a host caller
     molar_hip_ctx *contacts = nullptr;
     mh::DevBuf ct_g1, ct_g2, ct_acc, ct_frame, ct_occ;
+    // molar_hip_search_clusters: runs in the same second context (labels staged in its ct_g1); there live the forest and what is
+    // derived from it [parent | root | flag | rank | comp | sizes | iota | sorted keys | members | offsets], the scratch of its
+    // scans and sort, and the per-frame results of the frames form [ncomponents | largest | size_hist].  The switch and the four
+    // words of molar_hip_search_clusters_counters live in the caller's context.
+    mh::DevBuf cl_work, cl_tmp, cl_acc, cl_stats;
+    bool cl_counting = false;
 
     // ---- profiling (HIP events on `stream`)
     bool profiling = false;

@@ -1,6 +1,7 @@
 // contact_kernels.hpp - the fused contact consumer of the distance search (molar_hip_search_contacts): per-atom contact
 // counts and a group x group contact matrix straight from the pair loop, no pair written to memory.
-// Included by search.hip (ContactArgs, the launcher's declaration) and by pair_k9.hip, which instantiates the kernels.
+// Included by search.hip (ContactArgs, the launcher's declaration) and by pair_k9.hip, which instantiates the kernels; and by
+// cluster_kernels.hpp, whose kernel walks the same records with the same slot decode and hit decision (contact_slot, contact_hit).
 //
 // One kernel walks the slot records of the REGULAR plan (plan_kernel / slotmap_kernel: the list the count pass walks), every
 // class of entry through one row loop:
@@ -61,6 +62,79 @@ __device__ __forceinline__ float contact_wrapped_d2(const SearchParams &P, uint3
     return best2;
 }
 
+// What a wave needs of one slot record of the regular plan (prepare_search with live_rows = false): the header's fields and the
+// class of the entry.  Shared by the consumers that walk these records without writing a pair (contact_kernel here,
+// cluster_kernel of cluster_kernels.hpp), so that every class of entry is decided by the same code in all of them.
+struct ContactSlot {
+    uint32_t a0, n1, b0, n2;         // first atoms and sizes of the two cells in the sorted arrays
+    uint32_t i0, rows;               // first row of the slot in the first cell, rows of the slot (<= 64)
+    uint32_t wrap;                   // dimensions the entry wraps in
+    bool tri;                        // same cell: j > i only
+    bool wrapped;                    // the entry crosses a periodic boundary
+    bool approx;                     // ... and is band-classified (as run_fast): S moves the second cell next to the first one
+    float Sx, Sy, Sz;
+    float band_lo, band_hi, cutoff2;
+};
+
+// decodes slot record `slot`; false: the record is past the last slot or has no rows
+__device__ __forceinline__ bool contact_slot(const SearchParams &P, const SlotDesc *__restrict__ slot_desc, uint32_t slot, ContactSlot &S) {
+    const uint4 lo = reinterpret_cast<const uint4 *>(slot_desc + slot)[0];
+    const uint4 hi = reinterpret_cast<const uint4 *>(slot_desc + slot)[1];
+    const uint32_t fl = __builtin_amdgcn_readfirstlane(hi.y);
+    if (!(fl & 0x200u)) return false;                   // past the last slot
+    S.a0 = __builtin_amdgcn_readfirstlane(lo.x);
+    S.n1 = __builtin_amdgcn_readfirstlane(lo.y);
+    S.b0 = __builtin_amdgcn_readfirstlane(lo.z);
+    S.n2 = __builtin_amdgcn_readfirstlane(lo.w);
+    S.i0 = __builtin_amdgcn_readfirstlane(hi.z);
+    const uint32_t rps = fl >> 16;
+    S.wrap = fl & 7u;
+    S.tri = (fl & 0x100u) != 0u;
+    S.wrapped = P.use_box && S.wrap != 0u;
+    if (S.i0 >= S.n1) return false;
+    // band classification of a wrapped entry (as run_fast): b + S is the image of the second cell next to the first one
+    S.approx = S.wrapped && !S.tri && P.approx_wrapped != 0u && !(P.box.nshift != 0 && S.wrap == MOLAR_HIP_PBC_FULL);
+    S.Sx = S.Sy = S.Sz = 0.f;
+    if (S.approx) {
+        const uint32_t wrap_b = (fl >> 12) & 7u;
+        for (int d = 0; d < 3; ++d) {
+            if (!((S.wrap >> d) & 1u)) continue;
+            const float sgn = ((wrap_b >> d) & 1u) ? 1.0f : -1.0f;   // second cell wrapped: +col, first cell: -col
+            S.Sx += sgn * P.box.m[3 * d];
+            S.Sy += sgn * P.box.m[3 * d + 1];
+            S.Sz += sgn * P.box.m[3 * d + 2];
+        }
+    }
+    S.band_lo = P.band_lo;
+    S.band_hi = P.band_hi;
+    S.cutoff2 = P.cutoff2;
+    S.rows = S.n1 - S.i0 < rps ? S.n1 - S.i0 : rps;      // <= 64
+    return true;
+}
+
+// Is the lane's atom b (position jj of the second cell, `valid`: there is one; sb = b + S) within the cutoff of row r of the slot,
+// whose position is p?  The list's own decision; every lane of the wave calls it (the band's exact evaluation is entered on a ballot).
+__device__ __forceinline__ bool contact_hit(const SearchParams &P, const ContactSlot &S, bool valid, const float4 &b, float sbx, float sby, float sbz,
+                                            float px, float py, float pz, uint32_t jj, uint32_t r) {
+    const float dx = b.x - px, dy = b.y - py, dz = b.z - pz;            // p2 - p1
+    bool hit;
+    if (S.approx) {
+        const float ax = sbx - px, ay = sby - py, az = sbz - pz;
+        const float d2a = (ax * ax + ay * ay) + az * az;
+        const bool sure = d2a < S.band_lo, maybe = d2a <= S.band_hi;
+        hit = sure;
+        if (__builtin_amdgcn_ballot_w64(valid && maybe && !sure))
+            hit = sure || (maybe && contact_wrapped_d2(P, S.wrap, dx, dy, dz) <= S.cutoff2);
+    } else if (S.wrapped) {
+        hit = contact_wrapped_d2(P, S.wrap, dx, dy, dz) <= S.cutoff2;
+    } else {
+        hit = (dx * dx + dy * dy) + dz * dz <= S.cutoff2;                  // (:446, :460, :488)
+    }
+    hit = hit && valid;
+    if (S.tri) hit = hit && jj > S.i0 + r;
+    return hit;
+}
+
 constexpr int CONTACT_WAVES = 4;      // waves per workgroup; every wave walks its own slots
 
 template <int KIND>
@@ -72,37 +146,14 @@ __global__ void __launch_bounds__(64 * CONTACT_WAVES) contact_kernel(const Searc
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t w0 = blockIdx.x * CONTACT_WAVES + wave, stride = gridDim.x * CONTACT_WAVES;
     const bool has_map = A.g1 != nullptr;
-    const float cutoff2 = P.cutoff2;
     unsigned long long wave_total = 0;
 
     for (uint32_t w = w0; w < nslots; w += stride) {
         const uint32_t slot = nslots - 1u - w;          // the heavy wrapped entries at the far edge of the plan start first
-        const uint4 lo = reinterpret_cast<const uint4 *>(slot_desc + slot)[0];
-        const uint4 hi = reinterpret_cast<const uint4 *>(slot_desc + slot)[1];
-        const uint32_t fl = __builtin_amdgcn_readfirstlane(hi.y);
-        if (!(fl & 0x200u)) continue;                   // past the last slot
-        const uint32_t a0 = __builtin_amdgcn_readfirstlane(lo.x), n1 = __builtin_amdgcn_readfirstlane(lo.y);
-        const uint32_t b0 = __builtin_amdgcn_readfirstlane(lo.z), n2 = __builtin_amdgcn_readfirstlane(lo.w);
-        const uint32_t i0 = __builtin_amdgcn_readfirstlane(hi.z);
-        const uint32_t wrap = fl & 7u, rps = fl >> 16;
-        const bool tri = (fl & 0x100u) != 0u;
-        const bool wrapped = P.use_box && wrap != 0u;
-        if (i0 >= n1) continue;
-        // band classification of a wrapped entry (as run_fast): b + S is the image of the second cell next to the first one
-        const bool approx = wrapped && !tri && P.approx_wrapped != 0u && !(P.box.nshift != 0 && wrap == MOLAR_HIP_PBC_FULL);
-        float Sx = 0.f, Sy = 0.f, Sz = 0.f;
-        if (approx) {
-            const uint32_t wrap_b = (fl >> 12) & 7u;
-            for (int d = 0; d < 3; ++d) {
-                if (!((wrap >> d) & 1u)) continue;
-                const float sgn = ((wrap_b >> d) & 1u) ? 1.0f : -1.0f;   // second cell wrapped: +col, first cell: -col
-                Sx += sgn * P.box.m[3 * d];
-                Sy += sgn * P.box.m[3 * d + 1];
-                Sz += sgn * P.box.m[3 * d + 2];
-            }
-        }
-        const float band_lo = P.band_lo, band_hi = P.band_hi;
-        const uint32_t rows = n1 - i0 < rps ? n1 - i0 : rps;      // <= 64
+        ContactSlot S;
+        if (!contact_slot(P, slot_desc, slot, S)) continue;
+        const uint32_t a0 = S.a0, b0 = S.b0, n2 = S.n2, i0 = S.i0, rows = S.rows;
+        const bool tri = S.tri;
 
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
         if (lane < rows) a = gload4(P.sa, a0 + i0 + lane);
@@ -119,7 +170,7 @@ __global__ void __launch_bounds__(64 * CONTACT_WAVES) contact_kernel(const Searc
             float4 b = make_float4(3.0e38f, 3.0e38f, 3.0e38f, 0.f);
             if (valid) b = gload4(P.sb, b0 + jj);
             const uint32_t idb = __float_as_uint(b.w);
-            const float sbx = b.x + Sx, sby = b.y + Sy, sbz = b.z + Sz;          // the image (approx entries; S == 0 otherwise)
+            const float sbx = b.x + S.Sx, sby = b.y + S.Sy, sbz = b.z + S.Sz;          // the image (approx entries; S == 0 otherwise)
             // the chunk's label runs: lanes next to each other with the same label form a segment
             uint32_t gb = 0xFFFFFFFFu, seg = lane;
             bool tail = true, all_heads = true;
@@ -165,22 +216,7 @@ __global__ void __launch_bounds__(64 * CONTACT_WAVES) contact_kernel(const Searc
                         run = gr;
                     }
                 }
-                const float dx = b.x - px, dy = b.y - py, dz = b.z - pz;            // p2 - p1
-                bool hit;
-                if (approx) {
-                    const float ax = sbx - px, ay = sby - py, az = sbz - pz;
-                    const float d2a = (ax * ax + ay * ay) + az * az;
-                    const bool sure = d2a < band_lo, maybe = d2a <= band_hi;
-                    hit = sure;
-                    if (__builtin_amdgcn_ballot_w64(valid && maybe && !sure))
-                        hit = sure || (maybe && contact_wrapped_d2(P, wrap, dx, dy, dz) <= cutoff2);
-                } else if (wrapped) {
-                    hit = contact_wrapped_d2(P, wrap, dx, dy, dz) <= cutoff2;
-                } else {
-                    hit = (dx * dx + dy * dy) + dz * dz <= cutoff2;                  // (:446, :460, :488)
-                }
-                hit = hit && valid;
-                if (tri) hit = hit && jj > i0 + r;
+                const bool hit = contact_hit(P, S, valid, b, sbx, sby, sbz, px, py, pz, jj, r);
                 const unsigned long long mask = __builtin_amdgcn_ballot_w64(hit);
                 const uint32_t cnt = (uint32_t)__popcll(mask);
                 if (lane == r) rowdeg += cnt;

@@ -27,6 +27,7 @@
 
 #include "pair_kernels.hpp"
 #include "contact_kernels.hpp"
+#include "cluster_kernels.hpp"
 #include "search_shape.hpp"
 #include "stages.hpp"
 #include "unwrap_walk.hpp"
@@ -3058,6 +3059,21 @@ int contact_labels(molar_hip_ctx *s, const uint32_t *g, size_t n, size_t ngroups
     return 0;
 }
 
+// the second context of the contacts and clusters calls (molar_hip_ctx::contacts), made on first use, on the caller's stream
+int contacts_context(molar_hip_ctx *c, molar_hip_ctx **out) {
+    MH_HIP(hipSetDevice(c->device));
+    if (!c->contacts) {
+        molar_hip_ctx *s = molar_hip_create(c->device);
+        if (!s) return MOLAR_HIP_ERR_HIP;
+        (void)hipStreamDestroy(s->stream);
+        s->own_stream = false;
+        c->contacts = s;
+    }
+    c->contacts->stream = c->stream;
+    *out = c->contacts;
+    return 0;
+}
+
 int contacts_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
                    uint64_t *map, uint32_t *occ, ContactCall &K, const char *who) {
     if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", who);
@@ -3082,16 +3098,8 @@ int contacts_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar
     }
     K.nmap = G1 * G2;
     K.ng2 = G2;
-    MH_HIP(hipSetDevice(c->device));
-    if (!c->contacts) {
-        molar_hip_ctx *s = molar_hip_create(c->device);
-        if (!s) return MOLAR_HIP_ERR_HIP;
-        (void)hipStreamDestroy(s->stream);
-        s->own_stream = false;
-        c->contacts = s;
-    }
-    molar_hip_ctx *s = K.s = c->contacts;
-    s->stream = c->stream;
+    MH_TRY(contacts_context(c, &K.s));
+    molar_hip_ctx *s = K.s;
     if (want_map && K.nmap) {
         MH_TRY(contact_labels(s, groups->group1, K.n1, G1, s->ct_g1, &K.g1, who));
         if (K.two) MH_TRY(contact_labels(s, groups->group2, K.n2, G2, s->ct_g2, &K.g2, who));
@@ -3189,9 +3197,184 @@ int contacts_end(ContactCall &K, uint64_t *out_count) {
     return 0;
 }
 
+// ================================================================= connected components (cluster_kernels.hpp, pair_k12.hip)
+//
+// molar_hip_search_clusters / _frames.  Grid, plan and slot records as for the contacts calls, in the same second context and
+// under the same settings (ids are positions in the selection, consecutive rows, no hit history), so nothing the caller has
+// cached is touched.  Per frame, all on one stream: parent = identity; cluster_kernel unites the ends of every hit; then
+// flatten -> scan of the root flags (ranks) -> labels and sizes -> (members wanted) scan of the sizes and one stable sort of
+// (component, particle).  Everything is computed in this context's work area and copied to the caller's arrays, host or device.
+struct ClusterCall {
+    molar_hip_ctx *s = nullptr;        // the contacts context
+    size_t n = 0, np = 0;              // selected atoms, particles
+    const uint32_t *g = nullptr;       // device labels (NULL: every atom is a particle)
+    bool members = false;              // offsets / members are wanted
+    unsigned long long *stats = nullptr;
+    uint32_t *parent = nullptr, *root = nullptr, *flag = nullptr, *rank = nullptr, *comp = nullptr, *sizes = nullptr, *iota = nullptr,
+             *keys = nullptr, *memb = nullptr;
+    unsigned long long *offsets = nullptr;
+};
+
+int clusters_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, bool want_members, ClusterCall &K,
+                   const char *who) {
+    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+    if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
+        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: only the SINGLE kind has connected components (got kind %d)", who, q->kind);
+    if (!q->xyz1) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: xyz pointer is null");
+    K.n = q->idx1 ? q->n1 : q->natoms1;
+    const bool grouped = groups && groups->group1;
+    K.np = grouped ? groups->ngroups1 : K.n;
+    if (grouped && K.np == 0 && K.n != 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = 0", who);
+    if (K.np + 1 >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: %zu particles", who, K.np);
+    K.members = want_members;
+    MH_TRY(contacts_context(c, &K.s));
+    molar_hip_ctx *s = K.s;
+    if (grouped && K.n) MH_TRY(contact_labels(s, groups->group1, K.n, K.np, s->ct_g1, &K.g, who));
+    if (c->cl_counting) K.stats = c->cl_stats.as<unsigned long long>();
+    const size_t np = K.np, words = (9 * np + 3 + 1) & ~(size_t)1;
+    MH_TRY(s->cl_work.reserve(words * 4 + (np + 1) * 8));
+    uint32_t *w = s->cl_work.as<uint32_t>();
+    K.parent = w; w += np;
+    K.root = w; w += np;
+    K.flag = w; w += np + 1;
+    K.rank = w; w += np + 1;
+    K.comp = w; w += np;
+    K.sizes = w; w += np + 1;
+    K.iota = w; w += np;
+    K.keys = w; w += np;
+    K.memb = w;
+    K.offsets = reinterpret_cast<unsigned long long *>(s->cl_work.as<uint32_t>() + words);
+    return 0;
+}
+
+// one frame, enqueued: the forest, its union over the frame's hits, and what is derived from it
+int clusters_frame(ClusterCall &K, const molar_hip_search_desc *q) {
+    if (K.np == 0) return 0;
+    molar_hip_ctx *s = K.s;
+    const unsigned cus = (unsigned)s->num_cus;
+    const uint32_t np = (uint32_t)K.np;
+    launch_cluster_init(cus, s->stream, K.parent, np);
+    MH_HIP(hipGetLastError());
+    if (K.n != 0) {
+        molar_hip_search_desc qq = *q;
+        qq.ids_local = 1;                       // ids are positions in the selection
+        SearchCall call;
+        call.size_masks = false;
+        call.live_rows = false;                 // cluster_kernel walks consecutive rows
+        bool degenerate;
+        MH_TRY(prepare_search(s, &qq, call, &degenerate));
+        s->params_fresh = false;
+        const SearchShape &cur = s->cur;
+        if (!degenerate && cur.nslots_bound != 0) {
+            ClusterArgs A{};
+            A.g = K.g;
+            A.parent = K.parent;
+            A.stats = K.stats;
+            Prof prof(s, 3);
+            launch_clusters(cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)cur.nslots_bound, A);
+            MH_HIP(hipGetLastError());
+        }
+    }
+    launch_cluster_flatten(cus, s->stream, K.parent, np, K.root, K.flag);
+    MH_HIP(hipGetLastError());
+    MH_TRY(device_exclusive_sum_u32(s, s->cl_tmp, K.flag, K.rank, (size_t)np + 1));      // rank[np] = number of components
+    MH_HIP(hipMemsetAsync(K.sizes, 0, ((size_t)np + 1) * 4, s->stream));
+    launch_cluster_label(cus, s->stream, K.root, K.rank, np, K.comp, K.sizes, K.iota);
+    MH_HIP(hipGetLastError());
+    if (K.members) {
+        MH_TRY(device_exclusive_sum_u32_u64(s, s->cl_tmp, K.sizes, K.offsets, (size_t)np + 1));
+        int end_bit = 1;
+        while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)np) ++end_bit;
+        MH_TRY(device_sort_pairs_u32(s->stream, s->cl_tmp, K.comp, K.keys, K.iota, K.memb, np, end_bit));
+    }
+    return 0;
+}
+
+// a result of this context's work area to the caller's array, host or device
+int cluster_out(molar_hip_ctx *s, void *dst, const void *src, size_t bytes) {
+    if (!dst || bytes == 0) return 0;
+    if (is_device_ptr(dst)) {
+        MH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->stream));
+        return 0;
+    }
+    return read_back(s, dst, src, bytes);
+}
+
 }  // namespace
 
 extern "C" {
+
+int molar_hip_search_clusters(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint32_t *comp_of,
+                              uint32_t *sizes, uint64_t *offsets, uint32_t *members, uint32_t *out_ncomponents) {
+    ClusterCall K;
+    MH_TRY(clusters_begin(c, q, groups, offsets != nullptr || members != nullptr, K, "search_clusters"));
+    molar_hip_ctx *s = K.s;
+    if (out_ncomponents) *out_ncomponents = 0;
+    if (K.np == 0) {
+        if (offsets && is_device_ptr(offsets)) MH_HIP(hipMemsetAsync(offsets, 0, 8, s->stream));
+        else if (offsets) offsets[0] = 0;
+        MH_HIP(hipStreamSynchronize(s->stream));
+        return MOLAR_HIP_OK;
+    }
+    MH_TRY(clusters_frame(K, q));
+    MH_TRY(cluster_out(s, comp_of, K.comp, K.np * 4));
+    MH_TRY(cluster_out(s, sizes, K.sizes, K.np * 4));
+    MH_TRY(cluster_out(s, offsets, K.offsets, (K.np + 1) * 8));
+    MH_TRY(cluster_out(s, members, K.memb, K.np * 4));
+    if (out_ncomponents) MH_TRY(read_back(s, out_ncomponents, K.rank + K.np, 4));
+    MH_HIP(hipStreamSynchronize(s->stream));
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_search_clusters_frames(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, size_t nframes,
+                                     size_t xyz1_stride, const float *boxes9, uint32_t *ncomponents, uint32_t *largest, uint64_t *size_hist,
+                                     uint32_t *comp_of_frames) {
+    ClusterCall K;
+    MH_TRY(clusters_begin(c, q, groups, false, K, "search_clusters_frames"));
+    molar_hip_ctx *s = K.s;
+    if (nframes == 0) return MOLAR_HIP_OK;
+    // [size_hist of a host caller | ncomponents | largest], zeroed
+    const size_t nh = K.np + 1, acc_bytes = nh * 8 + nframes * 8;
+    MH_TRY(s->cl_acc.reserve(acc_bytes));
+    MH_HIP(hipMemsetAsync(s->cl_acc.p, 0, acc_bytes, s->stream));
+    unsigned long long *t_hist = s->cl_acc.as<unsigned long long>();
+    uint32_t *t_ncomp = reinterpret_cast<uint32_t *>(t_hist + nh), *t_largest = t_ncomp + nframes;
+    const bool host_hist = size_hist && !is_device_ptr(size_hist);
+    unsigned long long *hist = host_hist ? t_hist : reinterpret_cast<unsigned long long *>(size_hist);
+    for (size_t f = 0; f < nframes; ++f) {
+        molar_hip_search_desc qf = *q;
+        qf.xyz1 = q->xyz1 + f * xyz1_stride;
+        if (boxes9) qf.box9 = boxes9 + 9 * f;
+        MH_TRY(clusters_frame(K, &qf));
+        if (K.np == 0) continue;
+        launch_cluster_frame((unsigned)s->num_cus, s->stream, K.flag, K.rank, K.sizes, (uint32_t)K.np, t_ncomp + f, t_largest + f, hist);
+        MH_HIP(hipGetLastError());
+        if (comp_of_frames) MH_TRY(cluster_out(s, comp_of_frames + f * K.np, K.comp, K.np * 4));
+    }
+    MH_TRY(cluster_out(s, ncomponents, t_ncomp, nframes * 4));
+    MH_TRY(cluster_out(s, largest, t_largest, nframes * 4));
+    if (host_hist) {
+        std::vector<unsigned long long> h(nh);
+        MH_TRY(read_back(s, h.data(), t_hist, nh * 8));
+        for (size_t i = 0; i < nh; ++i) size_hist[i] += h[i];
+    }
+    MH_HIP(hipStreamSynchronize(s->stream));
+    return MOLAR_HIP_OK;
+}
+
+int molar_hip_search_clusters_counters(molar_hip_ctx *c, int32_t enable, uint64_t *out4) {
+    MH_CTX(c);
+    if (out4) {
+        for (int k = 0; k < 4; ++k) out4[k] = 0;
+        if (c->cl_stats.p) MH_TRY(read_back(c, out4, c->cl_stats.p, 32));
+    }
+    c->cl_counting = enable != 0;
+    if (c->cl_counting) {
+        MH_TRY(c->cl_stats.reserve(32));
+        MH_HIP(hipMemsetAsync(c->cl_stats.p, 0, 32, c->stream));
+    }
+    return MOLAR_HIP_OK;
+}
 
 int molar_hip_search_contacts(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
                               uint64_t *map, uint64_t *out_count) {

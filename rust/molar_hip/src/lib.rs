@@ -592,6 +592,32 @@ impl Engine {
         Ok(count)
     }
 
+    /// Connected components of the contact graph of `distance_search_single(_pbc)` (f32) without the list
+    /// (`molar_hip_search_clusters`): the particles are the selected atoms (positions in the selection) or, with `labels` (one
+    /// per selected atom, each below `ngroups`), the groups.  Returns `(comp_of, sizes)`: the component of every particle, and
+    /// the particles per component; components are numbered in the order of their smallest particle, so the pieces of a
+    /// selection (`split_mol_iter` taken by distance) are the runs of equal `comp_of`.
+    pub fn clusters(
+        &self, cutoff: f32, coords: &[[f32; 3]], index: Option<&[usize]>, box9: Option<&[f32; 9]>, pbc: u8, labels: Option<(&[u32], usize)>,
+    ) -> Result<(Vec<u32>, Vec<u32>), EngineError> {
+        check_index(index, coords.len(), "clusters")?;
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { coords.len() };
+        let g = check_contact_outputs("clusters", nsel, None, labels, None, 0, None, None)?;
+        let np = labels.map_or(nsel, |(_, ng)| ng);
+        let d = MolarHipSearchDesc {
+            kind: SEARCH_SINGLE, cutoff, xyz1: coords.as_ptr() as *const f32, natoms1: coords.len(), idx1: ip, n1: n,
+            box9: box9.map_or(std::ptr::null(), |m| m.as_ptr()), pbc, ..Default::default()
+        };
+        let (mut comp_of, mut sizes, mut ncomp) = (vec![0u32; np], vec![0u32; np], 0u32);
+        self.plugin.check(unsafe {
+            (self.plugin.fns.search_clusters)(self.ctx, &d, g.as_ref().map_or(std::ptr::null(), |g| g as *const MolarHipContactGroups),
+                                              comp_of.as_mut_ptr(), sizes.as_mut_ptr(), std::ptr::null_mut(), std::ptr::null_mut(), &mut ncomp)
+        })?;
+        sizes.truncate(ncomp as usize);
+        Ok((comp_of, sizes))
+    }
+
     /// Hydrogen bonds of one frame (`molar_hip_hbonds_counts` + `molar_hip_hbonds_fill`; the definition is in the header):
     /// donors `index1` and acceptors `index2` of ONE frame `coords`, the donors' hydrogens as a CSR over the donors
     /// (`h_offsets[ndonors + 1]`, `h_idx`: atom indices).  `angle_kind` 0: angle(D-H-A) >= `angle_deg`; 1: angle(H-D-A) <=
