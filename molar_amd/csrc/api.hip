@@ -179,30 +179,12 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
-    for (auto &gen : c->set_store) for (auto &s : gen) {
-        for (DevBuf *b : {&s.xyz_stage, &s.idx_stage, &s.vdw_stage, &s.key, &s.cell_count, &s.cnt_pad, &s.cursor, &s.tmp_key, &s.sort_buf,
-                          &s.sorted, &s.sorted_vdw, &s.aabb, &s.perm, &s.chunk_aabb, &s.h16, &s.cell_org, &s.live})
-            b->release();
-    }
+    // the second contexts go while this context's stream is still alive (the contacts one shares it)
     if (c->aux) molar_hip_destroy(c->aux);
-    if (c->contacts) {                                      // (shares this context's stream, which is still alive here)
-        c->contacts->stream = c->stream;
-        molar_hip_destroy(c->contacts);
-    }
-    for (DevBuf *b : {&c->xh_win[0], &c->xh_win[1], &c->xh_bins, &c->fit_redo, &c->ct_g1, &c->ct_g2, &c->ct_acc, &c->ct_frame, &c->ct_occ, &c->cl_work, &c->cl_tmp, &c->cl_acc, &c->cl_stats}) b->release();
-    for (auto &gen : c->hb_sets) for (auto &fr : gen) for (auto &s : fr) {
-        for (DevBuf *b : {&s.xyz_stage, &s.idx_stage, &s.vdw_stage, &s.key, &s.cell_count, &s.cnt_pad, &s.cursor, &s.tmp_key, &s.sort_buf,
-                          &s.sorted, &s.sorted_vdw, &s.aabb, &s.perm, &s.chunk_aabb, &s.h16, &s.cell_org, &s.live})
-            b->release();
-    }
-    for (DevBuf *b : {&c->hb_lean[0], &c->hb_lean[1], &c->hb_rest[0], &c->hb_rest[1], &c->hb_blocks[0], &c->hb_blocks[1]}) b->release();
+    mh::contacts_release(c);
     if (c->hb_pin) (void)hipHostFree(c->hb_pin);
     for (auto e : c->hb_pin_ev)
         if (e) (void)hipEventDestroy(e);
-    for (DevBuf *b : {&c->params, &c->task_desc, &c->task_nb, &c->slot_desc, &c->slot_cnt, &c->slot_base, &c->tile_sum, &c->scan_tmp, &c->sort_tmp, &c->sort_tmp_side, &c->scan_tmp_side, &c->scan_state, &c->fplan_tiles, &c->slot_stat, &c->out_pairs_set[0], &c->out_dist_set[0], &c->out_pairs_set[1], &c->out_dist_set[1], &c->out_ids,
-                      &c->wide_i, &c->wide_j, &c->hist, &c->hist_queue, &c->slot_desc_rest, &c->hist_edges, &c->dbg, &c->conn_deg, &c->conn_off, &c->conn_ent, &c->conn_neigh, &c->w_flags, &c->w_list, &c->w_part_cnt, &c->w_part, &c->w_tile_cnt, &c->w_tile_off, &c->task_mu, &c->task_moff, &c->maskbuf, &c->m_xyz1, &c->m_xyz2, &c->m_idx1, &c->m_idx2,
-                      &c->m_mass1, &c->m_mass2, &c->m_partials, &c->m_results, &c->m_out})
-        b->release();
     for (auto &s : c->spans) {
         (void)hipEventDestroy(s.a);
         (void)hipEventDestroy(s.b);
@@ -217,6 +199,8 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::msd_release(c);
     mh::hbonds_release(c);
     mh::lifetimes_release(c);
+    mh::within_release(c);
+    mh::connectivity_release(c);
     if (c->h_sizes) (void)hipHostFree(c->h_sizes);
     for (auto &t : c->tickets)
         if (t.done) (void)hipEventDestroy(t.done);
@@ -225,7 +209,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;       // the context's own device buffers free themselves here: nothing is in flight after the waits above
 }
 
 int molar_hip_set_stream(molar_hip_ctx *c, void *hip_stream) {

@@ -1,7 +1,7 @@
 // cluster_kernels.hpp - connected components of the contact graph (molar_hip_search_clusters): the third consumer of the slot
 // records of the REGULAR plan, beside the count / fill passes and contact_kernel.  No pair is written: where the contact kernel
 // adds one per hit, cluster_kernel unites the two ends of the hit in a lock-free union-find over the PARTICLES (the atoms of
-// the selection, or their groups).  Included by search.hip (ClusterArgs, the launchers' declarations) and by pair_k12.hip, which
+// the selection, or their groups).  Included by contacts.hip (ClusterArgs, the launchers' declarations) and by pair_k12.hip, which
 // instantiates the kernels.
 //
 // The forest.  parent[P], one word per particle, identity at the start (cluster_init_kernel).

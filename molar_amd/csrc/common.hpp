@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/molar_hip.h"
@@ -55,10 +56,25 @@ inline int fail(int code, const char *fmt, ...) {
     } while (0)
 
 // ---------------------------------------------------------------- grow-only device buffer
+// Owns its memory: whatever holds a DevBuf frees it by going away, so nothing keeps a list of buffers to release.  Move-only.
+// None lives at namespace scope or as a static: a destructor must not run after the HIP runtime has shut down.
 
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p = std::exchange(o.p, nullptr);
+            cap = std::exchange(o.cap, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes) {
         if (bytes <= cap) return 0;
         if (p) {
@@ -180,6 +196,9 @@ struct molar_hip_fluct_state;           // fits, packed deviations, partial cova
 struct molar_hip_msd_state;             // boxes, unwrapped particle trajectories, partial lag sums and staging of the displacements (msd.hip)
 struct molar_hip_hbonds_state;          // keys, the cached bonds of a frame or a block and the block's table (hbonds.hip)
 struct molar_hip_lifetimes_state;       // the bit matrix, histograms and staging of the lifetime correlations (lifetimes.hip)
+struct molar_hip_within_state;          // flags, lists and the cached `within` set (within.hip)
+struct molar_hip_connectivity_state;    // the cached SearchConnectivity CSR of either precision (connectivity.hip)
+struct molar_hip_contacts_state;        // the second context, labels, accumulators and forest of the contacts / clusters calls (contacts.hip)
 
 // frames per launch of molar_hip_search_histogram_frames (search.hip, hist_frames_group)
 #ifndef MH_HIST_BATCH
@@ -204,6 +223,9 @@ struct molar_hip_ctx {
     molar_hip_msd_state *msd = nullptr;           // created by the first molar_hip_msd*
     molar_hip_hbonds_state *hbonds = nullptr;     // created by the first molar_hip_hbonds*
     molar_hip_lifetimes_state *lifetimes = nullptr;   // created by the first molar_hip_lifetimes*
+    molar_hip_within_state *within = nullptr;         // created by the first molar_hip_within_count
+    molar_hip_connectivity_state *conn = nullptr;     // created by the first molar_hip_search_connectivity / _f64
+    molar_hip_contacts_state *contacts = nullptr;     // created by the first molar_hip_search_contacts* / _clusters*
     // ring of pinned chunks for large results that go to pageable host memory (hoststream.hpp), allocated on first use
     void *ring[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ring_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -216,10 +238,13 @@ struct molar_hip_ctx {
     //  * what OUTLASTS a request: have_search / total / mask_units, the buffers, the hints (occ_key, occ_cells, occ_valid), the
     //    tickets, the record of a held `within` grid (`held`);
     //  * what ONE request asks of the shared helpers (plan or not, side stream, output capacity ...) travels down the call
-    //    chain as a SearchCall argument (search.hip);
+    //    chain as a SearchCall argument (search_core.hpp);
     //  * WHERE a grid is built - the stream, that stream's scan and sort scratch, the launch shape that goes with it - is a
     //    GridLane argument (search.hip: main_lane, side_lane).  `stream` is assigned when the context is created or handed a
     //    stream and never swapped for the length of a call: whatever reads it gets the main stream.
+    // What a CONSUMER of the search keeps across its own calls - the `within` set, the connectivity CSR, the contacts and
+    // clusters calls' second context and work areas - is not here: each has a state of its own behind one pointer above
+    // (within.hip, connectivity.hip, contacts.hip; they reach the search through search_core.hpp).
     // have_search says that a count has finished and the fill calls may run - nothing else: a request that came to nothing
     // (empty vdW input) is reported by prepare_search through its `degenerate` argument.
     bool have_search = false;
@@ -315,21 +340,10 @@ struct molar_hip_ctx {
     mh::DevBuf hist_edges;     // f32[nbins + 1]: smallest d2 that reaches each bin (hist_kernel), for the cached (min, max, nbins)
     float edges_min = 0.f, edges_max = 0.f;
     size_t edges_nbins = 0;    // 0: no table cached
-    // SearchConnectivity on the device (molar_hip_search_connectivity / _fill)
-    mh::DevBuf conn_deg, conn_off, conn_ent, conn_neigh;
-    uint64_t conn_rows = 0, conn_entries = 0;
-    bool have_conn = false;
-    // molar_hip_within_hold: reuse of the first set's staged coordinates and grid across `within` requests
+    // molar_hip_within_hold: reuse of the first set's staged coordinates and grid across `within` requests (prepare_search reads
+    // and ends it: it belongs to the search, not to within.hip's state)
     bool within_hold = false;          // the caller's switch
     mh::HeldGrid held;
-    // `within` as a set (molar_hip_within_count / _fill)
-    mh::DevBuf w_list;         // small second sets: ids found, in the order they were found (within_small_kernel)
-    bool w_small = false;      // the cached within set was made by the small path (the list holds it)
-    uint64_t w_list_dirty = 0; // flags set through the list by the previous small-path call, to be cleared before the next
-    bool w_flags_all_dirty = false;   // the previous call went through the partner lists: any flag may be set
-    mh::DevBuf w_flags, w_part_cnt, w_part, w_tile_cnt, w_tile_off;
-    uint64_t within_nflags = 0, within_total = 0;
-    bool have_within = false;
     mh::DevBuf task_mu;        // u32 per task (+1): 64-word hit-history units of the task's slots
     mh::DevBuf task_moff;      // u64 per task (+1): exclusive scan of task_mu
     mh::DevBuf maskbuf;        // hit bits recorded by the count pass, replayed by the fill pass
@@ -338,19 +352,6 @@ struct molar_hip_ctx {
     // molar_hip_xtc_histogram: a second context for the decoder thread (its own stream and pinned staging), two windows of frames, bins + index
     molar_hip_ctx *aux = nullptr;
     mh::DevBuf xh_win[2], xh_bins;
-
-    // molar_hip_search_contacts: a second context on THIS context's stream holds the grid, plan and slot records of the contacts
-    // calls, so the cached search of this one (count -> fill, a held `within` grid) is not disturbed; the buffers below live in it:
-    // staged labels, 64-bit accumulators of outputs that go to host memory [count | deg1 | deg2 | map], the per-frame 32-bit map
-    // of the frames form and the occupancy of a host caller
-    molar_hip_ctx *contacts = nullptr;
-    mh::DevBuf ct_g1, ct_g2, ct_acc, ct_frame, ct_occ;
-    // molar_hip_search_clusters: runs in the same second context (labels staged in its ct_g1); there live the forest and what is
-    // derived from it [parent | root | flag | rank | comp | sizes | iota | sorted keys | members | offsets], the scratch of its
-    // scans and sort, and the per-frame results of the frames form [ncomponents | largest | size_hist].  The switch and the four
-    // words of molar_hip_search_clusters_counters live in the caller's context.
-    mh::DevBuf cl_work, cl_tmp, cl_acc, cl_stats;
-    bool cl_counting = false;
 
     // ---- profiling (HIP events on `stream`)
     bool profiling = false;
@@ -374,6 +375,25 @@ void fluct_release(molar_hip_ctx *c);
 void msd_release(molar_hip_ctx *c);
 void hbonds_release(molar_hip_ctx *c);
 void lifetimes_release(molar_hip_ctx *c);
+void within_release(molar_hip_ctx *c);
+void connectivity_release(molar_hip_ctx *c);
+void contacts_release(molar_hip_ctx *c);
+
+// ---------------------------------------------------------------- the per-context state of a unit
+
+// created by the first call that gets this far
+template <class State>
+State &state_of(State *&slot) {
+    if (!slot) slot = new State;
+    return *slot;
+}
+
+// the end of a *_release: the state (its DevBuf members free themselves) and the context's pointer
+template <class State>
+void release_state(State *&slot) {
+    delete slot;
+    slot = nullptr;
+}
 
 // The block result the context keeps after molar_hip_hbonds_frames, for the units that consume it in place (lifetimes.hip):
 // the frames' offsets (HOST memory, nframes + 1), the table row of every entry (DEVICE memory), the rows of the table.

@@ -1,6 +1,6 @@
 // contact_kernels.hpp - the fused contact consumer of the distance search (molar_hip_search_contacts): per-atom contact
 // counts and a group x group contact matrix straight from the pair loop, no pair written to memory.
-// Included by search.hip (ContactArgs, the launcher's declaration) and by pair_k9.hip, which instantiates the kernels; and by
+// Included by contacts.hip (ContactArgs, the launcher's declaration) and by pair_k9.hip, which instantiates the kernels; and by
 // cluster_kernels.hpp, whose kernel walks the same records with the same slot decode and hit decision (contact_slot, contact_hit).
 //
 // One kernel walks the slot records of the REGULAR plan (plan_kernel / slotmap_kernel: the list the count pass walks), every

@@ -1,11 +1,14 @@
-// csr_kernels.hpp - small kernels the f32 search (search.hip) and the f64 search (search_f64.hip) both launch: the block
-// scan, the compaction of a flag array into ascending ids (`within` as a set) and the last two steps of SearchConnectivity's
-// CSR.  Nothing here depends on the precision of the search that made the flags or the sorted entries.
+// csr_kernels.hpp - small kernels that do not depend on the precision of the search that made the flags or the sorted entries:
+// the block scan, the compaction of a flag array into ascending ids (`within` as a set, with the host function that launches
+// it) and the last two steps of SearchConnectivity's CSR.  Included by search.hip (the block scan), by within.hip and
+// search_f64.hip (the flags of the f32 and the f64 `within` set) and by connectivity.hip (the CSR of both precisions).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+
+#include "common.hpp"
 
 namespace {
 
@@ -75,6 +78,25 @@ __global__ void __launch_bounds__(256) flag_compact_kernel(const uint8_t *__rest
     unsigned long long o = tile_off[blockIdx.x] + at;
     for (uint32_t k = 0; k < 8u; ++k)
         if (f[k]) out[o++] = i + k;
+}
+
+// The end of a within_fill of either precision: the `total` set flags as ascending u64 ids into the caller's array - device
+// memory (`dev`) as it is, host memory through `stage`, complete when the call returns.  tile_off: the scanned tile counts.
+static inline int flags_to_ids(molar_hip_ctx *c, const uint8_t *flags, uint64_t nflags, const unsigned long long *tile_off, uint64_t total,
+                               mh::DevBuf &stage, uint64_t *ids, bool dev) {
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(ids);
+    if (!dev) {
+        MH_TRY(stage.reserve((size_t)total * 8));
+        dst = stage.as<unsigned long long>();
+    }
+    const uint64_t ntiles = (nflags + 2047) / 2048;
+    hipLaunchKernelGGL(flag_compact_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, flags, nflags, tile_off, dst);
+    MH_HIP(hipGetLastError());
+    if (!dev) {
+        MH_HIP(hipMemcpyAsync(ids, dst, (size_t)total * 8, hipMemcpyDeviceToHost, c->stream));
+        MH_HIP(hipStreamSynchronize(c->stream));
+    }
+    return MOLAR_HIP_OK;
 }
 
 }  // namespace

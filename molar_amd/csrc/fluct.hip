@@ -626,9 +626,7 @@ int fluct_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, s
 
 namespace mh {
 void fluct_release(molar_hip_ctx *c) {
-    if (!c->fluct) return;
-    molar_hip_fluct_state &Z = *c->fluct;
-    release_state(c->fluct, {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_ref, &Z.ws, &Z.out_mean, &Z.out_rmsf, &Z.out_cov, &Z.out_fit});
+    release_state(c->fluct);
 }
 }  // namespace mh
 

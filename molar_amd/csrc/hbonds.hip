@@ -16,6 +16,7 @@
 // Three 8-byte read-backs per frame: the pair count (inside the search), the keys, the bonds.
 #include <algorithm>
 #include <cmath>
+#include <utility>
 #include <vector>
 
 #include "boxmath.hpp"
@@ -237,8 +238,7 @@ int grow_keep(molar_hip_ctx *c, DevBuf &b, size_t used, size_t need) {
         MH_HIP(hipMemcpyAsync(g.p, b.p, used, hipMemcpyDeviceToDevice, c->stream));
         MH_HIP(hipStreamSynchronize(c->stream));
     }
-    b.release();
-    b = g;
+    b = std::move(g);
     return 0;
 }
 
@@ -504,10 +504,7 @@ int hb_table(HbCall &X, uint64_t E, uint64_t *rows) {
 
 namespace mh {
 void hbonds_release(molar_hip_ctx *c) {
-    if (!c->hbonds) return;
-    molar_hip_hbonds_state &Z = *c->hbonds;
-    release_state(c->hbonds, {&Z.in_off, &Z.in_hidx, &Z.in_g1, &Z.in_g2, &Z.ctr, &Z.keys, &Z.sorted, &Z.ukeys, &Z.triples, &Z.dda, &Z.dha, &Z.ang, &Z.acc,
-                              &Z.ent, &Z.bsorted, &Z.perm, &Z.tkeys, &Z.occ, &Z.boe, &Z.table});
+    release_state(c->hbonds);
 }
 
 bool hbonds_block_view(const molar_hip_ctx *c, HbondsBlockView *out) {

@@ -156,4 +156,12 @@ inline bool is_pinned_host(const void *p) {
     return a.type == hipMemoryTypeHost;
 }
 
+// the pinned ring is worth its host threads for results of some size that go to memory the runtime cannot DMA into
+inline bool ring_pays(size_t link_bytes, const void *a, const void *b = nullptr, const void *d = nullptr) {
+    if (link_bytes < (24u << 20)) return false;
+    for (const void *p : {a, b, d})
+        if (p && is_pinned_host(p)) return false;
+    return true;
+}
+
 }  // namespace mh

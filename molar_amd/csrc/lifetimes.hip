@@ -460,9 +460,7 @@ int lt_run(molar_hip_ctx *c, const LtCall &X, const uint32_t *group_of_row, size
 
 namespace mh {
 void lifetimes_release(molar_hip_ctx *c) {
-    if (!c->lifetimes) return;
-    molar_hip_lifetimes_state &Z = *c->lifetimes;
-    release_state(c->lifetimes, {&Z.in_off, &Z.in_rows, &Z.in_grp, &Z.ws, &Z.out_inter, &Z.out_cont, &Z.out_hist, &Z.out_ev, &Z.out_long, &Z.out_pres});
+    release_state(c->lifetimes);
 }
 }  // namespace mh
 

@@ -1622,11 +1622,7 @@ void molar_hip_fit_stream_destroy(molar_hip_fit_stream *s) {
         if (sl.h_out) (void)hipHostFree(sl.h_out);
         if (sl.h_rec) (void)hipHostFree(sl.h_rec);
         if (sl.done) (void)hipEventDestroy(sl.done);
-        sl.cur.release(); sl.part.release(); sl.out.release();
     }
-    s->ref_pk.release();
-    s->mass_pk.release();
-    s->mass_ref_pk.release();
     delete s;
 }
 

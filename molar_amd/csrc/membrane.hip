@@ -2293,8 +2293,6 @@ extern "C" void molar_hip_membrane_plan_destroy(molar_hip_membrane_plan *P) {
         (void)hipStreamDestroy(P->copy_stream);
     }
     for (auto &S : P->slot) {
-        S.blob.release();
-        S.xyz_stage.release();
         if (S.h) (void)hipHostFree(S.h);
         if (S.h_mid) (void)hipHostFree(S.h_mid);
         if (S.done) (void)hipEventDestroy(S.done);
@@ -2302,7 +2300,6 @@ extern "C" void molar_hip_membrane_plan_destroy(molar_hip_membrane_plan *P) {
         if (S.back) (void)hipEventDestroy(S.back);
     }
     if (P->h_fetch) (void)hipHostFree(P->h_fetch);
-    P->consts.release(); P->valid.release(); P->work.release();
     delete P;
 }
 

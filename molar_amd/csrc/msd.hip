@@ -584,9 +584,7 @@ int msd_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t F, siz
 
 namespace mh {
 void msd_release(molar_hip_ctx *c) {
-    if (!c->msd) return;
-    molar_hip_msd_state &Z = *c->msd;
-    release_state(c->msd, {&Z.in_frames, &Z.in_idx, &Z.in_mass, &Z.in_boxes, &Z.in_off, &Z.in_ref, &Z.tab, &Z.ws, &Z.out_msd, &Z.out_m4, &Z.out_mp, &Z.out_disp});
+    release_state(c->msd);
 }
 }  // namespace mh
 

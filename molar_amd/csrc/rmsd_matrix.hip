@@ -403,9 +403,7 @@ int rmsd_matrix_run(molar_hip_ctx *c, const char *who, const Real *frames1, size
 
 namespace mh {
 void rmsd_matrix_release(molar_hip_ctx *c) {
-    if (!c->rmsdm) return;
-    molar_hip_rmsd_matrix_state &Z = *c->rmsdm;
-    release_state(c->rmsdm, {&Z.in_frames1, &Z.in_frames2, &Z.in_idx, &Z.in_mass, &Z.ws, &Z.out});
+    release_state(c->rmsdm);
 }
 }  // namespace mh
 

@@ -567,7 +567,10 @@ int sasa_run(molar_hip_ctx *c, const char *who, const Real *frames, size_t nfram
     MH_TRY(Z.bounds.reserve(32));
     MH_TRY(Z.gridp.reserve(sizeof(GridP)));
     MH_TRY(Z.err.reserve(8));
-    for (DevBuf *b : {&Z.key_in, &Z.key_out, &Z.val_in, &Z.val_out}) MH_TRY(b->reserve((size_t)ns * 4));
+    MH_TRY(Z.key_in.reserve((size_t)ns * 4));
+    MH_TRY(Z.key_out.reserve((size_t)ns * 4));
+    MH_TRY(Z.val_in.reserve((size_t)ns * 4));
+    MH_TRY(Z.val_out.reserve((size_t)ns * 4));
     MH_TRY(Z.cell_count.reserve(((size_t)cap + 2) * 4));
     MH_TRY(Z.cell_start.reserve(((size_t)cap + 2) * 4));
     MH_TRY(Z.rec.reserve((size_t)ns * 4 * sizeof(Real)));
@@ -666,14 +669,7 @@ int sasa_points(const char *who, uint32_t npoints, Real *out_xyz) {
 
 namespace mh {
 void sasa_release(molar_hip_ctx *c) {
-    if (!c->sasa) return;
-    molar_hip_sasa_state &Z = *c->sasa;
-    for (DevBuf *b : {&Z.in_xyz, &Z.in_idx, &Z.in_vdw, &Z.table[0], &Z.table[1], &Z.bounds, &Z.gridp, &Z.err, &Z.key_in, &Z.key_out, &Z.val_in, &Z.val_out,
-                      &Z.cub_tmp, &Z.cell_count, &Z.cell_start, &Z.rec, &Z.partials, &Z.totals, &Z.vpartials, &Z.vtotals, &Z.out_areas, &Z.out_exposed,
-                      &Z.out_volumes})
-        b->release();
-    delete c->sasa;
-    c->sasa = nullptr;
+    release_state(c->sasa);
 }
 }  // namespace mh
 

@@ -26,11 +26,9 @@
 #include <algorithm>
 
 #include "pair_kernels.hpp"
-#include "contact_kernels.hpp"
-#include "cluster_kernels.hpp"
+#include "search_core.hpp"
 #include "search_shape.hpp"
 #include "stages.hpp"
-#include "unwrap_walk.hpp"
 
 namespace mh {
 // pair_small.hip: count / fill kernels for frames of small cells, 64 / lanes_per_slot slots per wave
@@ -1261,24 +1259,7 @@ static void occ_note(molar_hip_ctx *c, unsigned long long key, const SearchSizes
     c->occ_valid = true;
 }
 
-// What ONE request asks of the helpers below (prepare_search, build_grid, the plan, launch_pairs), beyond its descriptor.  It
-// lives on the caller's stack and goes down the call chain by reference; the context holds only what outlasts a request.
-// `side` is a wish: prepare_search decides (takes_side_lane) and hands the grid build the lane it chose (GridLane, above) - the
-// stream is an argument of the helpers that launch a grid, not a field they find swapped.
-struct SearchCall {
-    bool plan = true;              // prepare_search enqueues the plan (false: the caller walks cells, or plans inside launch_pairs)
-    bool within_set = false;       // the request is molar_hip_within_count's: its first set's grid may be held (molar_hip_within_hold)
-    bool hist_plan = false;        // fused histogram of the fixed-cutoff kinds: grid and slot bound for hist_plan_kernel
-    bool size_masks = true;        // count -> fill pair: read the plan's sizes back and size the hit-history buffer exactly
-    bool side = false;             // the grid may be built on the side stream (pipelined searches, asynchronous histograms) ...
-    hipEvent_t side_wait = nullptr;            // ... which first waits for this (the last reader of the grid generation)
-    unsigned long long out_cap = ~0ull;        // resident searches: the output capacity in the parameter block (plan kernel, pair passes)
-    SearchSizes *sizes_dev = nullptr;          // resident searches: device-side address of the pinned record the kernels write
-    bool drop_nonfinite = false;   // the grid leaves atoms with a non-finite coordinate out (stages.hpp, search_resident_enqueue)
-    uint32_t slot_launch = 0;      // resident searches: slots the count and fill passes launch (0: the bound; common.hpp, trim_real)
-    bool live_rows = true;         // the slots go to the count / fill passes, which walk live-ranked slots where live_row_slots() says so
-                                   // (false: another kernel reads the records - the contact kernels - and wants consecutive rows)
-};
+// (SearchCall - what ONE request asks of prepare_search, build_grid, the plan and launch_pairs - is in search_core.hpp)
 
 // the side stream (highest priority) and the event its grid builds end with, created on first use
 static int ensure_side_stream(molar_hip_ctx *c) {
@@ -1933,10 +1914,12 @@ bool takes_side_lane(const molar_hip_ctx *c, const molar_hip_search_desc *q, con
            cur.set[0].d_idx == q->idx1 && (!two || (cur.set[1].d_xyz == q->xyz2 && cur.set[1].d_idx == q->idx2));
 }
 
+}  // namespace
+
 // Everything of a search up to its pair passes: the request described in c->cur, the grids built, the plan enqueued.
 // *degenerate: the request came to nothing (empty vdW input) - nothing was enqueued, c->cur says one cell and no plan entries,
 // c->total is 0; what that means for the context's cached search is the caller's to say.
-int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call, bool *degenerate) {
+int mh::prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const SearchCall &call, bool *degenerate) {
     *degenerate = false;
     if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: null argument");
     if (q->kind < 0 || q->kind > 3) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: unknown kind %d", q->kind);
@@ -1977,6 +1960,8 @@ int prepare_search(molar_hip_ctx *c, const molar_hip_search_desc *q, const Searc
     return 0;
 }
 
+namespace {
+
 int finish_count(molar_hip_ctx *c) {
     Prof *prof = new Prof(c, 2);
     // (the look-back scan is slower here: ~140 chained tiles take 43 us against 14 us for the three-kernel scan)
@@ -1998,213 +1983,6 @@ int finish_count(molar_hip_ctx *c) {
     c->total = tot;
     c->have_search = true;
     return 0;
-}
-
-// ================================================================= SearchConnectivity on the device (connectivity.rs:19-35)
-// `for (i, j) in pairs { conn[i].push(j); conn[j].push(i) }` as CSR: degrees by atomics, an exclusive scan, every entry
-// dropped into its list in arrival order, then moved to its place - the number of entries of the same list that come from
-// earlier pairs (a pair feeds a list at most once per side; the entry of its i side precedes that of its j side when i == j
-// never happens: the single searches emit i != j).  Lists are a handful of bonded neighbours long, so the ranking reads its
-// own list; the result is the reference's push order exactly.
-// SearchConnectivity::from_iter (connectivity.rs:19-35): pair p pushes j onto i's list (entry 2p), then i onto j's (entry 2p + 1).
-// A list in push order is the entries of its row in entry order: a STABLE sort of the entries by row (devsort.hip).  (Until the end
-// of round 5: atomics into buckets, then every entry ranked against its whole list - quadratic in the list length, 10 ms of an
-// 11 ms call for 25k atoms at rc 1.0 nm, 420 entries per list.)
-__global__ void __launch_bounds__(256) conn_entries_kernel(const uint2 *__restrict__ pairs, unsigned long long npairs, uint32_t *__restrict__ row,
-                                                           uint32_t *__restrict__ nb) {
-    const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
-    if (p >= npairs) return;
-    const uint2 ij = pairs[p];
-    reinterpret_cast<uint2 *>(row)[p] = make_uint2(ij.x, ij.y);
-    reinterpret_cast<uint2 *>(nb)[p] = make_uint2(ij.y, ij.x);
-}
-
-// ================================================================= `within` as a set (selection/ast.rs:589-631)
-//
-// What a caller of distance_search_within(_pbc) keeps is the SET of first-set atoms with a second-set atom in range: the
-// raw stream (one id per plan entry in which the atom has a hit, :271-322,519-598) goes through SortedSet::from_unsorted
-// (selection_expr.rs:112).  A set needs no stream, no offsets and no second pass - and an atom that has been found needs
-// no further candidates, in ANY of its up to 28 plan entries:
-//  * within_partners_kernel inverts the plan (same decode_task as every other kernel, so the same wrap / drop rules and
-//    the same incomplete neighbourhoods of sheared boxes): per first-set cell the list of (second-set cell, wrap dims)
-//    it meets, from both halves of every entry;
-//  * within_flags_kernel: one wave per (first-set cell, share of its 64-row blocks) walks that list with a mask of the
-//    rows still looking; per partner the rows that cannot reach its bounding box are left out (plain entries: the
-//    exact f32 lower bound of run_fast), the partner's atoms are loaded 64 at a time, every remaining row is fetched
-//    with one LDS broadcast and tested with the reference's arithmetic (PeriodicBox::distance_squared over the entry's
-//    wrap dims for wrapped entries); a row leaves the mask at its first hit, the wave leaves the list when the mask is
-//    empty; found rows set flags[id];
-//  * ids are indices into a sorted selection (or 0..n), so the flagged positions in ascending order ARE the sorted,
-//    de-duplicated result: a count per 2048-flag tile, a scan of the tile counts and one compaction pass.
-constexpr uint32_t WITHIN_MAX_PART = 28;
-// every (mask, half) pair of the plan has exactly one first-set cell as its origin: a cell is the first cell of at most
-// 14 masks x 2 halves entries.  A plan with more masks or another stencil must grow the lists with it.
-static_assert(WITHIN_MAX_PART == 2u * sizeof(pairk::MASKS) / sizeof(pairk::MASKS[0]), "partner lists are sized for the plan's stencil");
-
-__global__ void __launch_bounds__(256) within_partners_kernel(const SearchParams *__restrict__ Pp, uint32_t *__restrict__ part_cnt,
-                                                              uint32_t *__restrict__ part) {
-    const SearchParams &P = *Pp;
-    const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (t >= P.ntasks) return;
-    const Task T = decode_task<MOLAR_HIP_SEARCH_WITHIN, false>(P, t);
-    if (!T.valid) return;
-    const uint32_t s = atomicAdd(&part_cnt[T.ca], 1u);
-    if (s < WITHIN_MAX_PART) part[(size_t)T.ca * WITHIN_MAX_PART + s] = T.cb | (T.wrap << 28);
-}
-
-// `within` against a SMALL second set (a ligand, a few residues: selection/ast.rs:589-631 on the shapes of
-// molar/benches/within_size_bench.rs): the plan is walked from the second set's side.  One wave per (second-set atom, one of
-// the 28 (mask, half) combinations); the wave of the FIRST atom of each occupied second-set cell finds the one plan entry
-// that has this cell as its second cell through that combination (decode_task on the candidate entry index: the
-// reference's own wrap / drop rules decide, nothing is re-derived), and tests the rows of the entry's first cell, 64 at a
-// time, lanes = rows, against the cell's few atoms with the reference's arithmetic (distance_squared over the entry's wrap
-// dims for wrapped entries).  A row that finds a partner sets its flag byte with an atomic OR on the containing word; the
-// lane that turned it on appends the id to a list - the result, unsorted, with its length in memory.  No partner lists over
-// all cells, no pass over the whole plan, no flag scan: two launches and one read-back for `within 0.8 of <20 atoms>`.
-__global__ void __launch_bounds__(64) within_small_kernel(const SearchParams *__restrict__ Pp, uint32_t n2, uint32_t ncells, uint32_t by_cell,
-                                                          uint32_t *__restrict__ flags32, uint32_t *__restrict__ list,
-                                                          uint32_t *__restrict__ list_n) {
-    const SearchParams &P = *Pp;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t j = blockIdx.x / 28u, combo = blockIdx.x % 28u;
-    uint32_t cell;
-    if (by_cell) {                  // fewer cells than second-set atoms (large cutoffs): one wave per (cell, combination)
-        cell = j;
-        if (cell >= ncells || P.csb[cell + 1] == P.csb[cell]) return;
-    } else {
-        if (j >= n2) return;
-        // the cell of sorted second-set atom j: the last cell whose start is <= j (binary search over cell_start)
-        uint32_t lo = 0u, hi = ncells;
-        while (hi - lo > 1u) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (P.csb[mid] <= j) lo = mid;
-            else hi = mid;
-        }
-        cell = lo;
-        if (P.csb[cell] != j) return;                               // not the first atom of its cell
-    }
-    const uint32_t m = combo >> 1, half = combo & 1u;
-    const uint32_t cz = cell / (P.dx * P.dy), cy = (cell / P.dx) % P.dy, cx = cell % P.dx;
-    const uint32_t cc[3] = {cx, cy, cz}, dims[3] = {P.dx, P.dy, P.dz};
-    uint32_t home[3];
-    for (int d = 0; d < 3; ++d) {
-        const uint32_t off = half ? MASKS[m][d] : MASKS[m][3 + d];   // offset of the entry's SECOND cell from its home cell
-        if (cc[d] >= off) home[d] = cc[d] - off;
-        else if ((P.pbc >> d) & 1u) home[d] = dims[d] - 1u;          // reached across the periodic boundary
-        else return;
-    }
-    const uint64_t cidx = ((uint64_t)home[0] * P.dy + home[1]) * P.dz + home[2];          // x outer, z inner
-    const uint64_t t = (cidx * 14ull + m) * 2ull + half;
-    if (t >= P.ntasks) return;
-    const Task T = decode_task<MOLAR_HIP_SEARCH_WITHIN, false>(P, t);
-    if (!T.valid || T.cb != cell) return;
-    const float cutoff2 = P.cutoff2;
-    const bool wrapped = P.use_box && T.wrap != 0u;
-    float4 lo4 = make_float4(0.f, 0.f, 0.f, 0.f), hi4 = lo4;
-    if (!wrapped) {
-        lo4 = gload4(P.aabb_b, 2 * T.cb);
-        hi4 = gload4(P.aabb_b, 2 * T.cb + 1);
-    }
-    // (blockIdx.y: a share of the first cell's 64-row blocks - large cutoffs mean cells of thousands of atoms)
-    for (uint32_t i0 = blockIdx.y * 64u; i0 < T.n1; i0 += gridDim.y * 64u) {
-        const bool have = i0 + lane < T.n1;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (have) a = gload4(P.sa, T.a0 + i0 + lane);
-        bool look = have;
-        if (!wrapped) look = look && !(aabb_d2(a.x, a.y, a.z, lo4.x, lo4.y, lo4.z, hi4.x, hi4.y, hi4.z) > cutoff2);
-        if (__builtin_amdgcn_ballot_w64(look) == 0ull) continue;
-        bool found = false;
-        for (uint32_t k0 = 0; k0 < T.n2; k0 += 64u) {
-            // 64 partner atoms at a time into the lanes, handed round with v_readlane (one load per 64 partners, not one each)
-            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (k0 + lane < T.n2) q = gload4(P.sb, T.b0 + k0 + lane);
-            const uint32_t cnt = T.n2 - k0 < 64u ? T.n2 - k0 : 64u;
-            for (uint32_t kk = 0; kk < cnt; ++kk) {
-                const float bx = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(q.x), kk));
-                const float by = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(q.y), kk));
-                const float bz = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(q.z), kk));
-                const float dx = bx - a.x, dy = by - a.y, dz = bz - a.z;                   // p2 - p1
-                const float d2 = wrapped ? wrapped_d2_exact<true>(P, T.wrap, dx, dy, dz)    // :306-321
-                                         : (dx * dx + dy * dy) + dz * dz;                  // :281-292
-                found = found || (look && d2 <= cutoff2);
-                if ((kk & 7u) == 7u && __builtin_amdgcn_ballot_w64(look && !found) == 0ull) break;      // every row has its partner (:289, :318)
-            }
-            if (__builtin_amdgcn_ballot_w64(look && !found) == 0ull) break;
-        }
-        if (found) {
-            const uint32_t id = __float_as_uint(a.w);
-            const uint32_t bit = 1u << (8u * (id & 3u));
-            const uint32_t old = atomicOr(&flags32[id >> 2], bit);
-            if (!(old & bit)) list[atomicAdd(list_n, 1u)] = id;
-        }
-    }
-}
-
-// clears the flags a small-path call set (through its list) instead of a memset over every flag
-__global__ void __launch_bounds__(256) within_clear_kernel(const uint32_t *__restrict__ list, uint32_t n, uint8_t *__restrict__ flags) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) flags[list[i]] = 0u;
-}
-
-__global__ void __launch_bounds__(64) within_flags_kernel(const SearchParams *__restrict__ Pp, const uint32_t *__restrict__ part_cnt,
-                                                          const uint32_t *__restrict__ part, uint8_t *__restrict__ flags,
-                                                          uint32_t nsplit) {
-    __shared__ float4 la[64];
-    const SearchParams &P = *Pp;
-    const uint32_t lane = threadIdx.x, ca = blockIdx.x, split = blockIdx.y;
-    const uint32_t a0 = P.csa[ca], n1 = P.csa[ca + 1] - a0;
-    uint32_t np = part_cnt[ca];
-    if (n1 == 0u || np == 0u) return;
-    if (np > WITHIN_MAX_PART) np = WITHIN_MAX_PART;
-    const float cutoff2 = P.cutoff2;
-    for (uint32_t i0 = split * 64u; i0 < n1; i0 += nsplit * 64u) {
-        const uint32_t rows = n1 - i0 < 64u ? n1 - i0 : 64u;
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lane < rows) a = gload4(P.sa, a0 + i0 + lane);
-        __builtin_amdgcn_wave_barrier();
-        la[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        const unsigned long long full = rows == 64u ? ~0ull : ((1ull << rows) - 1ull);
-        unsigned long long live = full;                      // rows still looking for a partner atom
-        for (uint32_t pi = 0; pi < np && live; ++pi) {
-            const uint32_t e = __builtin_amdgcn_readfirstlane(part[(size_t)ca * WITHIN_MAX_PART + pi]);
-            const uint32_t cb = e & 0x0FFFFFFFu, wrap = e >> 28;
-            const uint32_t b0 = P.csb[cb], n2 = P.csb[cb + 1] - b0;
-            unsigned long long cand = live;
-            if (!wrap) {       // rows that cannot reach the partner's box: the f32 lower bound of every d2 of the row (run_fast)
-                const float4 lo = gload4(P.aabb_b, 2 * cb), hi = gload4(P.aabb_b, 2 * cb + 1);
-                cand &= __builtin_amdgcn_ballot_w64(!(aabb_d2(a.x, a.y, a.z, lo.x, lo.y, lo.z, hi.x, hi.y, hi.z) > cutoff2));
-            }
-            for (uint32_t j0 = 0; j0 < n2 && cand; j0 += 64u) {
-                const bool inb = j0 + lane < n2;
-                float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (inb) q = gload4(P.sb, b0 + j0 + lane);
-                unsigned long long rm = cand;
-                while (rm) {
-                    const uint32_t r = (uint32_t)__builtin_ctzll(rm);
-                    rm &= rm - 1ull;
-                    const float4 p = lload4(la, r);                                  // one broadcast ds_read per row
-                    const float dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z;      // p2 - p1
-                    const float d2 = wrap ? wrapped_d2_exact<true>(P, wrap, dx, dy, dz)    // :306-321 (distance_squared over the entry's dims)
-                                          : (dx * dx + dy * dy) + dz * dz;          // :281-292
-                    if (__builtin_amdgcn_ballot_w64(inb && d2 <= cutoff2)) {         // `break` at the first hit (:289, :318)
-                        live &= ~(1ull << r);
-                        cand &= ~(1ull << r);
-                    }
-                }
-            }
-        }
-        const unsigned long long found = full & ~live;
-        if ((found >> lane) & 1ull) flags[__float_as_uint(a.w)] = 1u;
-    }
-}
-
-// the pinned ring is worth its host threads for results of some size that go to memory the runtime cannot DMA into
-bool ring_pays(size_t link_bytes, const void *a, const void *b = nullptr, const void *d = nullptr) {
-    if (link_bytes < (24u << 20)) return false;
-    for (const void *p : {a, b, d})
-        if (p && is_pinned_host(p)) return false;
-    return true;
 }
 
 }  // namespace
@@ -2440,6 +2218,20 @@ static int resident_run(molar_hip_ctx *c, const molar_hip_search_desc *q, mh::De
 }
 
 }  // extern "C"
+
+// search_core.hpp: what the units that are search requests themselves call besides prepare_search
+int mh::upload_search_params(molar_hip_ctx *c, const SearchShape &shape) {
+    MH_TRY(c->params.reserve(sizeof(SearchParams)));
+    const SearchParams P = make_params(c, shape);
+    hipLaunchKernelGGL(upload_params_kernel, dim3(1), dim3(256), 0, c->stream, P, c->params.as<SearchParams>());
+    return 0;
+}
+
+int mh::scan_counts_u64(molar_hip_ctx *c, const uint32_t *counts, unsigned long long *offsets, uint64_t n) {
+    return exclusive_scan<uint32_t, unsigned long long>(main_lane(c), counts, offsets, n);
+}
+
+int mh::resident_pairs(molar_hip_ctx *c, const molar_hip_search_desc *q) { return resident_run(c, q, c->out_pairs, c->out_dist, /*pairs_only=*/true); }
 
 // stages.hpp: the resident search for callers that chain device work behind it
 int mh::search_resident_enqueue(molar_hip_ctx *c, const molar_hip_search_desc *q, SearchSizes *sizes_pinned, ResidentLaunch *L,
@@ -2989,664 +2781,3 @@ int molar_hip_search_histogram_frames(molar_hip_ctx *c, const molar_hip_search_d
 }
 
 }  // extern "C"
-
-// ================================================================= fused contact counts (contact_kernels.hpp, pair_k9.hip)
-//
-// molar_hip_search_contacts / _frames.  The grid, the REGULAR plan and its slot records are those of the count pass
-// (prepare_search with ids_local forced on, so the id an atom carries is its position in the selection); contact_kernel walks
-// the slot list once and adds degrees, map and |L| on chip-summed portions.  All of it runs on a second context that shares
-// this context's stream (molar_hip_ctx::contacts): nothing the caller has cached here - a counted search waiting for its fill,
-// a held `within` grid, the histogram's grid generations - is touched.
-// Outputs in device memory are added into directly; outputs in host memory go through zeroed 64-bit accumulators that are
-// read back and added on the host at the end of the call (of the block, in the frames form).
-// Occupancy (frames form): the kernel adds the frame's map into ONE 32-bit scratch matrix of ngroups1 * ngroups2 words; behind
-// the frame's kernel contact_fold_kernel adds it into the map, counts its non-zero entries into the occupancy and clears it.
-// The frames are walked one after the other on one stream, so the fold of frame k is ordered in front of the kernel of
-// frame k + 1 and one scratch (4 bytes per map entry, 64 MiB at the 2^24 cap) serves the whole block.
-namespace {
-
-__global__ void __launch_bounds__(256) contact_check_labels_kernel(const uint32_t *__restrict__ g, size_t n, uint32_t ngroups, uint32_t *__restrict__ flag) {
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u)
-        if (g[i] >= ngroups) *flag = 1u;
-}
-
-__global__ void __launch_bounds__(256) contact_fold_kernel(uint32_t *__restrict__ frame, size_t n, unsigned long long *__restrict__ map,
-                                                           uint32_t *__restrict__ occ) {
-    for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
-        const uint32_t v = frame[i];
-        if (v) {
-            if (map) map[i] += v;
-            if (occ) occ[i] += 1u;
-            frame[i] = 0u;
-        }
-    }
-}
-
-struct ContactCall {
-    molar_hip_ctx *s = nullptr;        // the contacts context
-    bool two = false;
-    size_t n1 = 0, n2 = 0, nmap = 0;
-    const uint32_t *g1 = nullptr, *g2 = nullptr;                 // device labels (NULL: no map, no occupancy)
-    size_t ng2 = 0;
-    uint64_t *h_deg1 = nullptr, *h_deg2 = nullptr, *h_map = nullptr;   // caller's HOST outputs (added at the end)
-    uint32_t *h_occ = nullptr;
-    unsigned long long *t_count = nullptr, *t_deg1 = nullptr, *t_deg2 = nullptr, *t_map = nullptr;   // what the kernels add into
-    uint32_t *t_frame = nullptr, *t_occ = nullptr;
-};
-
-constexpr size_t CONTACT_MAP_MAX = (size_t)1 << 24;
-
-// labels of one set: checked (on the host when they are host memory, else by a kernel and a 4-byte read-back), then device-readable
-int contact_labels(molar_hip_ctx *s, const uint32_t *g, size_t n, size_t ngroups, DevBuf &stage, const uint32_t **out, const char *who) {
-    const uint32_t ng = (uint32_t)ngroups;
-    if (!is_device_ptr(g)) {
-        for (size_t i = 0; i < n; ++i)
-            if (g[i] >= ng)
-                return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: label %u of atom %zu is not below ngroups = %zu", who, g[i], i, ngroups);
-        return to_device(s, g, n, stage, out);
-    }
-    *out = g;
-    if (n == 0) return 0;
-    MH_TRY(s->hist.reserve(64));
-    uint32_t *flag = s->hist.as<uint32_t>();
-    MH_HIP(hipMemsetAsync(flag, 0, 4, s->stream));
-    const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 1024);
-    hipLaunchKernelGGL(contact_check_labels_kernel, dim3(nb), dim3(256), 0, s->stream, g, n, ng, flag);
-    MH_HIP(hipGetLastError());
-    uint32_t bad = 0;
-    MH_TRY(read_back(s, &bad, flag, 4));
-    if (bad) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = %zu", who, ngroups);
-    return 0;
-}
-
-// the second context of the contacts and clusters calls (molar_hip_ctx::contacts), made on first use, on the caller's stream
-int contacts_context(molar_hip_ctx *c, molar_hip_ctx **out) {
-    MH_HIP(hipSetDevice(c->device));
-    if (!c->contacts) {
-        molar_hip_ctx *s = molar_hip_create(c->device);
-        if (!s) return MOLAR_HIP_ERR_HIP;
-        (void)hipStreamDestroy(s->stream);
-        s->own_stream = false;
-        c->contacts = s;
-    }
-    c->contacts->stream = c->stream;
-    *out = c->contacts;
-    return 0;
-}
-
-int contacts_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
-                   uint64_t *map, uint32_t *occ, ContactCall &K, const char *who) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-    if (q->kind != MOLAR_HIP_SEARCH_SINGLE && q->kind != MOLAR_HIP_SEARCH_DOUBLE)
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: only the SINGLE and DOUBLE kinds have contact counts (got kind %d)", who, q->kind);
-    K.two = q->kind == MOLAR_HIP_SEARCH_DOUBLE;
-    if (!K.two && deg2) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: deg2 must be NULL for a single-set search (deg1 counts both members)", who);
-    if (!q->xyz1 || (K.two && !q->xyz2)) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: xyz pointer is null");
-    K.n1 = q->idx1 ? q->n1 : q->natoms1;
-    K.n2 = K.two ? (q->idx2 ? q->n2 : q->natoms2) : 0;
-    const bool want_map = map != nullptr || occ != nullptr;
-    size_t G1 = 0, G2 = 0;
-    if (want_map) {
-        if (!groups || !groups->group1 || (K.two && !groups->group2))
-            return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a map or an occupancy needs group labels", who);
-        G1 = groups->ngroups1;
-        G2 = K.two ? groups->ngroups2 : G1;
-        if (G1 > CONTACT_MAP_MAX || G2 > CONTACT_MAP_MAX || G1 * G2 > CONTACT_MAP_MAX)
-            return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: the map is dense, ngroups1 * ngroups2 may be 2^24 at most (got %zu x %zu)", who, G1, G2);
-        if ((G1 == 0 && K.n1 != 0) || (G2 == 0 && (K.two ? K.n2 : K.n1) != 0))
-            return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = 0", who);
-    }
-    K.nmap = G1 * G2;
-    K.ng2 = G2;
-    MH_TRY(contacts_context(c, &K.s));
-    molar_hip_ctx *s = K.s;
-    if (want_map && K.nmap) {
-        MH_TRY(contact_labels(s, groups->group1, K.n1, G1, s->ct_g1, &K.g1, who));
-        if (K.two) MH_TRY(contact_labels(s, groups->group2, K.n2, G2, s->ct_g2, &K.g2, who));
-        else K.g2 = K.g1;
-    }
-    // ---- where the sums go
-    const bool d1 = deg1 && !is_device_ptr(deg1), d2 = deg2 && !is_device_ptr(deg2), dm = map && !is_device_ptr(map);
-    const size_t words = 1 + (d1 ? K.n1 : 0) + (d2 ? K.n2 : 0) + (dm ? K.nmap : 0);
-    MH_TRY(s->ct_acc.reserve(words * 8));
-    MH_HIP(hipMemsetAsync(s->ct_acc.p, 0, words * 8, s->stream));
-    unsigned long long *w = s->ct_acc.as<unsigned long long>();
-    K.t_count = w;
-    w += 1;
-    K.t_deg1 = reinterpret_cast<unsigned long long *>(deg1);
-    K.t_deg2 = reinterpret_cast<unsigned long long *>(deg2);
-    K.t_map = reinterpret_cast<unsigned long long *>(map);
-    if (d1) { K.h_deg1 = deg1; K.t_deg1 = w; w += K.n1; }
-    if (d2) { K.h_deg2 = deg2; K.t_deg2 = w; w += K.n2; }
-    if (dm) { K.h_map = map; K.t_map = w; w += K.nmap; }
-    if (occ && K.nmap) {
-        MH_TRY(s->ct_frame.reserve(K.nmap * 4));
-        MH_HIP(hipMemsetAsync(s->ct_frame.p, 0, K.nmap * 4, s->stream));
-        K.t_frame = s->ct_frame.as<uint32_t>();
-        K.t_occ = occ;
-        if (!is_device_ptr(occ)) {
-            MH_TRY(s->ct_occ.reserve(K.nmap * 4));
-            MH_HIP(hipMemsetAsync(s->ct_occ.p, 0, K.nmap * 4, s->stream));
-            K.h_occ = occ;
-            K.t_occ = s->ct_occ.as<uint32_t>();
-        }
-    }
-    return 0;
-}
-
-// one frame: grid, plan, the contact kernel and (frames form with occupancy) the fold - enqueued, nothing waited for beyond what
-// prepare_search itself needs (the bounding box of a non-periodic request is read back)
-int contacts_frame(ContactCall &K, const molar_hip_search_desc *q) {
-    if (K.n1 == 0 || (K.two && K.n2 == 0)) return 0;
-    molar_hip_ctx *s = K.s;
-    molar_hip_search_desc qq = *q;
-    qq.ids_local = 1;                       // ids are positions in the selection, whatever the caller's list would carry
-    SearchCall call;
-    call.size_masks = false;
-    call.live_rows = false;                 // contact_kernel walks consecutive rows
-    bool degenerate;
-    MH_TRY(prepare_search(s, &qq, call, &degenerate));      // (the plan kernel leaves the parameter block in s->params)
-    s->params_fresh = false;
-    const SearchShape &cur = s->cur;
-    if (degenerate || cur.nslots_bound == 0) return 0;      // (degenerate: never - empty sets have returned above)
-    ContactArgs A{};
-    A.g1 = K.g1;
-    A.g2 = K.g2;
-    A.ng2 = (uint32_t)K.ng2;
-    A.deg1 = K.t_deg1;
-    A.deg2 = K.two ? K.t_deg2 : K.t_deg1;
-    A.map = K.t_frame ? nullptr : K.t_map;
-    A.map32 = K.t_frame;
-    if (!A.map && !A.map32) A.g1 = A.g2 = nullptr;
-    A.count = K.t_count;
-    {
-        Prof prof(s, 3);
-        launch_contacts(cur.kind, (unsigned)s->num_cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)cur.nslots_bound, A);
-        MH_HIP(hipGetLastError());
-    }
-    if (K.t_frame) {
-        const unsigned nb = (unsigned)std::min<size_t>((K.nmap + 255) / 256, (size_t)s->num_cus * 16);
-        hipLaunchKernelGGL(contact_fold_kernel, dim3(nb), dim3(256), 0, s->stream, K.t_frame, K.nmap, K.t_map, K.t_occ);
-        MH_HIP(hipGetLastError());
-    }
-    return 0;
-}
-
-int contacts_end(ContactCall &K, uint64_t *out_count) {
-    molar_hip_ctx *s = K.s;
-    auto add_back = [&](uint64_t *dst, const unsigned long long *src, size_t n) -> int {
-        if (!dst || n == 0) return 0;
-        std::vector<unsigned long long> h(n);
-        MH_TRY(read_back(s, h.data(), src, n * 8));
-        for (size_t i = 0; i < n; ++i) dst[i] += h[i];
-        return 0;
-    };
-    MH_TRY(add_back(K.h_deg1, K.t_deg1, K.n1));
-    MH_TRY(add_back(K.h_deg2, K.t_deg2, K.n2));
-    MH_TRY(add_back(K.h_map, K.t_map, K.nmap));
-    if (K.h_occ && K.nmap) {
-        std::vector<uint32_t> h(K.nmap);
-        MH_TRY(read_back(s, h.data(), K.t_occ, K.nmap * 4));
-        for (size_t i = 0; i < K.nmap; ++i) K.h_occ[i] += h[i];
-    }
-    if (out_count) {
-        unsigned long long tot = 0;
-        MH_TRY(read_back(s, &tot, K.t_count, 8));
-        *out_count = tot;
-    }
-    return 0;
-}
-
-// ================================================================= connected components (cluster_kernels.hpp, pair_k12.hip)
-//
-// molar_hip_search_clusters / _frames.  Grid, plan and slot records as for the contacts calls, in the same second context and
-// under the same settings (ids are positions in the selection, consecutive rows, no hit history), so nothing the caller has
-// cached is touched.  Per frame, all on one stream: parent = identity; cluster_kernel unites the ends of every hit; then
-// flatten -> scan of the root flags (ranks) -> labels and sizes -> (members wanted) scan of the sizes and one stable sort of
-// (component, particle).  Everything is computed in this context's work area and copied to the caller's arrays, host or device.
-struct ClusterCall {
-    molar_hip_ctx *s = nullptr;        // the contacts context
-    size_t n = 0, np = 0;              // selected atoms, particles
-    const uint32_t *g = nullptr;       // device labels (NULL: every atom is a particle)
-    bool members = false;              // offsets / members are wanted
-    unsigned long long *stats = nullptr;
-    uint32_t *parent = nullptr, *root = nullptr, *flag = nullptr, *rank = nullptr, *comp = nullptr, *sizes = nullptr, *iota = nullptr,
-             *keys = nullptr, *memb = nullptr;
-    unsigned long long *offsets = nullptr;
-};
-
-int clusters_begin(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, bool want_members, ClusterCall &K,
-                   const char *who) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-    if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: only the SINGLE kind has connected components (got kind %d)", who, q->kind);
-    if (!q->xyz1) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search: xyz pointer is null");
-    K.n = q->idx1 ? q->n1 : q->natoms1;
-    const bool grouped = groups && groups->group1;
-    K.np = grouped ? groups->ngroups1 : K.n;
-    if (grouped && K.np == 0 && K.n != 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a label is not below ngroups = 0", who);
-    if (K.np + 1 >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "%s: %zu particles", who, K.np);
-    K.members = want_members;
-    MH_TRY(contacts_context(c, &K.s));
-    molar_hip_ctx *s = K.s;
-    if (grouped && K.n) MH_TRY(contact_labels(s, groups->group1, K.n, K.np, s->ct_g1, &K.g, who));
-    if (c->cl_counting) K.stats = c->cl_stats.as<unsigned long long>();
-    const size_t np = K.np, words = (9 * np + 3 + 1) & ~(size_t)1;
-    MH_TRY(s->cl_work.reserve(words * 4 + (np + 1) * 8));
-    uint32_t *w = s->cl_work.as<uint32_t>();
-    K.parent = w; w += np;
-    K.root = w; w += np;
-    K.flag = w; w += np + 1;
-    K.rank = w; w += np + 1;
-    K.comp = w; w += np;
-    K.sizes = w; w += np + 1;
-    K.iota = w; w += np;
-    K.keys = w; w += np;
-    K.memb = w;
-    K.offsets = reinterpret_cast<unsigned long long *>(s->cl_work.as<uint32_t>() + words);
-    return 0;
-}
-
-// one frame, enqueued: the forest, its union over the frame's hits, and what is derived from it
-int clusters_frame(ClusterCall &K, const molar_hip_search_desc *q) {
-    if (K.np == 0) return 0;
-    molar_hip_ctx *s = K.s;
-    const unsigned cus = (unsigned)s->num_cus;
-    const uint32_t np = (uint32_t)K.np;
-    launch_cluster_init(cus, s->stream, K.parent, np);
-    MH_HIP(hipGetLastError());
-    if (K.n != 0) {
-        molar_hip_search_desc qq = *q;
-        qq.ids_local = 1;                       // ids are positions in the selection
-        SearchCall call;
-        call.size_masks = false;
-        call.live_rows = false;                 // cluster_kernel walks consecutive rows
-        bool degenerate;
-        MH_TRY(prepare_search(s, &qq, call, &degenerate));
-        s->params_fresh = false;
-        const SearchShape &cur = s->cur;
-        if (!degenerate && cur.nslots_bound != 0) {
-            ClusterArgs A{};
-            A.g = K.g;
-            A.parent = K.parent;
-            A.stats = K.stats;
-            Prof prof(s, 3);
-            launch_clusters(cus, s->stream, s->params.as<SearchParams>(), s->slot_desc.as<SlotDesc>(), (uint32_t)cur.nslots_bound, A);
-            MH_HIP(hipGetLastError());
-        }
-    }
-    launch_cluster_flatten(cus, s->stream, K.parent, np, K.root, K.flag);
-    MH_HIP(hipGetLastError());
-    MH_TRY(device_exclusive_sum_u32(s, s->cl_tmp, K.flag, K.rank, (size_t)np + 1));      // rank[np] = number of components
-    MH_HIP(hipMemsetAsync(K.sizes, 0, ((size_t)np + 1) * 4, s->stream));
-    launch_cluster_label(cus, s->stream, K.root, K.rank, np, K.comp, K.sizes, K.iota);
-    MH_HIP(hipGetLastError());
-    if (K.members) {
-        MH_TRY(device_exclusive_sum_u32_u64(s, s->cl_tmp, K.sizes, K.offsets, (size_t)np + 1));
-        int end_bit = 1;
-        while (end_bit < 32 && ((uint64_t)1 << end_bit) < (uint64_t)np) ++end_bit;
-        MH_TRY(device_sort_pairs_u32(s->stream, s->cl_tmp, K.comp, K.keys, K.iota, K.memb, np, end_bit));
-    }
-    return 0;
-}
-
-// a result of this context's work area to the caller's array, host or device
-int cluster_out(molar_hip_ctx *s, void *dst, const void *src, size_t bytes) {
-    if (!dst || bytes == 0) return 0;
-    if (is_device_ptr(dst)) {
-        MH_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->stream));
-        return 0;
-    }
-    return read_back(s, dst, src, bytes);
-}
-
-}  // namespace
-
-extern "C" {
-
-int molar_hip_search_clusters(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint32_t *comp_of,
-                              uint32_t *sizes, uint64_t *offsets, uint32_t *members, uint32_t *out_ncomponents) {
-    ClusterCall K;
-    MH_TRY(clusters_begin(c, q, groups, offsets != nullptr || members != nullptr, K, "search_clusters"));
-    molar_hip_ctx *s = K.s;
-    if (out_ncomponents) *out_ncomponents = 0;
-    if (K.np == 0) {
-        if (offsets && is_device_ptr(offsets)) MH_HIP(hipMemsetAsync(offsets, 0, 8, s->stream));
-        else if (offsets) offsets[0] = 0;
-        MH_HIP(hipStreamSynchronize(s->stream));
-        return MOLAR_HIP_OK;
-    }
-    MH_TRY(clusters_frame(K, q));
-    MH_TRY(cluster_out(s, comp_of, K.comp, K.np * 4));
-    MH_TRY(cluster_out(s, sizes, K.sizes, K.np * 4));
-    MH_TRY(cluster_out(s, offsets, K.offsets, (K.np + 1) * 8));
-    MH_TRY(cluster_out(s, members, K.memb, K.np * 4));
-    if (out_ncomponents) MH_TRY(read_back(s, out_ncomponents, K.rank + K.np, 4));
-    MH_HIP(hipStreamSynchronize(s->stream));
-    return MOLAR_HIP_OK;
-}
-
-int molar_hip_search_clusters_frames(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, size_t nframes,
-                                     size_t xyz1_stride, const float *boxes9, uint32_t *ncomponents, uint32_t *largest, uint64_t *size_hist,
-                                     uint32_t *comp_of_frames) {
-    ClusterCall K;
-    MH_TRY(clusters_begin(c, q, groups, false, K, "search_clusters_frames"));
-    molar_hip_ctx *s = K.s;
-    if (nframes == 0) return MOLAR_HIP_OK;
-    // [size_hist of a host caller | ncomponents | largest], zeroed
-    const size_t nh = K.np + 1, acc_bytes = nh * 8 + nframes * 8;
-    MH_TRY(s->cl_acc.reserve(acc_bytes));
-    MH_HIP(hipMemsetAsync(s->cl_acc.p, 0, acc_bytes, s->stream));
-    unsigned long long *t_hist = s->cl_acc.as<unsigned long long>();
-    uint32_t *t_ncomp = reinterpret_cast<uint32_t *>(t_hist + nh), *t_largest = t_ncomp + nframes;
-    const bool host_hist = size_hist && !is_device_ptr(size_hist);
-    unsigned long long *hist = host_hist ? t_hist : reinterpret_cast<unsigned long long *>(size_hist);
-    for (size_t f = 0; f < nframes; ++f) {
-        molar_hip_search_desc qf = *q;
-        qf.xyz1 = q->xyz1 + f * xyz1_stride;
-        if (boxes9) qf.box9 = boxes9 + 9 * f;
-        MH_TRY(clusters_frame(K, &qf));
-        if (K.np == 0) continue;
-        launch_cluster_frame((unsigned)s->num_cus, s->stream, K.flag, K.rank, K.sizes, (uint32_t)K.np, t_ncomp + f, t_largest + f, hist);
-        MH_HIP(hipGetLastError());
-        if (comp_of_frames) MH_TRY(cluster_out(s, comp_of_frames + f * K.np, K.comp, K.np * 4));
-    }
-    MH_TRY(cluster_out(s, ncomponents, t_ncomp, nframes * 4));
-    MH_TRY(cluster_out(s, largest, t_largest, nframes * 4));
-    if (host_hist) {
-        std::vector<unsigned long long> h(nh);
-        MH_TRY(read_back(s, h.data(), t_hist, nh * 8));
-        for (size_t i = 0; i < nh; ++i) size_hist[i] += h[i];
-    }
-    MH_HIP(hipStreamSynchronize(s->stream));
-    return MOLAR_HIP_OK;
-}
-
-int molar_hip_search_clusters_counters(molar_hip_ctx *c, int32_t enable, uint64_t *out4) {
-    MH_CTX(c);
-    if (out4) {
-        for (int k = 0; k < 4; ++k) out4[k] = 0;
-        if (c->cl_stats.p) MH_TRY(read_back(c, out4, c->cl_stats.p, 32));
-    }
-    c->cl_counting = enable != 0;
-    if (c->cl_counting) {
-        MH_TRY(c->cl_stats.reserve(32));
-        MH_HIP(hipMemsetAsync(c->cl_stats.p, 0, 32, c->stream));
-    }
-    return MOLAR_HIP_OK;
-}
-
-int molar_hip_search_contacts(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, uint64_t *deg1, uint64_t *deg2,
-                              uint64_t *map, uint64_t *out_count) {
-    ContactCall K;
-    MH_TRY(contacts_begin(c, q, groups, deg1, deg2, map, nullptr, K, "search_contacts"));
-    MH_TRY(contacts_frame(K, q));
-    return contacts_end(K, out_count);
-}
-
-int molar_hip_search_contacts_frames(molar_hip_ctx *c, const molar_hip_search_desc *q, const molar_hip_contact_groups *groups, size_t nframes,
-                                     size_t xyz1_stride, size_t xyz2_stride, const float *boxes9, uint64_t *deg1, uint64_t *deg2, uint64_t *map,
-                                     uint32_t *occupancy) {
-    ContactCall K;
-    MH_TRY(contacts_begin(c, q, groups, deg1, deg2, map, occupancy, K, "search_contacts_frames"));
-    for (size_t f = 0; f < nframes; ++f) {
-        molar_hip_search_desc qf = *q;
-        qf.xyz1 = q->xyz1 + f * xyz1_stride;
-        if (q->xyz2) qf.xyz2 = q->xyz2 + f * xyz2_stride;
-        if (boxes9) qf.box9 = boxes9 + 9 * f;
-        MH_TRY(contacts_frame(K, &qf));
-    }
-    return contacts_end(K, nullptr);
-}
-
-int molar_hip_within_count(molar_hip_ctx *c, const molar_hip_search_desc *q, uint64_t *out_count) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within: null argument");
-    if (q->kind != MOLAR_HIP_SEARCH_WITHIN) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within: the request must be of kind MOLAR_HIP_SEARCH_WITHIN");
-    c->have_within = false;
-    SearchCall call;
-    call.plan = false;                            // no slots, no offsets: this path walks cells
-    call.size_masks = false;
-    call.within_set = true;
-    bool degenerate;                              // (never: a WITHIN request is no vdW request)
-    MH_TRY(prepare_search(c, q, call, &degenerate));
-    c->have_search = false;                       // not a cached search for the fill calls of the stream form
-    const SearchShape &cur = c->cur;
-    const uint64_t nflags = q->ids_local ? cur.set[0].n : (q->idx1 ? q->natoms1 : cur.set[0].n);
-    c->within_nflags = nflags;
-    c->within_total = 0;
-    if (out_count) *out_count = 0;
-    if (cur.set[0].n == 0 || cur.set[1].n == 0 || nflags == 0) {
-        c->have_within = true;
-        return MOLAR_HIP_OK;
-    }
-    const uint32_t ncells = (uint32_t)grid_cells(cur);
-    const uint64_t ntiles = (nflags + 2047) / 2048;
-    const size_t flag_bytes = (nflags + 3) & ~(size_t)3;
-    const bool fresh_flags = c->w_flags.cap < flag_bytes;
-    MH_TRY(c->w_flags.reserve(flag_bytes));
-    MH_TRY(c->w_tile_cnt.reserve((ntiles + 1) * 4));
-    MH_TRY(c->w_tile_off.reserve((ntiles + 1) * 8));
-    MH_TRY(c->params.reserve(sizeof(SearchParams)));
-    const SearchParams P = make_params(c, cur);
-    hipLaunchKernelGGL(upload_params_kernel, dim3(1), dim3(256), 0, c->stream, P, c->params.as<SearchParams>());
-    // flags: all zero between calls.  A small-path call leaves only the flags of its list set: those are cleared through the list.
-    if (fresh_flags || c->w_flags_all_dirty) MH_HIP(hipMemsetAsync(c->w_flags.p, 0, flag_bytes, c->stream));
-    else if (c->w_list_dirty)
-        hipLaunchKernelGGL(within_clear_kernel, dim3((unsigned)((c->w_list_dirty + 255) / 256)), dim3(256), 0, c->stream, c->w_list.as<uint32_t>() + 1,
-                           (uint32_t)c->w_list_dirty, c->w_flags.as<uint8_t>());
-    c->w_flags_all_dirty = false;
-    c->w_list_dirty = 0;
-    c->w_small = (uint64_t)cur.set[1].n * 28ull <= (1ull << 17);           // <= 4681 second-set atoms: one wave per (atom, combination)
-    if (c->w_small) {
-        MH_TRY(c->w_list.reserve((nflags + 1) * 4));
-        MH_HIP(hipMemsetAsync(c->w_list.p, 0, 4, c->stream));               // word 0: the list's length, then the ids
-        // cells of many 64-row blocks (large cutoffs) get several waves per (cell, combination)
-        uint32_t wsplit = (uint32_t)(((uint64_t)cur.set[0].n / 64u) / ncells) + 1u;
-        if (wsplit > 64u) wsplit = 64u;
-        const uint32_t by_cell = ncells < cur.set[1].n ? 1u : 0u;
-        hipLaunchKernelGGL(within_small_kernel, dim3((by_cell ? ncells : cur.set[1].n) * 28u, wsplit), dim3(64), 0, c->stream, c->params.as<SearchParams>(), cur.set[1].n, ncells, by_cell,
-                           c->w_flags.as<uint32_t>(), c->w_list.as<uint32_t>() + 1, c->w_list.as<uint32_t>());
-        MH_HIP(hipGetLastError());
-        uint32_t tot = 0;
-        MH_TRY(read_back(c, &tot, c->w_list.p, 4));
-        c->within_total = tot;
-        c->w_list_dirty = tot;
-        c->have_within = true;
-        if (out_count) *out_count = tot;
-        return MOLAR_HIP_OK;
-    }
-    c->w_flags_all_dirty = true;
-    MH_TRY(c->w_part_cnt.reserve((size_t)ncells * 4));
-    MH_TRY(c->w_part.reserve((size_t)ncells * WITHIN_MAX_PART * 4));
-    MH_HIP(hipMemsetAsync(c->w_part_cnt.p, 0, (size_t)ncells * 4, c->stream));
-    MH_HIP(hipMemsetAsync(c->w_tile_cnt.p, 0, (ntiles + 1) * 4, c->stream));
-    hipLaunchKernelGGL(within_partners_kernel, dim3((unsigned)((cur.ntasks + 255) / 256)), dim3(256), 0, c->stream, c->params.as<SearchParams>(),
-                       c->w_part_cnt.as<uint32_t>(), c->w_part.as<uint32_t>());
-    // big cells get several waves (a share of their 64-row blocks each)
-    uint32_t nsplit = (uint32_t)(((uint64_t)cur.set[0].n / 64u) / ncells) + 1u;
-    if (nsplit > 64u) nsplit = 64u;
-    hipLaunchKernelGGL(within_flags_kernel, dim3(ncells, nsplit), dim3(64), 0, c->stream, c->params.as<SearchParams>(),
-                       c->w_part_cnt.as<uint32_t>(), c->w_part.as<uint32_t>(), c->w_flags.as<uint8_t>(), nsplit);
-    hipLaunchKernelGGL(flag_tile_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, c->w_flags.as<uint8_t>(), nflags,
-                       c->w_tile_cnt.as<uint32_t>());
-    MH_HIP(hipGetLastError());
-    MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
-    unsigned long long tot = 0;
-    MH_TRY(read_back(c, &tot, c->w_tile_off.as<unsigned long long>() + ntiles, 8));
-    c->within_total = tot;
-    c->have_within = true;
-    if (out_count) *out_count = tot;
-    return MOLAR_HIP_OK;
-}
-
-// The first set of consecutive `within` requests stays the same while a selection expression is evaluated against one frame
-// (`within 0.3 of resid 1`, `within 0.8 of resid 1`, ...: within_size_bench.rs:13-47 asks 1600 times): with the hold on, a
-// request that names the same first set (same pointers and sizes, same box and periodicity) and comes to the same grid
-// reuses the staged coordinates and the grid of the one before.  The CALLER promises that the first set's coordinates do not
-// change while the hold is on (in Rust: for as long as it holds the `&State`); any other search on the context ends the reuse.
-int molar_hip_within_hold(molar_hip_ctx *c, int on) {
-    if (!c) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "null context");
-    c->within_hold = on != 0;
-    if (!on) c->held.valid = false;
-    return MOLAR_HIP_OK;
-}
-
-int molar_hip_within_fill(molar_hip_ctx *c, uint64_t *ids) {
-    if (!c || !c->have_within) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached within set: call molar_hip_within_count first");
-    if (c->within_total == 0) return MOLAR_HIP_OK;
-    if (!ids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within_fill: null output");
-    MH_HIP(hipSetDevice(c->device));
-    const bool dev = is_device_ptr(ids);
-    // (the list of a small second set with a LARGE cutoff is long - 1.9e4 ids for `within 2.5 of 210 atoms` in a 100k-atom box: sorting it
-    // on the host took 0.25 ms of a 0.68 ms call; from 4096 ids on, the flags are compacted on the device like the large path's)
-    if (c->w_small && !dev && c->within_total <= 4096) {           // the list IS the set: bring it over, sort it (SortedSet::from_unsorted, selection_expr.rs:112), widen it
-        std::vector<uint32_t> l((size_t)c->within_total);
-        MH_TRY(read_back(c, l.data(), c->w_list.as<uint32_t>() + 1, l.size() * 4));
-        std::sort(l.begin(), l.end());
-        for (size_t k = 0; k < l.size(); ++k) ids[k] = l[k];
-        return MOLAR_HIP_OK;
-    }
-    unsigned long long *dst = reinterpret_cast<unsigned long long *>(ids);
-    if (c->w_small) {                   // device output: compact the flags (they hold the same set)
-        const uint64_t ntiles = (c->within_nflags + 2047) / 2048;
-        MH_HIP(hipMemsetAsync(c->w_tile_cnt.p, 0, (ntiles + 1) * 4, c->stream));
-        hipLaunchKernelGGL(flag_tile_count_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, c->w_flags.as<uint8_t>(), c->within_nflags,
-                           c->w_tile_cnt.as<uint32_t>());
-        MH_TRY((exclusive_scan<uint32_t, unsigned long long>(main_lane(c), c->w_tile_cnt.as<uint32_t>(), c->w_tile_off.as<unsigned long long>(), ntiles + 1)));
-    }
-    if (!dev) {
-        MH_TRY(c->wide_i.reserve((size_t)c->within_total * 8));
-        dst = c->wide_i.as<unsigned long long>();
-    }
-    const uint64_t ntiles = (c->within_nflags + 2047) / 2048;
-    hipLaunchKernelGGL(flag_compact_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, c->w_flags.as<uint8_t>(), c->within_nflags,
-                       c->w_tile_off.as<unsigned long long>(), dst);
-    MH_HIP(hipGetLastError());
-    if (!dev) {
-        MH_HIP(hipMemcpyAsync(ids, dst, (size_t)c->within_total * 8, hipMemcpyDeviceToHost, c->stream));
-        MH_HIP(hipStreamSynchronize(c->stream));
-    }
-    return MOLAR_HIP_OK;
-}
-
-// SearchConnectivity (connectivity.rs:8-60) of a single-selection search, built on the device from the resident pair list:
-// CSR over the id range of the request (local ids: the selection's length; global ids: natoms), lists in the reference's push
-// order.  Count-then-fill: the first call runs the search and builds the CSR in context-owned device memory and returns the
-// number of entries (2 x pairs); the second copies offsets (rows + 1) and neighbours to host or device memory.
-int molar_hip_search_connectivity(molar_hip_ctx *c, const molar_hip_search_desc *q, uint64_t *out_rows, uint64_t *out_entries) {
-    if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity: null argument");
-    if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
-        return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity: ids of one selection index the lists - the request must be of kind MOLAR_HIP_SEARCH_SINGLE");
-    c->have_conn = false;
-    // the lists hold ids only: the (i, j) plane alone (DistanceSearchOutput of (usize, usize), distance_search.rs:14-20)
-    MH_TRY(resident_run(c, q, c->out_pairs, c->out_dist, /*pairs_only=*/true));
-    const uint64_t npairs = c->total;
-    const uint32_t *d_pairs = c->out_pairs.as<uint32_t>();
-    const size_t nsel = q->idx1 ? q->n1 : q->natoms1;
-    const uint64_t nrows = q->ids_local ? nsel : (q->idx1 ? q->natoms1 : nsel);
-    if (nrows >= 0xFFFFFFF0ull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity: too many rows");
-    const uint64_t nent = 2ull * npairs;
-    if (nent >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity: %llu list entries", (unsigned long long)nent);
-    MH_TRY(c->conn_off.reserve((nrows + 1) * 8));
-    MH_TRY(c->conn_ent.reserve((nent ? nent : 1) * 16));           // four u32 arrays: rows and neighbours, unsorted and sorted
-    MH_TRY(c->conn_neigh.reserve((nent ? nent : 1) * 8));
-    uint32_t *row_in = c->conn_ent.as<uint32_t>(), *nb_in = row_in + nent, *row_out = nb_in + nent, *nb_out = row_out + nent;
-    const unsigned nbP = (unsigned)((npairs + 255) / 256), nbE = (unsigned)((nent + 255) / 256);
-    const uint2 *pairs = reinterpret_cast<const uint2 *>(d_pairs);
-    if (nbP) {
-        hipLaunchKernelGGL(conn_entries_kernel, dim3(nbP), dim3(256), 0, c->stream, pairs, (unsigned long long)npairs, row_in, nb_in);
-        int end_bit = 1;
-        while (end_bit < 32 && (nrows >> end_bit)) ++end_bit;
-        MH_TRY(device_sort_pairs_u32(c->stream, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
-        hipLaunchKernelGGL(conn_widen_kernel, dim3(nbE), dim3(256), 0, c->stream, nb_out, (unsigned long long)nent, c->conn_neigh.as<unsigned long long>());
-    }
-    hipLaunchKernelGGL(conn_offsets_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, c->stream, row_out, (unsigned long long)nent,
-                       (uint32_t)nrows, c->conn_off.as<unsigned long long>());
-    MH_HIP(hipGetLastError());
-    c->conn_rows = nrows;
-    c->conn_entries = nent;
-    c->have_conn = true;
-    if (out_rows) *out_rows = nrows;
-    if (out_entries) *out_entries = nent;
-    return MOLAR_HIP_OK;
-}
-
-int molar_hip_search_connectivity_fill(molar_hip_ctx *c, uint64_t *offsets, uint64_t *neigh) {
-    if (!c || !c->have_conn) return fail(MOLAR_HIP_ERR_NO_SEARCH, "no cached connectivity: call molar_hip_search_connectivity first");
-    MH_HIP(hipSetDevice(c->device));
-    if (offsets) MH_HIP(hipMemcpyAsync(offsets, c->conn_off.p, (c->conn_rows + 1) * 8, hipMemcpyDefault, c->stream));
-    if (neigh && c->conn_entries) {
-        // large lists into ordinary host memory: the pinned ring and its host threads (hoststream.hpp), as the pair lists travel
-        // (25k atoms at rc 1.0 nm: 83 MB of neighbours, 11 ms through the runtime's pageable copy)
-        if (!is_device_ptr(neigh) && ring_pays(c->conn_entries * 8, neigh)) {
-            MH_HIP(hipStreamSynchronize(c->stream));
-            std::vector<RingJob> jobs;
-            jobs.push_back(RingJob{c->conn_neigh.p, (size_t)c->conn_entries * 8, RING_COPY, neigh, nullptr});
-            return ring_to_host(c, jobs);
-        }
-        MH_HIP(hipMemcpyAsync(neigh, c->conn_neigh.p, c->conn_entries * 8, hipMemcpyDefault, c->stream));
-    }
-    MH_HIP(hipStreamSynchronize(c->stream));
-    return MOLAR_HIP_OK;
-}
-
-// Modify::unwrap_connectivity_dim (molar/src/modify.rs:72-131).  The neighbour search - the heavy part - runs on the GPU
-// (distance_search_single_pbc over the selection with LOCAL ids under full PBC, :77-78); the adjacency lists in push
-// order (SearchConnectivity::from_iter, connectivity.rs:19-35: for (i, j) in pair order conn[i].push(j), conn[j].push(i))
-// are built on the device from the resident pair list (molar_hip_search_connectivity), and the reference's stack walk (:84-128) - serial by nature: every
-// atom is pulled to the closest image of the atom it was REACHED FROM, whose position the walk may just have changed -
-// runs on the host over that CSR with the same f32 arithmetic (boxmath.hpp's closest_image, the one the kernels use).
-// Quirks kept: the atom a component starts from (0, then the lowest unused index) is not a member of the selection
-// the component returns (:97-98,111-113); a component of one atom returns no selection; members are emitted as the
-// reference's `select(&sel_vec)` makes them, sorted.
-int molar_hip_unwrap_connectivity(molar_hip_ctx *c, float *xyz, size_t natoms, const uint64_t *idx, size_t n, const float *box9,
-                                  float cutoff, uint8_t pbc_dims, uint64_t *group_offsets, uint64_t *group_ids, size_t *ngroups) {
-    if (!c || !xyz) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_connectivity: null argument");
-    if (!box9) return fail(MOLAR_HIP_ERR_NO_PBC, "no periodic box");                               // require_box (:76)
-    const size_t nsel = idx ? n : natoms;
-    if (nsel == 0) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "unwrap_connectivity of an empty selection");
-    if (nsel >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "unwrap_connectivity: %zu atoms exceed the 32-bit local ids", nsel);
-    MH_HIP(hipSetDevice(c->device));
-    molar_hip_box b;
-    MH_TRY(molar_hip_box_from_matrix(box9, &b));
-    // ---- the search, local ids (0..len), full PBC whatever `dims` (:77-78)
-    molar_hip_search_desc q{};
-    q.kind = MOLAR_HIP_SEARCH_SINGLE;
-    q.cutoff = cutoff;
-    q.xyz1 = xyz; q.natoms1 = natoms; q.idx1 = idx; q.n1 = n;
-    q.ids_local = 1;
-    q.box9 = box9;
-    q.pbc = MOLAR_HIP_PBC_FULL;
-    // ---- adjacency in push order: SearchConnectivity on the device, only the CSR comes to the host
-    uint64_t nrows = 0, nent = 0;
-    MH_TRY(molar_hip_search_connectivity(c, &q, &nrows, &nent));
-    std::vector<uint64_t> off(nsel + 1, 0), adj((size_t)(nent ? nent : 1));
-    MH_TRY(molar_hip_search_connectivity_fill(c, off.data(), adj.data()));
-    // ---- the coordinates of the frame on the host
-    const bool dev = is_device_ptr(xyz);
-    std::vector<float> hostcopy;
-    float *h = xyz;
-    if (dev) {
-        hostcopy.resize(natoms * 3);
-        MH_HIP(hipMemcpyAsync(hostcopy.data(), xyz, natoms * 12, hipMemcpyDeviceToHost, c->stream));
-        MH_HIP(hipStreamSynchronize(c->stream));
-        h = hostcopy.data();
-    }
-    std::vector<uint64_t> hidx;
-    if (idx && is_device_ptr(idx)) {      // the walk reads the selection on the host
-        hidx.resize(n);
-        MH_HIP(hipMemcpy(hidx.data(), idx, n * 8, hipMemcpyDeviceToHost));
-    }
-    const uint64_t *ix = hidx.empty() ? idx : hidx.data();
-    // ---- the walk (:80-128), one template with the f64 entry (unwrap_walk.hpp)
-    unwrap_walk<float, V3>(h, ix, nsel, b, pbc_dims & 7u, off.data(), adj.data(), group_offsets, group_ids, ngroups);
-    if (dev) {
-        MH_HIP(hipMemcpyAsync(xyz, hostcopy.data(), natoms * 12, hipMemcpyHostToDevice, c->stream));
-        MH_HIP(hipStreamSynchronize(c->stream));
-    }
-    return MOLAR_HIP_OK;
-}
-
-}  // extern "C"
-
-

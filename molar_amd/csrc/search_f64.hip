@@ -23,7 +23,7 @@
 //   * `within` as a set (molar_hip_within_count_f64 / _fill_f64) needs no slots: the plan is inverted into per-cell partner
 //     lists and one wave per (first cell, 64-row block) walks them with a mask of the rows still looking; found rows set a flag,
 //     the ascending flagged ids are the set (within64_flags_kernel, csr_kernels.hpp).  Not here: the kernel for small second
-//     sets walked from the inner selection's side and the grid hold of the f32 form (search.hip) - tunings, f32 only.
+//     sets walked from the inner selection's side and the grid hold of the f32 form (within.hip) - tunings, f32 only.
 //   * SearchConnectivity (molar_hip_search_connectivity_f64) and unwrap_connectivity (molar_hip_unwrap_connectivity_f64): the
 //     single-selection search into the context's columns, the CSR by one stable sort as in f32 (filled by
 //     molar_hip_search_connectivity_fill), the stack walk on the host by the template both precisions use (unwrap_walk.hpp).
@@ -39,6 +39,7 @@
 #include "common.hpp"
 #include "csr_kernels.hpp"
 #include "hoststream.hpp"
+#include "search_core.hpp"
 #include "stages.hpp"
 #include "unwrap_walk.hpp"
 
@@ -804,7 +805,7 @@ const void *hist64_fn() { return reinterpret_cast<const void *>(&hist64_kernel<K
 //
 // What a caller of distance_search_within(_pbc) keeps is SortedSet::from_unsorted(stream) (selection_expr.rs:112): the set of
 // first-set atoms with a second-set atom in range.  The set needs no stream, no offsets and no second pass, and an atom that
-// has been found needs no further candidate in ANY of its plan entries (search.hip has the f32 form of the same idea):
+// has been found needs no further candidate in ANY of its plan entries (within.hip has the f32 form of the same idea):
 //  * within64_partners_kernel inverts the plan with plan_entry - the same wrap / drop rules, the same incomplete
 //    neighbourhoods of sheared boxes, both halves of every two-set entry - into per-first-cell lists of (second cell, flags);
 //  * within64_flags_kernel: one wave per (first-set cell, share of its 64-row blocks).  The wave loads its rows once (one per
@@ -924,7 +925,7 @@ __global__ void __launch_bounds__(64) within64_flags_kernel(Params64 P, const ui
 }
 
 // SearchConnectivity::from_iter (connectivity.rs:19-35) over the f64 search's id columns: pair p pushes j onto i's list
-// (entry 2p), then i onto j's (entry 2p + 1) - conn_entries_kernel of search.hip for two uint64 columns
+// (entry 2p), then i onto j's (entry 2p + 1) - conn_entries_kernel of connectivity.hip for two uint64 columns
 __global__ void __launch_bounds__(256) conn64_entries_kernel(const unsigned long long *__restrict__ pi, const unsigned long long *__restrict__ pj,
                                                              unsigned long long npairs, uint32_t *__restrict__ row, uint32_t *__restrict__ nb) {
     const unsigned long long p = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
@@ -938,15 +939,7 @@ __global__ void __launch_bounds__(256) conn64_entries_kernel(const unsigned long
 
 namespace mh {
 void search64_release(molar_hip_ctx *c) {
-    if (!c->s64) return;
-    molar_hip_search64_state &Z = *c->s64;
-    for (DevBuf *b : {&Z.posA, &Z.idA, &Z.vdwA, &Z.posB, &Z.idB, &Z.vdwB, &Z.slots, &Z.slot_cnt, &Z.slot_base, &Z.box, &Z.out_i, &Z.out_j, &Z.out_d,
-                      &Z.in_xyz[0], &Z.in_xyz[1], &Z.in_idx[0], &Z.in_idx[1], &Z.in_vdw[0], &Z.in_vdw[1], &Z.key_in, &Z.key_out, &Z.val_in,
-                      &Z.val_out, &Z.pos3, &Z.aabbA, &Z.aabbB, &Z.startA, &Z.startB, &Z.task_ns, &Z.task_first, &Z.cub_tmp, &Z.partial, &Z.flags, &Z.hedges, &Z.hsum, &Z.hnext, &Z.w_part_cnt, &Z.w_part, &Z.w_flags, &Z.w_tile_cnt,
-                      &Z.w_tile_off, &Z.w_out})
-        b->release();
-    delete c->s64;
-    c->s64 = nullptr;
+    release_state(c->s64);
 }
 }  // namespace mh
 
@@ -1559,31 +1552,17 @@ int molar_hip_within_fill_f64(molar_hip_ctx *c, uint64_t *ids) {
     if (Z.w_total == 0) return MOLAR_HIP_OK;
     if (!ids) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "within_fill_f64: null output");
     MH_HIP(hipSetDevice(c->device));
-    const bool dev = is_device_ptr(ids);
-    unsigned long long *dst = reinterpret_cast<unsigned long long *>(ids);
-    if (!dev) {
-        MH_TRY(Z.w_out.reserve((size_t)Z.w_total * 8));
-        dst = Z.w_out.as<unsigned long long>();
-    }
-    const uint64_t ntiles = (Z.w_nflags + 2047) / 2048;
-    hipLaunchKernelGGL(flag_compact_kernel, dim3((unsigned)ntiles), dim3(256), 0, c->stream, Z.w_flags.as<uint8_t>(), Z.w_nflags,
-                       Z.w_tile_off.as<unsigned long long>(), dst);
-    MH_HIP(hipGetLastError());
-    if (!dev) {
-        MH_HIP(hipMemcpyAsync(ids, dst, (size_t)Z.w_total * 8, hipMemcpyDeviceToHost, c->stream));
-        MH_HIP(hipStreamSynchronize(c->stream));
-    }
-    return MOLAR_HIP_OK;
+    return flags_to_ids(c, Z.w_flags.as<uint8_t>(), Z.w_nflags, Z.w_tile_off.as<unsigned long long>(), Z.w_total, Z.w_out, ids, is_device_ptr(ids));
 }
 
 // SearchConnectivity (connectivity.rs:8-60) of the f64 single-selection search: count, scan and fill into the context's own
-// columns, then the CSR on the device exactly as molar_hip_search_connectivity builds it - one stable sort of the entries by
-// row, offsets by bisection, neighbours widened - into the SAME context fields: molar_hip_search_connectivity_fill copies it out.
+// columns, then the CSR on the device by the one build both precisions share (connectivity.hip: connectivity_begin, the
+// entries written here, connectivity_finish) - molar_hip_search_connectivity_fill copies it out.
 int molar_hip_search_connectivity_f64(molar_hip_ctx *c, const molar_hip_search_desc_f64 *q, uint64_t *out_rows, uint64_t *out_entries) {
     if (!c || !q) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity_f64: null argument");
     if (q->kind != MOLAR_HIP_SEARCH_SINGLE)
         return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "search_connectivity_f64: ids of one selection index the lists - the request must be of kind MOLAR_HIP_SEARCH_SINGLE");
-    c->have_conn = false;
+    connectivity_forget(c);
     uint64_t npairs = 0;
     MH_TRY(molar_hip_search_count_f64(c, q, &npairs));
     const size_t nsel = q->idx1 ? q->n1 : q->natoms1;
@@ -1593,25 +1572,13 @@ int molar_hip_search_connectivity_f64(molar_hip_ctx *c, const molar_hip_search_d
     if (nent >= 0x7FFFFFFFull) return fail(MOLAR_HIP_ERR_TOO_LARGE, "search_connectivity_f64: %llu list entries", (unsigned long long)nent);
     MH_TRY(fill64(c, nullptr, nullptr, nullptr, false));          // (i, j, d) into the context's columns; nothing leaves the device
     molar_hip_search64_state &Z = *c->s64;
-    MH_TRY(c->conn_off.reserve((nrows + 1) * 8));
-    MH_TRY(c->conn_ent.reserve((nent ? nent : 1) * 16));           // four u32 arrays: rows and neighbours, unsorted and sorted
-    MH_TRY(c->conn_neigh.reserve((nent ? nent : 1) * 8));
-    uint32_t *row_in = c->conn_ent.as<uint32_t>(), *nb_in = row_in + nent, *row_out = nb_in + nent, *nb_out = row_out + nent;
-    const unsigned nbP = (unsigned)((npairs + 255) / 256), nbE = (unsigned)((nent + 255) / 256);
-    if (nbP) {
+    uint32_t *row_in = nullptr, *nb_in = nullptr;
+    MH_TRY(connectivity_begin(c, nrows, npairs, &row_in, &nb_in));
+    const unsigned nbP = (unsigned)((npairs + 255) / 256);
+    if (nbP)
         hipLaunchKernelGGL(conn64_entries_kernel, dim3(nbP), dim3(256), 0, c->stream, Z.out_i.as<unsigned long long>(),
                            Z.out_j.as<unsigned long long>(), (unsigned long long)npairs, row_in, nb_in);
-        int end_bit = 1;
-        while (end_bit < 32 && (nrows >> end_bit)) ++end_bit;
-        MH_TRY(device_sort_pairs_u32(c->stream, c->conn_deg, row_in, row_out, nb_in, nb_out, (size_t)nent, end_bit));
-        hipLaunchKernelGGL(conn_widen_kernel, dim3(nbE), dim3(256), 0, c->stream, nb_out, (unsigned long long)nent, c->conn_neigh.as<unsigned long long>());
-    }
-    hipLaunchKernelGGL(conn_offsets_kernel, dim3((unsigned)((nrows + 1 + 255) / 256)), dim3(256), 0, c->stream, row_out, (unsigned long long)nent,
-                       (uint32_t)nrows, c->conn_off.as<unsigned long long>());
-    MH_HIP(hipGetLastError());
-    c->conn_rows = nrows;
-    c->conn_entries = nent;
-    c->have_conn = true;
+    MH_TRY(connectivity_finish(c));
     if (out_rows) *out_rows = nrows;
     if (out_entries) *out_entries = nent;
     return MOLAR_HIP_OK;

@@ -1,10 +1,8 @@
 // traj_block.hpp - what the analyses over a block of trajectory frames share (rmsd_matrix.hip, fluct.hip, msd.hip): a block of
 // frames with a stride, natoms, an optional idx and an optional mass, host or device memory on either side.  Plain functions
 // and two kernels, no state: the gather of a selection, the centring of every frame, the C layout of the f64 MFMA, the carving
-// of a workspace, the staging of results, the host checks of the selection and the per-context state's life.
+// of a workspace, the staging of results, and the host checks of the selection.  (The per-context state's life, state_of / release_state, is in common.hpp.)
 #pragma once
-
-#include <initializer_list>
 
 #include "common.hpp"
 
@@ -204,23 +202,6 @@ inline int check_selection(molar_hip_ctx *c, const uint32_t *index_flag_dev, con
     if (*flag) return fail(MOLAR_HIP_ERR_INVALID_ARGUMENT, "%s: a selection index is not below natoms = %zu", who, natoms);
     if (*sum == 0.0) return fail(MOLAR_HIP_ERR_ZERO_MASS, "%s: the selected masses add up to zero", who);
     return 0;
-}
-
-// ---------------------------------------------------------------- the per-context state of an analysis
-
-// created by the first call that gets this far
-template <class State>
-State &state_of(State *&slot) {
-    if (!slot) slot = new State;
-    return *slot;
-}
-
-// the end of a *_release: the state's buffers, the state, the context's pointer
-template <class State>
-void release_state(State *&slot, std::initializer_list<DevBuf *> bufs) {
-    for (DevBuf *b : bufs) b->release();
-    delete slot;
-    slot = nullptr;
 }
 
 }  // namespace mh

@@ -1,5 +1,5 @@
 // unwrap_walk.hpp - the stack walk of Modify::unwrap_connectivity_dim (molar/src/modify.rs:80-128) on the host, ONE
-// template over the real type: molar_hip_unwrap_connectivity (search.hip: float, molar_hip_box, V3) and
+// template over the real type: molar_hip_unwrap_connectivity (connectivity.hip: float, molar_hip_box, V3) and
 // molar_hip_unwrap_connectivity_f64 (search_f64.hip: double, BoxD, D3; boxmath.hpp) both run it over the CSR that
 // SearchConnectivity built on the device.  Serial by nature: every atom is pulled to the closest image of the atom it was
 // REACHED FROM, whose position the walk may just have changed.  closest_image is the one of the box type's header, with

@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../molar_amd/csrc/traj_block.hpp"
@@ -94,7 +96,21 @@ static void test_checks() {
     CHECK(failed_with(check_index("fluct", "idx", big.data(), big.size(), big.size() - 1), INV, "fluct: idx[99999] = 99999 is not below natoms = 99999"));
 }
 
-// "create on first use" and "release these buffers, delete, null" with buffers that hold nothing (no device call is made)
+// a DevBuf owns its memory: it cannot be copied, and a move leaves the source empty
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a DevBuf is never copied");
+static_assert(std::is_nothrow_move_constructible<DevBuf>::value, "a DevBuf moves without throwing");
+
+// moves of buffers that hold nothing (no device call is made): source and target stay {nullptr, 0}
+static void test_devbuf_move() {
+    DevBuf a;
+    DevBuf b(std::move(a));
+    CHECK(a.p == nullptr && a.cap == 0 && b.p == nullptr && b.cap == 0);
+    DevBuf c;
+    c = std::move(b);
+    CHECK(b.p == nullptr && b.cap == 0 && c.p == nullptr && c.cap == 0);
+}
+
+// "create on first use" and "delete (the buffers free themselves), null" with buffers that hold nothing (no device call is made)
 struct State {
     DevBuf a, b;
     int tag = 7;
@@ -106,7 +122,7 @@ static void test_state() {
     CHECK(slot == &s && s.tag == 7);
     s.tag = 8;
     CHECK(&state_of(slot) == &s && slot->tag == 8);
-    release_state(slot, {&s.a, &s.b});
+    release_state(slot);
     CHECK(slot == nullptr);
 }
 
@@ -115,6 +131,7 @@ int main() {
     test_even_splits();
     test_checks();
     test_state();
+    test_devbuf_move();
     if (failures) {
         std::printf("%d traj-block checks FAILED\n", failures);
         return 1;

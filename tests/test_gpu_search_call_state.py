@@ -373,3 +373,112 @@ def test_empty_vdw_request_between_ordinary_ones(a, sys_, fresh_single):
     assert cnt == 0 and not np.asarray(bins).any()
     assert e.grid_dims() == (1, 1, 1)
     same_list(count_fill(a, e, s), fresh_single, "count + fill after the empty vdW histogram")
+
+
+# ---- the consumers of the search keep their states apart: within.hip, connectivity.hip, contacts.hip
+# `within` as a set, SearchConnectivity and the contacts / clusters calls each keep what outlasts a call in a state of their own
+# behind one pointer of the context, made on first use.  Sizes are those of sys_; the partner-list path of `within` needs a
+# second set of at least 4682 atoms (the branch is n2 * 28 <= 2^17), so one more frame of 5000 atoms in the same box.
+N2_PARTNERS = 5000
+
+
+def test_calls_on_states_that_were_never_created(a):
+    import ctypes as C
+    from molar_amd import _lib
+    e = a.Engine(0)
+    ids, off = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
+    assert e.lib.molar_hip_within_fill(e.ctx, ids.ctypes.data) == NO_SEARCH
+    assert _lib.last_error() == "no cached within set: call molar_hip_within_count first"
+    assert e.lib.molar_hip_search_connectivity_fill(e.ctx, off.ctypes.data, ids.ctypes.data) == NO_SEARCH
+    assert _lib.last_error() == "no cached connectivity: call molar_hip_search_connectivity first"
+    out4 = (C.c_uint64 * 4)(7, 7, 7, 7)
+    assert e.lib.molar_hip_search_clusters_counters(e.ctx, 0, out4) == 0 and list(out4) == [0, 0, 0, 0]
+    assert e.lib.molar_hip_within_hold(e.ctx, 1) == 0 and e.lib.molar_hip_within_hold(e.ctx, 0) == 0
+    e.close()
+
+
+def within_and_connectivity(a, e, s, second, between):
+    """within_count .. within_fill (to host and to device memory) and search_connectivity .. _fill by raw calls, with
+    `between` run inside each pair."""
+    import ctypes as C
+    import torch
+    d, _k = e.make_search_desc(a.SEARCH_WITHIN, CUTOFF, s["pos"], xyz2=second, box=s["box"], pbc=7)
+    cnt = C.c_uint64(0)
+    assert e.lib.molar_hip_within_count(e.ctx, C.byref(d), C.byref(cnt)) == 0
+    between()
+    ids = np.empty(cnt.value, np.uint64)
+    assert e.lib.molar_hip_within_fill(e.ctx, ids.ctypes.data) == 0
+    dev = torch.empty(cnt.value, dtype=torch.int64, device="cuda")
+    assert e.lib.molar_hip_within_fill(e.ctx, dev.data_ptr()) == 0
+    e.synchronize()
+    d, _k = e.make_search_desc(a.SEARCH_SINGLE, CUTOFF, s["pos"], box=s["box"], pbc=7, ids_local=True)
+    rows, ent = C.c_uint64(0), C.c_uint64(0)
+    assert e.lib.molar_hip_search_connectivity(e.ctx, C.byref(d), C.byref(rows), C.byref(ent)) == 0
+    between()
+    off, nb = np.empty(rows.value + 1, np.uint64), np.empty(max(ent.value, 1), np.uint64)
+    assert e.lib.molar_hip_search_connectivity_fill(e.ctx, off.ctypes.data, nb.ctypes.data) == 0
+    return ids, dev.cpu().numpy().view(np.uint64), off, nb[:ent.value]
+
+
+@pytest.mark.parametrize("n2", [N2, N2_PARTNERS], ids=["small_list", "partner_lists"])
+def test_a_cached_result_survives_the_other_consumers(a, sys_, n2):
+    s = sys_
+    assert N2 * 28 <= 2 ** 17 < N2_PARTNERS * 28
+    second = s["pos2"] if n2 == N2 else synth.frame(n2, s["box"], 9, seed=77)
+    e = a.Engine(0)
+
+    def others():
+        c = e.search_contacts(a.SEARCH_SINGLE, CUTOFF, s["pos2"], box=s["box"], pbc=7)
+        k = e.search_clusters(CUTOFF, s["pos2"], box=s["box"], pbc=7)
+        assert c.count > 0 and 0 < k.ncomponents < N2
+    got = within_and_connectivity(a, e, s, second, others)
+    want = within_and_connectivity(a, a.Engine(0), s, second, lambda: None)
+    for g, w, name in zip(got, want, ("ids", "ids left on the device", "offsets", "neighbours")):
+        assert g.dtype == w.dtype and g.tobytes() == w.tobytes() and len(w) > 1, name
+    assert got[0].tobytes() == got[1].tobytes() and np.all(np.diff(got[0].astype(np.int64)) > 0)
+
+
+def csr_in_push_order(ref, rows):
+    """SearchConnectivity::from_iter (connectivity.rs:19-35): pair p pushes j onto i's list (entry 2p), i onto j's (2p + 1)"""
+    npairs = len(ref["i"])
+    row = np.empty(2 * npairs, np.uint64); nb = np.empty(2 * npairs, np.uint64)
+    row[0::2], row[1::2] = ref["i"], ref["j"]
+    nb[0::2], nb[1::2] = ref["j"], ref["i"]
+    order = np.argsort(row, kind="stable")
+    off = np.searchsorted(row[order], np.arange(rows + 1, dtype=np.uint64)).astype(np.uint64)
+    return off, nb[order]
+
+
+def test_one_csr_home_for_both_precisions(a, sys_, orc32, orc64):
+    """The f64 entry and the f32 entry build their CSR in the same place and the one _fill copies it out: first the f64 lists,
+    then, after an f32 request on another cutoff, the f32 lists."""
+    s = sys_
+    e = a.Engine(0)
+    pos64, box64 = s["pos"].astype(np.float64), s["box"].astype(np.float64)
+    off, nb = e.search_connectivity_f64(CUTOFF, pos64, box=box64, pbc=7)
+    woff, wnb = csr_in_push_order(orc64.search_single_pbc(CUTOFF, pos64, orc64.box_from_matrix(box64), 7, nthreads=4), N)
+    assert len(wnb) > N and np.array_equal(off, woff) and np.array_equal(nb, wnb)
+    off, nb = e.search_connectivity(0.6, s["pos"], box=s["box"], pbc=7)
+    woff32, wnb32 = csr_in_push_order(orc32.search_single_pbc(0.6, s["pos"], orc32.box_from_matrix(s["box"]), 7, nthreads=4), N)
+    assert N < len(wnb32) < len(wnb) and np.array_equal(off, woff32) and np.array_equal(nb, wnb32)
+
+
+def test_engines_that_used_every_consumer_close_cleanly(a, sys_, fresh_single):
+    """Three times: an Engine that has made every state - the `within` set, the connectivity CSR, the contacts and clusters
+    calls' second context and work areas, a cached search - is closed; every release path and the buffers that free themselves
+    run once per cycle.  A fresh Engine then answers as ever."""
+    s = sys_
+    labels = (np.arange(N) % 8).astype(np.uint32)
+    for _ in range(3):
+        e = a.Engine(0)
+        assert len(e.within_set(CUTOFF, s["pos"], xyz2=s["pos2"], box=s["box"], pbc=7)) > 0
+        assert len(e.search_connectivity(CUTOFF, s["pos"], box=s["box"], pbc=7)[1]) > 0
+        c = e.search_contacts(a.SEARCH_SINGLE, CUTOFF, s["pos"], box=s["box"], pbc=7, group1=labels, ngroups1=8)
+        assert c.count > 0 and np.asarray(c.map).any()
+        assert e.search_clusters(CUTOFF, s["pos"], box=s["box"], pbc=7).ncomponents >= 1
+        blk = e.search_clusters_frames(CUTOFF, s["frames"][:2], box=s["boxes"][:2], pbc=7)
+        assert len(blk.ncomponents) == 2 and min(blk.ncomponents) >= 1
+        assert count_fill(a, e, s)[0] == fresh_single[0]
+        e.close()
+        assert e.ctx is None
+    same_list(count_fill(a, a.Engine(0), s), fresh_single, "count + fill after three engines were closed")
