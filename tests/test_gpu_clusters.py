@@ -67,7 +67,8 @@ def test_entry_classes_with_structure(eng, orc32, case):
 # ---------------------------------------------------------------- 2. grids of very few cells
 
 def test_tiny_grid_dense(eng, orc32):
-    """grid (2, 2, 3): repeated cell pairs, cells against their own image, second cells of ~900 atoms; one component"""
+    """grid (2, 2, 3): repeated cell pairs, cells against their own image, second cells of ~2500 atoms (2418..2585 by fractional binning with
+    the oracle's dims); one component.  Crowded cells WITH structure are in test_gpu_clusters_pinned.py"""
     n, cutoff = 30000, 2.1
     box = synth.box_a(n)
     pos = synth.frame(n, box)

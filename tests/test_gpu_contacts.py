@@ -82,8 +82,9 @@ def check_single(c, ref, n, g=None, G=0, times=1):
     ("box_a", 3000, 0.5, 1),           # partial pbc on a triclinic box: no band classification, dropped atoms
     ("box_ortho", 3000, 0.5, 3),       # z not periodic
     (None, 5000, 0.6, 0),              # no box
-    ("box_a", 30000, 2.1, 7),          # grid (2, 2, 3): duplicates of the small grid, cells against their own image, second cells of ~900 atoms
-])
+    ("box_a", 30000, 2.1, 7),          # grid (2, 2, 3): duplicates of the small grid, cells against their own image, second cells of ~2500 atoms
+])          # atoms per cell (fractional binning with the oracle's dims): 4..20, 54..100, 2..19 for the first three, 2418..2585 for the last;
+            # chosen occupancies (0, 1 .. 3, 62 .. 66, 127 .. 129, 191 .. 193, 200) are in test_gpu_contacts_pinned.py
 def test_single_entry_classes(eng, orc32, boxname, n, cutoff, pbc):
     a = api()
     pos, box, ref = ref_single(orc32, boxname, n, cutoff, pbc)
