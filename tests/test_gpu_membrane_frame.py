@@ -2,8 +2,14 @@
 -> initial normals -> smoothing -> order without a host round trip) against the stage-by-stage calls it replaces: the
 same kernels and the same arithmetic, so every array has to agree bit for bit.  The stage-by-stage path is compared with
 the CPU checker in tests/test_gpu_membrane.py."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from test_gpu_membrane import check_smooth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -36,11 +42,18 @@ def same_result(got, want, what=""):
         same_bits(a, b, f"{what}order[{t}]")
 
 
-def pair(eng, per_leaflet, natoms, **opts):
+def pair(eng, per_leaflet, natoms, area_per_lipid=0.62, **opts):
     from molar_amd import membrane as mb
-    xyz, box, first, tpl, masses = mb.build_bilayer(per_leaflet, natoms)
+    xyz, box, first, tpl, masses = mb.build_bilayer(per_leaflet, natoms, area_per_lipid=area_per_lipid)
     mk = lambda fused: mb.Membrane(eng, len(xyz), first, tpl, masses, mb.MembraneOptions(fused=fused, **opts))
     return xyz, box, mk(True), mk(False)
+
+
+# Patch lengths on both sides of the 96 members the sixteen-lane fit holds in LDS (launch_fit from the chained call).  The
+# generator's leaflets have their heads 4.0 nm apart, and a cutoff that reaches the other leaflet costs every lipid its fit (no
+# lipid of 600 stays valid from 4.2 nm on), so the crowding comes from a denser lattice (0.45 nm^2 a lipid) under a cutoff that
+# stays below 4 nm, half the box height: the f32 checker gives 80 .. 105 members there, 227 of 600 lipids above 96.
+CROWDED = dict(cutoff=3.8, order_type=1, area_per_lipid=0.45)
 
 
 def frames_of(xyz, n, seed=5, sigma=0.02):
@@ -49,9 +62,11 @@ def frames_of(xyz, n, seed=5, sigma=0.02):
 
 
 @pytest.mark.parametrize("opts", [dict(cutoff=1.5, order_type=1), dict(cutoff=2.5, order_type=2), dict(cutoff=1.2, order_type=0, max_smooth_iter=3),
-                                  dict(cutoff=1.5, order_type=1, unwrap=False), dict(cutoff=1.5, order_type=2, global_normal=(0.0, 0.0, 1.0))])
-def test_chained_frame_equals_the_stages(eng, opts):
-    xyz, box, fused, staged = pair(eng, 150, 30000, **opts)
+                                  dict(cutoff=1.5, order_type=1, unwrap=False), dict(cutoff=1.5, order_type=2, global_normal=(0.0, 0.0, 1.0)),
+                                  CROWDED])
+def test_chained_frame_equals_the_stages(eng, orc32, opts):
+    crowded = opts is CROWDED
+    xyz, box, fused, staged = pair(eng, 300, 60000, **opts) if crowded else pair(eng, 150, 30000, **opts)
     assert fused.fusable() and not staged.fusable()
     for f, frame in enumerate(frames_of(xyz, 3)):
         a, b = frame.copy(), frame.copy()
@@ -59,6 +74,15 @@ def test_chained_frame_equals_the_stages(eng, opts):
         same_bits(a, b, "unwrapped frame")
         same_result(got, want, f"frame {f}: ")
         assert np.array_equal(fused.valid, staged.valid)
+        if crowded:
+            lens = np.diff(want["patch_off"].astype(np.int64))[want["valid"].astype(bool)]
+            print(f"frame {f}: patches of {lens.min()} .. {lens.max()} members over {len(lens)} valid lipids, {np.count_nonzero(lens > 96)} above 96")
+            assert lens.min() < 96 < lens.max() and opts["cutoff"] < 0.5 * float(np.diag(box).min())
+            if f == 0:                                   # every lipid valid on entry: the staged smoothing against the CPU checker
+                K = len(want["valid"])
+                so = orc32.membrane_smooth(orc32.box_from_matrix(box), want["head"], want["initial_normals"], np.ones(K, np.uint8),
+                                           want["patch_off"], want["patch_ids"])
+                check_smooth(want, so, want["patch_off"], K)
     assert np.count_nonzero(fused.valid) > (250 if opts.get("unwrap", True) and opts.get("max_smooth_iter", 1) == 1 else 10)
 
 
