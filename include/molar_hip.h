@@ -834,6 +834,79 @@ int molar_hip_msd_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, 
                       size_t max_lag, size_t origin_stride, uint32_t msd_dims, double *msd, double *m4,
                       double *msd_particle, size_t ld, double *disp);
 
+/* ---- Density profiles and density maps of a block of trajectory frames: every selected atom of every frame is put into a
+ * bin of a regular grid by its position, and the bins' sums of weights per unit volume are averaged over the frames (gmx
+ * density with -center / -relative, gmx densmap, VMD volmap / gmx spatial on fitted frames).  The frame block, idx, boxes,
+ * box_stride and pbc are those of molar_hip_msd.  Operation by operation (Real = float, or double for _f64; positions,
+ * centres and bin coordinates are formed in double from the exact inputs; F = nframes):
+ *   selection idx[0..n), idx == NULL: atoms 0 .. n-1.  w_k = weight[idx[k]] (one per ATOM, any sign: masses, charges,
+ *     electron counts); weight == NULL: number density, w_k = 1.  labels[n] (one per SELECTED atom) below ngroups gives the
+ *     group g of an atom; labels == NULL: one group, G = 1 (ngroups is not read).
+ *   grid: nbins[d] bins along dimension d (1 integrates over it: (1,1,nz) is a profile along z, (nx,ny,1) a lateral map,
+ *     (nx,ny,nz) a volume map), bin index (bx ny + by) nz + bz, nb = nx ny nz < 2^31, G nb < 2^31.
+ *     mode BOX (fractional coordinates, right under a fluctuating box):  s = inv(box_f) p (the inverse of from_matrix,
+ *       M v as ((M_r0 v0) + M_r1 v1) + M_r2 v2);  u_d = s_d;  on a periodic dimension of pbc  u_d -= floor(u_d);  on the
+ *       others an atom with u_d outside [0, 1) is dropped.  binvol_f = |det box_f| / nb.  lo and hi are not read.
+ *     mode LAB (frames the caller has fitted):  u_d = ((p_d - c_d) - lo_d) * (1 / (hi_d - lo_d)), c = 0 without centring;
+ *       atoms with u_d outside [0, 1) are dropped: intervals are half-open, an atom on an interior edge belongs to the
+ *       upper bin, one on hi is outside.  binvol = ((w_x / nx) (w_y / ny)) (w_z / nz), w_d = hi_d - lo_d.  Boxes are not read.
+ *     b_d = min(floor(u_d nbins[d]), nbins[d] - 1) (the min only guards a product that rounds up to nbins[d]).
+ *   centring: centre_idx[0..ncentre) (NULL: atoms 0 .. ncentre-1), centre_weight (one per ATOM, >= 0, NULL: 1) and the mask
+ *     grid.centre_dims (bits x, y, z); ncentre == 0 or a mask of 0: none.  Per frame, thread t of 256 adds atoms t, t + 256,
+ *     ... in that order and a fixed tree adds the threads (as the centres of molar_hip_rmsd_matrix).  On a masked dimension
+ *     that is periodic in BOX mode the centre is the circular mean of the fractional coordinate, theta = 2 pi s,
+ *     c = atan2(-sum w sin theta, -sum w cos theta) / (2 pi) + 1/2: right for a slab split across the cell boundary.  On a
+ *     masked non-periodic dimension in BOX mode c = sum w s / sum w, and in both  u_d = (s_d - c_d) + 1/2  before wrapping.
+ *     In LAB mode c = sum w p / sum w on the masked dimensions and lo, hi are relative to it.
+ *   accumulation, in integers alone:  q_k = llrint(w_k 2^S) (round to nearest even),  S = 62 - ceil(log2 n) - e  clamped
+ *     to at most 52, e the smallest integer with max |w_k| < 2^e over the selection (all weights zero: S = 52;
+ *     weight == NULL: S = 0, q = 1), so that n |q| < 2^62 and no sum can overflow whatever the bins; S is returned through
+ *     weight_scale_log2 (host memory, may be NULL).  I_f[g][b] = sum of q_k over the atoms of group g in bin b of frame f.
+ *   outputs:  density[G][nb] = (sum over f in frame order of (double)I_f[g][b] * (2^-S / binvol_f)) / F, rounded to Real: the
+ *     mean over the frames of sum w per unit volume;  count[G][nb] (uint64): atoms over the whole block;  outside[F]
+ *     (uint64): selected atoms of frame f that were dropped, outside the range or with a coordinate that is not finite (a
+ *     centre that is not finite drops every atom of its frame; the status stays MOLAR_HIP_OK);  centre[F][3]: the centre
+ *     used, fractional in BOX mode, 0 on the dimensions not masked;  binvol[F].
+ *   Only integer atomics are used and every floating-point sum has a fixed order: the same call gives the same bits.
+ * frames, idx, weight, labels, boxes, centre_idx, centre_weight and every output may each be host or device memory, and
+ * every output may be NULL.  Device outputs are written on the context's stream and not waited for (the call itself waits
+ * once, for the 64 bytes that decide its status and carry the largest |weight|).
+ * Errors: n == 0, labels with ngroups == 0: ERR_SIZES; a stride below 3 natoms (with more than one frame), an index not
+ * below natoms, n (or ncentre) > natoms without an index, natoms == 0, a box_stride other than 0 and 9, pbc > 7, a mode
+ * other than the two, nbins[d] == 0, hi <= lo (or a range that is not finite) in LAB mode, centre_dims > 7, a selected
+ * weight that is not finite, weights so large that raw S < 0, a label not below ngroups, a centre weight that is negative or
+ * not finite: ERR_INVALID_ARGUMENT; BOX mode with boxes == NULL: ERR_NO_PBC; a box with a vector of zero length:
+ * ERR_ZERO_LENGTH_VECTOR, one without an inverse: ERR_INVERSE_FAILED; centre weights that add up to zero: ERR_ZERO_MASS;
+ * 2^31 bins, cells, atoms or frames, or a workspace that cannot be allocated: ERR_TOO_LARGE (the byte count in
+ * molar_hip_last_error()).  The errors of the arguments alone are reported before the context is used; weights, labels and
+ * indices in device memory are judged on the device before any kernel uses one, and no output is touched after an error.
+ * nframes == 0 is a successful no-op.
+ * molar_hip_density_plan is a pure host function: the bytes of device workspace such a call allocates (kept by the context,
+ * grows only; staging of host-memory arguments not included; never smaller for a larger argument), frame_chunk, the frames
+ * whose integer bins are held at once and folded in order, atom_chunk, the selected atoms of one frame a workgroup of the
+ * binning kernels takes, and lds_cells, the largest G nb the on-chip binning kernel takes (above it: integer atomics
+ * straight into memory; both give the same integers). */
+enum { MOLAR_HIP_DENSITY_BOX = 0, MOLAR_HIP_DENSITY_LAB = 1 };
+typedef struct {
+    uint32_t mode;
+    uint32_t nbins[3];
+    double lo[3], hi[3];
+    uint32_t centre_dims;
+} molar_hip_density_grid;
+int molar_hip_density_plan(size_t nframes, size_t n, size_t ngroups, const molar_hip_density_grid *grid,
+                           size_t *workspace_bytes, uint32_t *frame_chunk, uint32_t *atom_chunk, uint32_t *lds_cells);
+int molar_hip_density(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *idx, size_t n, const float *weight, const uint32_t *labels, size_t ngroups,
+                      const float *boxes, size_t box_stride, uint8_t pbc, const molar_hip_density_grid *grid,
+                      const uint64_t *centre_idx, size_t ncentre, const float *centre_weight, float *density,
+                      uint64_t *count, uint64_t *outside, float *centre, float *binvol, int32_t *weight_scale_log2);
+int molar_hip_density_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                          const uint64_t *idx, size_t n, const double *weight, const uint32_t *labels, size_t ngroups,
+                          const double *boxes, size_t box_stride, uint8_t pbc, const molar_hip_density_grid *grid,
+                          const uint64_t *centre_idx, size_t ncentre, const double *centre_weight, double *density,
+                          uint64_t *count, uint64_t *outside, double *centre, double *binvol,
+                          int32_t *weight_scale_log2);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -597,6 +597,99 @@ inline MsdOf<double> msd_f64(Engine &eng, const double *frames, size_t nframes, 
     return out;
 }
 
+// Density profiles and maps of a block of frames (molar_hip_density; the definition: molar_hip.h): the mean over the frames
+// of the sum of the weights per unit volume in every bin of `grid`, per group.  `weight`: one per ATOM (null: number
+// density; density() takes the selection's masses with mass_weighted); `labels`: one per SELECTED atom, below ngroups
+// (empty: one group); `boxes`: one column-major box9, or one per frame with per_frame_boxes (BOX grids need them);
+// `centre_index`: the set a centred grid is centred on in every frame (weighted by the same per-atom column `centre_weight`).
+inline molar_hip_density_grid profile_grid(int axis, uint32_t nbins, bool centre = false) {
+    molar_hip_density_grid g{};
+    g.mode = MOLAR_HIP_DENSITY_BOX;
+    for (int d = 0; d < 3; ++d) {
+        g.nbins[d] = d == axis ? nbins : 1u;
+        g.lo[d] = 0.0;
+        g.hi[d] = 1.0;
+    }
+    g.centre_dims = centre ? 1u << axis : 0u;
+    return g;
+}
+inline molar_hip_density_grid map_grid(uint32_t nx, uint32_t ny) {
+    molar_hip_density_grid g = profile_grid(2, 1);
+    g.nbins[0] = nx;
+    g.nbins[1] = ny;
+    return g;
+}
+inline molar_hip_density_grid volume_grid(const double *lo3, const double *hi3, const uint32_t *nbins3, bool centre = false) {
+    molar_hip_density_grid g{};
+    g.mode = MOLAR_HIP_DENSITY_LAB;
+    for (int d = 0; d < 3; ++d) {
+        g.nbins[d] = nbins3[d];
+        g.lo[d] = lo3[d];
+        g.hi[d] = hi3[d];
+    }
+    g.centre_dims = centre ? 7u : 0u;
+    return g;
+}
+struct DensityOptions {
+    uint8_t pbc = MOLAR_HIP_PBC_FULL;
+    bool per_frame_boxes = false;
+    bool mass_weighted = false;       // density(): the selection's masses as weights
+    size_t ngroups = 1;               // read with labels
+};
+template <class Real>
+struct DensityOf {
+    std::vector<Real> density;        // [G][nb], nb = nx ny nz, bin (bx ny + by) nz + bz
+    std::vector<uint64_t> count;      // [G][nb]
+    std::vector<uint64_t> outside;    // [F]
+    std::vector<Real> centre;         // [F][3]
+    std::vector<Real> binvol;         // [F]
+    int32_t weight_scale_log2 = 0;
+    size_t ngroups = 0, nbins = 0;
+};
+using Density = DensityOf<Float>;
+template <class Real>
+inline void density_sizes(DensityOf<Real> &out, size_t F, const molar_hip_density_grid &grid, size_t G) {
+    out.ngroups = G;
+    out.nbins = (size_t)grid.nbins[0] * grid.nbins[1] * grid.nbins[2];
+    out.density.resize(G * out.nbins);
+    out.count.resize(G * out.nbins);
+    out.outside.resize(F);
+    out.centre.resize(F * 3);
+    out.binvol.resize(F);
+}
+inline Density density(const SelBound &sel, const std::vector<Pos> &frames, const molar_hip_density_grid &grid, const Float *boxes = nullptr,
+                       const DensityOptions &opt = DensityOptions(), const std::vector<uint32_t> &labels = {}, const std::vector<usize> &centre_index = {},
+                       const Float *weight = nullptr, const Float *centre_weight = nullptr) {
+    const size_t natoms = sel.natoms(), n = sel.len();
+    if (natoms == 0 || frames.size() % natoms) throw MolarError(MOLAR_HIP_ERR_SIZES, "density: the block is not a whole number of frames");
+    if (!labels.empty() && labels.size() != n) throw MolarError(MOLAR_HIP_ERR_SIZES, "density: one label per selected atom");
+    const size_t F = frames.size() / natoms;
+    Density out;
+    if (F == 0) return out;
+    density_sizes(out, F, grid, labels.empty() ? 1 : opt.ngroups);
+    check(molar_hip_density(sel.ctx(), &frames[0].x, F, natoms * 3, natoms, sel.get_index_slice().data(), n, weight ? weight : (opt.mass_weighted ? sel.masses() : nullptr),
+                            labels.empty() ? nullptr : labels.data(), opt.ngroups, boxes, opt.per_frame_boxes ? 9 : 0, opt.pbc, &grid,
+                            centre_index.empty() ? nullptr : centre_index.data(), centre_index.size(), centre_weight, out.density.data(), out.count.data(),
+                            out.outside.data(), out.centre.data(), out.binvol.data(), &out.weight_scale_log2));
+    return out;
+}
+// the same on f64 frames, weights and boxes (MolAR's f64 feature): molar_hip_density_f64; an empty index means every atom
+inline DensityOf<double> density_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const std::vector<usize> &index,
+                                     const molar_hip_density_grid &grid, const double *weight = nullptr, const double *boxes = nullptr,
+                                     const DensityOptions &opt = DensityOptions(), const std::vector<uint32_t> &labels = {},
+                                     const std::vector<usize> &centre_index = {}, const double *centre_weight = nullptr) {
+    const size_t n = index.empty() ? natoms : index.size();
+    if (!labels.empty() && labels.size() != n) throw MolarError(MOLAR_HIP_ERR_SIZES, "density_f64: one label per selected atom");
+    DensityOf<double> out;
+    if (nframes == 0) return out;
+    density_sizes(out, nframes, grid, labels.empty() ? 1 : opt.ngroups);
+    check(molar_hip_density_f64(eng.ctx(), frames, nframes, natoms * 3, natoms, index.empty() ? nullptr : index.data(), n, weight,
+                                labels.empty() ? nullptr : labels.data(), opt.ngroups, boxes, opt.per_frame_boxes ? 9 : 0, opt.pbc, &grid,
+                                centre_index.empty() ? nullptr : centre_index.data(), centre_index.size(), centre_weight, out.density.data(), out.count.data(),
+                                out.outside.data(), out.centre.data(), out.binvol.data(), &out.weight_scale_log2));
+    return out;
+}
+
 // Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
 // donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
 // images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's

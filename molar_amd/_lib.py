@@ -47,6 +47,11 @@ class ContactGroups(C.Structure):
     _fields_ = [("group1", C.c_void_p), ("ngroups1", C.c_size_t), ("group2", C.c_void_p), ("ngroups2", C.c_size_t)]
 
 
+class DensityGrid(C.Structure):
+    """molar_hip_density_grid: the mode (0 BOX, 1 LAB), the bins per dimension, the LAB range and the mask of centred dimensions."""
+    _fields_ = [("mode", C.c_uint32), ("nbins", C.c_uint32 * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("centre_dims", C.c_uint32)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -206,6 +211,9 @@ SYMBOLS = {
     "molar_hip_msd_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _I, _I, _P, _P, _P]),
     "molar_hip_msd": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),
     "molar_hip_msd_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _U8, _P, _SZ, _P, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _SZ, _P]),
+    "molar_hip_density_plan": (_I, [_SZ, _SZ, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_density": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_density_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

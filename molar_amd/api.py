@@ -1430,6 +1430,20 @@ class Engine:
         return _msd_call(self.lib, self.lib.molar_hip_msd, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride, dims,
                          msd, m4, per_particle, disp, out, np.float32)
 
+    def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
+                centre_weight=None, want=None, out=None):
+        """Density profiles and maps of frames [F, natoms, 3] float32 over `grid` (profile_grid, map_grid, volume_grid;
+        molar_hip_density, the definition: molar_hip.h): the mean over the frames of the sum of `weight` (one per ATOM: masses,
+        charges, electron counts; None: number density) per unit volume in every bin, per group of `labels` (one per SELECTED
+        atom, below `ngroups`; None: one group).  `boxes`: [9] column-major, [3, 3] rows, or [F, 9], needed by the fractional
+        grids; `pbc`: the periodic dimensions, wrapped.  `centre_idx` / `centre_weight` (per ATOM): the set a centred grid is
+        centred on in every frame.  Returns Density(density [G, nx, ny, nz], count (uint64; torch: int64), outside [F],
+        centre [F, 3], binvol [F], weight_scale_log2, grid); with `want` (a tuple of those names) the others are None.  numpy in, numpy out;
+        torch CUDA in, torch CUDA out, written on the ENGINE's stream and not waited for (`Engine.synchronize()` before torch
+        reads them).  `out`: an optional Density (or 5-tuple) of destinations.  The same call gives the same bits."""
+        return _density_call(self.lib, self.lib.molar_hip_density, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, pbc, centre_idx,
+                             centre_weight, want, out, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -1911,6 +1925,157 @@ def _msd_call(lib, fn, ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_
     return Msd(*res)
 
 
+Density = collections.namedtuple("Density", ["density", "count", "outside", "centre", "binvol", "weight_scale_log2", "grid"])
+DensityGrid = collections.namedtuple("DensityGrid", ["mode", "nbins", "lo", "hi", "centre_dims"])
+DENSITY_BOX, DENSITY_LAB = 0, 1
+
+
+def profile_grid(axis, nbins, centre=False):
+    """The grid of a profile along box vector `axis` (0, 1, 2) in fractional coordinates (gmx density -relative): `nbins` bins
+    along it, the other two dimensions integrated over.  centre=True: the profile is centred per frame on the centre set of
+    the call (the circular mean on a periodic dimension), which then sits at the middle of the range."""
+    axis = int(axis)
+    assert axis in (0, 1, 2)
+    nb = [1, 1, 1]
+    nb[axis] = int(nbins)
+    return DensityGrid(DENSITY_BOX, tuple(nb), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), (1 << axis) if centre else 0)
+
+
+def map_grid(nbins_xy, centre=False):
+    """The grid of a lateral map in fractional coordinates (gmx densmap): nbins_xy = (nx, ny), z integrated over."""
+    nx, ny = (int(v) for v in nbins_xy)
+    return DensityGrid(DENSITY_BOX, (nx, ny, 1), (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), 3 if centre else 0)
+
+
+def volume_grid(lo, hi, nbins, centre=False):
+    """The grid of a volume map in the coordinates of the frames as they are (VMD volmap, gmx spatial on fitted frames): the
+    half-open range lo .. hi with nbins = (nx, ny, nz) bins.  centre=True: lo and hi are relative to the centre of the
+    call's centre set in each frame."""
+    lo = tuple(float(v) for v in lo)
+    hi = tuple(float(v) for v in hi)
+    nb = tuple(int(v) for v in nbins)
+    assert len(lo) == len(hi) == len(nb) == 3
+    return DensityGrid(DENSITY_LAB, nb, lo, hi, 7 if centre else 0)
+
+
+def _grid_struct(grid):
+    g = _lib.DensityGrid()
+    g.mode = int(grid.mode)
+    for d in range(3):
+        g.nbins[d] = int(grid.nbins[d])
+        g.lo[d] = float(grid.lo[d])
+        g.hi[d] = float(grid.hi[d])
+    g.centre_dims = int(grid.centre_dims)
+    return g
+
+
+def density_plan(nframes, n, grid, ngroups=1):
+    """(workspace_bytes, frame_chunk, atom_chunk, lds_cells) of a density call of these sizes (molar_hip_density_plan): the
+    device workspace, the frames whose integer bins are held at once, the atoms of one frame a workgroup bins, and the
+    largest ngroups * bins the on-chip binning kernel takes.  A host function: no GPU is needed."""
+    g = _grid_struct(grid)
+    ws, fc, ac, lc = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_density_plan(int(nframes), int(n), int(ngroups), C.addressof(g), C.addressof(ws), C.addressof(fc),
+                                             C.addressof(ac), C.addressof(lc)))
+    return int(ws.value), int(fc.value), int(ac.value), int(lc.value)
+
+
+def density_axis(grid, d, box=None):
+    """The centres of the bins along dimension d, float64.  LAB grid: lo + (i + 1/2) (hi - lo) / nbins (relative to the centre
+    when the grid is centred).  BOX grid: the fractional (i + 1/2) / nbins, minus 1/2 when dimension d is centred (the centre
+    set then sits at 0); with `box` ([9] column-major or [3, 3] rows: one box, the mean box of the block say) times the
+    length of box vector d."""
+    nb = int(grid.nbins[d])
+    u = (np.arange(nb, dtype=np.float64) + 0.5) / nb
+    if grid.mode == DENSITY_LAB:
+        return grid.lo[d] + u * (grid.hi[d] - grid.lo[d])
+    if grid.centre_dims >> d & 1:
+        u = u - 0.5
+    if box is None:
+        return u
+    b = np.asarray(box, np.float64)
+    vec = b[d] if b.ndim == 2 else b.reshape(9)[3 * d:3 * d + 3]
+    return u * float(np.sqrt((vec * vec).sum()))
+
+
+def density_symmetrize(density, grid, d):
+    """The mean of a density and its mirror image about the middle of the range of dimension d (gmx density -symm), for an
+    array whose last three dimensions are the grid's (or one flattened over them); float64 on the host."""
+    a = np.asarray(density, np.float64)
+    shape = a.shape
+    nb = tuple(int(v) for v in grid.nbins)
+    if shape[-3:] != nb:
+        a = a.reshape(shape[:-1] + nb)
+    out = 0.5 * (a + np.flip(a, axis=a.ndim - 3 + d))
+    return out.reshape(shape)
+
+
+def _density_call(lib, fn, ctx, frames, grid, idx, weight, labels, ngroups, boxes, pbc, centre_idx, centre_weight, want, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (idx, weight, labels, boxes, centre_idx, centre_weight)
+    idx = _u64(idx); weight = conv(weight); labels = _u32(labels); centre_idx = _u64(centre_idx); centre_weight = conv(centre_weight)
+    box_stride = 0
+    if boxes is not None:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    n = natoms if idx is None else idx.shape[0]
+    ncentre = 0 if centre_idx is None else centre_idx.shape[0]
+    G = 1
+    if labels is not None:
+        assert labels.shape[0] == n, "one label per selected atom"
+        G = int(ngroups) if ngroups is not None else (int(labels.max()) + 1 if n else 1)
+    for w in (weight, centre_weight):
+        if w is not None:
+            assert w.shape[0] == natoms, "one weight per atom"
+    nbins = tuple(int(v) for v in grid.nbins)
+    names = ("density", "count", "outside", "centre", "binvol")
+    want = names if want is None else tuple(want)
+    shapes = ((G,) + nbins, (G,) + nbins, (F,), (F, 3), (F,))
+    given = tuple(out[:5]) if out is not None else (None,) * 5
+    res = []
+    for name, shape, g in zip(names, shapes, given):
+        integer = name in ("count", "outside")
+        if name not in want:
+            res.append(None)
+        elif g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape
+            if dev:
+                import torch
+                assert g.dtype == (torch.int64 if integer else fr.dtype) and g.is_contiguous()
+            else:
+                assert g.dtype == (np.uint64 if integer else real) and g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            import torch
+            res.append(torch.zeros(shape, dtype=torch.int64 if integer else fr.dtype, device=fr.device))
+        else:
+            res.append(np.zeros(shape, np.uint64 if integer else real))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    gs = _grid_struct(grid)
+    scale = C.c_int32(0)
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ia, k1 = _addr(idx); wa, k2 = _addr(weight); la, k3 = _addr(labels); ba, k4 = _addr(boxes); ca, k5 = _addr(centre_idx)
+    cwa, k6 = _addr(centre_weight)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ia, n, wa, la, G, ba, box_stride, int(pbc), C.addressof(gs), ca, ncentre, cwa,
+             addr[0], addr[1], addr[2], addr[3], addr[4], C.addressof(scale)))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((idx, weight, labels, boxes, centre_idx, centre_weight), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return Density(*res, int(scale.value), grid)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -2108,6 +2273,12 @@ class MeasureF64:
         """Engine.msd on float64 frames, masses and boxes (molar_hip_msd_f64): float64 results."""
         return _msd_call(self.lib, self.lib.molar_hip_msd_f64, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride,
                          dims, msd, m4, per_particle, disp, out, np.float64)
+
+    def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
+                centre_weight=None, want=None, out=None):
+        """Engine.density on float64 frames, weights and boxes (molar_hip_density_f64): float64 results."""
+        return _density_call(self.lib, self.lib.molar_hip_density_f64, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, pbc,
+                             centre_idx, centre_weight, want, out, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

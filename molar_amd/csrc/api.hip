@@ -197,6 +197,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::rmsd_matrix_release(c);
     mh::fluct_release(c);
     mh::msd_release(c);
+    mh::density_release(c);
     mh::hbonds_release(c);
     mh::lifetimes_release(c);
     mh::within_release(c);

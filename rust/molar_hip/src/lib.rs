@@ -1012,6 +1012,81 @@ impl Engine {
         Ok((ws, pc, lb))
     }
 
+    /// Density profiles and maps of a block of frames through molar_hip_density (the definition: molar_hip.h): the mean over the
+    /// frames of the sum of `weights` (one per ATOM; None: number density) per unit volume in every bin of `grid`, per group
+    /// of `labels` ((one label per SELECTED atom, ngroups); None: one group).  `boxes`: one column-major box of 9 numbers, or
+    /// 9 per frame (the BOX grids need them); `pbc`: the PbcDims byte; `centre`: (the set a centred grid is centred on in
+    /// every frame, its per-ATOM weights or None).  Only integer atomics are used: the same call gives the same bits.
+    #[allow(clippy::too_many_arguments)]
+    pub fn density(
+        &self, frames: &[[f32; 3]], natoms: usize, index: Option<&[usize]>, weights: Option<&[f32]>, labels: Option<(&[u32], usize)>,
+        boxes: Option<&[f32]>, pbc: u8, grid: &MolarHipDensityGrid, centre: Option<(&[usize], Option<&[f32]>)>,
+    ) -> Result<Density, EngineError> {
+        check_index(index, natoms, "density")?;
+        check_index(centre.map(|c| c.0), natoms, "density: centre set")?;
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("density: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        if let Some(w) = weights {
+            check_column(w.len(), natoms, "density: weights")?;
+        }
+        if let Some((_, Some(w))) = centre {
+            check_column(w.len(), natoms, "density: centre weights")?;
+        }
+        let nframes = frames.len() / natoms;
+        let (ip, n) = idx_ptr(index);
+        let nsel = if index.is_some() { n } else { natoms };
+        if nsel == 0 {
+            return Err(EngineError::Sizes("density: empty selection".into()));
+        }
+        let box_stride = match boxes {
+            None => 0,
+            Some(b) if b.len() == 9 => 0,
+            Some(b) if b.len() == 9 * nframes => 9,
+            Some(b) => return Err(EngineError::Sizes(format!("density: {} box numbers for {nframes} frames", b.len()))),
+        };
+        let (lp, ngroups) = match labels {
+            Some((l, _)) if l.len() != nsel => return Err(EngineError::Sizes(format!("density: {} labels for {nsel} selected atoms", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        let nb = grid.nbins.iter().map(|&b| b as usize).product::<usize>();
+        let mut out = Density {
+            density: vec![0f32; ngroups * nb],
+            count: vec![0u64; ngroups * nb],
+            outside: vec![0u64; nframes],
+            centre: vec![[0f32; 3]; nframes],
+            binvol: vec![0f32; nframes],
+            weight_scale_log2: 0,
+            ngroups,
+            nbins: nb,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        let wp = weights.map_or(std::ptr::null(), |w| w.as_ptr());
+        let bp = boxes.map_or(std::ptr::null(), |b| b.as_ptr());
+        let (cp, ncentre) = centre.map_or((std::ptr::null(), 0), |c| (c.0.as_ptr() as *const u64, c.0.len()));
+        let cwp = centre.and_then(|c| c.1).map_or(std::ptr::null(), |w| w.as_ptr());
+        self.plugin.check(unsafe {
+            (self.plugin.fns.density)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, ip, nsel, wp, lp, ngroups, bp, box_stride, pbc,
+                                      grid as *const MolarHipDensityGrid, cp, ncentre, cwp, out.density.as_mut_ptr(), out.count.as_mut_ptr(),
+                                      out.outside.as_mut_ptr(), out.centre.as_mut_ptr() as *mut f32, out.binvol.as_mut_ptr(), &mut out.weight_scale_log2)
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes, the frames whose integer bins are held at once, the atoms of one frame per workgroup of the
+    /// binning kernels and the largest ngroups * bins the on-chip kernel takes, for a `density` call of these sizes
+    /// (molar_hip_density_plan, a host function).
+    pub fn density_plan(&self, nframes: usize, n: usize, ngroups: usize, grid: &MolarHipDensityGrid) -> Result<(usize, u32, u32, u32), EngineError> {
+        let (mut ws, mut fc, mut ac, mut lc) = (0usize, 0u32, 0u32, 0u32);
+        self.plugin.check(unsafe {
+            (self.plugin.fns.density_plan)(nframes, n, ngroups, grid as *const MolarHipDensityGrid, &mut ws, &mut fc, &mut ac, &mut lc)
+        })?;
+        Ok((ws, fc, ac, lc))
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
@@ -1120,6 +1195,20 @@ pub struct Msd {
     pub msd_particle: Vec<f32>,
     pub disp: Vec<[f32; 3]>,
     pub nparticles: usize,
+}
+
+/// What `Engine::density` returns: the density [group][bin] (bin (bx ny + by) nz + bz), the atoms counted per group and bin over
+/// the block, per frame the selected atoms that were dropped, the centre used and the bin volume, and the scale of the weights.
+#[derive(Debug, Clone, Default)]
+pub struct Density {
+    pub density: Vec<f32>,
+    pub count: Vec<u64>,
+    pub outside: Vec<u64>,
+    pub centre: Vec<[f32; 3]>,
+    pub binvol: Vec<f32>,
+    pub weight_scale_log2: i32,
+    pub ngroups: usize,
+    pub nbins: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless

@@ -77,6 +77,22 @@ impl Default for MolarHipContactGroups {
     }
 }
 
+/// `molar_hip_density_grid`: the grid of the density calls - `mode` (0: BOX, fractional coordinates of each frame's box; 1: LAB,
+/// the range `lo .. hi`), the bins per dimension (1 integrates over it), and the mask of the dimensions that are centred.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct MolarHipDensityGrid {
+    pub mode: u32,
+    pub nbins: [u32; 3],
+    pub lo: [f64; 3],
+    pub hi: [f64; 3],
+    pub centre_dims: u32,
+}
+
+/// `MolarHipDensityGrid::mode`
+pub const DENSITY_BOX: u32 = 0;
+pub const DENSITY_LAB: u32 = 1;
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
