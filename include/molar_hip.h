@@ -907,6 +907,81 @@ int molar_hip_density_f64(molar_hip_ctx *ctx, const double *frames, size_t nfram
                           uint64_t *count, uint64_t *outside, double *centre, double *binvol,
                           int32_t *weight_scale_log2);
 
+/* ---- Internal coordinates of a block of trajectory frames: the distance, the angle or the dihedral of every tuple of
+ * atoms in every frame (gmx distance, gmx angle, gmx angle -type dihedral / gmx chi / gmx rama), as a series, as histograms
+ * per group of tuples, as joint histograms of pairs of tuples (the Ramachandran / Janin map) and as a mean and a spread per
+ * tuple.  The frame block, boxes, box_stride and pbc are those of molar_hip_msd.  Operation by operation (Real = float, or
+ * double for _f64; everything is formed in double from the exact inputs and rounded to Real at the end; F = nframes,
+ * T = ntuples, one kind per call, spec.kind = atoms per tuple):
+ *   tuples[T][kind]: atom indices into a frame.  Every bond vector B - A is formed on its own and, when pbc != 0, reduced
+ *     with shortest_vector (the f64 PeriodicBox of that frame's box, the masked dimensions): a molecule split across the
+ *     cell boundary needs no unwrap.  dot(a, b) = ((ax bx) + ay by) + az bz, the cross product without fused operations.
+ *   DISTANCE (A,B):      |B - A|.
+ *   ANGLE (A,B,C):       u = A - B, v = C - B;  theta = atan2(|u x v|, u . v) in [0, pi].
+ *   DIHEDRAL (A,B,C,D):  b1 = B - A, b2 = C - B, b3 = D - C, n1 = b1 x b2, n2 = b2 x b3;
+ *                        phi = atan2(|b2| (b1 . n2), n1 . n2) in (-pi, pi], radians: IUPAC, cis = 0, trans = pi, the sign of
+ *                        (b1 x b2) . b3.
+ *   invalid values: a coordinate of the tuple that is not finite, |u|^2 = 0 or |v|^2 = 0 (ANGLE), n1 = 0 or n2 = 0 in every
+ *     component (DIHEDRAL), or a value that is not finite (a box that is not).  An invalid value is NaN in `values` and
+ *     enters nothing else; the status stays MOLAR_HIP_OK.  (A DISTANCE of 0 is valid.)
+ *   values[F][T], row stride ld >= T: the series.
+ *   hist[G][nbins] (uint64): counts over all frames per group labels[t] < ngroups; labels == NULL: one group, G = 1
+ *     (ngroups is not read).  The bin of a value v:
+ *       DISTANCE  floor((v - lo) / (hi - lo) * nbins) for lo <= v < hi only (others are not counted),
+ *       ANGLE     floor(v / pi * nbins), v = pi in the last bin,
+ *       DIHEDRAL  floor((v + pi) / (2 pi) * nbins) mod nbins,
+ *     each capped at nbins - 1 (the cap only guards a product that rounds up to nbins).
+ *   map[G2][map_bins][map_bins] (uint64): the joint histogram of (value of tuple pairs[p][0], value of tuple pairs[p][1])
+ *     within a frame by the same rule with map_bins bins, the first value the slower index; a frame is counted only when
+ *     both values are valid (and, for DISTANCE, in range); per group pair_labels[p] < npair_groups (NULL: one group).  The
+ *     two values are recomputed: the map does not need the series.
+ *   mean[T], spread[T] over the n valid frames of a tuple, added in frame order within chunks of frame_chunk frames and
+ *     the chunks added in chunk order:  DISTANCE, ANGLE: S1 = sum v, S2 = sum v v, mean = S1 / n,
+ *     spread = sqrt(max(0, S2 / n - mean mean));  DIHEDRAL: C = sum cos phi, S = sum sin phi, mean = atan2(S, C),
+ *     spread = 1 - hypot(C, S) / n, the circular variance.  n = 0: both NaN.  valid[T] (uint64) = n.
+ *   Only integer atomics are used and every floating-point sum has a fixed order: the same call gives the same bits.
+ * frames, tuples, labels, boxes, pairs, pair_labels and every output may each be host or device memory, and every output
+ * may be NULL (pairs and pair_labels are read only for a map).  Device outputs are written on the context's stream and not
+ * waited for (the call waits once, for the 64 bytes of its status, when a box or an index in device memory is to be judged).
+ * Errors: labels with ngroups == 0, pair_labels with npair_groups == 0: ERR_SIZES; a spec that is NULL, a kind other than
+ * the three, reserved != 0, for DISTANCE a range that is not finite or lo >= hi, G nbins >= 2^31, G2 map_bins^2 >= 2^31,
+ * hist with nbins == 0, map with map_bins == 0 or without pairs, ld < T, tuples == NULL, natoms == 0, a stride below
+ * 3 natoms (with more than one frame), a box_stride other than 0 and 9, pbc > 7, a tuple index not below natoms, a label not
+ * below its number of groups, a pair entry not below T: ERR_INVALID_ARGUMENT; pbc != 0 with boxes == NULL: ERR_NO_PBC; a
+ * box with a vector of zero length: ERR_ZERO_LENGTH_VECTOR, one without an inverse: ERR_INVERSE_FAILED; 2^31 tuples, pairs,
+ * frames or workgroups, or memory that cannot be allocated: ERR_TOO_LARGE.  The errors of the arguments alone are reported
+ * before the context is used; tuples, pairs and labels in device memory are judged on the device before any kernel uses
+ * one as an address, and no output is touched after an error.  nframes == 0 or ntuples == 0 is a successful no-op.
+ * molar_hip_intcoord_plan is a pure host function: the bytes of device workspace such a call allocates (the chunk partials
+ * [frame chunks][T] when want_stats, i.e. when mean, spread or valid is asked for; kept by the context, grows only; staging
+ * of host-memory arguments and results and the per-frame box records not included; never smaller for a larger argument),
+ * frame_chunk and tuple_chunk, the frames and the tuples (or pairs) a workgroup takes, and lds_cells, the largest G nbins
+ * (G2 map_bins^2) the on-chip histogram takes (above it: integer atomics straight into memory; both give the same
+ * integers; the environment variable MOLAR_HIP_INTCOORD_GLOBAL forces the latter). */
+enum { MOLAR_HIP_IC_DISTANCE = 2, MOLAR_HIP_IC_ANGLE = 3, MOLAR_HIP_IC_DIHEDRAL = 4 };
+typedef struct {
+    uint32_t kind;
+    uint32_t nbins;
+    uint32_t map_bins;
+    uint32_t reserved;
+    double lo, hi;
+} molar_hip_intcoord_spec;
+int molar_hip_intcoord_plan(size_t nframes, size_t ntuples, size_t ngroups, size_t npairs, size_t npair_groups,
+                            const molar_hip_intcoord_spec *spec, int want_stats, size_t *workspace_bytes,
+                            uint32_t *frame_chunk, uint32_t *tuple_chunk, uint32_t *lds_cells);
+int molar_hip_intcoord(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                       const uint64_t *tuples, size_t ntuples, const uint32_t *labels, size_t ngroups,
+                       const float *boxes, size_t box_stride, uint8_t pbc, const molar_hip_intcoord_spec *spec,
+                       const uint64_t *pairs, size_t npairs, const uint32_t *pair_labels, size_t npair_groups,
+                       float *values, size_t ld, uint64_t *hist, uint64_t *map, float *mean, float *spread,
+                       uint64_t *valid);
+int molar_hip_intcoord_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                           const uint64_t *tuples, size_t ntuples, const uint32_t *labels, size_t ngroups,
+                           const double *boxes, size_t box_stride, uint8_t pbc, const molar_hip_intcoord_spec *spec,
+                           const uint64_t *pairs, size_t npairs, const uint32_t *pair_labels, size_t npair_groups,
+                           double *values, size_t ld, uint64_t *hist, uint64_t *map, double *mean, double *spread,
+                           uint64_t *valid);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

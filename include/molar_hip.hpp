@@ -690,6 +690,83 @@ inline DensityOf<double> density_f64(Engine &eng, const double *frames, size_t n
     return out;
 }
 
+// Internal coordinates (molar_hip_intcoord*; the definition: molar_hip.h): the distance, angle or dihedral (kind = 2, 3, 4 =
+// atoms per tuple, radians) of every tuple of atom indices `tuples` ([T][kind]) in every frame of a block, as a series,
+// histograms per group of `labels`, the joint histogram of the two tuples of every row of `pairs` ([P][2]: the Ramachandran
+// map) per group of `pair_labels`, and the mean and spread (dihedrals: circular mean and circular variance) per tuple.
+struct InternalCoordsOptions {
+    uint8_t pbc = MOLAR_HIP_PBC_FULL; // read with boxes: every bond vector takes its minimum image
+    bool per_frame_boxes = false;
+    uint32_t nbins = 0;               // the histogram; 0: none
+    uint32_t map_bins = 0;            // the map, per side; 0 (or no pairs): none
+    double lo = 0.0, hi = 1.0;        // the half-open range of a distance histogram
+    size_t ngroups = 1;               // read with labels
+    size_t npair_groups = 1;          // read with pair_labels
+    bool want_values = true;          // the series [F][T]
+    bool want_stats = true;           // mean, spread and valid
+};
+template <class Real>
+struct InternalCoordsOf {
+    std::vector<Real> values;         // [F][T], NaN where invalid
+    std::vector<uint64_t> hist;       // [G][nbins]
+    std::vector<uint64_t> map;        // [G2][map_bins][map_bins]
+    std::vector<Real> mean, spread;   // [T]
+    std::vector<uint64_t> valid;      // [T]: the frames that entered
+    size_t nframes = 0, ntuples = 0, ngroups = 0, npair_groups = 0;
+};
+using InternalCoords = InternalCoordsOf<Float>;
+template <class Real, class Fn>
+inline InternalCoordsOf<Real> internal_coords_call(Fn fn, const char *who, Engine &eng, const Real *frames, size_t nframes, size_t natoms,
+                                                   const std::vector<usize> &tuples, uint32_t kind, const Real *boxes, const InternalCoordsOptions &opt,
+                                                   const std::vector<uint32_t> &labels, const std::vector<usize> &pairs,
+                                                   const std::vector<uint32_t> &pair_labels) {
+    if (kind < 2 || kind > 4 || tuples.size() % kind) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": the tuples are not a whole number of tuples of `kind` atoms");
+    const size_t T = tuples.size() / kind, P = pairs.size() / 2;
+    if (!labels.empty() && labels.size() != T) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per tuple");
+    if (pairs.size() % 2 || (!pair_labels.empty() && pair_labels.size() != P)) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": pairs are [P][2], one label per pair");
+    InternalCoordsOf<Real> out;
+    out.nframes = nframes;
+    out.ntuples = T;
+    out.ngroups = labels.empty() ? 1 : opt.ngroups;
+    out.npair_groups = pair_labels.empty() ? 1 : opt.npair_groups;
+    if (nframes == 0 || T == 0) return out;
+    const bool want_map = opt.map_bins != 0 && P != 0;
+    if (opt.want_values) out.values.resize(nframes * T);
+    if (opt.nbins) out.hist.resize(out.ngroups * opt.nbins);
+    if (want_map) out.map.resize(out.npair_groups * opt.map_bins * opt.map_bins);
+    if (opt.want_stats) {
+        out.mean.resize(T);
+        out.spread.resize(T);
+        out.valid.resize(T);
+    }
+    molar_hip_intcoord_spec spec{};
+    spec.kind = kind;
+    spec.nbins = opt.nbins;
+    spec.map_bins = opt.map_bins;
+    spec.lo = opt.lo;
+    spec.hi = opt.hi;
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    check(fn(eng.ctx(), frames, nframes, natoms * 3, natoms, tuples.data(), T, labels.empty() ? nullptr : labels.data(), opt.ngroups, boxes,
+             opt.per_frame_boxes ? 9 : 0, boxes ? opt.pbc : (uint8_t)0, &spec, want_map ? pairs.data() : nullptr, want_map ? P : 0,
+             want_map && !pair_labels.empty() ? pair_labels.data() : nullptr, opt.npair_groups, ptr(out.values), T, ptr(out.hist), ptr(out.map), ptr(out.mean),
+             ptr(out.spread), ptr(out.valid)));
+    return out;
+}
+inline InternalCoords internal_coords(Engine &eng, const Float *frames, size_t nframes, size_t natoms, const std::vector<usize> &tuples, uint32_t kind,
+                                      const Float *boxes = nullptr, const InternalCoordsOptions &opt = InternalCoordsOptions(),
+                                      const std::vector<uint32_t> &labels = {}, const std::vector<usize> &pairs = {},
+                                      const std::vector<uint32_t> &pair_labels = {}) {
+    return internal_coords_call<Float>(molar_hip_intcoord, "internal_coords", eng, frames, nframes, natoms, tuples, kind, boxes, opt, labels, pairs, pair_labels);
+}
+// the same on f64 frames and boxes (MolAR's f64 feature): molar_hip_intcoord_f64
+inline InternalCoordsOf<double> internal_coords_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const std::vector<usize> &tuples,
+                                                    uint32_t kind, const double *boxes = nullptr, const InternalCoordsOptions &opt = InternalCoordsOptions(),
+                                                    const std::vector<uint32_t> &labels = {}, const std::vector<usize> &pairs = {},
+                                                    const std::vector<uint32_t> &pair_labels = {}) {
+    return internal_coords_call<double>(molar_hip_intcoord_f64, "internal_coords_f64", eng, frames, nframes, natoms, tuples, kind, boxes, opt, labels, pairs,
+                                        pair_labels);
+}
+
 // Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
 // donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
 // images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's

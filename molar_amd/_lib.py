@@ -52,6 +52,12 @@ class DensityGrid(C.Structure):
     _fields_ = [("mode", C.c_uint32), ("nbins", C.c_uint32 * 3), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("centre_dims", C.c_uint32)]
 
 
+class IntcoordSpec(C.Structure):
+    """molar_hip_intcoord_spec: the kind (atoms per tuple: 2 distance, 3 angle, 4 dihedral), the bins of the histogram and of
+    the map (0: none) and the half-open range of a DISTANCE histogram."""
+    _fields_ = [("kind", C.c_uint32), ("nbins", C.c_uint32), ("map_bins", C.c_uint32), ("reserved", C.c_uint32), ("lo", C.c_double), ("hi", C.c_double)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -214,6 +220,9 @@ SYMBOLS = {
     "molar_hip_density_plan": (_I, [_SZ, _SZ, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_density": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_density_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_intcoord_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _P, _I, _P, _P, _P, _P]),
+    "molar_hip_intcoord": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_intcoord_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

@@ -1430,6 +1430,22 @@ class Engine:
         return _msd_call(self.lib, self.lib.molar_hip_msd, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride, dims,
                          msd, m4, per_particle, disp, out, np.float32)
 
+    def internal_coords(self, frames, tuples, kind=None, labels=None, ngroups=None, boxes=None, pbc=7, nbins=0, range=None, pairs=None,
+                        pair_labels=None, npair_groups=None, map_bins=0, want=None, out=None):
+        """Distances, angles or dihedrals of `tuples` [T, 2 | 3 | 4] (atom indices; kind: from tuples.shape[1]) in every frame of
+        frames [F, natoms, 3] float32 (molar_hip_intcoord, the definition: molar_hip.h), radians, all arithmetic in double.
+        Every bond vector takes the minimum image under `boxes` ([9] column-major, [3, 3] rows or [F, 9]; None: no image is
+        removed) on the dimensions of `pbc`.  Returns InternalCoords(values [F, T] (NaN where invalid), hist [G, nbins] per
+        group of `labels` (one per tuple), map [G2, map_bins, map_bins]: the joint histogram of the two tuples of every row of
+        `pairs` [P, 2] per group of `pair_labels` (the Ramachandran map), mean [T], spread [T] (the standard deviation; the
+        circular variance for dihedrals, see circular_std), valid [T]: the frames that entered, edges: the bin edges of hist,
+        or of one side of the map without one).  Distances are binned in the half-open `range` = (lo, hi).  `want`: the names to
+        compute (default: all that the arguments allow); numpy in gives numpy out, torch CUDA in gives torch CUDA out
+        (integers as int64).  `out`: an optional InternalCoords (or 6-tuple) of destinations; values may have a row stride
+        above T.  The same call gives the same bits."""
+        return _intcoord_call(self.lib, self.lib.molar_hip_intcoord, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, nbins, range, pairs,
+                              pair_labels, npair_groups, map_bins, want, out, np.float32)
+
     def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
                 centre_weight=None, want=None, out=None):
         """Density profiles and maps of frames [F, natoms, 3] float32 over `grid` (profile_grid, map_grid, volume_grid;
@@ -2076,6 +2092,195 @@ def _density_call(lib, fn, ctx, frames, grid, idx, weight, labels, ngroups, boxe
     return Density(*res, int(scale.value), grid)
 
 
+InternalCoords = collections.namedtuple("InternalCoords", ["values", "hist", "map", "mean", "spread", "valid", "edges"])
+IC_DISTANCE, IC_ANGLE, IC_DIHEDRAL = 2, 3, 4
+
+
+def _intcoord_spec(kind, nbins, range, map_bins):
+    sp = _lib.IntcoordSpec()
+    sp.kind = int(kind)
+    sp.nbins = int(nbins)
+    sp.map_bins = int(map_bins)
+    sp.reserved = 0
+    if range is None:
+        assert int(kind) != IC_DISTANCE or (int(nbins) == 0 and int(map_bins) == 0), "a distance histogram needs range=(lo, hi)"
+        range = (0.0, 1.0)
+    sp.lo, sp.hi = float(range[0]), float(range[1])
+    return sp
+
+
+def intcoord_plan(nframes, ntuples, kind, ngroups=1, npairs=0, npair_groups=1, nbins=0, range=None, map_bins=0, want_stats=True):
+    """(workspace_bytes, frame_chunk, tuple_chunk, lds_cells) of an internal_coords call of these sizes
+    (molar_hip_intcoord_plan): the device workspace (the chunk partials of mean / spread / valid), the frames and the tuples
+    (or pairs) a workgroup takes, and the largest ngroups * nbins (npair_groups * map_bins^2) the on-chip histogram takes.  A
+    host function: no GPU is needed."""
+    sp = _intcoord_spec(kind, nbins, range, map_bins)
+    ws, fc, tc, lc = C.c_size_t(0), C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    check(_lib.load().molar_hip_intcoord_plan(int(nframes), int(ntuples), int(ngroups), int(npairs), int(npair_groups), C.addressof(sp),
+                                              1 if want_stats else 0, C.addressof(ws), C.addressof(fc), C.addressof(tc), C.addressof(lc)))
+    return int(ws.value), int(fc.value), int(tc.value), int(lc.value)
+
+
+def intcoord_edges(kind, nbins, range=None):
+    """The nbins + 1 bin edges of an internal_coords histogram (or of one side of its map), float64: lo .. hi for distances,
+    0 .. pi for angles, -pi .. pi for dihedrals."""
+    if int(kind) == IC_DISTANCE:
+        lo, hi = (float(v) for v in range)
+    elif int(kind) == IC_ANGLE:
+        lo, hi = 0.0, np.pi
+    else:
+        lo, hi = -np.pi, np.pi
+    return lo + (hi - lo) * (np.arange(int(nbins) + 1, dtype=np.float64) / int(nbins))
+
+
+def intcoord_degrees(x):
+    """Radians to degrees for angles, dihedrals, their means and bin edges (numpy or torch; distances and the circular
+    variance are not angles)."""
+    return x * (180.0 / np.pi)
+
+
+def circular_std(spread):
+    """The circular standard deviation sqrt(-2 ln(1 - V)) in radians of the circular variance V that internal_coords
+    returns as the `spread` of dihedrals (V = 1: infinite)."""
+    v = np.asarray(spread, np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt(-2.0 * np.log1p(-v))
+
+
+def backbone_dihedrals(names, resids, chains=None):
+    """The backbone dihedrals of a protein from per-atom columns (gro.GroTopology's names and resids; chains: an optional
+    per-atom chain column).  Returns (phi, psi, omega, phi_res, psi_res, omega_res, pairs): the uint64 [n, 4] tuples
+    phi = C(i-1) N CA C, psi = N CA C N(i+1), omega = CA C N(i+1) CA(i+1); for each, the index of its residue i among the
+    residues in order of first appearance; and pairs [m, 2]: (row of phi, row of psi) of every residue that has both, rows
+    of psi counted from len(phi) - the pairs of internal_coords(tuples=concatenate([phi, psi]), pairs=pairs).  Neighbours are
+    consecutive residues of one chain whose resids differ by one; a residue that lacks a neighbour or an atom gets no tuple."""
+    names = [str(n).strip() for n in names]
+    resids = np.asarray(resids).astype(np.int64)
+    n = len(names)
+    assert resids.shape == (n,)
+    chains = None if chains is None else list(chains)
+    res = []                                  # (resid, chain, {name: atom})
+    for a in range(n):
+        key = (int(resids[a]), None if chains is None else chains[a])
+        if not res or (res[-1][0], res[-1][1]) != key:
+            res.append((key[0], key[1], {}))
+        res[-1][2].setdefault(names[a], a)
+
+    def linked(i, j):
+        return 0 <= i and j < len(res) and res[i][1] == res[j][1] and res[j][0] == res[i][0] + 1
+
+    def tup(*atoms):
+        return None if any(a is None for a in atoms) else atoms
+
+    phi, psi, omega, rphi, rpsi, romega, pairs = [], [], [], [], [], [], []
+    for i, (_, _, at) in enumerate(res):
+        t_phi = tup(res[i - 1][2].get("C"), at.get("N"), at.get("CA"), at.get("C")) if linked(i - 1, i) else None
+        nxt = res[i + 1][2] if linked(i, i + 1) else None
+        t_psi = tup(at.get("N"), at.get("CA"), at.get("C"), nxt.get("N")) if nxt is not None else None
+        t_om = tup(at.get("CA"), at.get("C"), nxt.get("N"), nxt.get("CA")) if nxt is not None else None
+        if t_phi is not None and t_psi is not None:
+            pairs.append((len(phi), len(psi)))
+        if t_phi is not None:
+            phi.append(t_phi); rphi.append(i)
+        if t_psi is not None:
+            psi.append(t_psi); rpsi.append(i)
+        if t_om is not None:
+            omega.append(t_om); romega.append(i)
+    t4 = lambda v: np.asarray(v, np.uint64).reshape(-1, 4)
+    pr = np.asarray(pairs, np.uint64).reshape(-1, 2)
+    pr[:, 1] += len(phi)
+    return (t4(phi), t4(psi), t4(omega), np.asarray(rphi, np.int64), np.asarray(rpsi, np.int64), np.asarray(romega, np.int64), pr)
+
+
+def _intcoord_call(lib, fn, ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, nbins, range, pairs, pair_labels, npair_groups, map_bins, want,
+                   out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (tuples, labels, boxes, pairs, pair_labels)
+    tuples = _u64(tuples); labels = _u32(labels); pairs = _u64(pairs); pair_labels = _u32(pair_labels)
+    assert tuples.ndim == 2 and tuples.shape[1] in (2, 3, 4), "tuples are [T, 2], [T, 3] or [T, 4]"
+    kind = int(tuples.shape[1]) if kind is None else int(kind)
+    assert kind == tuples.shape[1], "kind is the number of atoms per tuple"
+    T = int(tuples.shape[0])
+    box_stride = 0
+    if boxes is not None:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    else:
+        pbc = 0
+    G = 1
+    if labels is not None:
+        assert labels.shape[0] == T, "one label per tuple"
+        G = int(ngroups) if ngroups is not None else (int(labels.max()) + 1 if T else 1)
+    P, G2 = 0, 1
+    if pairs is not None:
+        assert pairs.ndim == 2 and pairs.shape[1] == 2, "pairs are [P, 2]"
+        P = int(pairs.shape[0])
+    if pair_labels is not None:
+        assert pairs is not None and pair_labels.shape[0] == P, "one label per pair"
+        G2 = int(npair_groups) if npair_groups is not None else (int(pair_labels.max()) + 1 if P else 1)
+    nbins, map_bins = int(nbins), int(map_bins)
+    names = ("values", "hist", "map", "mean", "spread", "valid")
+    if want is None:
+        want = tuple(nm for nm in names if not (nm == "hist" and nbins == 0) and not (nm == "map" and (map_bins == 0 or pairs is None)))
+    want = tuple(want)
+    shapes = ((F, T), (G, nbins), (G2, map_bins, map_bins), (T,), (T,), (T,))
+    given = tuple(out[:6]) if out is not None else (None,) * 6
+    res, ld = [], T
+    for name, shape, g in zip(names, shapes, given):
+        integer = name in ("hist", "map", "valid")
+        if name not in want:
+            res.append(None)
+        elif g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape
+            if dev:
+                import torch
+                assert g.dtype == (torch.int64 if integer else fr.dtype)
+                if name == "values" and F > 1:
+                    assert g.stride(1) == 1 and g.stride(0) >= T, "values: rows contiguous"
+                    ld = int(g.stride(0))
+                else:
+                    assert g.is_contiguous()
+            else:
+                assert g.dtype == (np.uint64 if integer else real)
+                if name == "values" and F > 1 and T > 0:
+                    e = g.dtype.itemsize
+                    assert g.strides[1] == e and g.strides[0] % e == 0 and g.strides[0] >= T * e, "values: rows contiguous"
+                    ld = g.strides[0] // e
+                else:
+                    assert g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            import torch
+            res.append(torch.zeros(shape, dtype=torch.int64 if integer else fr.dtype, device=fr.device))
+        else:
+            res.append(np.zeros(shape, np.uint64 if integer else real))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    sp = _intcoord_spec(kind, nbins, range, map_bins)
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ta, k1 = _addr(tuples); la, k2 = _addr(labels); ba, k3 = _addr(boxes); pa, k4 = _addr(pairs); pla, k5 = _addr(pair_labels)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ta, T, la, G, ba, box_stride, int(pbc), C.addressof(sp), pa, P, pla, G2,
+             addr[0], ld, addr[1], addr[2], addr[3], addr[4], addr[5]))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((tuples, labels, boxes, pairs, pair_labels), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    edges = None
+    if nbins or map_bins:
+        edges = intcoord_edges(kind, nbins if nbins else map_bins, range)
+    return InternalCoords(*res, edges)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -2273,6 +2478,12 @@ class MeasureF64:
         """Engine.msd on float64 frames, masses and boxes (molar_hip_msd_f64): float64 results."""
         return _msd_call(self.lib, self.lib.molar_hip_msd_f64, self.ctx, frames, idx, mass, boxes, pbc, groups, ref_idx, max_lag, origin_stride,
                          dims, msd, m4, per_particle, disp, out, np.float64)
+
+    def internal_coords(self, frames, tuples, kind=None, labels=None, ngroups=None, boxes=None, pbc=7, nbins=0, range=None, pairs=None,
+                        pair_labels=None, npair_groups=None, map_bins=0, want=None, out=None):
+        """Engine.internal_coords on float64 frames and boxes (molar_hip_intcoord_f64): float64 results."""
+        return _intcoord_call(self.lib, self.lib.molar_hip_intcoord_f64, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, nbins, range,
+                              pairs, pair_labels, npair_groups, map_bins, want, out, np.float64)
 
     def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
                 centre_weight=None, want=None, out=None):

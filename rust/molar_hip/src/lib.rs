@@ -1087,6 +1087,86 @@ impl Engine {
         Ok((ws, fc, ac, lc))
     }
 
+    /// Distances, angles or dihedrals (radians) of `tuples` (`spec.kind` atom indices each) in every frame of a block through
+    /// molar_hip_intcoord (the definition: molar_hip.h): the series, the histograms per group of `labels` ((one label per tuple,
+    /// ngroups); None: one group), the joint histogram of the two tuples of every pair of `pairs` ((pairs, their labels and
+    /// groups or None): the Ramachandran map), and the mean, the spread (dihedrals: the circular variance) and the valid frames
+    /// per tuple.  `boxes`: one column-major box of 9 numbers or 9 per frame, every bond vector then takes its minimum image on
+    /// the dimensions of `pbc`; None: no image is removed.  Only integer atomics are used: the same call gives the same bits.
+    #[allow(clippy::too_many_arguments)]
+    pub fn internal_coords(
+        &self, frames: &[[f32; 3]], natoms: usize, tuples: &[usize], labels: Option<(&[u32], usize)>, boxes: Option<&[f32]>, pbc: u8,
+        spec: &MolarHipIntcoordSpec, pairs: Option<(&[[usize; 2]], Option<(&[u32], usize)>)>,
+    ) -> Result<InternalCoords, EngineError> {
+        let kind = spec.kind as usize;
+        if !(2..=4).contains(&kind) || tuples.len() % kind != 0 {
+            return Err(EngineError::Sizes(format!("internal_coords: {} indices are not tuples of {kind} atoms", tuples.len())));
+        }
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("internal_coords: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        check_index(Some(tuples), natoms, "internal_coords")?;
+        let nframes = frames.len() / natoms;
+        let ntuples = tuples.len() / kind;
+        let box_stride = match boxes {
+            None => 0,
+            Some(b) if b.len() == 9 => 0,
+            Some(b) if b.len() == 9 * nframes => 9,
+            Some(b) => return Err(EngineError::Sizes(format!("internal_coords: {} box numbers for {nframes} frames", b.len()))),
+        };
+        let (lp, ngroups) = match labels {
+            Some((l, _)) if l.len() != ntuples => return Err(EngineError::Sizes(format!("internal_coords: {} labels for {ntuples} tuples", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        let want_map = spec.map_bins != 0 && pairs.is_some();
+        let (pp, npairs, plp, npair_groups) = match pairs {
+            Some((p, Some((l, _)))) if l.len() != p.len() => return Err(EngineError::Sizes(format!("internal_coords: {} labels for {} pairs", l.len(), p.len()))),
+            Some((p, Some((l, g)))) if want_map => (p.as_ptr() as *const u64, p.len(), l.as_ptr(), g),
+            Some((p, None)) if want_map => (p.as_ptr() as *const u64, p.len(), std::ptr::null(), 1),
+            _ => (std::ptr::null(), 0, std::ptr::null(), 1),
+        };
+        let (nbins, mb) = (spec.nbins as usize, spec.map_bins as usize);
+        let mut out = InternalCoords {
+            values: vec![0f32; nframes * ntuples],
+            hist: vec![0u64; ngroups * nbins],
+            map: vec![0u64; if want_map { npair_groups * mb * mb } else { 0 }],
+            mean: vec![0f32; ntuples],
+            spread: vec![0f32; ntuples],
+            valid: vec![0u64; ntuples],
+            nframes,
+            ntuples,
+            ngroups,
+            npair_groups,
+        };
+        if nframes == 0 || ntuples == 0 {
+            return Ok(out);
+        }
+        let bp = boxes.map_or(std::ptr::null(), |b| b.as_ptr());
+        let hp = if nbins != 0 { out.hist.as_mut_ptr() } else { std::ptr::null_mut() };
+        let mp = if want_map { out.map.as_mut_ptr() } else { std::ptr::null_mut() };
+        self.plugin.check(unsafe {
+            (self.plugin.fns.intcoord)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, tuples.as_ptr() as *const u64, ntuples, lp, ngroups, bp,
+                                       box_stride, if boxes.is_some() { pbc } else { 0 }, spec as *const MolarHipIntcoordSpec, pp, npairs, plp, npair_groups,
+                                       out.values.as_mut_ptr(), ntuples, hp, mp, out.mean.as_mut_ptr(), out.spread.as_mut_ptr(), out.valid.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes, the frames and the tuples (or pairs) a workgroup takes and the largest groups * bins the
+    /// on-chip histogram takes, for an `internal_coords` call of these sizes (molar_hip_intcoord_plan, a host function).
+    #[allow(clippy::too_many_arguments)]
+    pub fn internal_coords_plan(
+        &self, nframes: usize, ntuples: usize, ngroups: usize, npairs: usize, npair_groups: usize, spec: &MolarHipIntcoordSpec, want_stats: bool,
+    ) -> Result<(usize, u32, u32, u32), EngineError> {
+        let (mut ws, mut fc, mut tc, mut lc) = (0usize, 0u32, 0u32, 0u32);
+        self.plugin.check(unsafe {
+            (self.plugin.fns.intcoord_plan)(nframes, ntuples, ngroups, npairs, npair_groups, spec as *const MolarHipIntcoordSpec, want_stats as i32, &mut ws, &mut fc,
+                                            &mut tc, &mut lc)
+        })?;
+        Ok((ws, fc, tc, lc))
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
@@ -1209,6 +1289,23 @@ pub struct Density {
     pub weight_scale_log2: i32,
     pub ngroups: usize,
     pub nbins: usize,
+}
+
+/// What `Engine::internal_coords` returns: the series [frame][tuple] (NaN where invalid), the histogram [group][bin] (empty
+/// without bins), the map [pair group][bin of the first][bin of the second] (empty without map bins or pairs), and per tuple the
+/// mean, the spread and the frames that entered.
+#[derive(Debug, Clone, Default)]
+pub struct InternalCoords {
+    pub values: Vec<f32>,
+    pub hist: Vec<u64>,
+    pub map: Vec<u64>,
+    pub mean: Vec<f32>,
+    pub spread: Vec<f32>,
+    pub valid: Vec<u64>,
+    pub nframes: usize,
+    pub ntuples: usize,
+    pub ngroups: usize,
+    pub npair_groups: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless

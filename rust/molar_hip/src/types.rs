@@ -93,6 +93,24 @@ pub struct MolarHipDensityGrid {
 pub const DENSITY_BOX: u32 = 0;
 pub const DENSITY_LAB: u32 = 1;
 
+/// `molar_hip_intcoord_spec`: what the internal-coordinate calls compute - `kind` (the atoms per tuple: 2 distance, 3 angle,
+/// 4 dihedral), the bins of the histogram and of the map per side (0: none), and the half-open range of a distance histogram.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct MolarHipIntcoordSpec {
+    pub kind: u32,
+    pub nbins: u32,
+    pub map_bins: u32,
+    pub reserved: u32,
+    pub lo: f64,
+    pub hi: f64,
+}
+
+/// `MolarHipIntcoordSpec::kind`
+pub const IC_DISTANCE: u32 = 2;
+pub const IC_ANGLE: u32 = 3;
+pub const IC_DIHEDRAL: u32 = 4;
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
