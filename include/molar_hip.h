@@ -982,6 +982,85 @@ int molar_hip_intcoord_f64(molar_hip_ctx *ctx, const double *frames, size_t nfra
                            double *values, size_t ld, uint64_t *hist, uint64_t *map, double *mean, double *spread,
                            uint64_t *valid);
 
+/* ---- Time correlation functions of vectors over a block of trajectory frames: the reorientation of bond vectors, dipoles
+ * and plane normals (gmx rotacf -P 1 / -P 2), N-H order parameters, the velocity autocorrelation (gmx velacc), the
+ * autocorrelation of a dihedral as the vector (cos phi, sin phi, 0) - over all time origins, per vector and per group of
+ * vectors.  The frame block, boxes, box_stride and pbc are those of molar_hip_msd; max_lag and origin_stride work as there.
+ * Operation by operation (Real = float, or double for _f64; everything is formed in double from the exact inputs and
+ * rounded to Real at the end; F = nframes, V = nvectors, L = max_lag, os = origin_stride, one kind per call):
+ *   tuples[V][kind]: atom indices into a frame.  The vector w of tuple v in frame f:
+ *     kind 1 (A):      w = p[A]: the block holds any per-atom 3-vectors (velocities, dipoles, (cos phi, sin phi, 0));
+ *                      boxes and pbc are not read.
+ *     kind 2 (A,B):    w = sv(p[B] - p[A]), sv = shortest_vector of that frame's f64 PeriodicBox on the dimensions of pbc
+ *                      when pbc != 0 (else the difference as it is): a molecule cut by the cell boundary needs no unwrap.
+ *     kind 3 (A,B,C):  w = sv(p[B] - p[A]) x sv(p[C] - p[A]), the plane normal; the cross product without fused operations.
+ *     The components outside spec.dims (bits x, y, z) are then set to 0.
+ *     mode UNIT: u = w / sqrt((wx wx + wy wy) + wz wz), every component divided;  mode RAW: u = w.
+ *   bad frames: a frame is bad for v when a component of w (after the mask) is not finite, or, in UNIT mode, when
+ *     (wx wx + wy wy) + wz wz is exactly 0.  A vector with at least one bad frame is left out of every sum: its rows of
+ *     c1_vec and c2_vec, its mean and its s2 are NaN; bad_frames[v] (uint32) = its bad frames; the status stays
+ *     MOLAR_HIP_OK.  So the number of terms of a lag is n(tau) = (F - 1 - tau) / os + 1 (integer division) for every valid
+ *     vector, and the results of the other vectors are bit for bit what they would be without it.
+ *   per pair of frames d = fma(uz(t), uz(t + tau), fma(uy(t), uy(t + tau), ux(t) ux(t + tau)));
+ *     S1_v[tau] = sum_t d,  S2_v[tau] = sum_t fma(d, d, .),  t = 0, os, 2 os, ... while t + tau <= F - 1, in that order.
+ *   c1_vec[V][ld], c2_vec[V][ld], ld >= L + 1 (the rest of a row is not touched):
+ *     c1_vec = S1_v / n(tau),  c2_vec = 1.5 (S2_v / n(tau)) - 0.5.
+ *   c1[G][L + 1], c2[G][L + 1]: per group labels[v] < ngroups (labels == NULL: one group, G = 1, ngroups is not read) the
+ *     S_v of the group's valid vectors added in index order within chunks of vec_chunk vectors (a run of one label within
+ *     a chunk is added up first), the chunks in chunk order;  c1 = S1 / (N_g n(tau)),  c2 = 1.5 (S2 / (N_g n(tau))) - 0.5;
+ *     N_g = nvalid[g] (uint64), the valid vectors of the group; N_g = 0: a NaN row.
+ *   c2 is the Legendre polynomial P2 of the cosine between u(t) and u(t + tau) WHATEVER dims is: with a mask the masked
+ *     (projected) vector is normalised and P2(x) = (3 x^2 - 1) / 2 is applied to its cosine, not a two-dimensional analogue.
+ *   mean[V][3] = sum_f u(f) / F;  s2[V] = 1.5 q - 0.5,  q = ((xx^2 + yy^2) + zz^2) + 2 ((xy^2 + xz^2) + yz^2) of the second
+ *     moments ab = sum_f u_a(f) u_b(f) / F: the long-time limit of c2, the generalised order parameter S^2 of Lipari and
+ *     Szabo.  The sums run in frame order within chunks of frame_chunk frames, the chunks in chunk order.
+ *   c2, c2_vec and s2 are defined in UNIT mode only.
+ *   No floating-point atomics are used and every sum has an order fixed by the sizes alone: the same call gives the same
+ *   bits.
+ * frames, tuples, labels, boxes and every output may each be host or device memory, and every output may be NULL; the lag
+ * stage does not run when none of c1, c2, c1_vec, c2_vec is asked for, and d^2 is not formed when neither c2 nor c2_vec is.
+ * Device outputs are written on the context's stream and not waited for; the call waits once, for the 64 bytes of its
+ * status (and once more for results that go to host memory).
+ * Errors: nvectors == 0, labels with ngroups == 0, ld < max_lag + 1 with c1_vec or c2_vec: ERR_SIZES; a spec that is NULL, a
+ * kind other than 1, 2, 3, a mode other than the two, dims == 0 or > 7, reserved != 0, pbc > 7, a box_stride other than 0
+ * and 9, max_lag >= nframes (with nframes >= 1), origin_stride == 0, c2, c2_vec or s2 in RAW mode, tuples == NULL,
+ * natoms == 0, a stride below 3 natoms (with more than one frame), a tuple index not below natoms, a label not below
+ * ngroups: ERR_INVALID_ARGUMENT; pbc != 0 with boxes == NULL for kinds 2 and 3: ERR_NO_PBC; a box with a vector of zero
+ * length: ERR_ZERO_LENGTH_VECTOR, one without an inverse: ERR_INVERSE_FAILED; 2^31 vectors, groups, frames or workgroups, or
+ * a workspace that cannot be allocated (its bytes are in molar_hip_last_error()): ERR_TOO_LARGE.  The errors of the
+ * arguments alone are reported before the context is used; tuples and labels in device memory are judged on the device
+ * before any kernel uses one as an address (the vector stage reads atom 0 for a bad index and writes the workspace only),
+ * and no output is touched after an error.  nframes == 0 is a successful no-op.
+ * molar_hip_tcf_plan is a pure host function: the bytes of device workspace such a call allocates (the status, the boxes,
+ * 76 bytes per vector and chunk of frame_chunk frames; with want_lags - any of c1, c2, c1_vec, c2_vec - the f64 vectors
+ * U[V][F][3]; with want_groups - c1 or c2 - 16 bytes per chunk of vectors, group and lag; kept by the context, grows only;
+ * staging of host-memory arguments and results not included; never smaller for a larger argument), and the launch shape:
+ * frame_chunk, the frames a lane of the vector stage walks; vec_chunk, the vectors a workgroup of the lag stage adds up;
+ * lag_block = 64 lags_per_lane, the lags of a workgroup; lags_per_lane (R: a lane owns R consecutive lags and takes R
+ * origins at a time when origin_stride == 1; the lags behind the last whole block go to one block of the narrowest lane
+ * of 1, 2 or 4 lags that holds them; the environment variable MOLAR_HIP_TCF_R = 1, 2 or 4 overrides R for A/B runs);
+ * segment, the origins staged at a time, and window = segment + lag_block, the frames they reach. */
+enum { MOLAR_HIP_TCF_UNIT = 0, MOLAR_HIP_TCF_RAW = 1 };
+typedef struct {
+    uint32_t kind;
+    uint32_t mode;
+    uint32_t dims;
+    uint32_t reserved;
+} molar_hip_tcf_spec;
+int molar_hip_tcf_plan(size_t nframes, size_t nvectors, size_t ngroups, size_t max_lag, int per_frame_boxes, int want_lags,
+                       int want_groups, size_t *workspace_bytes, uint32_t *frame_chunk, uint32_t *vec_chunk,
+                       uint32_t *lag_block, uint32_t *lags_per_lane, uint32_t *segment, uint32_t *window);
+int molar_hip_tcf(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                  const uint64_t *tuples, size_t nvectors, const uint32_t *labels, size_t ngroups, const float *boxes,
+                  size_t box_stride, uint8_t pbc, const molar_hip_tcf_spec *spec, size_t max_lag, size_t origin_stride,
+                  float *c1, float *c2, float *c1_vec, float *c2_vec, size_t ld, uint64_t *nvalid, float *mean, float *s2,
+                  uint32_t *bad_frames);
+int molar_hip_tcf_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *tuples, size_t nvectors, const uint32_t *labels, size_t ngroups, const double *boxes,
+                      size_t box_stride, uint8_t pbc, const molar_hip_tcf_spec *spec, size_t max_lag, size_t origin_stride,
+                      double *c1, double *c2, double *c1_vec, double *c2_vec, size_t ld, uint64_t *nvalid, double *mean,
+                      double *s2, uint32_t *bad_frames);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -767,6 +767,87 @@ inline InternalCoordsOf<double> internal_coords_f64(Engine &eng, const double *f
                                         pair_labels);
 }
 
+// Time correlation functions of vectors (molar_hip_tcf*; the definition: molar_hip.h): for every tuple of `tuples` ([V][kind];
+// kind 1: the atom's own 3-vector, 2: the bond vector, 3: the plane normal) the first and second Legendre polynomial of
+// u(t) . u(t + tau) over all time origins, per group of `labels` and (want_per_vector) per vector, with the mean vector, the
+// order parameter S^2 and the bad frames of every vector.  A vector with a bad frame is left out of every sum and NaN in its
+// own rows.
+struct VectorCorrelationsOptions {
+    uint8_t pbc = MOLAR_HIP_PBC_FULL; // read with boxes (kinds 2 and 3): every bond vector takes its minimum image
+    bool per_frame_boxes = false;
+    uint32_t mode = MOLAR_HIP_TCF_UNIT; // MOLAR_HIP_TCF_RAW: the vectors as they are; no c2, c2_vec, s2
+    uint32_t dims = 7;                // the bits x, y, z of the components that enter
+    size_t max_lag = (size_t)-1;      // (size_t)-1: nframes - 1
+    size_t origin_stride = 1;
+    size_t ngroups = 1;               // read with labels
+    bool want_groups = true;          // c1, c2 and nvalid
+    bool want_per_vector = false;     // c1_vec, c2_vec
+    bool want_stats = true;           // mean, s2 and bad_frames
+};
+template <class Real>
+struct VectorCorrelationsOf {
+    std::vector<Real> c1, c2;         // [G][L + 1]; c2 empty in RAW mode
+    std::vector<Real> c1_vec, c2_vec; // [V][L + 1]
+    std::vector<uint64_t> nvalid;     // [G]
+    std::vector<Real> mean;           // [V][3]
+    std::vector<Real> s2;             // [V]; empty in RAW mode
+    std::vector<uint32_t> bad_frames; // [V]
+    size_t nframes = 0, nvectors = 0, ngroups = 0, nlags = 0;
+};
+using VectorCorrelations = VectorCorrelationsOf<Float>;
+template <class Real, class Fn>
+inline VectorCorrelationsOf<Real> vector_correlations_call(Fn fn, const char *who, Engine &eng, const Real *frames, size_t nframes, size_t natoms,
+                                                           const std::vector<usize> &tuples, uint32_t kind, const Real *boxes,
+                                                           const VectorCorrelationsOptions &opt, const std::vector<uint32_t> &labels) {
+    if (kind < 1 || kind > 3 || tuples.size() % kind) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": the tuples are not a whole number of tuples of `kind` atoms");
+    const size_t V = tuples.size() / kind;
+    if (!labels.empty() && labels.size() != V) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per vector");
+    VectorCorrelationsOf<Real> out;
+    out.nframes = nframes;
+    out.nvectors = V;
+    out.ngroups = labels.empty() ? 1 : opt.ngroups;
+    if (nframes == 0) return out;
+    const size_t L = opt.max_lag == (size_t)-1 ? nframes - 1 : opt.max_lag, G = out.ngroups;
+    out.nlags = L + 1;
+    const bool unit = opt.mode == MOLAR_HIP_TCF_UNIT;
+    if (opt.want_groups) {
+        out.c1.resize(G * (L + 1));
+        if (unit) out.c2.resize(G * (L + 1));
+        out.nvalid.resize(G);
+    }
+    if (opt.want_per_vector) {
+        out.c1_vec.resize(V * (L + 1));
+        if (unit) out.c2_vec.resize(V * (L + 1));
+    }
+    if (opt.want_stats) {
+        out.mean.resize(V * 3);
+        if (unit) out.s2.resize(V);
+        out.bad_frames.resize(V);
+    }
+    molar_hip_tcf_spec spec{};
+    spec.kind = kind;
+    spec.mode = opt.mode;
+    spec.dims = opt.dims;
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    const bool use_box = boxes && kind >= 2;
+    check(fn(eng.ctx(), frames, nframes, natoms * 3, natoms, tuples.data(), V, labels.empty() ? nullptr : labels.data(), opt.ngroups, use_box ? boxes : nullptr,
+             opt.per_frame_boxes ? 9 : 0, use_box ? opt.pbc : (uint8_t)0, &spec, L, opt.origin_stride, ptr(out.c1), ptr(out.c2), ptr(out.c1_vec), ptr(out.c2_vec),
+             L + 1, ptr(out.nvalid), ptr(out.mean), ptr(out.s2), ptr(out.bad_frames)));
+    return out;
+}
+inline VectorCorrelations vector_correlations(Engine &eng, const Float *frames, size_t nframes, size_t natoms, const std::vector<usize> &tuples, uint32_t kind,
+                                              const Float *boxes = nullptr, const VectorCorrelationsOptions &opt = VectorCorrelationsOptions(),
+                                              const std::vector<uint32_t> &labels = {}) {
+    return vector_correlations_call<Float>(molar_hip_tcf, "vector_correlations", eng, frames, nframes, natoms, tuples, kind, boxes, opt, labels);
+}
+// the same on f64 frames and boxes (MolAR's f64 feature): molar_hip_tcf_f64
+inline VectorCorrelationsOf<double> vector_correlations_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const std::vector<usize> &tuples,
+                                                            uint32_t kind, const double *boxes = nullptr,
+                                                            const VectorCorrelationsOptions &opt = VectorCorrelationsOptions(),
+                                                            const std::vector<uint32_t> &labels = {}) {
+    return vector_correlations_call<double>(molar_hip_tcf_f64, "vector_correlations_f64", eng, frames, nframes, natoms, tuples, kind, boxes, opt, labels);
+}
+
 // Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
 // donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
 // images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's

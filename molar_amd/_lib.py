@@ -58,6 +58,12 @@ class IntcoordSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("nbins", C.c_uint32), ("map_bins", C.c_uint32), ("reserved", C.c_uint32), ("lo", C.c_double), ("hi", C.c_double)]
 
 
+class TcfSpec(C.Structure):
+    """molar_hip_tcf_spec: the kind (atoms per tuple: 1 the atom's own 3-vector, 2 the bond, 3 the plane normal), the mode
+    (0 unit vectors, 1 the vectors as they are) and the component mask dims (bits x, y, z)."""
+    _fields_ = [("kind", C.c_uint32), ("mode", C.c_uint32), ("dims", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -223,6 +229,9 @@ SYMBOLS = {
     "molar_hip_intcoord_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _P, _I, _P, _P, _P, _P]),
     "molar_hip_intcoord": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_intcoord_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_tcf_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_tcf": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _SZ, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    "molar_hip_tcf_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _SZ, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

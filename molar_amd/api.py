@@ -1446,6 +1446,25 @@ class Engine:
         return _intcoord_call(self.lib, self.lib.molar_hip_intcoord, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, nbins, range, pairs,
                               pair_labels, npair_groups, map_bins, want, out, np.float32)
 
+    def vector_correlations(self, frames, tuples, kind=None, labels=None, ngroups=None, boxes=None, pbc=7, mode="unit", dims=7, max_lag=None,
+                            origin_stride=1, want=None, out=None):
+        """Time correlation functions over all time origins of the vectors of `tuples` [V, 1 | 2 | 3] (atom indices; kind: from
+        tuples.shape[1]; a 1-D array is kind 1) in frames [F, natoms, 3] float32 (molar_hip_tcf, the definition:
+        molar_hip.h), all arithmetic in double.  Kind 1: the atom's own 3-vector (a block of velocities, dipoles or
+        angle_vectors); kind 2: the bond vector B - A; kind 3: the plane normal (B - A) x (C - A); bonds take the minimum image
+        under `boxes` ([9] column-major, [3, 3] rows or [F, 9]; None: no image is removed) on the dimensions of `pbc`.
+        mode "unit": unit vectors, "raw": the vectors as they are (c2, c2_vec and s2 are defined for "unit" only); `dims`: the
+        bits x, y, z of the components that enter.  Lags 0 .. max_lag (None: F - 1), origins 0, origin_stride, ...  Returns
+        VectorCorrelations(c1 [G, L + 1], c2 [G, L + 1] per group of `labels` (one per vector), c1_vec [V, L + 1],
+        c2_vec [V, L + 1], nvalid [G], mean [V, 3], s2 [V], bad_frames [V], lags: n(tau)); a vector with a bad frame (a
+        component that is not finite, zero length in "unit" mode) is left out of every sum and is NaN in its own rows.
+        `want`: the names to compute (default: c1, c2, nvalid, mean, s2, bad_frames - those the mode allows); numpy in
+        gives numpy out, torch CUDA in gives torch CUDA out (nvalid as int64, bad_frames as int32), written on the ENGINE's
+        stream and not waited for.  `out`: an optional VectorCorrelations (or 8-tuple) of destinations; c1_vec and c2_vec may
+        share a row stride above L + 1.  The same call gives the same bits."""
+        return _tcf_call(self.lib, self.lib.molar_hip_tcf, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, mode, dims, max_lag,
+                         origin_stride, want, out, np.float32)
+
     def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
                 centre_weight=None, want=None, out=None):
         """Density profiles and maps of frames [F, natoms, 3] float32 over `grid` (profile_grid, map_grid, volume_grid;
@@ -2281,6 +2300,156 @@ def _intcoord_call(lib, fn, ctx, frames, tuples, kind, labels, ngroups, boxes, p
     return InternalCoords(*res, edges)
 
 
+VectorCorrelations = collections.namedtuple("VectorCorrelations", ["c1", "c2", "c1_vec", "c2_vec", "nvalid", "mean", "s2", "bad_frames", "lags"])
+TCF_UNIT, TCF_RAW = 0, 1
+
+
+def _tcf_spec(kind, mode, dims):
+    sp = _lib.TcfSpec()
+    sp.kind = int(kind)
+    sp.mode = {"unit": TCF_UNIT, "raw": TCF_RAW}.get(mode, mode)
+    sp.dims = int(dims)
+    sp.reserved = 0
+    return sp
+
+
+def tcf_plan(nframes, nvectors, ngroups=1, max_lag=None, per_frame_boxes=False, want_lags=True, want_groups=True):
+    """(workspace_bytes, frame_chunk, vec_chunk, lag_block, lags_per_lane, segment, window) of a vector_correlations call of
+    these sizes (molar_hip_tcf_plan): the device workspace and the launch shape - the frames a lane of the vector stage walks,
+    the vectors and the lags a workgroup of the lag kernel owns, the lags of one lane, the origins staged at a time and the
+    frames they reach.  max_lag=None: nframes - 1; want_lags=False: only mean / s2 / bad_frames / nvalid are asked for;
+    want_groups=False: no group curve (c1, c2).  A host function: no GPU is needed."""
+    L = max(int(nframes) - 1, 0) if max_lag is None else int(max_lag)
+    ws = C.c_size_t(0)
+    u = [C.c_uint32(0) for _ in range(6)]
+    check(_lib.load().molar_hip_tcf_plan(int(nframes), int(nvectors), int(ngroups), L, 1 if per_frame_boxes else 0, 1 if want_lags else 0,
+                                         1 if want_groups else 0, C.addressof(ws), *(C.addressof(x) for x in u)))
+    return (int(ws.value),) + tuple(int(x.value) for x in u)
+
+
+def tcf_lags(nframes, max_lag=None, origin_stride=1):
+    """n(tau) = (F - 1 - tau) // origin_stride + 1 for tau = 0 .. max_lag (None: F - 1), int64: the time origins that enter
+    every lag of a vector_correlations (or msd) call."""
+    F = int(nframes)
+    L = F - 1 if max_lag is None else int(max_lag)
+    assert 0 <= L < F and int(origin_stride) >= 1
+    return (F - 1 - np.arange(L + 1, dtype=np.int64)) // min(int(origin_stride), F) + 1
+
+
+def correlation_time(curve, dt):
+    """The integral of a correlation curve over tau * dt by the trapezoid rule, from lag 0 up to its first zero crossing (the
+    crossing itself interpolated linearly) or, without one, to its end; float64.  A curve that starts at or below 0: 0."""
+    y = np.asarray(curve, np.float64)
+    assert y.ndim == 1 and y.shape[0] >= 1
+    below = np.nonzero(y <= 0.0)[0]
+    if below.size == 0:
+        return float(dt) * float(((y[1:] + y[:-1]) * 0.5).sum())
+    k = int(below[0])
+    if k == 0:
+        return 0.0
+    whole = float(((y[1:k] + y[:k - 1]) * 0.5).sum())
+    frac = y[k - 1] / (y[k - 1] - y[k])                  # where the line from lag k - 1 to lag k meets zero
+    return float(dt) * (whole + 0.5 * float(y[k - 1]) * float(frac))
+
+
+def angle_vectors(values):
+    """An angle series [F, T] (the `values` of internal_coords for dihedrals, radians; numpy or torch) as the block
+    [F, T, 3] of (cos, sin, 0): vector_correlations(block, arange(T), mode="raw") then gives <cos(phi(t + tau) - phi(t))>, the
+    dihedral autocorrelation.  A NaN angle gives a bad frame of its vector."""
+    if _is_torch(values):
+        import torch
+        return torch.stack([torch.cos(values), torch.sin(values), torch.zeros_like(values)], dim=-1).contiguous()
+    v = np.asarray(values)
+    return np.ascontiguousarray(np.stack([np.cos(v), np.sin(v), np.zeros_like(v)], axis=-1))
+
+
+def _tcf_call(lib, fn, ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, mode, dims, max_lag, origin_stride, want, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (tuples, labels, boxes)
+    tuples = _u64(tuples); labels = _u32(labels)
+    if tuples.ndim == 1:
+        tuples = tuples.reshape(-1, 1)
+    assert tuples.ndim == 2 and tuples.shape[1] in (1, 2, 3), "tuples are [V], [V, 1], [V, 2] or [V, 3]"
+    kind = int(tuples.shape[1]) if kind is None else int(kind)
+    assert kind == tuples.shape[1], "kind is the number of atoms per tuple"
+    V = int(tuples.shape[0])
+    box_stride = 0
+    if boxes is not None and kind >= 2:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    else:
+        boxes, pbc = None, 0
+    G = 1
+    if labels is not None:
+        assert labels.shape[0] == V, "one label per vector"
+        G = int(ngroups) if ngroups is not None else (int(labels.max()) + 1 if V else 1)
+    L = max(F - 1, 0) if max_lag is None else int(max_lag)
+    sp = _tcf_spec(kind, mode, dims)
+    names = ("c1", "c2", "c1_vec", "c2_vec", "nvalid", "mean", "s2", "bad_frames")
+    if want is None:
+        want = tuple(nm for nm in ("c1", "c2", "nvalid", "mean", "s2", "bad_frames") if sp.mode == TCF_UNIT or nm not in ("c2", "s2"))
+    want = tuple(want)
+    assert all(nm in names for nm in want), "want holds names of VectorCorrelations"
+    shapes = ((G, L + 1), (G, L + 1), (V, L + 1), (V, L + 1), (G,), (V, 3), (V,), (V,))
+    given = tuple(out[:8]) if out is not None else (None,) * 8
+    res, ld = [], L + 1
+    for name, shape, g in zip(names, shapes, given):
+        if name not in want:
+            res.append(None)
+            continue
+        if dev:
+            import torch
+            dt = torch.int64 if name == "nvalid" else torch.int32 if name == "bad_frames" else fr.dtype
+        else:
+            dt = np.uint64 if name == "nvalid" else np.uint32 if name == "bad_frames" else real
+        if g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape and g.dtype == dt
+            if name in ("c1_vec", "c2_vec") and V > 1:
+                if dev:
+                    assert g.stride(1) == 1 and g.stride(0) >= L + 1, f"{name}: rows contiguous"
+                    row = int(g.stride(0))
+                else:
+                    e = g.dtype.itemsize
+                    assert g.strides[1] == e and g.strides[0] % e == 0 and g.strides[0] >= (L + 1) * e, f"{name}: rows contiguous"
+                    row = g.strides[0] // e
+                assert ld in (L + 1, row) or row == L + 1, "c1_vec and c2_vec share one row stride"
+                ld = max(ld, row)
+            else:
+                assert g.is_contiguous() if dev else g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            res.append(torch.zeros(shape, dtype=dt, device=fr.device))
+        else:
+            res.append(np.zeros(shape, dt))
+    if ld != L + 1:
+        for name, r in zip(names, res):
+            if name in ("c1_vec", "c2_vec") and r is not None and V > 1:
+                row = int(r.stride(0)) if dev else r.strides[0] // r.dtype.itemsize
+                assert row == ld, "c1_vec and c2_vec share one row stride"
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ta, k1 = _addr(tuples); la, k2 = _addr(labels); ba, k3 = _addr(boxes)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ta, V, la, G, ba, box_stride, int(pbc), C.addressof(sp), L, int(origin_stride),
+             addr[0], addr[1], addr[2], addr[3], ld, addr[4], addr[5], addr[6], addr[7]))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((tuples, labels, boxes), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    lags = tcf_lags(F, L, origin_stride) if F > 0 and int(origin_stride) >= 1 and L < F else None
+    return VectorCorrelations(*res, lags)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -2484,6 +2653,12 @@ class MeasureF64:
         """Engine.internal_coords on float64 frames and boxes (molar_hip_intcoord_f64): float64 results."""
         return _intcoord_call(self.lib, self.lib.molar_hip_intcoord_f64, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, nbins, range,
                               pairs, pair_labels, npair_groups, map_bins, want, out, np.float64)
+
+    def vector_correlations(self, frames, tuples, kind=None, labels=None, ngroups=None, boxes=None, pbc=7, mode="unit", dims=7, max_lag=None,
+                            origin_stride=1, want=None, out=None):
+        """Engine.vector_correlations on float64 frames and boxes (molar_hip_tcf_f64): float64 results."""
+        return _tcf_call(self.lib, self.lib.molar_hip_tcf_f64, self.ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, mode, dims, max_lag,
+                         origin_stride, want, out, np.float64)
 
     def density(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, pbc=7, centre_idx=None,
                 centre_weight=None, want=None, out=None):

@@ -1167,6 +1167,89 @@ impl Engine {
         Ok((ws, fc, tc, lc))
     }
 
+    /// Time correlation functions of the vectors of `tuples` (`spec.kind` atom indices each: 1 the atom's own 3-vector, 2 the
+    /// bond vector, 3 the plane normal) over all time origins of a block of frames through molar_hip_tcf (the definition:
+    /// molar_hip.h): c1 and c2 (the first and second Legendre polynomial of u(t) . u(t + tau)) per group of `labels` ((one label
+    /// per vector, ngroups); None: one group) for the lags 0 ..= `max_lag` and the origins 0, `origin_stride`, ..., per vector
+    /// as well with `per_vector`, and the mean vector, the order parameter S^2 and the bad frames of every vector.  `boxes`:
+    /// one column-major box of 9 numbers or 9 per frame, every bond vector then takes its minimum image on the dimensions of
+    /// `pbc`; None: no image is removed.  In RAW mode c2, c2_vec and s2 stay empty.  No floating-point atomics are used: the
+    /// same call gives the same bits.
+    #[allow(clippy::too_many_arguments)]
+    pub fn vector_correlations(
+        &self, frames: &[[f32; 3]], natoms: usize, tuples: &[usize], labels: Option<(&[u32], usize)>, boxes: Option<&[f32]>, pbc: u8,
+        spec: &MolarHipTcfSpec, max_lag: usize, origin_stride: usize, per_vector: bool,
+    ) -> Result<VectorCorrelations, EngineError> {
+        let kind = spec.kind as usize;
+        if !(1..=3).contains(&kind) || tuples.len() % kind != 0 {
+            return Err(EngineError::Sizes(format!("vector_correlations: {} indices are not tuples of {kind} atoms", tuples.len())));
+        }
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("vector_correlations: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        check_index(Some(tuples), natoms, "vector_correlations")?;
+        let nframes = frames.len() / natoms;
+        let nvectors = tuples.len() / kind;
+        let use_box = boxes.is_some() && kind >= 2;
+        let box_stride = match boxes {
+            None => 0,
+            Some(b) if b.len() == 9 => 0,
+            Some(b) if b.len() == 9 * nframes => 9,
+            Some(b) => return Err(EngineError::Sizes(format!("vector_correlations: {} box numbers for {nframes} frames", b.len()))),
+        };
+        let (lp, ngroups) = match labels {
+            Some((l, _)) if l.len() != nvectors => return Err(EngineError::Sizes(format!("vector_correlations: {} labels for {nvectors} vectors", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        let unit = spec.mode == TCF_UNIT;
+        let nlags = max_lag + 1;
+        let mut out = VectorCorrelations {
+            c1: vec![0f32; ngroups * nlags],
+            c2: vec![0f32; if unit { ngroups * nlags } else { 0 }],
+            c1_vec: vec![0f32; if per_vector { nvectors * nlags } else { 0 }],
+            c2_vec: vec![0f32; if per_vector && unit { nvectors * nlags } else { 0 }],
+            nvalid: vec![0u64; ngroups],
+            mean: vec![0f32; nvectors * 3],
+            s2: vec![0f32; if unit { nvectors } else { 0 }],
+            bad_frames: vec![0u32; nvectors],
+            nframes,
+            nvectors,
+            ngroups,
+            nlags,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        fn ptr<T>(v: &mut Vec<T>) -> *mut T {
+            if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() }
+        }
+        let bp = if use_box { boxes.map_or(std::ptr::null(), |b| b.as_ptr()) } else { std::ptr::null() };
+        self.plugin.check(unsafe {
+            (self.plugin.fns.tcf)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, tuples.as_ptr() as *const u64, nvectors, lp, ngroups, bp,
+                                  box_stride, if use_box { pbc } else { 0 }, spec as *const MolarHipTcfSpec, max_lag, origin_stride, ptr(&mut out.c1),
+                                  ptr(&mut out.c2), ptr(&mut out.c1_vec), ptr(&mut out.c2_vec), nlags, ptr(&mut out.nvalid), ptr(&mut out.mean),
+                                  ptr(&mut out.s2), ptr(&mut out.bad_frames))
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and the launch shape (frame_chunk, vec_chunk, lag_block, lags_per_lane, segment, window) of a
+    /// `vector_correlations` call of these sizes (molar_hip_tcf_plan, a host function).
+    #[allow(clippy::too_many_arguments)]
+    pub fn vector_correlations_plan(
+        &self, nframes: usize, nvectors: usize, ngroups: usize, max_lag: usize, per_frame_boxes: bool, want_lags: bool, want_groups: bool,
+    ) -> Result<(usize, [u32; 6]), EngineError> {
+        let mut ws = 0usize;
+        let mut s = [0u32; 6];
+        let p = s.as_mut_ptr();
+        self.plugin.check(unsafe {
+            (self.plugin.fns.tcf_plan)(nframes, nvectors, ngroups, max_lag, per_frame_boxes as i32, want_lags as i32, want_groups as i32, &mut ws, p, p.add(1),
+                                       p.add(2), p.add(3), p.add(4), p.add(5))
+        })?;
+        Ok((ws, s))
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
@@ -1306,6 +1389,25 @@ pub struct InternalCoords {
     pub ntuples: usize,
     pub ngroups: usize,
     pub npair_groups: usize,
+}
+
+/// What `Engine::vector_correlations` returns: c1 and c2 [group][lag] (a group without a valid vector: NaN), c1_vec and c2_vec
+/// [vector][lag] (empty unless asked for), the valid vectors per group, and per vector the mean [3], the order parameter S^2 and
+/// the bad frames; c2, c2_vec and s2 are empty in RAW mode.  A vector with a bad frame is NaN in its own rows.
+#[derive(Debug, Clone, Default)]
+pub struct VectorCorrelations {
+    pub c1: Vec<f32>,
+    pub c2: Vec<f32>,
+    pub c1_vec: Vec<f32>,
+    pub c2_vec: Vec<f32>,
+    pub nvalid: Vec<u64>,
+    pub mean: Vec<f32>,
+    pub s2: Vec<f32>,
+    pub bad_frames: Vec<u32>,
+    pub nframes: usize,
+    pub nvectors: usize,
+    pub ngroups: usize,
+    pub nlags: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless

@@ -111,6 +111,22 @@ pub const IC_DISTANCE: u32 = 2;
 pub const IC_ANGLE: u32 = 3;
 pub const IC_DIHEDRAL: u32 = 4;
 
+/// `molar_hip_tcf_spec`: what the time correlation calls compute - `kind` (the atoms per tuple: 1 the atom's own 3-vector,
+/// 2 the bond vector, 3 the plane normal), `mode` (TCF_UNIT: unit vectors, TCF_RAW: the vectors as they are) and `dims` (the
+/// bits x, y, z of the components that enter, 1 ..= 7).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub struct MolarHipTcfSpec {
+    pub kind: u32,
+    pub mode: u32,
+    pub dims: u32,
+    pub reserved: u32,
+}
+
+/// `MolarHipTcfSpec::mode`
+pub const TCF_UNIT: u32 = 0;
+pub const TCF_RAW: u32 = 1;
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
