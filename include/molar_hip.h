@@ -1061,6 +1061,94 @@ int molar_hip_tcf_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, 
                       double *c1, double *c2, double *c1_vec, double *c2_vec, size_t ld, uint64_t *nvalid, double *mean,
                       double *s2, uint32_t *bad_frames);
 
+/* ---- Static structure factors over a block of trajectory frames, by the direct sum over the reciprocal lattice of each
+ * frame's own box: the structure factor of a liquid (gmx saxs, gmx scattering), the partial structure factors S_ab(q) that
+ * X-ray and neutron intensities are assembled from, the lateral S(q_xy) of the head groups of a bilayer, and the per-frame
+ * collective density rho(q, t) an intermediate scattering function starts from.  The frame block, idx, boxes and
+ * box_stride (0: one box, 9: one per frame) are those of molar_hip_density; there is no pbc argument: the lattice is
+ * whatever 3 x 3 matrix the caller passes - normally the frame's box, or a fixed "virtual" box for a fixed q grid under
+ * NPT or for a system that is not periodic.  Operation by operation (Real = float, or double for _f64; everything is
+ * formed in double from the exact inputs and rounded to Real at the end; F = nframes, G = the groups, P = G (G + 1) / 2):
+ *   selection, weights, groups: as in molar_hip_density.  idx[0 .. n), or atoms 0 .. n-1; weight: one per ATOM, of any sign
+ *     (scattering lengths of hydrogen are negative), NULL: 1; labels[n]: one per SELECTED atom, below ngroups, the species,
+ *     NULL: one group (ngroups is not read); groups may be empty.
+ *   fractional coordinate: s = inv(box_f) p with the inverse and the association of the density call's BOX mode,
+ *     s_d = ((inv_d0 x) + inv_d1 y) + inv_d2 z; then s_d -= floor(s_d), which is exact and only keeps the phase small:
+ *     periodicity of the system is not assumed.
+ *   lattice: Miller indices m = (h, k, l), h in [0, H], k in [-K, K], l in [-L, L], (H, K, L) = grid.hmax;
+ *     Q = (H + 1)(2K + 1)(2L + 1); the index of m is (h (2K + 1) + (k + K)) (2L + 1) + (l + L).  Only h >= 0 is stored: real
+ *     weights give rho(-m) = conj rho(m); the plane h = 0 holds both halves.  q_f(m) = 2 pi inv(box_f)^T m.  A lateral
+ *     analysis is L = 0, the Fourier series of a profile K = L = 0.
+ *   collective density: rho_g(m; f) = sum over the atoms j of group g of w_j exp(-2 pi i m.s_j(f)), formed as
+ *     sum_j (Ex_j^h Ey_j^k) (w_j Ez_j^l), E_d = (cos, -sin)(2 pi s_d), on the f64 matrix cores.  A power E^p, p >= 0: the
+ *     powers a block of the lattice needs are taken in runs of 8 consecutive p; the first of a run is
+ *     (cos, -sin)(2 pi t), t = p s_d - floor(p s_d), by sincospi(2 t), every next one the product of the one before with
+ *     E^1 (re = ar br - ai bi, im = ar bi + ai br): at most 7 products behind a sincospi.  A negative power is the conjugate.
+ *     Ex^h Ey^k is one such complex product, w Ez^l two real ones.  The sum over the atoms: the atoms of a group in the order
+ *     of the selection, padded to a multiple of 4 with terms of weight 0, in K splits of atom_chunk atoms; within a split the
+ *     MFMA chain (four atoms per step; per step re += Ar Br, re += (-Ai) Bi, im += Ar Bi, im += Ai Br), then the splits in
+ *     order.
+ *   rho[F][G][Q][2]: the series (re, im); row (f, g) starts at (f G + g) rho_stride, rho_stride >= 2 Q (the rest of a row is
+ *     not touched).
+ *   frame_ok[F] (uint32): 0 where a selected coordinate of the frame is not finite.  Such a frame's rows of rho are NaN
+ *     and it enters no average; the status stays MOLAR_HIP_OK.  Fv = the ok frames; Fv = 0: every average is NaN.
+ *   rho_mean[G][Q][2] = sum_f rho / Fv over the ok frames in frame order: the coherent part, so that the caller can form
+ *     <|rho|^2> - |<rho>|^2.
+ *   sab[P][Q] = sum_f Re(rho_a conj rho_b) / Fv, Re(x conj y) = xr yr + xi yi of the double rho, the ok frames in frame
+ *     order; the pairs a <= b are ordered a-major.  It is not normalised: divide by N or by sum w^2 (sfactor_normalize in
+ *     the Python package).
+ *   shell[P][nshells], shell_count[nshells] (uint64): the spherical (for L = 0 circular) average.  For every ok frame,
+ *     every m of the canonical half-space - h > 0, or h = 0 and k > 0, or h = k = 0 and l > 0, never m = 0 - with
+ *     v_r = (inv_0r h + inv_1r k) + inv_2r l (column r of that frame's inverse), |q| = 2 pi sqrt((v0 v0 + v1 v1) + v2 v2)
+ *     and bin = floor((|q| - qmin) / dq), kept when in [0, nshells): |q| comes from that frame's box, so a box that
+ *     fluctuates is handled.  shell[p][b] = (the sum of Re(rho_a conj rho_b) over the members) / shell_count[b], NaN where
+ *     the count is 0; shell_count: the members over the whole block.  box_stride == 9: the members of a frame are added
+ *     in index order, then the frames in order.  box_stride == 0: the membership is the same in every frame, and the sums
+ *     over the frames of S_ab are binned once, the members in index order.  nshells == 0: no shells.
+ *   No floating-point atomics are used and every sum has an order fixed by the sizes and the plan: the same call gives the
+ *   same bits.  The bits may depend on atom_chunk (where a K split ends) and on box_stride (the two orders of the shells),
+ *   on nothing else of the plan: not on frame_block, not on the device's occupancy.
+ * frames, idx, weight, labels, boxes and every output may each be host or device memory, and every output may be NULL.
+ * Device outputs are written on the context's stream and not waited for; the call waits once, for the 64 bytes of its
+ * status (and once more for results that go to host memory).
+ * Errors: n == 0, labels with ngroups == 0: ERR_SIZES; a grid that is NULL, reserved != 0, dq <= 0 or dq or qmin not finite
+ * with nshells > 0, a box_stride other than 0 and 9, natoms == 0, n > natoms without an index, a stride below 3 natoms
+ * (with more than one frame), rho_stride < 2 Q with rho, an index not below natoms, a selected weight that is not finite, a
+ * label not below ngroups: ERR_INVALID_ARGUMENT; boxes == NULL: ERR_NO_PBC; a box with a vector of zero length:
+ * ERR_ZERO_LENGTH_VECTOR, one without an inverse: ERR_INVERSE_FAILED; hmax[d] >= 2^10, G Q >= 2^31, P Q >= 2^40, 2^31 atoms or
+ * frames, more than 65535 K splits and groups together, or a workspace that cannot be allocated (its bytes are in
+ * molar_hip_last_error()): ERR_TOO_LARGE.  The errors of the arguments alone are reported before the context is used;
+ * indices, labels and weights in device memory are judged on the device before one is used as an address, and no output is
+ * touched after an error.  nframes == 0 is a successful no-op.
+ * molar_hip_sfactor_plan is a pure host function: the bytes of device workspace such a call allocates (the boxes, the
+ * partition, the running sums and staged results, and per frame of a block the blocks of the K splits, rho in double and
+ * its staging, the bins and the shells' partial sums; kept by the context, grows only; staging of host-memory inputs and
+ * the scratch of the sort not included; never smaller for a larger argument), and the launch shape: layout (0: rows
+ * enumerate (h, k) and columns l; 1, taken for L = 0 with K > 0: rows enumerate k and columns h; with K = L = 0 layout 0
+ * has one live column in its column tile - a limit), row_block x col_block: the block of rows and columns of a workgroup
+ * (2 x 2 waves of 64 x 32), atom_chunk: the atoms of a K split (a multiple of 16), ksplits = ceil(n / atom_chunk),
+ * frame_block: the frames whose rho is held at once.  The environment variables MOLAR_HIP_SFACTOR_ATOM_CHUNK and
+ * MOLAR_HIP_SFACTOR_FRAME_BLOCK override the two, for the plan and the call alike (A/B runs and tests). */
+typedef struct {
+    uint32_t hmax[3];
+    double qmin, dq;
+    uint32_t nshells;
+    uint32_t reserved;
+} molar_hip_sfactor_grid;
+int molar_hip_sfactor_plan(size_t nframes, size_t n, size_t ngroups, const molar_hip_sfactor_grid *grid,
+                           size_t *workspace_bytes, uint32_t *layout, uint32_t *row_block, uint32_t *col_block,
+                           uint32_t *atom_chunk, uint32_t *ksplits, uint32_t *frame_block);
+int molar_hip_sfactor(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *idx, size_t n, const float *weight, const uint32_t *labels, size_t ngroups,
+                      const float *boxes, size_t box_stride, const molar_hip_sfactor_grid *grid, float *rho,
+                      size_t rho_stride, uint32_t *frame_ok, float *rho_mean, float *sab, float *shell,
+                      uint64_t *shell_count);
+int molar_hip_sfactor_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                          const uint64_t *idx, size_t n, const double *weight, const uint32_t *labels, size_t ngroups,
+                          const double *boxes, size_t box_stride, const molar_hip_sfactor_grid *grid, double *rho,
+                          size_t rho_stride, uint32_t *frame_ok, double *rho_mean, double *sab, double *shell,
+                          uint64_t *shell_count);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -848,6 +848,75 @@ inline VectorCorrelationsOf<double> vector_correlations_f64(Engine &eng, const d
     return vector_correlations_call<double>(molar_hip_tcf_f64, "vector_correlations_f64", eng, frames, nframes, natoms, tuples, kind, boxes, opt, labels);
 }
 
+// Static structure factors (molar_hip_sfactor*; the definition: molar_hip.h): the collective density rho_g(m) of every group of
+// `labels` over the reciprocal lattice of `boxes` up to the Miller indices opt.hmax (h >= 0 only), its mean over the ok frames,
+// the partial products S_ab(m) for a <= b and their average over shells of |q|.  `idx` empty: atoms 0 .. natoms - 1; `weight`
+// empty: unit weights (one per ATOM otherwise).  S_ab is not normalised.
+struct StructureFactorOptions {
+    uint32_t hmax[3] = {0, 0, 0};     // (H, K, L): h in [0, H], k in [-K, K], l in [-L, L]
+    double qmin = 0.0, dq = 0.0;      // shells [qmin + b dq, qmin + (b + 1) dq)
+    uint32_t nshells = 0;             // 0: no shells
+    bool per_frame_boxes = false;
+    size_t ngroups = 1;               // read with labels
+    bool want_rho = false;            // rho [F][G][Q][2]
+    bool want_mean = false;           // rho_mean [G][Q][2]
+    bool want_sab = true;             // sab [P][Q]
+};
+template <class Real>
+struct StructureFactorOf {
+    std::vector<Real> rho, rho_mean, sab, shell;   // shell [P][nshells]
+    std::vector<uint32_t> frame_ok;                // [F]
+    std::vector<uint64_t> shell_count;             // [nshells]
+    size_t nframes = 0, ngroups = 0, npairs = 0, nq = 0, nshells = 0;
+};
+using StructureFactor = StructureFactorOf<Float>;
+template <class Real, class Fn>
+inline StructureFactorOf<Real> structure_factor_call(Fn fn, const char *who, Engine &eng, const Real *frames, size_t nframes, size_t natoms, const Real *boxes,
+                                                     const StructureFactorOptions &opt, const std::vector<usize> &idx, const std::vector<Real> &weight,
+                                                     const std::vector<uint32_t> &labels) {
+    const size_t n = idx.empty() ? natoms : idx.size();
+    if (!labels.empty() && labels.size() != n) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per selected atom");
+    if (!weight.empty() && weight.size() != natoms) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one weight per atom");
+    StructureFactorOf<Real> out;
+    const size_t G = labels.empty() ? 1 : opt.ngroups, P = G * (G + 1) / 2;
+    const size_t Q = (size_t)(opt.hmax[0] + 1) * (2 * (size_t)opt.hmax[1] + 1) * (2 * (size_t)opt.hmax[2] + 1);
+    out.nframes = nframes;
+    out.ngroups = G;
+    out.npairs = P;
+    out.nq = Q;
+    out.nshells = opt.nshells;
+    if (nframes == 0) return out;
+    if (opt.want_rho) out.rho.resize(nframes * G * Q * 2);
+    if (opt.want_mean) out.rho_mean.resize(G * Q * 2);
+    if (opt.want_sab) out.sab.resize(P * Q);
+    if (opt.nshells) {
+        out.shell.resize(P * opt.nshells);
+        out.shell_count.resize(opt.nshells);
+    }
+    out.frame_ok.resize(nframes);
+    molar_hip_sfactor_grid grid{};
+    for (int d = 0; d < 3; ++d) grid.hmax[d] = opt.hmax[d];
+    grid.qmin = opt.qmin;
+    grid.dq = opt.dq;
+    grid.nshells = opt.nshells;
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    check(fn(eng.ctx(), frames, nframes, natoms * 3, natoms, idx.empty() ? nullptr : idx.data(), n, weight.empty() ? nullptr : weight.data(),
+             labels.empty() ? nullptr : labels.data(), opt.ngroups, boxes, opt.per_frame_boxes ? 9 : 0, &grid, ptr(out.rho), 2 * Q, ptr(out.frame_ok),
+             ptr(out.rho_mean), ptr(out.sab), ptr(out.shell), ptr(out.shell_count)));
+    return out;
+}
+inline StructureFactor structure_factor(Engine &eng, const Float *frames, size_t nframes, size_t natoms, const Float *boxes,
+                                        const StructureFactorOptions &opt = StructureFactorOptions(), const std::vector<usize> &idx = {},
+                                        const std::vector<Float> &weight = {}, const std::vector<uint32_t> &labels = {}) {
+    return structure_factor_call<Float>(molar_hip_sfactor, "structure_factor", eng, frames, nframes, natoms, boxes, opt, idx, weight, labels);
+}
+// the same on f64 frames, weights and boxes (MolAR's f64 feature): molar_hip_sfactor_f64
+inline StructureFactorOf<double> structure_factor_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const double *boxes,
+                                                      const StructureFactorOptions &opt = StructureFactorOptions(), const std::vector<usize> &idx = {},
+                                                      const std::vector<double> &weight = {}, const std::vector<uint32_t> &labels = {}) {
+    return structure_factor_call<double>(molar_hip_sfactor_f64, "structure_factor_f64", eng, frames, nframes, natoms, boxes, opt, idx, weight, labels);
+}
+
 // Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
 // donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
 // images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's

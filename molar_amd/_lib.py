@@ -64,6 +64,12 @@ class TcfSpec(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("mode", C.c_uint32), ("dims", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SfactorGrid(C.Structure):
+    """molar_hip_sfactor_grid: the largest Miller indices (H, K, L), the first edge and the width of the shells of |q|, and
+    their number (0: none)."""
+    _fields_ = [("hmax", C.c_uint32 * 3), ("qmin", C.c_double), ("dq", C.c_double), ("nshells", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -232,6 +238,9 @@ SYMBOLS = {
     "molar_hip_tcf_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_tcf": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _SZ, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
     "molar_hip_tcf_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _U8, _P, _SZ, _SZ, _P, _P, _P, _P, _SZ, _P, _P, _P, _P]),
+    "molar_hip_sfactor_plan": (_I, [_SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_sfactor": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_sfactor_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

@@ -1479,6 +1479,23 @@ class Engine:
         return _density_call(self.lib, self.lib.molar_hip_density, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, pbc, centre_idx,
                              centre_weight, want, out, np.float32)
 
+    def structure_factor(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, want=None, out=None):
+        """Static structure factors of frames [F, natoms, 3] float32 by the direct sum over the reciprocal lattice of `boxes`
+        ([9] column-major, [3, 3] rows, or [F, 9]: the frame's box, or any fixed matrix for a fixed q grid) up to the Miller
+        indices of `grid` (sfactor_grid; molar_hip_sfactor, the definition: molar_hip.h), all arithmetic in double on the f64
+        matrix cores.  `weight`: one per ATOM, of any sign (scattering lengths, electron counts; None: 1); `labels`: one per
+        SELECTED atom, below `ngroups`, the species (None: one group).  Returns StructureFactor(rho [F, G, Q, 2]: the
+        collective density (re, im) of every group at every lattice point, h >= 0 only (sfactor_miller); frame_ok [F]: 0 where
+        a selected coordinate is not finite - that frame is NaN in rho and enters no average; rho_mean [G, Q, 2]: its mean over
+        the ok frames; sab [P, Q]: the mean of Re(rho_a conj rho_b) over the ok frames for the pairs a <= b, a-major, not
+        normalised (sfactor_normalize); shell [P, nshells], shell_count [nshells]: the average over the lattice points of
+        each shell of |q| (sfactor_shell_centres), |q| from each frame's own box; grid).  `want`: the names to compute
+        (default: frame_ok, sab, and shell, shell_count when the grid has shells); numpy in gives numpy out, torch CUDA in
+        gives torch CUDA out (frame_ok as int32, shell_count as int64), written on the ENGINE's stream and not waited for.
+        `out`: an optional StructureFactor (or 6-tuple) of destinations; rho may have a row stride above 2 Q (a wider last but
+        one dimension sliced).  The same call gives the same bits."""
+        return _sfactor_call(self.lib, self.lib.molar_hip_sfactor, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, want, out, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -2450,6 +2467,209 @@ def _tcf_call(lib, fn, ctx, frames, tuples, kind, labels, ngroups, boxes, pbc, m
     return VectorCorrelations(*res, lags)
 
 
+StructureFactor = collections.namedtuple("StructureFactor", ["rho", "frame_ok", "rho_mean", "sab", "shell", "shell_count", "grid"])
+SfactorGrid = collections.namedtuple("SfactorGrid", ["hmax", "qmin", "dq", "nshells"])
+
+
+def sfactor_grid(hmax, qmin=0.0, dq=0.0, nshells=0):
+    """The reciprocal lattice of a structure_factor call: Miller indices h in [0, H], k in [-K, K], l in [-L, L] with
+    hmax = (H, K, L) - (H, K, 0) is a lateral analysis, (H, 0, 0) the Fourier series of a profile - and `nshells` shells
+    of |q| of width `dq` from `qmin` (0: no shells)."""
+    hm = tuple(int(v) for v in hmax)
+    assert len(hm) == 3 and all(v >= 0 for v in hm)
+    return SfactorGrid(hm, float(qmin), float(dq), int(nshells))
+
+
+def _sfactor_struct(grid):
+    g = _lib.SfactorGrid()
+    for d in range(3):
+        g.hmax[d] = int(grid.hmax[d])
+    g.qmin = float(grid.qmin)
+    g.dq = float(grid.dq)
+    g.nshells = int(grid.nshells)
+    g.reserved = 0
+    return g
+
+
+def sfactor_plan(nframes, n, grid, ngroups=1):
+    """(workspace_bytes, layout, row_block, col_block, atom_chunk, ksplits, frame_block) of a structure_factor call of these
+    sizes (molar_hip_sfactor_plan): the device workspace; the layout (0: rows enumerate (h, k) and columns l; 1, for L = 0 with
+    K > 0: rows k and columns h); the block of rows and columns of a workgroup; the atoms of a K split and how many splits n
+    atoms make; the frames whose rho is held at once.  The environment variables MOLAR_HIP_SFACTOR_ATOM_CHUNK and
+    MOLAR_HIP_SFACTOR_FRAME_BLOCK override the last two, here and in the call.  A host function: no GPU is needed."""
+    g = _sfactor_struct(grid)
+    ws = C.c_size_t(0)
+    u = [C.c_uint32(0) for _ in range(6)]
+    check(_lib.load().molar_hip_sfactor_plan(int(nframes), int(n), int(ngroups), C.addressof(g), C.addressof(ws), *(C.addressof(x) for x in u)))
+    return (int(ws.value),) + tuple(int(x.value) for x in u)
+
+
+def sfactor_miller(hmax):
+    """(m [Q, 3] int64, canonical [Q] bool): the Miller indices (h, k, l) of every lattice index of a grid with this hmax, index
+    (h (2K + 1) + (k + K)) (2L + 1) + (l + L), and the mask of the canonical half-space the shells are averaged over (h > 0,
+    or h = 0 and k > 0, or h = k = 0 and l > 0: one of every pair m, -m, never m = 0)."""
+    H, K, L = (int(v) for v in hmax)
+    h, k, l = np.meshgrid(np.arange(H + 1, dtype=np.int64), np.arange(-K, K + 1, dtype=np.int64), np.arange(-L, L + 1, dtype=np.int64), indexing="ij")
+    m = np.stack([h.ravel(), k.ravel(), l.ravel()], axis=1)
+    canonical = (m[:, 0] > 0) | ((m[:, 0] == 0) & (m[:, 1] > 0)) | ((m[:, 0] == 0) & (m[:, 1] == 0) & (m[:, 2] > 0))
+    return m, canonical
+
+
+def _boxes_colmajor(boxes):
+    """[9] or [F, 9] column-major float64 from [9], [3, 3] rows or [F, 9]."""
+    b = np.asarray(boxes, np.float64)
+    if b.ndim == 2 and b.shape == (3, 3):
+        b = np.ascontiguousarray(b.T).reshape(9)
+    assert b.shape[-1] == 9 and b.ndim in (1, 2), "a box is [9] column-major or [3, 3], per-frame boxes are [F, 9]"
+    return b
+
+
+def sfactor_qvectors(boxes, hmax):
+    """q(m) = 2 pi inv(box)^T m of every lattice index, float64: [Q, 3] for one box ([9] column-major or [3, 3] rows),
+    [F, Q, 3] for per-frame boxes [F, 9]."""
+    b = _boxes_colmajor(boxes)
+    m, _ = sfactor_miller(hmax)
+    mats = b.reshape(-1, 3, 3).transpose(0, 2, 1)            # [F, row, column]
+    inv = np.linalg.inv(mats)
+    q = 2.0 * np.pi * np.einsum("fcr,qc->fqr", inv, m.astype(np.float64))
+    return q[0] if b.ndim == 1 else q
+
+
+def sfactor_shell_centres(grid):
+    """The middle of every shell of |q|: qmin + (b + 1/2) dq, float64."""
+    return float(grid.qmin) + (np.arange(int(grid.nshells), dtype=np.float64) + 0.5) * float(grid.dq)
+
+
+def sfactor_pairs(ngroups):
+    """The pairs (a, b), a <= b, in the order of sab and shell (a-major), [P, 2] int64."""
+    G = int(ngroups)
+    return np.array([(a, b) for a in range(G) for b in range(a, G)], np.int64).reshape(-1, 2)
+
+
+def sfactor_normalize(sab, weights=None, labels=None, ngroups=None, how="n", n=None):
+    """sab or shell [P, ...] of a structure_factor call divided, pair (a, b) by pair, by sqrt(N_a N_b) (how="n": the atoms of the
+    two groups - the Ashcroft-Langreth partials, S_aa -> 1 at large q for unit weights) or by sqrt(W_a W_b), W_g the sum of
+    w^2 over group g (how="w2").  `weights`: one per SELECTED atom (None: 1); `labels`: one per selected atom (None: one group
+    of `n` atoms, or of len(weights)).  A pair with an empty group is NaN.  float64 on the host."""
+    s = np.asarray(sab, np.float64)
+    assert how in ("n", "w2")
+    if labels is None:
+        count = int(n) if n is not None else len(weights)
+        lab = np.zeros(count, np.int64)
+        G = 1
+    else:
+        lab = np.asarray(labels).astype(np.int64)
+        G = int(ngroups) if ngroups is not None else int(lab.max()) + 1
+    w = np.ones(lab.shape[0], np.float64) if weights is None else np.asarray(weights, np.float64)
+    assert w.shape[0] == lab.shape[0], "one weight per selected atom"
+    norm = np.bincount(lab, weights=(w * w if how == "w2" else np.ones_like(w)), minlength=G)
+    pairs = sfactor_pairs(G)
+    assert s.shape[0] == pairs.shape[0], "one row per pair a <= b"
+    d = np.sqrt(norm[pairs[:, 0]] * norm[pairs[:, 1]])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return s / np.where(d > 0.0, d, np.nan).reshape((-1,) + (1,) * (s.ndim - 1))
+
+
+def sfactor_intensity(sab_or_shell, form_factors):
+    """I(q) = sum over the pairs a <= b of (2 - delta_ab) f_a(q) f_b(q) S_ab(q) from sab or shell [P, X] and the form
+    factors [G] (constants) or [G, X] (one per lattice point or shell): how q-dependent form factors enter, since the call
+    itself takes one weight per atom.  float64 on the host."""
+    s = np.asarray(sab_or_shell, np.float64)
+    f = np.asarray(form_factors, np.float64)
+    if f.ndim == 1:
+        f = f[:, None]
+    pairs = sfactor_pairs(f.shape[0])
+    assert s.ndim == 2 and s.shape[0] == pairs.shape[0], "one row per pair a <= b of the form factors' groups"
+    mult = np.where(pairs[:, 0] == pairs[:, 1], 1.0, 2.0)[:, None]
+    return (mult * f[pairs[:, 0]] * f[pairs[:, 1]] * s).sum(axis=0)
+
+
+def sfactor_as_vectors(rho):
+    """The series rho [F, G, Q, 2] (numpy or torch) as the block [F, G Q, 3] of (Re, Im, 0): vector_correlations(block,
+    arange(G Q), mode="raw") then gives in c1_vec the intermediate scattering function F(q, tau) = <Re(rho(t) conj
+    rho(t + tau))> of every group and lattice point (divide by N).  A NaN frame makes the series of its points bad."""
+    F = rho.shape[0]
+    if _is_torch(rho):
+        import torch
+        r = rho.reshape(F, -1, 2)
+        return torch.cat([r, torch.zeros_like(r[..., :1])], dim=-1).contiguous()
+    r = np.asarray(rho).reshape(F, -1, 2)
+    return np.ascontiguousarray(np.concatenate([r, np.zeros_like(r[..., :1])], axis=-1))
+
+
+def _sfactor_call(lib, fn, ctx, frames, grid, idx, weight, labels, ngroups, boxes, want, out, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (idx, weight, labels, boxes)
+    idx = _u64(idx); weight = conv(weight); labels = _u32(labels)
+    box_stride = 0
+    if boxes is not None:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    n = natoms if idx is None else idx.shape[0]
+    G = 1
+    if labels is not None:
+        assert labels.shape[0] == n, "one label per selected atom"
+        G = int(ngroups) if ngroups is not None else (int(labels.max()) + 1 if n else 1)
+    if weight is not None:
+        assert weight.shape[0] == natoms, "one weight per atom"
+    H, K, L = (int(v) for v in grid.hmax)
+    Q = (H + 1) * (2 * K + 1) * (2 * L + 1)
+    P = G * (G + 1) // 2
+    ns = int(grid.nshells)
+    names = ("rho", "frame_ok", "rho_mean", "sab", "shell", "shell_count")
+    if want is None:
+        want = ("frame_ok", "sab") + (("shell", "shell_count") if ns else ())
+    want = tuple(want)
+    assert all(nm in names for nm in want), "want holds names of StructureFactor"
+    shapes = ((F, G, Q, 2), (F,), (G, Q, 2), (P, Q), (P, ns), (ns,))
+    given = tuple(out[:6]) if out is not None else (None,) * 6
+    res, rho_stride = [], 2 * Q
+    for name, shape, g in zip(names, shapes, given):
+        if name not in want:
+            res.append(None)
+            continue
+        if dev:
+            import torch
+            dt = torch.int32 if name == "frame_ok" else torch.int64 if name == "shell_count" else fr.dtype
+        else:
+            dt = np.uint32 if name == "frame_ok" else np.uint64 if name == "shell_count" else real
+        if g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape and g.dtype == dt
+            if name == "rho" and F * G > 1:
+                st = tuple(int(v) for v in g.stride()) if dev else tuple(v // g.dtype.itemsize for v in g.strides)
+                assert st[3] == 1 and st[2] == 2 and st[1] >= 2 * Q and (F == 1 or st[0] == G * st[1]), "rho: rows (f, g) contiguous, one row stride"
+                rho_stride = st[1] if G > 1 else (st[0] if F > 1 else 2 * Q)
+            else:
+                assert g.is_contiguous() if dev else g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            res.append(torch.zeros(shape, dtype=dt, device=fr.device))
+        else:
+            res.append(np.zeros(shape, dt))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    gs = _sfactor_struct(grid)
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ia, k1 = _addr(idx); wa, k2 = _addr(weight); la, k3 = _addr(labels); ba, k4 = _addr(boxes)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ia, n, wa, la, G, ba, box_stride, C.addressof(gs), addr[0], rho_stride, addr[1], addr[2], addr[3],
+             addr[4], addr[5]))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((idx, weight, labels, boxes), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return StructureFactor(*res, grid)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -2665,6 +2885,10 @@ class MeasureF64:
         """Engine.density on float64 frames, weights and boxes (molar_hip_density_f64): float64 results."""
         return _density_call(self.lib, self.lib.molar_hip_density_f64, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, pbc,
                              centre_idx, centre_weight, want, out, np.float64)
+
+    def structure_factor(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, want=None, out=None):
+        """Engine.structure_factor on float64 frames, weights and boxes (molar_hip_sfactor_f64): float64 results."""
+        return _sfactor_call(self.lib, self.lib.molar_hip_sfactor_f64, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, want, out, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

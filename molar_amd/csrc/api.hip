@@ -200,6 +200,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::density_release(c);
     mh::intcoord_release(c);
     mh::tcf_release(c);
+    mh::sfactor_release(c);
     mh::hbonds_release(c);
     mh::lifetimes_release(c);
     mh::within_release(c);

@@ -1250,6 +1250,82 @@ impl Engine {
         Ok((ws, s))
     }
 
+    /// Static structure factors of a block of frames through molar_hip_sfactor (the definition: molar_hip.h): the collective
+    /// density rho_g(m) of every group of `labels` ((one label per selected atom, ngroups); None: one group) over the reciprocal
+    /// lattice of `boxes` (one column-major matrix of 9 numbers or 9 per frame) up to the Miller indices of `grid`, h >= 0 only,
+    /// with `weight` (one per ATOM, of any sign; None: 1) - per frame with `want_rho`, its mean over the ok frames with
+    /// `want_mean` - the partial products S_ab for a <= b, not normalised, and their average over the shells of |q| of `grid`.
+    /// A frame with a selected coordinate that is not finite is 0 in `frame_ok`, NaN in rho and enters no average.  No
+    /// floating-point atomics are used: the same call gives the same bits.
+    #[allow(clippy::too_many_arguments)]
+    pub fn structure_factor(
+        &self, frames: &[[f32; 3]], natoms: usize, idx: Option<&[usize]>, weight: Option<&[f32]>, labels: Option<(&[u32], usize)>, boxes: &[f32],
+        grid: &MolarHipSfactorGrid, want_rho: bool, want_mean: bool,
+    ) -> Result<StructureFactor, EngineError> {
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("structure_factor: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        check_index(idx, natoms, "structure_factor")?;
+        let nframes = frames.len() / natoms;
+        let n = idx.map_or(natoms, |i| i.len());
+        let box_stride = match boxes.len() {
+            9 => 0,
+            l if l == 9 * nframes => 9,
+            l => return Err(EngineError::Sizes(format!("structure_factor: {l} box numbers for {nframes} frames"))),
+        };
+        if let Some(w) = weight {
+            if w.len() != natoms {
+                return Err(EngineError::Sizes(format!("structure_factor: {} weights for {natoms} atoms", w.len())));
+            }
+        }
+        let (lp, ngroups) = match labels {
+            Some((l, _)) if l.len() != n => return Err(EngineError::Sizes(format!("structure_factor: {} labels for {n} selected atoms", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        let nq = (grid.hmax[0] as usize + 1) * (2 * grid.hmax[1] as usize + 1) * (2 * grid.hmax[2] as usize + 1);
+        let npairs = ngroups * (ngroups + 1) / 2;
+        let nshells = grid.nshells as usize;
+        let mut out = StructureFactor {
+            rho: vec![0f32; if want_rho { nframes * ngroups * nq * 2 } else { 0 }],
+            frame_ok: vec![0u32; nframes],
+            rho_mean: vec![0f32; if want_mean { ngroups * nq * 2 } else { 0 }],
+            sab: vec![0f32; npairs * nq],
+            shell: vec![0f32; npairs * nshells],
+            shell_count: vec![0u64; nshells],
+            nframes,
+            ngroups,
+            npairs,
+            nq,
+            nshells,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        fn ptr<T>(v: &mut Vec<T>) -> *mut T {
+            if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() }
+        }
+        self.plugin.check(unsafe {
+            (self.plugin.fns.sfactor)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, idx.map_or(std::ptr::null(), |i| i.as_ptr() as *const u64),
+                                      n, weight.map_or(std::ptr::null(), |w| w.as_ptr()), lp, ngroups, boxes.as_ptr(), box_stride,
+                                      grid as *const MolarHipSfactorGrid, ptr(&mut out.rho), 2 * nq, ptr(&mut out.frame_ok), ptr(&mut out.rho_mean),
+                                      ptr(&mut out.sab), ptr(&mut out.shell), ptr(&mut out.shell_count))
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and the launch shape (layout, row_block, col_block, atom_chunk, ksplits, frame_block) of a
+    /// `structure_factor` call of these sizes (molar_hip_sfactor_plan, a host function).
+    pub fn structure_factor_plan(&self, nframes: usize, n: usize, ngroups: usize, grid: &MolarHipSfactorGrid) -> Result<(usize, [u32; 6]), EngineError> {
+        let mut ws = 0usize;
+        let mut s = [0u32; 6];
+        let p = s.as_mut_ptr();
+        self.plugin.check(unsafe {
+            (self.plugin.fns.sfactor_plan)(nframes, n, ngroups, grid as *const MolarHipSfactorGrid, &mut ws, p, p.add(1), p.add(2), p.add(3), p.add(4), p.add(5))
+        })?;
+        Ok((ws, s))
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
@@ -1408,6 +1484,24 @@ pub struct VectorCorrelations {
     pub nvectors: usize,
     pub ngroups: usize,
     pub nlags: usize,
+}
+
+/// What `Engine::structure_factor` returns: rho [frame][group][m][re, im] and rho_mean [group][m][re, im] (empty unless asked
+/// for), frame_ok [frame], sab [pair a <= b, a-major][m], shell [pair][shell] (NaN for a shell without a member) and the members
+/// of every shell over the block; m is the lattice index (h (2K + 1) + (k + K)) (2L + 1) + (l + L).
+#[derive(Debug, Clone, Default)]
+pub struct StructureFactor {
+    pub rho: Vec<f32>,
+    pub frame_ok: Vec<u32>,
+    pub rho_mean: Vec<f32>,
+    pub sab: Vec<f32>,
+    pub shell: Vec<f32>,
+    pub shell_count: Vec<u64>,
+    pub nframes: usize,
+    pub ngroups: usize,
+    pub npairs: usize,
+    pub nq: usize,
+    pub nshells: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless

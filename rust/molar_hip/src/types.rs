@@ -127,6 +127,18 @@ pub struct MolarHipTcfSpec {
 pub const TCF_UNIT: u32 = 0;
 pub const TCF_RAW: u32 = 1;
 
+/// `molar_hip_sfactor_grid`: the reciprocal lattice of the structure factor calls - the largest Miller indices (H, K, L): h in
+/// 0 ..= H, k in -K ..= K, l in -L ..= L - and `nshells` shells of |q| of width `dq` from `qmin` (0: no shells).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct MolarHipSfactorGrid {
+    pub hmax: [u32; 3],
+    pub qmin: f64,
+    pub dq: f64,
+    pub nshells: u32,
+    pub reserved: u32,
+}
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
