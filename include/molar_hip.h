@@ -1149,6 +1149,94 @@ int molar_hip_sfactor_f64(molar_hip_ctx *ctx, const double *frames, size_t nfram
                           size_t rho_stride, uint32_t *frame_ok, double *rho_mean, double *sab, double *shell,
                           uint64_t *shell_count);
 
+/* ---- Minimum distances between two selections (or inside one) over a block of trajectory frames: how close two
+ * selections come in every frame and which pair it is (gmx mindist, gmx pairdist), how far every atom is from the other
+ * selection (every water from the protein, every lipid from a peptide), and the matrix of smallest distances between
+ * groups - residues, lipids, molecules - with its mean, minimum and contact frequency over the frames (gmx mdmat).  There
+ * is no cutoff in the search: every pair is evaluated, O(n1 n2) per frame.  The frame block, the boxes and box_stride (0:
+ * one box, 9: one per frame) are those of molar_hip_intcoord.  Operation by operation (Real = float, or double for _f64;
+ * everything is formed in double from the exact inputs and rounded to Real at the end; F = nframes):
+ *   sets: set 1 is idx1[0 .. n1), or atoms 0 .. n1-1; set 2 is idx2[0 .. n2), or atoms 0 .. n2-1.  i and j below are POSITIONS
+ *     within the sets.  labels1[n1] below ngroups1 and labels2[n2] below ngroups2 make the groups G1 and G2; NULL: one
+ *     group (the ngroups is not read).  Groups may be empty and labels need not be sorted.
+ *   spec.same = 1: set 2 is set 1 (idx2, labels2 must be NULL; n2, ngroups2 are not read; atom2 must be NULL, it would be
+ *     atom1).  The pair i = j is skipped, and with spec.exclude_same_group = 1 so is every pair inside one group (without
+ *     labels that is every pair).
+ *   distance of a pair: d2 = norm2(shortest_vector(box_f, x_j - x_i, spec.pbc)) with shortest_vector and box_from_matrix
+ *     of PeriodicBox in double - any PbcDims mask, triclinic cells, the correction shifts for a full mask - the metric of
+ *     molar_hip_intcoord and molar_hip_msd; boxes == NULL or spec.pbc == 0: the plain difference (the boxes are not read).
+ *     The distance is sqrt(d2).  Every minimum is taken over d2; equal d2 give the lowest i, then the lowest j.
+ *   dist[F], pair[F][2] (uint64): the smallest distance of the frame and the pair (i, j) that has it - the smallest under
+ *     the order (d2, i, j).  No pair at all (one atom with same, everything excluded): +inf and UINT64_MAX.  dist[f] is
+ *     bit-equal to what molar_hip_intcoord returns for the distance of that pair.
+ *   atom1[F][n1], near1[F][n1] (uint64): for every atom of set 1 its distance to set 2 and the position j of its nearest atom
+ *     there (the lowest j among equal distances; +inf and UINT64_MAX without a partner).  Row f of both starts at f ld1,
+ *     ld1 >= n1 (the rest of a row is not touched).
+ *   atom2[F][n2]: the same seen from set 2; row f starts at f ld2, ld2 >= n2.
+ *   mat[F][G1][G2]: the smallest distance between group a of set 1 and group b of set 2 in every frame; +inf for an empty
+ *     group, a group of one atom against itself, or an excluded diagonal.  With same the matrix is exactly symmetric.
+ *   frame_ok[F] (uint32): 0 where a selected coordinate of either set is not finite, or (with boxes and spec.pbc != 0)
+ *     box_from_matrix refuses the frame's box (a vector of zero length, no inverse).  Every per-frame output of such a
+ *     frame is NaN (pair, near1: UINT64_MAX), it enters none of the three reductions below, and the status stays
+ *     MOLAR_HIP_OK.  nvalid[1] (uint64): the valid frames.
+ *   mat_mean[G1][G2] (double in both entries) = the sum over the valid frames, in frame order, of the double distances,
+ *     divided by nvalid: +inf where any valid frame gave +inf, NaN without a valid frame.
+ *   mat_min[G1][G2]: the minimum over the valid frames (+inf without one).
+ *   mat_freq[G1][G2] (uint32): the valid frames whose double distance is below spec.cutoff: the contact frequency map.
+ *   spec.frame_block: the frames walked at once (0: chosen from the plan; 256 at the most).  The frames of a block are
+ *     folded in frame order, so no result depends on it, and mat of the whole block is never held: the reductions do not
+ *     need the mat output.
+ *   Every reduction is a minimum under a total order, or a sum in frame order; the only atomics are 64-bit integer minima on
+ *   the bits of d2.  The same call gives the same bits, whatever the plan.
+ * frames, idx1, idx2, labels1, labels2, boxes and every output may each be host or device memory, and every output may be
+ * NULL.  Device outputs are written on the context's stream and not waited for; the call waits once, for the 64 bytes of its
+ * status (and once more for results that go to host memory).
+ * Errors: n1 == 0 or n2 == 0, labels with ngroups == 0: ERR_SIZES; a spec that is NULL, pbc > 7, same or exclude_same_group
+ * other than 0 and 1, exclude_same_group without same, a cutoff that is NaN, same with idx2, labels2 or atom2, a box_stride
+ * other than 0 and 9, natoms == 0, n1 or n2 > natoms without an index, a stride below 3 natoms, ld1 < n1 or ld2 < n2 (each
+ * with more than one frame), an index not below natoms, a label not below its ngroups: ERR_INVALID_ARGUMENT; 2^31 atoms,
+ * frames or cells G1 G2, or a workspace that cannot be allocated: ERR_TOO_LARGE.  The errors of the arguments alone are
+ * reported before the context is used; indices and labels in device memory are judged on the device before one is used as an
+ * address, and no output is touched after an error.  nframes == 0 is a successful no-op.
+ * molar_hip_mindist_plan is a pure host function.  outputs: which results the call would be asked for, the sum of
+ * MOLAR_HIP_MINDIST_DIST (dist, pair), _ATOM1 (atom1, near1), _ATOM2 and _MAT (any of the four matrices).  It gives the bytes of
+ * device workspace (the boxes, the partition, the running reductions, and per frame of a block both sets in double, the row
+ * partials of every column split, the group matrix and staged results; kept by the context, grows only; staging of
+ * host-memory inputs and the scratch of the sort not included) and the launch shape: rows_per_wave (a lane owns two atoms of
+ * the row set), rows_per_block (four waves), cols_per_tile (a column split is a whole number of tiles), col_splits (the
+ * splits of the column set of the first pass, more when rows and frames alone do not fill the device), frame_block.  The
+ * passes: rows of set 1 against columns of set 2 for atom1 / near1 (and dist / pair); rows of set 2 for atom2 (dist / pair
+ * come from it when atom1 / near1 are not asked for); the group pass for the matrices.  The environment variables
+ * MOLAR_HIP_MINDIST_COL_SPLITS and MOLAR_HIP_MINDIST_FRAME_BLOCK override the two, for the plan and the call alike (A/B runs
+ * and tests); spec.frame_block goes before the variable. */
+#define MOLAR_HIP_MINDIST_DIST 1u
+#define MOLAR_HIP_MINDIST_ATOM1 2u
+#define MOLAR_HIP_MINDIST_ATOM2 4u
+#define MOLAR_HIP_MINDIST_MAT 8u
+typedef struct {
+    uint32_t pbc;
+    uint32_t same;
+    uint32_t exclude_same_group;
+    uint32_t frame_block;
+    double cutoff;
+} molar_hip_mindist_spec;
+int molar_hip_mindist_plan(size_t nframes, size_t n1, size_t n2, size_t ngroups1, size_t ngroups2,
+                           const molar_hip_mindist_spec *spec, uint32_t outputs, size_t *workspace_bytes,
+                           uint32_t *rows_per_wave, uint32_t *rows_per_block, uint32_t *cols_per_tile, uint32_t *col_splits,
+                           uint32_t *frame_block);
+int molar_hip_mindist(molar_hip_ctx *ctx, const float *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *idx1, size_t n1, const uint32_t *labels1, size_t ngroups1, const uint64_t *idx2,
+                      size_t n2, const uint32_t *labels2, size_t ngroups2, const float *boxes, size_t box_stride,
+                      const molar_hip_mindist_spec *spec, float *dist, uint64_t *pair, float *atom1, uint64_t *near1,
+                      size_t ld1, float *atom2, size_t ld2, float *mat, double *mat_mean, float *mat_min,
+                      uint32_t *mat_freq, uint32_t *frame_ok, uint64_t *nvalid);
+int molar_hip_mindist_f64(molar_hip_ctx *ctx, const double *frames, size_t nframes, size_t frame_stride, size_t natoms,
+                          const uint64_t *idx1, size_t n1, const uint32_t *labels1, size_t ngroups1,
+                          const uint64_t *idx2, size_t n2, const uint32_t *labels2, size_t ngroups2, const double *boxes,
+                          size_t box_stride, const molar_hip_mindist_spec *spec, double *dist, uint64_t *pair,
+                          double *atom1, uint64_t *near1, size_t ld1, double *atom2, size_t ld2, double *mat,
+                          double *mat_mean, double *mat_min, uint32_t *mat_freq, uint32_t *frame_ok, uint64_t *nvalid);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

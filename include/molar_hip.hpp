@@ -917,6 +917,90 @@ inline StructureFactorOf<double> structure_factor_f64(Engine &eng, const double 
     return structure_factor_call<double>(molar_hip_sfactor_f64, "structure_factor_f64", eng, frames, nframes, natoms, boxes, opt, idx, weight, labels);
 }
 
+// Minimum distances between two selections over a block of frames (molar_hip_mindist*; the definition: molar_hip.h): `idx1` /
+// `idx2` empty: atoms 0 .. natoms - 1; opt.same: set 2 is set 1 (idx2, labels2 stay empty).  `labels1` / `labels2`: one label
+// per selected atom below opt.ngroups1 / opt.ngroups2 (empty: one group).  `boxes` null: plain differences.  i and j are
+// positions within the sets; without a pair a distance is +inf and a position UINT64_MAX; a frame that is not valid is NaN.
+struct MinDistanceOptions {
+    uint32_t pbc = MOLAR_HIP_PBC_FULL;
+    bool per_frame_boxes = false;
+    bool same = false, exclude_same_group = false;
+    double cutoff = 0.0;              // mat_freq counts the valid frames with a group distance below it
+    uint32_t frame_block = 0;         // 0: chosen by the call
+    size_t ngroups1 = 1, ngroups2 = 1;   // read with labels
+    bool want_dist = true;            // dist [F], pair [F][2]
+    bool want_atom1 = false;          // atom1 [F][n1], near1 [F][n1]
+    bool want_atom2 = false;          // atom2 [F][n2]
+    bool want_mat = false;            // mat [F][G1][G2]
+    bool want_mat_stats = false;      // mat_mean, mat_min, mat_freq [G1][G2]
+};
+template <class Real>
+struct MinDistancesOf {
+    std::vector<Real> dist, atom1, atom2, mat, mat_min;
+    std::vector<double> mat_mean;
+    std::vector<uint64_t> pair, near1;
+    std::vector<uint32_t> mat_freq, frame_ok;
+    uint64_t nvalid = 0;
+    size_t nframes = 0, n1 = 0, n2 = 0, ngroups1 = 0, ngroups2 = 0;
+};
+using MinDistances = MinDistancesOf<Float>;
+template <class Real, class Fn>
+inline MinDistancesOf<Real> min_distances_call(Fn fn, const char *who, Engine &eng, const Real *frames, size_t nframes, size_t natoms, const Real *boxes,
+                                               const MinDistanceOptions &opt, const std::vector<usize> &idx1, const std::vector<usize> &idx2,
+                                               const std::vector<uint32_t> &labels1, const std::vector<uint32_t> &labels2) {
+    const size_t n1 = idx1.empty() ? natoms : idx1.size(), n2 = opt.same ? n1 : (idx2.empty() ? natoms : idx2.size());
+    if (!labels1.empty() && labels1.size() != n1) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per atom of set 1");
+    if (!labels2.empty() && labels2.size() != n2) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per atom of set 2");
+    MinDistancesOf<Real> out;
+    const size_t G1 = labels1.empty() ? 1 : opt.ngroups1, G2 = opt.same ? G1 : (labels2.empty() ? 1 : opt.ngroups2);
+    out.nframes = nframes;
+    out.n1 = n1;
+    out.n2 = n2;
+    out.ngroups1 = G1;
+    out.ngroups2 = G2;
+    if (nframes == 0) return out;
+    if (opt.want_dist) {
+        out.dist.resize(nframes);
+        out.pair.resize(2 * nframes);
+    }
+    if (opt.want_atom1) {
+        out.atom1.resize(nframes * n1);
+        out.near1.resize(nframes * n1);
+    }
+    if (opt.want_atom2) out.atom2.resize(nframes * n2);
+    if (opt.want_mat) out.mat.resize(nframes * G1 * G2);
+    if (opt.want_mat_stats) {
+        out.mat_mean.resize(G1 * G2);
+        out.mat_min.resize(G1 * G2);
+        out.mat_freq.resize(G1 * G2);
+    }
+    out.frame_ok.resize(nframes);
+    molar_hip_mindist_spec spec{};
+    spec.pbc = boxes ? opt.pbc : 0u;
+    spec.same = opt.same ? 1u : 0u;
+    spec.exclude_same_group = opt.exclude_same_group ? 1u : 0u;
+    spec.frame_block = opt.frame_block;
+    spec.cutoff = opt.cutoff;
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    check(fn(eng.ctx(), frames, nframes, natoms * 3, natoms, idx1.empty() ? nullptr : idx1.data(), n1, labels1.empty() ? nullptr : labels1.data(), opt.ngroups1,
+             idx2.empty() ? nullptr : idx2.data(), n2, labels2.empty() ? nullptr : labels2.data(), opt.ngroups2, boxes, opt.per_frame_boxes ? 9 : 0, &spec,
+             ptr(out.dist), ptr(out.pair), ptr(out.atom1), ptr(out.near1), n1, ptr(out.atom2), n2, ptr(out.mat), ptr(out.mat_mean), ptr(out.mat_min),
+             ptr(out.mat_freq), ptr(out.frame_ok), &out.nvalid));
+    return out;
+}
+inline MinDistances min_distances(Engine &eng, const Float *frames, size_t nframes, size_t natoms, const Float *boxes,
+                                  const MinDistanceOptions &opt = MinDistanceOptions(), const std::vector<usize> &idx1 = {}, const std::vector<usize> &idx2 = {},
+                                  const std::vector<uint32_t> &labels1 = {}, const std::vector<uint32_t> &labels2 = {}) {
+    return min_distances_call<Float>(molar_hip_mindist, "min_distances", eng, frames, nframes, natoms, boxes, opt, idx1, idx2, labels1, labels2);
+}
+// the same on f64 frames and boxes (MolAR's f64 feature): molar_hip_mindist_f64
+inline MinDistancesOf<double> min_distances_f64(Engine &eng, const double *frames, size_t nframes, size_t natoms, const double *boxes,
+                                                const MinDistanceOptions &opt = MinDistanceOptions(), const std::vector<usize> &idx1 = {},
+                                                const std::vector<usize> &idx2 = {}, const std::vector<uint32_t> &labels1 = {},
+                                                const std::vector<uint32_t> &labels2 = {}) {
+    return min_distances_call<double>(molar_hip_mindist_f64, "min_distances_f64", eng, frames, nframes, natoms, boxes, opt, idx1, idx2, labels1, labels2);
+}
+
 // Hydrogen bonds (molar_hip_hbonds_*; the definition: molar_hip.h): `donors` and `acceptors` are selections of ONE system, the
 // donors' hydrogens a CSR over the donors (h_offsets[donors.len() + 1], h_idx: atom indices of the system).  use_box: minimum
 // images and the periodic search over opt.pbc in the state's box.  The triples come sorted by (donor's position, hydrogen's

@@ -70,6 +70,12 @@ class SfactorGrid(C.Structure):
     _fields_ = [("hmax", C.c_uint32 * 3), ("qmin", C.c_double), ("dq", C.c_double), ("nshells", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MindistSpec(C.Structure):
+    """molar_hip_mindist_spec: the PbcDims mask, whether set 2 is set 1, whether pairs inside one group are skipped then, the
+    frames walked at once (0: from the plan) and the cutoff of the contact frequency map."""
+    _fields_ = [("pbc", C.c_uint32), ("same", C.c_uint32), ("exclude_same_group", C.c_uint32), ("frame_block", C.c_uint32), ("cutoff", C.c_double)]
+
+
 class SearchDescF64(C.Structure):
     """molar_hip_search_desc_f64: the request of the f64 drivers (MolAR's `f64` feature)."""
     _fields_ = [
@@ -241,6 +247,9 @@ SYMBOLS = {
     "molar_hip_sfactor_plan": (_I, [_SZ, _SZ, _SZ, _P, _P, _P, _P, _P, _P, _P, _P]),
     "molar_hip_sfactor": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_sfactor_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _P, _SZ, _P, _SZ, _P, _P, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_mindist_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_mindist": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_mindist_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

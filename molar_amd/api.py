@@ -1496,6 +1496,28 @@ class Engine:
         one dimension sliced).  The same call gives the same bits."""
         return _sfactor_call(self.lib, self.lib.molar_hip_sfactor, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, want, out, np.float32)
 
+    def min_distances(self, frames, idx1=None, idx2=None, labels1=None, labels2=None, ngroups1=None, ngroups2=None, boxes=None, pbc=7, same=False,
+                      exclude_same_group=False, cutoff=0.0, frame_block=0, want=None, out=None, n1=None, n2=None):
+        """Minimum distances between two selections of frames [F, natoms, 3] float32 (molar_hip_mindist, the definition:
+        molar_hip.h): every pair is evaluated under the minimum image of each frame's own box (`boxes` [9] column-major,
+        [3, 3] rows or [F, 9]; None: plain differences; `pbc`: the PbcDims mask), in double.  Set 1 is `idx1` (None: atoms
+        0 .. n1 - 1, n1 = natoms by default), set 2 `idx2`; `same=True`: set 2 is set 1, the pair i = i is skipped, and with
+        `exclude_same_group` every pair inside one group.  `labels1` / `labels2`: one label per SELECTED atom, below
+        `ngroups1` / `ngroups2`: residues, lipids, molecules (mindist_groups_from_resindex).  Returns MinDistances(dist [F],
+        pair [F, 2]: the smallest distance of the frame and the positions (i, j) within the sets that have it, the lowest (i, j)
+        among equal distances; atom1 [F, n1], near1 [F, n1]: for every atom of set 1 its distance to set 2 and the position
+        of its nearest atom there; atom2 [F, n2]: the distances seen from set 2; mat [F, G1, G2]: the smallest distance
+        between every pair of groups; mat_mean (float64), mat_min, mat_freq [G1, G2]: its mean, its minimum and the number of
+        frames below `cutoff` over the valid frames; frame_ok [F]: 0 where a selected coordinate is not finite or the box is
+        refused - that frame is NaN (pair, near1: the largest uint64, -1 as int64) and enters no reduction; nvalid [1]).
+        `want`: the names to compute (default: dist, pair, frame_ok, nvalid); numpy in gives numpy out, torch CUDA in gives
+        torch CUDA out (pair, near1, nvalid as int64, mat_freq, frame_ok as int32), written on the ENGINE's stream and not
+        waited for.  `out`: an optional MinDistances (or 11-tuple) of destinations; atom1, near1 and atom2 may have a row
+        stride (a wider last dimension sliced; atom1 and near1 the same one).  Only minima under a total order and sums in
+        frame order: the same call gives the same bits, whatever `frame_block` is."""
+        return _mindist_call(self.lib, self.lib.molar_hip_mindist, self.ctx, frames, idx1, idx2, labels1, labels2, ngroups1, ngroups2, boxes, pbc, same,
+                             exclude_same_group, cutoff, frame_block, want, out, n1, n2, np.float32)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -2670,6 +2692,137 @@ def _sfactor_call(lib, fn, ctx, frames, grid, idx, weight, labels, ngroups, boxe
     return StructureFactor(*res, grid)
 
 
+MinDistances = collections.namedtuple("MinDistances", ["dist", "pair", "atom1", "near1", "atom2", "mat", "mat_mean", "mat_min", "mat_freq", "frame_ok", "nvalid"])
+MINDIST_DIST, MINDIST_ATOM1, MINDIST_ATOM2, MINDIST_MAT = 1, 2, 4, 8          # MOLAR_HIP_MINDIST_*
+_MINDIST_BITS = {"dist": 1, "pair": 1, "atom1": 2, "near1": 2, "atom2": 4, "mat": 8, "mat_mean": 8, "mat_min": 8, "mat_freq": 8, "frame_ok": 0, "nvalid": 0}
+
+
+def _mindist_spec(pbc, same, exclude_same_group, cutoff, frame_block):
+    sp = _lib.MindistSpec()
+    sp.pbc = int(pbc)
+    sp.same = int(bool(same))
+    sp.exclude_same_group = int(bool(exclude_same_group))
+    sp.frame_block = int(frame_block)
+    sp.cutoff = float(cutoff)
+    return sp
+
+
+def mindist_plan(nframes, n1, n2=None, ngroups1=1, ngroups2=1, want=("dist", "pair"), same=False, frame_block=0):
+    """(workspace_bytes, rows_per_wave, rows_per_block, cols_per_tile, col_splits, frame_block) of a min_distances call of
+    these sizes asked for the outputs `want` (molar_hip_mindist_plan): the device workspace; the atoms of the row set a wave
+    and a workgroup own; the columns a column split is a whole number of; the splits of the column set of the first pass;
+    the frames walked at once.  The environment variables MOLAR_HIP_MINDIST_COL_SPLITS and MOLAR_HIP_MINDIST_FRAME_BLOCK
+    override the last two, here and in the call.  A host function: no GPU is needed."""
+    sp = _mindist_spec(7, same, False, 0.0, frame_block)
+    outputs = 0
+    for nm in want:
+        outputs |= _MINDIST_BITS[nm]
+    ws = C.c_size_t(0)
+    u = [C.c_uint32(0) for _ in range(5)]
+    check(_lib.load().molar_hip_mindist_plan(int(nframes), int(n1), int(n1 if n2 is None else n2), int(ngroups1), int(ngroups2), C.addressof(sp), outputs,
+                                             C.addressof(ws), *(C.addressof(x) for x in u)))
+    return (int(ws.value),) + tuple(int(x.value) for x in u)
+
+
+def mindist_groups_from_resindex(resids, idx=None):
+    """(labels uint32, ngroups) for min_distances from the residue column of a GRO topology (GroTopology.resids, one number
+    per atom): a residue is a run of atoms with one number (the column wraps at 99999, so equal numbers far apart are
+    different residues).  `idx`: the selection the labels are for (None: every atom); the residues the selection touches are
+    numbered 0 .. ngroups - 1 in the order of the file."""
+    r = np.asarray(resids).astype(np.int64).ravel()
+    if r.shape[0] == 0:
+        return np.zeros(0, np.uint32), 0
+    residue = np.concatenate([[0], np.cumsum(r[1:] != r[:-1])])
+    if idx is not None:
+        residue = residue[np.asarray(idx).astype(np.int64)]
+    present, labels = np.unique(residue, return_inverse=True)
+    return labels.astype(np.uint32).reshape(-1), int(present.shape[0])
+
+
+def _mindist_call(lib, fn, ctx, frames, idx1, idx2, labels1, labels2, ngroups1, ngroups2, boxes, pbc, same, exclude_same_group, cutoff, frame_block, want, out,
+                  n1, n2, real):
+    conv = _f32 if real == np.float32 else _f64
+    fr, F, natoms, stride = _frame_block(frames, real)
+    dev = _is_torch(fr)
+    given_in = (idx1, idx2, labels1, labels2, boxes)
+    idx1 = _u64(idx1); idx2 = _u64(idx2); labels1 = _u32(labels1); labels2 = _u32(labels2)
+    same = bool(same)
+    assert not (same and (idx2 is not None or labels2 is not None)), "same=True takes no second index or labels"
+    box_stride = 0
+    if boxes is not None:
+        boxes = conv(boxes)
+        if boxes.ndim == 2 and tuple(boxes.shape) == (3, 3):
+            boxes = (boxes.T.contiguous() if _is_torch(boxes) else np.ascontiguousarray(boxes.T)).reshape(9)      # rows -> column-major
+        if boxes.ndim == 2:
+            assert tuple(boxes.shape) == (F, 9), "per-frame boxes are [F, 9], column-major"
+            box_stride = 9
+        else:
+            assert tuple(boxes.shape) == (9,), "a box is [9] column-major or [3, 3]"
+    else:
+        pbc = 0
+    n1 = int(idx1.shape[0]) if idx1 is not None else (natoms if n1 is None else int(n1))
+    n2 = n1 if same else (int(idx2.shape[0]) if idx2 is not None else (natoms if n2 is None else int(n2)))
+    G1 = G2 = 1
+    if labels1 is not None:
+        assert labels1.shape[0] == n1, "one label per atom of set 1"
+        G1 = int(ngroups1) if ngroups1 is not None else (int(labels1.max()) + 1 if n1 else 1)
+    if labels2 is not None:
+        assert labels2.shape[0] == n2, "one label per atom of set 2"
+        G2 = int(ngroups2) if ngroups2 is not None else (int(labels2.max()) + 1 if n2 else 1)
+    if same:
+        G2 = G1
+    names = MinDistances._fields
+    if want is None:
+        want = ("dist", "pair", "frame_ok", "nvalid")
+    want = tuple(want)
+    assert all(nm in names for nm in want), "want holds names of MinDistances"
+    assert not (same and "atom2" in want), "same=True: atom2 would be atom1"
+    shapes = ((F,), (F, 2), (F, n1), (F, n1), (F, n2), (F, G1, G2), (G1, G2), (G1, G2), (G1, G2), (F,), (1,))
+    given = tuple(out[:11]) if out is not None else (None,) * 11
+    res, ld = [], {"atom1": n1, "near1": n1, "atom2": n2}
+    for name, shape, g in zip(names, shapes, given):
+        if name not in want:
+            res.append(None)
+            continue
+        if dev:
+            import torch
+            dt = torch.int64 if name in ("pair", "near1", "nvalid") else torch.int32 if name in ("mat_freq", "frame_ok") else \
+                torch.float64 if name == "mat_mean" else fr.dtype
+        else:
+            dt = np.uint64 if name in ("pair", "near1", "nvalid") else np.uint32 if name in ("mat_freq", "frame_ok") else \
+                np.float64 if name == "mat_mean" else real
+        if g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape and g.dtype == dt
+            if name in ld and F > 1 and shape[1] > 0:
+                st = tuple(int(v) for v in g.stride()) if dev else tuple(v // g.dtype.itemsize for v in g.strides)
+                assert st[1] == 1 and st[0] >= shape[1], name + ": rows contiguous"
+                ld[name] = st[0]
+            else:
+                assert g.is_contiguous() if dev else g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            res.append(torch.zeros(shape, dtype=dt, device=fr.device))
+        else:
+            res.append(np.zeros(shape, dt))
+    if "atom1" in want and "near1" in want:
+        assert ld["atom1"] == ld["near1"], "atom1 and near1 share one row stride"
+    ld1 = ld["atom1"] if "atom1" in want else ld["near1"]
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    sp = _mindist_spec(pbc, same, exclude_same_group, cutoff, frame_block)
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    i1, k1 = _addr(idx1); i2, k2 = _addr(idx2); l1, k3 = _addr(labels1); l2, k4 = _addr(labels2); ba, k5 = _addr(boxes)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, i1, n1, l1, G1, i2, n2, l2, G2, ba, box_stride, C.addressof(sp), addr[0], addr[1], addr[2], addr[3], ld1, addr[4],
+             ld["atom2"], addr[5], addr[6], addr[7], addr[8], addr[9], addr[10]))
+    if dev and (fr is not frames or any(a is not b for a, b in zip((idx1, idx2, labels1, labels2, boxes), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    return MinDistances(*res)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -2889,6 +3042,12 @@ class MeasureF64:
     def structure_factor(self, frames, grid, idx=None, weight=None, labels=None, ngroups=None, boxes=None, want=None, out=None):
         """Engine.structure_factor on float64 frames, weights and boxes (molar_hip_sfactor_f64): float64 results."""
         return _sfactor_call(self.lib, self.lib.molar_hip_sfactor_f64, self.ctx, frames, grid, idx, weight, labels, ngroups, boxes, want, out, np.float64)
+
+    def min_distances(self, frames, idx1=None, idx2=None, labels1=None, labels2=None, ngroups1=None, ngroups2=None, boxes=None, pbc=7, same=False,
+                      exclude_same_group=False, cutoff=0.0, frame_block=0, want=None, out=None, n1=None, n2=None):
+        """Engine.min_distances on float64 frames and boxes (molar_hip_mindist_f64): float64 results."""
+        return _mindist_call(self.lib, self.lib.molar_hip_mindist_f64, self.ctx, frames, idx1, idx2, labels1, labels2, ngroups1, ngroups2, boxes, pbc,
+                             same, exclude_same_group, cutoff, frame_block, want, out, n1, n2, np.float64)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

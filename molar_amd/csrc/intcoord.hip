@@ -65,43 +65,6 @@ Layout make_layout(size_t F, size_t T, bool want_stats) {
     return Y;
 }
 
-// PeriodicBox::from_matrix in double on the device (box_from_matrix of boxmath.hpp, operation by operation, its two errors
-// included); 0: a box, 1: a box vector of zero length, 2: a matrix without an inverse.
-__device__ int ic_build_box(const double *m9, BoxD *out) {
-    D3 col[3];
-    bool ok = true;
-    for (int k = 0; k < 3; ++k) {
-        col[k] = D3{m9[3 * k], m9[3 * k + 1], m9[3 * k + 2]};
-        if (sqrt(norm2(col[k])) == 0.0) ok = false;
-    }
-    for (int q = 0; q < 9; ++q) {
-        out->m[q] = m9[q];
-        out->inv[q] = __builtin_nan("");
-    }
-    out->nshift = 0;
-    if (!ok) return 1;
-    if (!inverse3(out->m, out->inv)) return 2;
-    const bool ortho = m9[3] == 0.0 && m9[6] == 0.0 && m9[1] == 0.0 && m9[7] == 0.0 && m9[2] == 0.0 && m9[5] == 0.0;
-    if (ortho) return 0;
-    const D3 a = col[0], b = col[1], c = col[2], na = D3{-a.x, -a.y, -a.z};
-    const double longest = fmax(fmax(fmax(sqrt(norm2((a + b) + c)), sqrt(norm2((a + b) - c))), sqrt(norm2((a - b) + c))), sqrt(norm2((na + b) + c)));
-    const double half_diag = 0.5 * longest, two = 2.0 * half_diag, bound2 = two * two;
-    for (int i = -1; i <= 1; ++i)
-        for (int j = -1; j <= 1; ++j)
-            for (int k = -1; k <= 1; ++k) {
-                if (!i && !j && !k) continue;
-                const double fi = (double)i, fj = (double)j, fk = (double)k;
-                const D3 sft = (D3{fi * a.x, fi * a.y, fi * a.z} + D3{fj * b.x, fj * b.y, fj * b.z}) + D3{fk * c.x, fk * c.y, fk * c.z};
-                if (norm2(sft) < bound2) {
-                    double *dst = out->shifts + 3 * out->nshift++;
-                    dst[0] = sft.x;
-                    dst[1] = sft.y;
-                    dst[2] = sft.z;
-                }
-            }
-    return 0;
-}
-
 // One thread per box.
 template <class Real>
 __global__ void __launch_bounds__(64) ic_box_kernel(const Real *__restrict__ boxes, size_t nbox, BoxD *__restrict__ out, uint32_t *__restrict__ flags) {
@@ -110,7 +73,7 @@ __global__ void __launch_bounds__(64) ic_box_kernel(const Real *__restrict__ box
     double m9[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) m9[q] = (double)boxes[f * 9 + q];
-    const int bad = ic_build_box(m9, out + f);
+    const int bad = box_from_matrix_device(m9, out + f);
     if (bad == 1) flags[3] = 1u;
     if (bad == 2) flags[1] = 1u;
 }

@@ -1326,6 +1326,96 @@ impl Engine {
         Ok((ws, s))
     }
 
+    /// Minimum distances between two selections of a block of frames through molar_hip_mindist (the definition: molar_hip.h):
+    /// every pair under the minimum image of `boxes` (None: plain differences; one column-major matrix of 9 numbers or 9 per
+    /// frame) with the mask `spec.pbc`.  `idx1` / `idx2`: the sets (None: atoms 0 .. natoms - 1); `spec.same` = 1: set 2 is set
+    /// 1 (`idx2`, `labels2` stay None).  `labels1` / `labels2`: (one label per selected atom, ngroups), None: one group.  `want`:
+    /// the sum of MINDIST_DIST (dist, pair), MINDIST_ATOM1 (atom1, near1), MINDIST_ATOM2 and MINDIST_MAT (mat, mat_mean, mat_min,
+    /// mat_freq).  Positions are those within the sets; without a pair a distance is +inf and a position u64::MAX; a frame
+    /// with a selected coordinate that is not finite, or a refused box, is 0 in `frame_ok`, NaN in every per-frame result and
+    /// enters no reduction.  Only minima under a total order and sums in frame order: the same call gives the same bits.
+    #[allow(clippy::too_many_arguments)]
+    pub fn min_distances(
+        &self, frames: &[[f32; 3]], natoms: usize, idx1: Option<&[usize]>, idx2: Option<&[usize]>, labels1: Option<(&[u32], usize)>,
+        labels2: Option<(&[u32], usize)>, boxes: Option<&[f32]>, spec: &MolarHipMindistSpec, want: u32,
+    ) -> Result<MinDistances, EngineError> {
+        if natoms == 0 || frames.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("min_distances: the block is not a whole number of frames of {natoms} atoms")));
+        }
+        check_index(idx1, natoms, "min_distances")?;
+        check_index(idx2, natoms, "min_distances")?;
+        let nframes = frames.len() / natoms;
+        let n1 = idx1.map_or(natoms, |i| i.len());
+        let n2 = if spec.same != 0 { n1 } else { idx2.map_or(natoms, |i| i.len()) };
+        let box_stride = match boxes.map_or(9, |b| b.len()) {
+            9 => 0,
+            l if l == 9 * nframes => 9,
+            l => return Err(EngineError::Sizes(format!("min_distances: {l} box numbers for {nframes} frames"))),
+        };
+        let (l1, g1) = match labels1 {
+            Some((l, _)) if l.len() != n1 => return Err(EngineError::Sizes(format!("min_distances: {} labels for {n1} atoms of set 1", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        let (l2, g2) = match labels2 {
+            Some((l, _)) if l.len() != n2 => return Err(EngineError::Sizes(format!("min_distances: {} labels for {n2} atoms of set 2", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), if spec.same != 0 { g1 } else { 1 }),
+        };
+        let cells = g1 * g2;
+        let on = |bit: u32, len: usize| if want & bit != 0 { len } else { 0 };
+        let mut out = MinDistances {
+            dist: vec![0f32; on(MINDIST_DIST, nframes)],
+            pair: vec![0u64; on(MINDIST_DIST, 2 * nframes)],
+            atom1: vec![0f32; on(MINDIST_ATOM1, nframes * n1)],
+            near1: vec![0u64; on(MINDIST_ATOM1, nframes * n1)],
+            atom2: vec![0f32; on(MINDIST_ATOM2, nframes * n2)],
+            mat: vec![0f32; on(MINDIST_MAT, nframes * cells)],
+            mat_mean: vec![0f64; on(MINDIST_MAT, cells)],
+            mat_min: vec![0f32; on(MINDIST_MAT, cells)],
+            mat_freq: vec![0u32; on(MINDIST_MAT, cells)],
+            frame_ok: vec![0u32; nframes],
+            nvalid: 0,
+            nframes,
+            n1,
+            n2,
+            ngroups1: g1,
+            ngroups2: g2,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        fn ptr<T>(v: &mut Vec<T>) -> *mut T {
+            if v.is_empty() { std::ptr::null_mut() } else { v.as_mut_ptr() }
+        }
+        let mut sp = *spec;
+        if boxes.is_none() {
+            sp.pbc = 0;
+        }
+        self.plugin.check(unsafe {
+            (self.plugin.fns.mindist)(self.ctx, frames.as_ptr() as *const f32, nframes, natoms * 3, natoms, idx1.map_or(std::ptr::null(), |i| i.as_ptr() as *const u64),
+                                      n1, l1, g1, idx2.map_or(std::ptr::null(), |i| i.as_ptr() as *const u64), n2, l2, g2,
+                                      boxes.map_or(std::ptr::null(), |b| b.as_ptr()), box_stride, &sp as *const MolarHipMindistSpec, ptr(&mut out.dist),
+                                      ptr(&mut out.pair), ptr(&mut out.atom1), ptr(&mut out.near1), n1, ptr(&mut out.atom2), n2, ptr(&mut out.mat),
+                                      ptr(&mut out.mat_mean), ptr(&mut out.mat_min), ptr(&mut out.mat_freq), ptr(&mut out.frame_ok), &mut out.nvalid)
+        })?;
+        Ok(out)
+    }
+
+    /// Device workspace in bytes and the launch shape (rows_per_wave, rows_per_block, cols_per_tile, col_splits, frame_block) of a
+    /// `min_distances` call of these sizes asked for `want` (molar_hip_mindist_plan, a host function).
+    pub fn min_distances_plan(&self, nframes: usize, n1: usize, n2: usize, ngroups1: usize, ngroups2: usize, spec: &MolarHipMindistSpec, want: u32)
+        -> Result<(usize, [u32; 5]), EngineError> {
+        let mut ws = 0usize;
+        let mut s = [0u32; 5];
+        let p = s.as_mut_ptr();
+        self.plugin.check(unsafe {
+            (self.plugin.fns.mindist_plan)(nframes, n1, n2, ngroups1, ngroups2, spec as *const MolarHipMindistSpec, want, &mut ws, p, p.add(1), p.add(2), p.add(3),
+                                           p.add(4))
+        })?;
+        Ok((ws, s))
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many
@@ -1502,6 +1592,29 @@ pub struct StructureFactor {
     pub npairs: usize,
     pub nq: usize,
     pub nshells: usize,
+}
+
+/// What `Engine::min_distances` returns: dist [frame] and pair [frame][i, j]; atom1, near1 [frame][atom of set 1]; atom2
+/// [frame][atom of set 2]; mat [frame][group of set 1][group of set 2] and its mean, minimum and count below the cutoff over the
+/// valid frames; frame_ok [frame] and the number of valid frames.  Empty where not asked for.
+#[derive(Debug, Clone, Default)]
+pub struct MinDistances {
+    pub dist: Vec<f32>,
+    pub pair: Vec<u64>,
+    pub atom1: Vec<f32>,
+    pub near1: Vec<u64>,
+    pub atom2: Vec<f32>,
+    pub mat: Vec<f32>,
+    pub mat_mean: Vec<f64>,
+    pub mat_min: Vec<f32>,
+    pub mat_freq: Vec<u32>,
+    pub frame_ok: Vec<u32>,
+    pub nvalid: u64,
+    pub nframes: usize,
+    pub n1: usize,
+    pub n2: usize,
+    pub ngroups1: usize,
+    pub ngroups2: usize,
 }
 
 /// What `Engine::fluctuations` returns: the mean structure, the per-atom RMSF, the 3n x 3n covariance row by row (empty unless

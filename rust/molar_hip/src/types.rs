@@ -139,6 +139,23 @@ pub struct MolarHipSfactorGrid {
     pub reserved: u32,
 }
 
+/// `molar_hip_mindist_spec`: the request of the minimum-distance calls - the PbcDims mask, whether set 2 is set 1 (`same`) and
+/// whether pairs inside one group are skipped then, the frames walked at once (0: chosen by the call) and the cutoff of the
+/// contact frequency map.
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct MolarHipMindistSpec {
+    pub pbc: u32,
+    pub same: u32,
+    pub exclude_same_group: u32,
+    pub frame_block: u32,
+    pub cutoff: f64,
+}
+pub const MINDIST_DIST: u32 = 1;
+pub const MINDIST_ATOM1: u32 = 2;
+pub const MINDIST_ATOM2: u32 = 4;
+pub const MINDIST_MAT: u32 = 8;
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
