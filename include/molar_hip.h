@@ -1237,6 +1237,68 @@ int molar_hip_mindist_f64(molar_hip_ctx *ctx, const double *frames, size_t nfram
                           double *atom1, uint64_t *near1, size_t ld1, double *atom2, size_t ld2, double *mat,
                           double *mat_mean, double *mat_min, uint32_t *mat_freq, uint32_t *frame_ok, uint64_t *nvalid);
 
+/* ---- The self part of the van Hove function G_s(r, tau) over a block of trajectory frames: the distribution of the
+ * displacements of every particle over a list of lags and all time origins, per group of particles (gmx vanhove) - what
+ * MSD(tau) and its fourth moment (molar_hip_msd) summarise in two numbers: hopping, cage escape, exponential tails.  traj is an
+ * ALREADY UNWRAPPED particle trajectory: frame f is at traj + f * frame_stride (elements, >= 3 natoms), particle a at 3 a of
+ * its frame - the disp [F][P][3] of molar_hip_msd (natoms = P), which does the no-jump unwrap, the centres of mass and the
+ * drift removal, or the raw coordinates of a system that is not periodic.  The call takes no box and removes no image.
+ * Operation by operation (Real = float, or double for _f64; everything is formed in double from the exact inputs; F = nframes):
+ *   selection idx[0..n), shared by all frames; idx == NULL: particles 0 .. n-1.  k below is a POSITION within the selection.
+ *   lags[0..L) (uint64): strictly increasing, each below F; lag 0 is allowed.  A list, not a range.
+ *   origins: t = 0, origin_stride, 2 origin_stride, ... while t + tau <= F - 1;
+ *     norigins[l] = (F - 1 - lags[l]) / origin_stride + 1.
+ *   dims: the bits x, y, z (1 .. 7) of the components that enter, nd of them.
+ *   labels[0..n) (uint32), each below ngroups = G; NULL: one group (ngroups is not read).  Groups may be empty and labels need
+ *     not be sorted.
+ *   per particle k, lag l and origin t:  Delta_d = x_k,d(t + tau_l) - x_k,d(t) in double for the components of dims;
+ *     v = sqrt(r2), r2 = 0, then r2 = fma(Delta_d, Delta_d, r2) for d = x, y, z in that order (as molar_hip_msd forms r^2),
+ *     sqrt correctly rounded;  flags & MOLAR_HIP_VANHOVE_SIGNED (one component only): v = Delta_d.
+ *     lo <= v < hi: the pair enters bin floor((v - lo) / (hi - lo) * nbins) of hist[g][l], a bin above nbins - 1 (a product
+ *     that rounds up) taken as nbins - 1 - the DISTANCE formula of molar_hip_intcoord; otherwise it is counted in
+ *     outside[g][l].
+ *   a particle with a coordinate of dims that is not finite in any frame of the block is left out of every count: bad[k] is
+ *     the number of such frames of particle k, nvalid[g] the particles of group g with bad[k] == 0.  The counts of the other
+ *     particles are as without it.
+ *   For every (g, l):  sum_b hist[g][l][b] + outside[g][l] = nvalid[g] * norigins[l].
+ * Outputs (each may be NULL, host or device memory): hist [G][L][nbins], outside [G][L], norigins [L], nvalid [G] (uint64),
+ * bad [n] (uint32).  Only integer atomics: the same call gives the same bits.  traj, idx, labels and lags may each be host or
+ * device memory.  Device outputs are written on the context's stream and not waited for; the call waits once, for the 64
+ * bytes of its status (and once more for results that go to host memory).
+ * Errors: n == 0, nlags == 0, labels with ngroups == 0: ERR_SIZES; a lag not below F, lags that are not
+ * strictly increasing, origin_stride == 0, dims == 0 or > 7, an unknown bit of flags, SIGNED with more than one bit of dims,
+ * lo >= hi, a lo or hi that is not finite, nbins == 0, a label not below G, an index not below natoms, natoms == 0,
+ * n > natoms without an index, a stride below 3 natoms (with more than one frame), a null lags or (with frames) traj:
+ * ERR_INVALID_ARGUMENT; 2^31 particles, frames or cells G L nbins, or a workspace that cannot be allocated: ERR_TOO_LARGE.  The
+ * errors of the arguments alone are reported before the context is used; labels, lags and indices in device memory are judged on the device
+ * before one is used as an address, and no output is touched after an error.  nframes == 0 is a successful no-op.
+ * molar_hip_vanhove_plan is a pure host function (ndims = 1, 2 or 3: the bits set in dims).  It gives the bytes of device
+ * workspace (the partition by label, bad, nvalid and the particle-major f64 trajectories [n][ndims][F]; kept by the context,
+ * grows only; staging of host-memory arguments and the scratch of the sort not included; never smaller for a larger argument)
+ * and every launch-shape size the kernels branch on: particles_per_wg, the sorted particles a workgroup walks;
+ * origins_per_pass, the frames of origins a workgroup holds in registers at a time; lag_tile, the lags of one workgroup;
+ * on_chip, whether the counts go to an on-chip histogram (nbins <= lds_cells; lag_tile * nbins <= lds_cells then) or straight
+ * to memory; lds_cells, that limit; pass_splits, the workgroups that share the passes of one (particle chunk, lag tile);
+ * pairs_per_flush, the largest number of pairs one 32-bit on-chip cell can receive between two flushes - particles_per_wg
+ * times the origins a workgroup walks, below 2^32 for every call the entry accepts.  The environment variable
+ * MOLAR_HIP_VANHOVE_ONCHIP = 0 sends the counts to memory whatever nbins is, for the plan and the call alike, and
+ * MOLAR_HIP_VANHOVE_COMBINE = 1 switches on the combining of equal cells of a wave (A/B runs and tests; no count changes). */
+#define MOLAR_HIP_VANHOVE_SIGNED 1u
+int molar_hip_vanhove_plan(size_t nframes, size_t n, size_t ngroups, size_t nlags, size_t nbins, uint32_t ndims,
+                           size_t *workspace_bytes, uint32_t *particles_per_wg, uint32_t *origins_per_pass,
+                           uint32_t *lag_tile, uint32_t *on_chip, uint32_t *lds_cells, uint32_t *pass_splits,
+                           uint64_t *pairs_per_flush);
+int molar_hip_vanhove(molar_hip_ctx *ctx, const float *traj, size_t nframes, size_t frame_stride, size_t natoms,
+                      const uint64_t *idx, size_t n, const uint32_t *labels, size_t ngroups, const uint64_t *lags,
+                      size_t nlags, size_t origin_stride, uint32_t dims, uint32_t flags, double lo, double hi,
+                      size_t nbins, uint64_t *hist, uint64_t *outside, uint64_t *norigins, uint64_t *nvalid,
+                      uint32_t *bad);
+int molar_hip_vanhove_f64(molar_hip_ctx *ctx, const double *traj, size_t nframes, size_t frame_stride, size_t natoms,
+                          const uint64_t *idx, size_t n, const uint32_t *labels, size_t ngroups, const uint64_t *lags,
+                          size_t nlags, size_t origin_stride, uint32_t dims, uint32_t flags, double lo, double hi,
+                          size_t nbins, uint64_t *hist, uint64_t *outside, uint64_t *norigins, uint64_t *nvalid,
+                          uint32_t *bad);
+
 /* the per-frame loop of benches/comparison_small.rs:14-25 in f64, same argument meaning as molar_hip_fit_rmsd_batch:
  * every frame's selection fitted onto the reference selection (masses of the frame's atoms; the reference centre with
  * the same column through ref_idx), RMSD / centre of mass / gyration of the FITTED selection, frames moved if apply.

@@ -597,6 +597,59 @@ inline MsdOf<double> msd_f64(Engine &eng, const double *frames, size_t nframes, 
     return out;
 }
 
+// The self part of the van Hove function (molar_hip_vanhove*; the definition: molar_hip.h) of an ALREADY UNWRAPPED particle
+// trajectory traj [nframes][natoms][3] - the disp of msd() with want_disp, or raw coordinates of a system that is not periodic:
+// the displacements over the lags of `lags` (strictly increasing, below nframes) and all origins, counted into opt.nbins bins
+// of [opt.lo, opt.hi) per group of `labels` (one per selected particle, below opt.ngroups; empty: one group).  `index` empty:
+// every particle.  Every count is an integer.
+struct VanHoveOptions {
+    double lo = 0.0, hi = 1.0;
+    size_t nbins = 100;
+    size_t origin_stride = 1;
+    uint32_t dims = 7;                // bits x, y, z
+    bool is_signed = false;           // the one component of dims itself, lo < 0 as a rule
+    size_t ngroups = 1;               // read with labels
+};
+struct VanHove {
+    std::vector<uint64_t> hist;       // [ngroups][nlags][nbins]
+    std::vector<uint64_t> outside;    // [ngroups][nlags]: the pairs beyond the range
+    std::vector<uint64_t> norigins;   // [nlags]
+    std::vector<uint64_t> nvalid;     // [ngroups]: the particles that entered
+    std::vector<uint32_t> bad;        // [n]: the frames of a particle with a coordinate that is not finite
+    std::vector<double> edges;        // [nbins + 1]
+    size_t ngroups = 0, nlags = 0, nbins = 0;
+};
+template <class Real, class Fn>
+inline VanHove van_hove_call(Fn fn, const char *who, Engine &eng, const Real *traj, size_t nframes, size_t natoms, const std::vector<uint64_t> &lags,
+                             const VanHoveOptions &opt, const std::vector<usize> &index, const std::vector<uint32_t> &labels) {
+    const size_t n = index.empty() ? natoms : index.size();
+    if (!labels.empty() && labels.size() != n) throw MolarError(MOLAR_HIP_ERR_SIZES, std::string(who) + ": one label per selected particle");
+    VanHove out;
+    out.ngroups = labels.empty() ? 1 : opt.ngroups;
+    out.nlags = lags.size();
+    out.nbins = opt.nbins;
+    out.hist.assign(out.ngroups * out.nlags * out.nbins, 0);
+    out.outside.assign(out.ngroups * out.nlags, 0);
+    out.norigins.assign(out.nlags, 0);
+    out.nvalid.assign(out.ngroups, 0);
+    out.bad.assign(n, 0);
+    for (size_t b = 0; b <= opt.nbins && opt.nbins; ++b) out.edges.push_back(opt.lo + (opt.hi - opt.lo) * (double)b / (double)opt.nbins);
+    auto ptr = [](auto &v) { return v.empty() ? nullptr : v.data(); };
+    check(fn(eng.ctx(), traj, nframes, natoms * 3, natoms, index.empty() ? nullptr : index.data(), n, labels.empty() ? nullptr : labels.data(), opt.ngroups,
+             lags.empty() ? nullptr : lags.data(), lags.size(), opt.origin_stride, opt.dims, opt.is_signed ? MOLAR_HIP_VANHOVE_SIGNED : 0u, opt.lo, opt.hi,
+             opt.nbins, ptr(out.hist), ptr(out.outside), ptr(out.norigins), ptr(out.nvalid), ptr(out.bad)));
+    return out;
+}
+inline VanHove van_hove(Engine &eng, const Float *traj, size_t nframes, size_t natoms, const std::vector<uint64_t> &lags,
+                        const VanHoveOptions &opt = VanHoveOptions(), const std::vector<usize> &index = {}, const std::vector<uint32_t> &labels = {}) {
+    return van_hove_call<Float>(molar_hip_vanhove, "van_hove", eng, traj, nframes, natoms, lags, opt, index, labels);
+}
+// the same on an f64 trajectory (MolAR's f64 feature): molar_hip_vanhove_f64
+inline VanHove van_hove_f64(Engine &eng, const double *traj, size_t nframes, size_t natoms, const std::vector<uint64_t> &lags,
+                            const VanHoveOptions &opt = VanHoveOptions(), const std::vector<usize> &index = {}, const std::vector<uint32_t> &labels = {}) {
+    return van_hove_call<double>(molar_hip_vanhove_f64, "van_hove_f64", eng, traj, nframes, natoms, lags, opt, index, labels);
+}
+
 // Density profiles and maps of a block of frames (molar_hip_density; the definition: molar_hip.h): the mean over the frames
 // of the sum of the weights per unit volume in every bin of `grid`, per group.  `weight`: one per ATOM (null: number
 // density; density() takes the selection's masses with mass_weighted); `labels`: one per SELECTED atom, below ngroups

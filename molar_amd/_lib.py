@@ -250,6 +250,9 @@ SYMBOLS = {
     "molar_hip_mindist_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, _P, C.c_uint32, _P, _P, _P, _P, _P, _P]),
     "molar_hip_mindist": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
     "molar_hip_mindist_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_vanhove_plan": (_I, [_SZ, _SZ, _SZ, _SZ, _SZ, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "molar_hip_vanhove": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _SZ, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _SZ, _P, _P, _P, _P, _P]),
+    "molar_hip_vanhove_f64": (_I, [_P, _P, _SZ, _SZ, _SZ, _P, _SZ, _P, _SZ, _P, _SZ, _SZ, C.c_uint32, C.c_uint32, C.c_double, C.c_double, _SZ, _P, _P, _P, _P, _P]),
     "molar_hip_center_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _P]),
     "molar_hip_unwrap_simple_batch": (_I, [_P, _P, _SZ, _P, _P, _SZ, _P, _U8]),
     "molar_hip_membrane_initial_normals": (_I, [_SZ, _P, _P, _P, _P, _P, _P]),

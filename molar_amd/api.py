@@ -1518,6 +1518,33 @@ class Engine:
         return _mindist_call(self.lib, self.lib.molar_hip_mindist, self.ctx, frames, idx1, idx2, labels1, labels2, ngroups1, ngroups2, boxes, pbc, same,
                              exclude_same_group, cutoff, frame_block, want, out, n1, n2, np.float32)
 
+    def van_hove(self, traj, lags, range, nbins, idx=None, labels=None, ngroups=None, origin_stride=1, dims=7, signed=False, want=None, out=None):
+        """The self part of the van Hove function of an ALREADY UNWRAPPED particle trajectory traj [F, natoms, 3] float32 - the
+        `disp` of msd(), or raw coordinates of a system that is not periodic (molar_hip_vanhove, the definition: molar_hip.h):
+        for every lag of the list `lags` (strictly increasing, below F, 0 allowed; vanhove_lags) and every origin 0,
+        origin_stride, ... the displacement sqrt(sum of the squared components of `dims`) of every selected particle (`idx`,
+        None: all), or with signed=True the one component itself, counted into `nbins` bins of the half-open `range` =
+        (lo, hi) per group of `labels` (one per SELECTED particle, below `ngroups`; None: one group), all in double.  No box is
+        taken and no image removed: that is msd's work (van_hove_frames chains the two).  Returns VanHove(hist [G, L, nbins],
+        outside [G, L]: the pairs beyond the range, norigins [L], nvalid [G]: the particles that entered, bad [n]: the frames
+        with a coordinate that is not finite, per particle - such a particle enters no count -, edges [nbins + 1]).  For
+        every (g, l): hist.sum(-1) + outside == nvalid[g] * norigins[l].  `want`: the names to compute (default: all);
+        numpy in gives numpy out (uint64, bad uint32), torch CUDA in gives torch CUDA out (int64, bad int32), written on the
+        ENGINE's stream and not waited for.  `out`: an optional VanHove (or 5-tuple) of destinations.  Every result is an
+        integer: the same call gives the same bits.  vanhove_density and vanhove_fs turn the counts into G_s and F_s(q, tau)."""
+        return _vanhove_call(self.lib, self.lib.molar_hip_vanhove, self.ctx, traj, lags, range, nbins, idx, labels, ngroups, origin_stride, dims, signed,
+                             want, out, np.float32)
+
+    def van_hove_frames(self, frames, lags, range, nbins, idx=None, boxes=None, pbc=7, mass=None, groups=None, ref_idx=None, labels=None, ngroups=None,
+                        origin_stride=1, dims=7, signed=False, want=None, out=None):
+        """van_hove of WRAPPED frames [F, natoms, 3] float32: msd(frames, idx, mass, boxes, pbc, groups, ref_idx, disp=True,
+        msd=False, m4=False) makes the unwrapped particle trajectory (no-jump unwrap under `boxes`, centres of mass of the CSR
+        `groups`, the drift of `ref_idx` removed), then van_hove runs on that `disp` with `labels` one per PARTICLE (per group
+        of `groups`, or per selected atom without them).  With torch CUDA frames `disp` stays on the device between the two
+        calls; with numpy frames it makes one extra round trip through host memory.  Returns the VanHove of van_hove."""
+        return _vanhove_frames_call(self.msd, self.van_hove, frames, lags, range, nbins, idx, mass, boxes, pbc, groups, ref_idx, labels, ngroups,
+                                    origin_stride, dims, signed, want, out)
+
 
 class FitStream:
     """molar_hip_fit_stream_*: the per-frame fit loop of benches/comparison_small.rs:14-25 for frames in HOST memory (numpy),
@@ -2823,6 +2850,158 @@ def _mindist_call(lib, fn, ctx, frames, idx1, idx2, labels1, labels2, ngroups1, 
     return MinDistances(*res)
 
 
+VanHove = collections.namedtuple("VanHove", ["hist", "outside", "norigins", "nvalid", "bad", "edges"])
+VanHovePlan = collections.namedtuple("VanHovePlan", ["workspace_bytes", "particles_per_wg", "origins_per_pass", "lag_tile", "on_chip", "lds_cells",
+                                                     "pass_splits", "pairs_per_flush"])
+VANHOVE_SIGNED = 1                                 # MOLAR_HIP_VANHOVE_SIGNED
+
+
+def vanhove_plan(nframes, n, ngroups=1, nlags=1, nbins=1, ndims=3):
+    """VanHovePlan of a van_hove call of these sizes (molar_hip_vanhove_plan): the device workspace and every launch-shape size
+    the kernels branch on - the sorted particles a workgroup walks, the frames of origins of one pass, the lags of one tile,
+    whether the counts go to the on-chip histogram (nbins <= lds_cells) and that limit, the workgroups that share the passes
+    of one (particle chunk, lag tile), and the largest number of pairs an on-chip 32-bit cell can receive between two
+    flushes (below 2^32).  ndims: the components that enter (1, 2 or 3).  A host function: no GPU is needed."""
+    ws, ppf = C.c_size_t(0), C.c_uint64(0)
+    u = [C.c_uint32(0) for _ in range(6)]
+    check(_lib.load().molar_hip_vanhove_plan(int(nframes), int(n), int(ngroups), int(nlags), int(nbins), int(ndims), C.addressof(ws),
+                                             *(C.addressof(x) for x in u), C.addressof(ppf)))
+    return VanHovePlan(int(ws.value), *(int(x.value) for x in u), int(ppf.value))
+
+
+def vanhove_lags(nframes, per_decade=8):
+    """Log-spaced lags for van_hove: the distinct integers round(10^(k / per_decade)), k = 0, 1, ..., that stay below nframes,
+    increasing, uint64 (1, 2, 3, ... at first, then `per_decade` lags per factor of ten).  One frame: the lag 0 alone."""
+    F, per = int(nframes), int(per_decade)
+    assert F >= 1 and per >= 1
+    if F == 1:
+        return np.zeros(1, np.uint64)
+    k = np.arange(int(np.floor(np.log10(F - 1) * per)) + 2, dtype=np.float64)
+    lags = np.unique(np.round(10.0 ** (k / per)).astype(np.int64))
+    return lags[lags <= F - 1].astype(np.uint64)
+
+
+def vanhove_edges(range, nbins):
+    """The nbins + 1 bin edges of a van_hove histogram over the half-open range (lo, hi), float64."""
+    lo, hi = float(range[0]), float(range[1])
+    return lo + (hi - lo) * np.arange(int(nbins) + 1, dtype=np.float64) / int(nbins)
+
+
+def vanhove_density(hist, nvalid, norigins, edges, ndims):
+    """G_s(r, tau) as a probability density, float64 [G, L, nbins]: hist over the pairs nvalid[g] * norigins[l] and over the
+    exact volume of the shell between the bin's edges - 4/3 pi (r1^3 - r0^3) for ndims = 3, pi (r1^2 - r0^2) for 2, r1 - r0
+    for 1 (and for signed displacements).  Its integral over the shells is 1 minus the fraction of the pairs outside the
+    range; NaN for a group without a valid particle."""
+    h = np.asarray(hist, np.float64)
+    e = np.asarray(edges, np.float64)
+    pairs = np.asarray(nvalid, np.float64).reshape(-1, 1, 1) * np.asarray(norigins, np.float64).reshape(1, -1, 1)
+    nd = int(ndims)
+    assert nd in (1, 2, 3) and h.ndim == 3 and e.shape[0] == h.shape[2] + 1
+    vol = e[1:] - e[:-1] if nd == 1 else np.pi * (e[1:] ** 2 - e[:-1] ** 2) if nd == 2 else 4.0 / 3.0 * np.pi * (e[1:] ** 3 - e[:-1] ** 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return h / pairs / vol
+
+
+def bessel_j0(x):
+    """J0(x) from its integral representation (1 / pi) int_0^pi cos(x sin theta) d theta by the trapezoid rule; the integrand
+    is smooth and periodic, so the rule converges faster than any power once its panels outnumber |x|: float64 accuracy."""
+    x = np.asarray(x, np.float64)
+    flat = np.abs(x).reshape(-1)
+    out = np.empty_like(flat)
+    for s in np.arange(0, flat.shape[0], 4096):
+        part = flat[s:s + 4096]
+        m = int(np.ceil(part.max())) + 48 if part.size else 48
+        theta = np.pi * np.arange(m + 1, dtype=np.float64) / m
+        w = np.ones(m + 1)
+        w[0] = w[-1] = 0.5
+        out[s:s + 4096] = (np.cos(part[:, None] * np.sin(theta)[None, :]) * w).sum(axis=1) / m
+    return out.reshape(x.shape)
+
+
+def vanhove_fs(hist, outside, edges, q, ndims):
+    """The isotropic self-intermediate scattering function F_s(q, tau) = <K(q r)> from a van_hove histogram, with r at the bin
+    centres: K = sin(qr) / (qr) for ndims = 3, J0(qr) (bessel_j0) for 2, cos(qx) for 1 (signed or not).  hist [G, L, nbins],
+    outside [G, L], q a number or [nq]; returns float64 [G, L, nq].  NaN where outside is not zero - a truncated distribution
+    has no transform - and where no pair was counted.  Binning error: a value anywhere in a bin stands at its centre, which
+    changes F_s by O((q dr)^2), dr the bin width: to leading order at most 5/24 (q dr)^2 (1/8 from the curvature of K inside
+    a bin, 1/12 from the slope of the distribution across it)."""
+    h = np.asarray(hist, np.float64)
+    o = np.asarray(outside, np.float64)
+    e = np.asarray(edges, np.float64)
+    qs = np.atleast_1d(np.asarray(q, np.float64))
+    nd = int(ndims)
+    assert nd in (1, 2, 3) and h.ndim == 3 and e.shape[0] == h.shape[2] + 1 and qs.ndim == 1
+    x = qs[:, None] * (0.5 * (e[1:] + e[:-1]))[None, :]                    # [nq, nbins]
+    if nd == 1:
+        K = np.cos(x)
+    elif nd == 2:
+        K = bessel_j0(x)
+    else:
+        K = np.sinc(x / np.pi)
+    total = h.sum(axis=2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fs = np.einsum("glb,qb->glq", h, K) / total[:, :, None]
+    fs[(o != 0) | (total == 0)] = np.nan
+    return fs
+
+
+def _vanhove_call(lib, fn, ctx, traj, lags, range, nbins, idx, labels, ngroups, origin_stride, dims, signed, want, out, real):
+    fr, F, natoms, stride = _frame_block(traj, real)
+    dev = _is_torch(fr)
+    given_in = (idx, labels, lags)
+    idx = _u64(idx); labels = _u32(labels); lags = _u64(lags)
+    assert lags.ndim == 1, "lags is a list"
+    n = natoms if idx is None else int(idx.shape[0])
+    L = int(lags.shape[0])
+    G = 1
+    if labels is not None:
+        assert labels.shape[0] == n, "one label per selected particle"
+        G = int(ngroups) if ngroups is not None else (int(labels.max()) + 1 if n else 1)
+    nbins = int(nbins)
+    lo, hi = float(range[0]), float(range[1])
+    names = VanHove._fields[:5]
+    want = names if want is None else tuple(want)
+    assert all(nm in names for nm in want), "want holds names of VanHove"
+    shapes = ((G, L, nbins), (G, L), (L,), (G,), (n,))
+    given = tuple(out[:5]) if out is not None else (None,) * 5
+    res = []
+    for name, shape, g in zip(names, shapes, given):
+        if name not in want:
+            res.append(None)
+            continue
+        if dev:
+            import torch
+            dt = torch.int32 if name == "bad" else torch.int64
+        else:
+            dt = np.uint32 if name == "bad" else np.uint64
+        if g is not None:
+            assert _is_torch(g) == dev and tuple(g.shape) == shape and g.dtype == dt
+            assert g.is_contiguous() if dev else g.flags.c_contiguous
+            res.append(g)
+        elif dev:
+            res.append(torch.zeros(shape, dtype=dt, device=fr.device))
+        else:
+            res.append(np.zeros(shape, dt))
+    addr = [None if r is None else (r.data_ptr() if dev else r.ctypes.data) for r in res]
+    fa = fr.data_ptr() if dev else fr.ctypes.data
+    ia, k1 = _addr(idx); la, k2 = _addr(labels); ga, k3 = _addr(lags)
+    if dev:
+        # torch made the outputs and any contiguous copy on ITS stream; the engine reads and writes on its own
+        import torch
+        torch.cuda.current_stream().synchronize()
+    check(fn(ctx, fa, F, stride, natoms, ia, n, la, G, ga, L, int(origin_stride), int(dims), VANHOVE_SIGNED if signed else 0, lo, hi, nbins, *addr))
+    if dev and (fr is not traj or any(_is_torch(a) and a is not b for a, b in zip((idx, labels, lags), given_in))):
+        # a temporary copy would go back to torch's allocator with the kernels that read it still enqueued: wait for them
+        check(lib.molar_hip_synchronize(ctx))
+    edges = vanhove_edges((lo, hi), nbins) if nbins >= 1 and np.isfinite(lo) and np.isfinite(hi) else None
+    return VanHove(*res, edges)
+
+
+def _vanhove_frames_call(msd, van_hove, frames, lags, range, nbins, idx, mass, boxes, pbc, groups, ref_idx, labels, ngroups, origin_stride, dims, signed, want, out):
+    disp = msd(frames, idx=idx, mass=mass, boxes=boxes, pbc=pbc, groups=groups, ref_idx=ref_idx, disp=True, msd=False, m4=False).disp
+    return van_hove(disp, lags, range, nbins, labels=labels, ngroups=ngroups, origin_stride=origin_stride, dims=dims, signed=signed, want=want, out=out)
+
+
 Fluctuations = collections.namedtuple("Fluctuations", ["mean", "rmsf", "cov", "fit"])
 
 
@@ -3048,6 +3227,17 @@ class MeasureF64:
         """Engine.min_distances on float64 frames and boxes (molar_hip_mindist_f64): float64 results."""
         return _mindist_call(self.lib, self.lib.molar_hip_mindist_f64, self.ctx, frames, idx1, idx2, labels1, labels2, ngroups1, ngroups2, boxes, pbc,
                              same, exclude_same_group, cutoff, frame_block, want, out, n1, n2, np.float64)
+
+    def van_hove(self, traj, lags, range, nbins, idx=None, labels=None, ngroups=None, origin_stride=1, dims=7, signed=False, want=None, out=None):
+        """Engine.van_hove for traj [F, natoms, 3] float64 (molar_hip_vanhove_f64); the counts are integers either way."""
+        return _vanhove_call(self.lib, self.lib.molar_hip_vanhove_f64, self.ctx, traj, lags, range, nbins, idx, labels, ngroups, origin_stride, dims, signed, want,
+                             out, np.float64)
+
+    def van_hove_frames(self, frames, lags, range, nbins, idx=None, boxes=None, pbc=7, mass=None, groups=None, ref_idx=None, labels=None, ngroups=None,
+                        origin_stride=1, dims=7, signed=False, want=None, out=None):
+        """Engine.van_hove_frames for frames [F, natoms, 3] float64: self.msd, then self.van_hove on its `disp`."""
+        return _vanhove_frames_call(self.msd, self.van_hove, frames, lags, range, nbins, idx, mass, boxes, pbc, groups, ref_idx, labels, ngroups,
+                                    origin_stride, dims, signed, want, out)
 
     def sasa(self, xyz, vdw, idx=None, probe=0.14, npoints=960, want_exposed=False):
         """Engine.sasa on float64 coordinates and radii (molar_hip_sasa_f64): every operation of the two compares in f64."""

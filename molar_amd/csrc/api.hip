@@ -202,6 +202,7 @@ void molar_hip_destroy(molar_hip_ctx *c) {
     mh::tcf_release(c);
     mh::sfactor_release(c);
     mh::mindist_release(c);
+    mh::vanhove_release(c);
     mh::hbonds_release(c);
     mh::lifetimes_release(c);
     mh::within_release(c);

@@ -199,6 +199,7 @@ struct molar_hip_intcoord_state;        // staged inputs, the boxes, staged resu
 struct molar_hip_tcf_state;             // staged inputs, the f64 vector trajectories, chunk partials and staged results of the time correlation calls (tcf.hip)
 struct molar_hip_sfactor_state;         // staged inputs, the partition by label, the blocks of the gram kernel, rho of a block of frames and the running sums of the structure factor calls (sfactor.hip)
 struct molar_hip_mindist_state;         // staged inputs, the boxes, the partition by label, both sets of a block of frames in f64, row partials, the block's group matrix and the running reductions of the minimum-distance calls (mindist.hip)
+struct molar_hip_vanhove_state;         // staged inputs, the partition by label, the particle-major f64 trajectories and staged counts of the van Hove calls (vanhove.hip)
 struct molar_hip_hbonds_state;          // keys, the cached bonds of a frame or a block and the block's table (hbonds.hip)
 struct molar_hip_lifetimes_state;       // the bit matrix, histograms and staging of the lifetime correlations (lifetimes.hip)
 struct molar_hip_within_state;          // flags, lists and the cached `within` set (within.hip)
@@ -231,6 +232,7 @@ struct molar_hip_ctx {
     molar_hip_tcf_state *tcf = nullptr;           // created by the first molar_hip_tcf*
     molar_hip_sfactor_state *sfactor = nullptr;   // created by the first molar_hip_sfactor*
     molar_hip_mindist_state *mindist = nullptr;   // created by the first molar_hip_mindist*
+    molar_hip_vanhove_state *vanhove = nullptr;   // created by the first molar_hip_vanhove*
     molar_hip_hbonds_state *hbonds = nullptr;     // created by the first molar_hip_hbonds*
     molar_hip_lifetimes_state *lifetimes = nullptr;   // created by the first molar_hip_lifetimes*
     molar_hip_within_state *within = nullptr;         // created by the first molar_hip_within_count
@@ -388,6 +390,7 @@ void intcoord_release(molar_hip_ctx *c);
 void tcf_release(molar_hip_ctx *c);
 void sfactor_release(molar_hip_ctx *c);
 void mindist_release(molar_hip_ctx *c);
+void vanhove_release(molar_hip_ctx *c);
 void hbonds_release(molar_hip_ctx *c);
 void lifetimes_release(molar_hip_ctx *c);
 void within_release(molar_hip_ctx *c);

@@ -1416,6 +1416,75 @@ impl Engine {
         Ok((ws, s))
     }
 
+    /// The self part of the van Hove function through molar_hip_vanhove (the definition: molar_hip.h) of an ALREADY UNWRAPPED
+    /// particle trajectory `traj` (frames of `natoms` particles: the `disp` of `msd`, or raw coordinates of a system that is not
+    /// periodic; no box is taken): the displacements over `lags` (strictly increasing, below the number of frames, 0 allowed) and
+    /// the origins 0, `spec.origin_stride`, ..., counted into `spec.nbins` bins of [`spec.lo`, `spec.hi`) per group.  `idx`:
+    /// the selection (None: every particle); `labels`: (one label per selected particle, ngroups), None: one group.  A particle
+    /// with a coordinate of `spec.dims` that is not finite enters no count.  Every result is an integer: the same call gives
+    /// the same bits.
+    pub fn van_hove(
+        &self, traj: &[[f32; 3]], natoms: usize, idx: Option<&[usize]>, labels: Option<(&[u32], usize)>, lags: &[u64], spec: &VanHoveSpec,
+    ) -> Result<VanHove, EngineError> {
+        if natoms == 0 || traj.len() % natoms != 0 {
+            return Err(EngineError::Sizes(format!("van_hove: the block is not a whole number of frames of {natoms} particles")));
+        }
+        check_index(idx, natoms, "van_hove")?;
+        let nframes = traj.len() / natoms;
+        let n = idx.map_or(natoms, |i| i.len());
+        let (lp, g) = match labels {
+            Some((l, _)) if l.len() != n => return Err(EngineError::Sizes(format!("van_hove: {} labels for {n} particles", l.len()))),
+            Some((l, g)) => (l.as_ptr(), g),
+            None => (std::ptr::null(), 1),
+        };
+        if lags.is_empty() || n == 0 || g == 0 {
+            return Err(EngineError::Sizes("van_hove: no lags, no particles or no groups".into()));
+        }
+        if lags.windows(2).any(|w| w[1] <= w[0]) || (nframes > 0 && lags[lags.len() - 1] >= nframes as u64) {
+            return Err(EngineError::Sizes(format!("van_hove: the lags must increase strictly and stay below the {nframes} frames")));
+        }
+        let ndims = (spec.dims & 7).count_ones();
+        if spec.dims == 0 || spec.dims > 7 || spec.flags & !VANHOVE_SIGNED != 0 || (spec.flags & VANHOVE_SIGNED != 0 && ndims != 1) {
+            return Err(EngineError::Sizes(format!("van_hove: dims = {} with flags = {}", spec.dims, spec.flags)));
+        }
+        if !(spec.lo.is_finite() && spec.hi.is_finite() && spec.lo < spec.hi) || spec.nbins == 0 || spec.origin_stride == 0 {
+            return Err(EngineError::Sizes("van_hove: a finite range lo < hi, nbins >= 1 and origin_stride >= 1 are needed".into()));
+        }
+        let cells = g.checked_mul(lags.len()).and_then(|c| c.checked_mul(spec.nbins)).filter(|&c| c < 1usize << 31);
+        let cells = cells.ok_or_else(|| EngineError::Sizes("van_hove: 2^31 histogram cells or more".into()))?;
+        let mut out = VanHove {
+            hist: vec![0u64; cells],
+            outside: vec![0u64; g * lags.len()],
+            norigins: vec![0u64; lags.len()],
+            nvalid: vec![0u64; g],
+            bad: vec![0u32; n],
+            edges: (0..=spec.nbins).map(|b| spec.lo + (spec.hi - spec.lo) * b as f64 / spec.nbins as f64).collect(),
+            ngroups: g,
+            nlags: lags.len(),
+            nbins: spec.nbins,
+        };
+        if nframes == 0 {
+            return Ok(out);
+        }
+        self.plugin.check(unsafe {
+            (self.plugin.fns.vanhove)(self.ctx, traj.as_ptr() as *const f32, nframes, natoms * 3, natoms, idx.map_or(std::ptr::null(), |i| i.as_ptr() as *const u64), n,
+                                      lp, g, lags.as_ptr(), lags.len(), spec.origin_stride, spec.dims, spec.flags, spec.lo, spec.hi, spec.nbins,
+                                      out.hist.as_mut_ptr(), out.outside.as_mut_ptr(), out.norigins.as_mut_ptr(), out.nvalid.as_mut_ptr(), out.bad.as_mut_ptr())
+        })?;
+        Ok(out)
+    }
+
+    /// The device workspace and the launch shape of a `van_hove` call of these sizes (molar_hip_vanhove_plan, a host function);
+    /// `ndims`: the components that enter (1, 2 or 3).
+    pub fn van_hove_plan(&self, nframes: usize, n: usize, ngroups: usize, nlags: usize, nbins: usize, ndims: u32) -> Result<VanHovePlan, EngineError> {
+        let mut p = VanHovePlan::default();
+        self.plugin.check(unsafe {
+            (self.plugin.fns.vanhove_plan)(nframes, n, ngroups, nlags, nbins, ndims, &mut p.workspace_bytes, &mut p.particles_per_wg, &mut p.origins_per_pass,
+                                           &mut p.lag_tile, &mut p.on_chip, &mut p.lds_cells, &mut p.pass_splits, &mut p.pairs_per_flush)
+        })?;
+        Ok(p)
+    }
+
     /// Lifetime correlations of a sparse presence matrix frames x rows (`molar_hip_lifetimes`; the definition is in the header):
     /// the rows present in frame t are `row_of_entry[frame_offsets[t] .. frame_offsets[t + 1]]`.  `labels`: (one label per row,
     /// ngroups), None: one group.  Lags 0 ..= `max_lag`, origins 0, `origin_stride`, ...; `gap`: zero runs of at most that many

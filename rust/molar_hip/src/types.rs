@@ -156,6 +156,51 @@ pub const MINDIST_ATOM1: u32 = 2;
 pub const MINDIST_ATOM2: u32 = 4;
 pub const MINDIST_MAT: u32 = 8;
 
+/// `MOLAR_HIP_VANHOVE_SIGNED`: the one component of `dims` itself instead of the length of the displacement.
+pub const VANHOVE_SIGNED: u32 = 1;
+
+/// The parameters of `Engine::van_hove` (molar_hip_vanhove; the definition: molar_hip.h): the half-open range [lo, hi) and its
+/// bins, the stride of the time origins, the bits x, y, z of the components that enter, and `VANHOVE_SIGNED` or 0.
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct VanHoveSpec {
+    pub lo: f64,
+    pub hi: f64,
+    pub nbins: usize,
+    pub origin_stride: usize,
+    pub dims: u32,
+    pub flags: u32,
+}
+
+/// What `Engine::van_hove` returns: hist [group][lag][bin], outside [group][lag] (the pairs beyond the range), norigins [lag],
+/// nvalid [group] (the particles that entered), bad [selected particle] (its frames with a coordinate that is not finite) and
+/// the nbins + 1 bin edges.  For every (g, l): the sum of hist over the bins plus outside equals nvalid[g] * norigins[l].
+#[derive(Debug, Clone, Default)]
+pub struct VanHove {
+    pub hist: Vec<u64>,
+    pub outside: Vec<u64>,
+    pub norigins: Vec<u64>,
+    pub nvalid: Vec<u64>,
+    pub bad: Vec<u32>,
+    pub edges: Vec<f64>,
+    pub ngroups: usize,
+    pub nlags: usize,
+    pub nbins: usize,
+}
+
+/// What `Engine::van_hove_plan` returns (molar_hip_vanhove_plan): the device workspace and every launch-shape size the kernels
+/// branch on.
+#[derive(Debug, Clone, Copy, Default, PartialEq)]
+pub struct VanHovePlan {
+    pub workspace_bytes: usize,
+    pub particles_per_wg: u32,
+    pub origins_per_pass: u32,
+    pub lag_tile: u32,
+    pub on_chip: u32,
+    pub lds_cells: u32,
+    pub pass_splits: u32,
+    pub pairs_per_flush: u64,
+}
+
 /// `molar_hip_search_desc_f64`: the same request for MolAR built with its `f64` feature (Float = f64).
 #[repr(C)]
 #[derive(Clone, Copy)]
