@@ -10,7 +10,9 @@ dictate the label runs inside every cell; PERMUTED order interleaves the cells.
     frame(box, dims, pops, rng, order)  -> pos float32 [n, 3], box, pops[ncells], cell of every atom
     binned(pos, box, dims)              -> population of every cell by fractional binning (for the oracle's dims)
 
-Boxes: ortho_box(dims, cutoff), tric_box(cutoff) (a synth.box_a-style shear: lattice shifts exist).  tests/test_pinned_cells_cpu.py
+Boxes: ortho_box(dims, cutoff), tric_box(cutoff) (a synth.box_a-style shear: lattice shifts exist); for the f32 search's
+instance cases (tests/search_f32_cases.py) ortho_box_edges (a cell edge per axis: few long cells), sheared_box (a shear with chosen
+lab extents), plant (a table of populations inside a background) and corner_cells.  tests/test_pinned_cells_cpu.py
 asserts on the reference alone that every frame the GPU tests use is what it was built to be.
 """
 import numpy as np
@@ -24,6 +26,44 @@ ORDERS = ("cell_major", "permuted")
 def ortho_box(dims, cutoff=CUTOFF, edge=1.02):
     """cells of `edge` cutoffs: floor(dims * edge) == dims for every edge in [1, 1 + 1 / dims)"""
     return np.diag([d * edge * cutoff for d in dims]).astype(np.float32)
+
+
+def ortho_box_edges(dims, edges, cutoff=CUTOFF):
+    """cells of edges[d] cutoffs along d: floor(dims[d] * edges[d]) == dims[d] needs 1 <= edges[d] < 1 + 1 / dims[d] - one cell
+    may be up to 2 cutoffs long, two cells 1.5, four cells 1.25 (asserted)"""
+    assert all(int(np.floor(d * e)) == d for d, e in zip(dims, edges)), (dims, edges)
+    return np.diag([d * e * cutoff for d, e in zip(dims, edges)]).astype(np.float32)
+
+
+def sheared_box(rows, shear=(-0.4, -0.3), cutoff=CUTOFF):
+    """An upper-triangular box (c leans by shear[0] / shear[1] cutoffs in x / y) whose ROW sums - the reference's lab extents,
+    which size its grid - are rows[d] cutoffs: lattice shifts exist, and floor(rows[d]) cells along d"""
+    sx, sy = shear
+    return (np.array([[rows[0] - sx, 0.0, sx], [0.0, rows[1] - sy, sy], [0.0, 0.0, rows[2]]]) * cutoff).astype(np.float32)
+
+
+def plant(dims, values, background, rng, fixed=None):
+    """Populations with every entry of `values` in a cell of its own (cells drawn without replacement) inside a background drawn
+    uniformly from background = (lo, hi), both included; fixed = {cell: population} is applied last (its cells are kept free of
+    `values`)."""
+    nc = ncells(dims)
+    fixed = dict(fixed or {})
+    free = np.array([c for c in rng.permutation(nc) if int(c) not in fixed], np.int64)
+    assert len(values) <= len(free), (len(values), len(free))
+    pops = rng.integers(background[0], background[1] + 1, size=nc).astype(np.int64)
+    pops[free[: len(values)]] = np.asarray(values, np.int64)
+    for c, v in fixed.items():
+        pops[c] = v
+    return pops
+
+
+def corner_cells(dims):
+    """(first cells, second cells) of the four plan entries that wrap in all three dimensions (masks 7, 11, 12, 13 of the cell
+    (dx - 1, dy - 1, dz - 1)), as flat indices, entry by entry"""
+    dx, dy, dz = (int(d) for d in dims)
+    first = [(dx - 1, dy - 1, dz - 1), (0, 0, dz - 1), (0, dy - 1, 0), (dx - 1, 0, 0)]
+    second = [(0, 0, 0), (dx - 1, dy - 1, 0), (dx - 1, 0, dz - 1), (0, dy - 1, dz - 1)]
+    return [cell_index(dims, *c) for c in first], [cell_index(dims, *c) for c in second]
 
 
 TRIC_DIMS = (3, 3, 4)          # what the reference makes of tric_box (asserted in the CPU test, from one oracle call)

@@ -109,6 +109,40 @@ def plan_slots(occ1, occ2, dims, pbc):
     return total
 
 
+def plan_cell_pairs(dims, pbc, two=False):
+    """The 14-mask plan entry by entry, in plan order (x outer, z inner, the masks; two sets: (c1, c2) then (c2, c1)): arrays
+    (first cell, second cell, wrap) - flat cell indices into the first and the second set's grid, and the dimensions in which
+    one of the two cells went round the periodic boundary (bit d).  Entries that leave the grid in a non-periodic dimension
+    are dropped; empty cells are not looked at."""
+    dx, dy, dz = (int(x) for x in dims)
+    out = []
+    for x in range(dx):
+        for y in range(dy):
+            for z in range(dz):
+                for m in MASKS:
+                    cells, wrap = [], 0
+                    for off in (m[:3], m[3:]):
+                        c = [x + int(off[0]), y + int(off[1]), z + int(off[2])]
+                        for d in range(3):
+                            if c[d] == (dx, dy, dz)[d]:
+                                if (pbc >> d) & 1:
+                                    c[d] = 0
+                                    wrap |= 1 << d
+                                else:
+                                    c = None
+                                    break
+                        cells.append(None if c is None else c[0] + dx * (c[1] + dy * c[2]))
+                        if c is None:
+                            break
+                    if None in cells:
+                        continue
+                    out.append((cells[0], cells[1], wrap))
+                    if two:
+                        out.append((cells[1], cells[0], wrap))
+    a = np.array(out, np.int64).reshape(-1, 3)
+    return a[:, 0], a[:, 1], a[:, 2]
+
+
 def planted_wrap_pairs(box, rc, dims, per_mask, seed, emin=-15.5, emax=-8.0):
     """Pairs at rc * (1 +- 10^e), e uniform in [emin, emax], across every face, edge and corner of the periodic cell: for each of
     the seven wrap masks `per_mask` pairs whose second atom leaves the cell in exactly that mask's dimensions (on the low or

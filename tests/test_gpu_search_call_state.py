@@ -166,8 +166,13 @@ def sequence(a, e, s):
     out["hist"] = b.cpu().numpy()
     e.within_hold(True)
     dev_ids = lambda n: torch.empty(n, dtype=torch.int64, device="cuda")
-    out["within1"] = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2"], box=s["box"], pbc=7, device_out=dev_ids).cpu().numpy()
-    out["within2"] = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2b"], box=s["box"], pbc=7, device_out=dev_ids).cpu().numpy()
+    # (a fill into device memory is enqueued on the engine's stream, which torch's copy does not wait for: synchronize first)
+    w1 = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2"], box=s["box"], pbc=7, device_out=dev_ids)
+    e.synchronize()
+    out["within1"] = w1.cpu().numpy()
+    w2 = e.within_set(CUTOFF, s["d_pos"], xyz2=s["d_pos2b"], box=s["box"], pbc=7, device_out=dev_ids)
+    e.synchronize()
+    out["within2"] = w2.cpu().numpy()
     e.within_hold(False)
     c = e.search_contacts(a.SEARCH_SINGLE, CUTOFF, s["d_pos"], box=s["box"], pbc=7)
     out["contacts"] = (c.count, c.deg1.cpu().numpy())
